@@ -2,7 +2,12 @@
 """
 bench.py — georef + resample throughput on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, spin-up and the W warm-up steps, ONE timed region of K steps,
+the outputs of its last step if --dump-outputs is given, and the JSON line.  --full adds everything else the line can carry:
+seven timed regions (the median one reported), the PCIe-inclusive upload run, the measured copy / fill rates of the roofline,
+the other configurations ("variants"), the CPU baselines and the oracle parity check.
 
 With N > 1 and no WORLD_SIZE in the environment this process touches no GPU: it starts
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py`` as a child,
@@ -41,10 +46,12 @@ LAUNCH_STREAMS = 1      # --launch-streams
 MAX_RESIDENT_IMAGES = 128  # distinct images kept in HBM (72 MB each); longer runs cycle through them
 # the pipelines' own coordinate buffers in strip-padded rows (amt_georef_out.row_layout; AMT_PADDED_ROWS=0: contiguous, A/B runs)
 PADDED = os.environ.get('AMT_PADDED_ROWS', '1') != '0'
-# The K-step timed region (barrier + synchronize, K steps, barrier + synchronize) runs REPEATS times back to back on the same frames
-# in the same warm state, and the line reports the MEDIAN region: a 20-step region lasts 3 ms, and single regions on one box
-# differ by more than the effect of a round's optimisations (-5.6 % between two rounds with no kernel change)
+# With --full the K-step timed region (barrier + synchronize, K steps, barrier + synchronize) runs REPEATS times back to back on the
+# same frames in the same warm state, and the line reports the MEDIAN region: a 20-step region lasts 3 ms, and single regions on
+# one machine differ by more than the effect of a round's optimisations (-5.6 % between two rounds with no kernel change).
+# A plain run times K steps once: choose K for a region long enough to measure.
 REPEATS = 7
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs writes at most this much
 
 
 def median_index(values):
@@ -81,7 +88,7 @@ def parse_args(argv=None):
     ap.add_argument('--steps', type=int, default=None, help='frames per rank in the timed region (default 192 for every N: weak scaling; BASELINE.json configs[4], the '
                          '256-frame job on 8 GPUs, is --gpus 8 --steps 32)')
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--cpu-rows', type=int, default=2832, help='rows of the frame the CPU baseline processes (0 = skip)')
+    ap.add_argument('--cpu-rows', type=int, default=2832, help='with --full: rows of the frame the CPU baseline processes (0 = skip)')
     ap.add_argument('--exact', action='store_true', help='exact centre rays instead of fast centres')
     ap.add_argument('--magnetic', action='store_true',
                     help='configs[3] instead of configs[2]: MLat/MLT outputs and the (MLat, SM longitude) grid of '
@@ -106,7 +113,7 @@ def parse_args(argv=None):
     ap.add_argument('--launch-streams', type=int, default=1, choices=(1, 2),
                     help='fused plan: 2 = consecutive launches of the big kernel alternate between two HIP streams')
     ap.add_argument('--no-variants', action='store_true',
-                    help='skip the short extra runs (exact centres, configs[3]) whose figures the JSON line carries as '
+                    help='with --full: skip the short extra runs (exact centres, configs[3]) whose figures the JSON line carries as '
                          '"variants" (they run on rank 0 at N = 1 only, after the timed region)')
     ap.add_argument('--spinup-ms', type=float, default=400.0,
                     help='untimed: before the W warm-up steps the same loop runs for about this long, so that the clocks '
@@ -114,9 +121,16 @@ def parse_args(argv=None):
                          'runs its first few dozen launches 3-5 %% slower; MI355X_MICROARCH.md asks for 2 s of back-to-back '
                          'launches before trusting an in-kernel clock); 0 disables')
     ap.add_argument('--cpu-procs', type=int, default=16,
-                    help='processes of the N-process CPU baseline (cpu_baseline.n_process: one oracle process per frame, the '
+                    help='with --full: processes of the N-process CPU baseline (cpu_baseline.n_process: one oracle process per frame, the '
                          'reference\'s only data parallelism, SURVEY 8d (ii)); 0 = skip')
     ap.add_argument('--cpu-worker', type=int, default=None, help=argparse.SUPPRESS)      # internal: one such process
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: %d timed regions instead of one (the '
+                         'median reported), the upload run, the copy / fill rates, the variants, the CPU baselines and the '
+                         'parity check against the oracle' % REPEATS)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (rank 0\'s last frame: binned grid, '
+                         'counts, rounded image, mask, grid coordinates) as DIR/<name>.npy in float32 / float64')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / reporting path only: gloo on the CPU, no GPU, a step is a sleep (tests)')
     args = ap.parse_args(argv)
@@ -599,6 +613,32 @@ def directions_in_run(imgs, first, warmup, steps, fence, n_dirs=6, batch=3, repe
                 grid=grid, repeats=repeats, georef_ms_min=min(r['georef_ms'] for r in regions))
 
 
+def dump_outputs(res, directory):
+    """--dump-outputs: the result of the last timed step as a caller of SequencePipeline.process(keep_on_device=False) receives it
+    (binned mean, counts, rounded image, mask and the grid's corner / centre coordinates), one DIR/<name>.npy each: the image
+    and the mask as float32, everything else as float64, all exact.  The mean of an empty cell (mask 1) is NaN; it is written as
+    0, like the rounded image there, so that every value in the files is finite (a NaN in a filled cell is left as it is).  A
+    frame's grid is about 100 x 100 cells; should the arrays ever exceed DUMP_LIMIT_BYTES, every k-th grid row of each is
+    written (a fixed sample, the same in every run)."""
+    import torch
+    from auromat_amd.resample import grid_coordinates
+    assert res is not None, 'the last timed frame has no valid pixel'
+    arrays = dict(grid_coordinates(res))
+    for name in ('mean', 'count', 'img', 'mask'):
+        v = res[name]
+        arrays[name] = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    if arrays['img'].dtype == np.int16:             # uint16 values in the frame buffers' int16 layout
+        arrays['img'] = arrays['img'].view(np.uint16)
+    arrays = {k: np.asarray(v).astype(np.float32 if k in ('img', 'mask') else np.float64) for k, v in arrays.items()}
+    arrays['mean'][arrays['mask'] != 0] = 0.0
+    stride = 1
+    while sum(a[::stride].nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        stride += 1
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a[::stride])
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -712,11 +752,13 @@ def main(argv=None):
 
     run = timed_run(make_frames(total, args.magnetic), args.warmup, args.steps, fast, args.plan, args.magnetic,
                     args.batch, args.streams, not args.no_hints, shared, own_buffers=args.upload, fence=fence,
-                    after=gather, spinup_ms=args.spinup_ms, geodetic_arrays=args.nine_arrays)
-    # the median of the REPEATS timed regions (each one: barrier + synchronize, K steps, gather, barrier + synchronize; with N
+                    after=gather, spinup_ms=args.spinup_ms, geodetic_arrays=args.nine_arrays, repeats=REPEATS if args.full else 1)
+    # the median of the timed regions (each one: barrier + synchronize, K steps, gather, barrier + synchronize; with N
     # ranks a region's time is the maximum over the ranks)
     m_region, region_times, reg = pick_region(run, use_dist, cdev)
     elapsed = region_times[m_region]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(run['results'][-1], args.dump_outputs)
     rank_records = None
     if use_dist:
         own_elapsed = reg['elapsed']
@@ -751,7 +793,7 @@ def main(argv=None):
 
     upload = None
     host_imgs = None
-    want_upload = not args.no_variants and not args.upload and shared is None and args.plan == 'fused' and not args.exact
+    want_upload = args.full and not args.no_variants and not args.upload and shared is None and args.plan == 'fused' and not args.exact
     if want_upload:
         # The PCIe-inclusive form of the same job (never the headline value): every rank streams its frames'
         # images from its OWN pinned host buffers (four distinct 72 MB images, cycled), uploaded on a copy stream beside the
@@ -811,8 +853,8 @@ def main(argv=None):
         seq, results, plans = run['seq'], run['results'], reg['plans']
         georef_ms, bin_ms = reg['georef_ms'], reg['bin_ms']
         npx = WIDTH * HEIGHT
-        copy_gbs = measured_copy_gbs(device)
-        fill_gbs = measured_fill_gbs(device)
+        copy_gbs = measured_copy_gbs(device) if args.full else None
+        fill_gbs = measured_fill_gbs(device) if args.full else None
         ab = algorithmic_bytes(WIDTH, HEIGHT)
         info = ctx.device_info()
         res = results[-1]
@@ -937,7 +979,7 @@ def main(argv=None):
         import gc
         gc.collect()        # the pipeline's drivers are freed HERE (hipFree synchronises the device), not whenever the
                             # cycle collector gets to them in the middle of a later timed region
-        if world == 1 and not args.no_variants and shared is None and not (args.exact or args.magnetic or args.upload or not fused):
+        if world == 1 and args.full and not args.no_variants and shared is None and not (args.exact or args.magnetic or args.upload or not fused):
             # the other configurations of SURVEY 8d on the record of the same run: short runs of the same loop
             torch.cuda.empty_cache()
             variants = {}
@@ -1040,7 +1082,7 @@ def main(argv=None):
             out['variants'] = variants
         if upload is not None:
             out.setdefault('variants', {})['upload'] = upload
-        if world == 1 and args.cpu_rows > 0:
+        if world == 1 and args.full and args.cpu_rows > 0:
             parity = {}
             out['cpu_baseline'] = cpu_baseline(min(args.cpu_rows, HEIGHT), parity=parity)
             if args.cpu_procs > 0:

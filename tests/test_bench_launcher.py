@@ -51,3 +51,48 @@ def test_default_steps_are_the_same_per_rank_for_every_n():
     assert bench.parse_args(['--gpus', '8']).steps == bench.parse_args([]).steps >= 32
     assert bench.parse_args(['--gpus', '8', '--steps', '32']).steps * 8 == 256
     assert bench.parse_args([]).gpus == 1
+
+
+def test_plain_run_is_the_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    args = bench.parse_args(['--steps', '5'])
+    assert args.full is False and args.dump_outputs is None and args.steps == 5
+    args = bench.parse_args(['--full', '--dump-outputs', 'out'])
+    assert args.full is True and args.dump_outputs == 'out'
+
+
+def test_dump_outputs_writes_the_result_arrays_as_floats_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs on a result dict of the pipeline's shape (host tensors stand in for the device ones): one .npy per array,
+    float32 / float64, values unchanged except the NaN mean of empty cells, which is written as 0 (every value finite); above
+    the size limit every k-th grid row of each array, and never more than the limit."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from auromat_amd.resample import cached_grid
+    grid = cached_grid((10, 10), 50.0, 56.2, 10.0, 20.1)
+    ny, nx = grid.lat_c.shape
+    gen = torch.Generator().manual_seed(5)
+    res = dict(grid=grid, contains_pole=False, contains_discontinuity=False, altitude=110.0,
+               mean=torch.rand(ny, nx, 4, dtype=torch.float64, generator=gen),
+               count=torch.randint(0, 9, (ny, nx), generator=gen).double(),
+               img=torch.randint(-32768, 32767, (ny, nx, 3), dtype=torch.int16, generator=gen),
+               mask=torch.randint(0, 2, (ny, nx), dtype=torch.uint8, generator=gen))
+    empty = res['mask'].numpy() == 1
+    res['mean'][torch.from_numpy(empty)] = float('nan')            # as the binning leaves an empty cell
+    bench.dump_outputs(res, str(tmp_path / 'all'))
+    got = {f[:-4]: np.load(str(tmp_path / 'all' / f)) for f in os.listdir(str(tmp_path / 'all'))}
+    assert sorted(got) == ['count', 'img', 'lat', 'lat_c', 'lon', 'lon_c', 'mask', 'mean']
+    assert all(np.isfinite(a).all() for a in got.values())
+    assert got['mean'].dtype == np.float64 and np.array_equal(got['mean'], np.where(empty[..., None], 0.0, res['mean'].numpy()))
+    assert got['img'].dtype == np.float32 and np.array_equal(got['img'], res['img'].numpy().view(np.uint16))
+    assert got['mask'].dtype == np.float32 and np.array_equal(got['mask'], res['mask'].numpy())
+    assert np.array_equal(got['lat'], grid.lat) and np.array_equal(got['lon_c'], grid.lon_c)
+    total = sum(a.nbytes for a in got.values())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', total // 10)
+    bench.dump_outputs(res, str(tmp_path / 'sample'))
+    part = {f[:-4]: np.load(str(tmp_path / 'sample' / f)) for f in os.listdir(str(tmp_path / 'sample'))}
+    assert sum(a.nbytes for a in part.values()) <= total // 10
+    assert sorted(part) == sorted(got)
+    assert [k for k in range(2, ny + 1) if all(np.array_equal(a, got[name][::k]) for name, a in part.items())]

@@ -22,7 +22,7 @@ def test_bench_with_several_ranks_on_one_gpu(world, steps):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(AMT_BENCH_BACKEND='gloo', AMT_BENCH_ONE_GPU='1')
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', str(steps), '--warmup', '2',
-                          '--cpu-rows', '0', '--no-variants'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          '--cpu-rows', '0', '--no-variants', '--full'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          universal_newlines=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -35,7 +35,7 @@ def test_bench_with_several_ranks_on_one_gpu(world, steps):
     assert abs(out['value'] - world * steps * npx / 1e6 / (out['ms_per_step'] * steps * 1e-3)) < 1e-6 * out['value']
     assert out['config']['workload'].startswith('configs[')
     assert out['roofline']['frac'] > 0 and out['roofline']['bound'] == 'hbm'
-    # the value is that of the median of seven timed regions (each: barrier, K steps, gather, barrier; maximum over the ranks)
+    # with --full the value is that of the median of seven timed regions (each: barrier, K steps, gather, barrier; maximum over the ranks)
     assert out['repeats'] == 7 and len(out['regions_ms']) == 7
     assert out['ms_per_step_min'] <= out['ms_per_step'] <= out['ms_per_step_max']
     assert sorted(out['regions_ms'])[3] == pytest.approx(out['ms_per_step'] * steps, rel=1e-9)
@@ -59,13 +59,13 @@ def test_bench_with_several_ranks_on_one_gpu(world, steps):
 
 
 def test_n_rank_line_carries_the_upload_variant():
-    """Without --no-variants the N-rank line also holds `variants.upload`: the same job with every rank streaming its frames'
+    """With --full and without --no-variants the N-rank line also holds `variants.upload`: the same job with every rank streaming its frames'
     images from its own page-locked host buffers (what a real 256-frame run does), with the PCIe rate each rank reached."""
     world, steps = 2, 6
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update(AMT_BENCH_BACKEND='gloo', AMT_BENCH_ONE_GPU='1')
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', str(steps), '--warmup', '2',
-                          '--cpu-rows', '0'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True,
+                          '--cpu-rows', '0', '--full'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True,
                          timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -95,9 +95,10 @@ def test_a_rank_that_fails_in_the_timed_region_ends_the_run():
     env.update(AMT_BENCH_BACKEND='gloo', AMT_BENCH_ONE_GPU='1', AMT_BENCH_FAIL_RANK='1', AMT_DIST_TIMEOUT_S='120')
     t0 = time.time()
     res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--steps', str(steps), '--warmup', '2',
-                          '--cpu-rows', '0', '--no-variants', '--magnetic'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          '--cpu-rows', '0', '--no-variants', '--magnetic', '--full'], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          universal_newlines=True, timeout=300)
-    # (--magnetic: the MLat / MLT grid needs the IGRF dipole of the frame's date, which amt_run_push refuses beyond the table)
+    # (--magnetic: the MLat / MLT grid needs the IGRF dipole of the frame's date, which amt_run_push refuses beyond the table;
+    # --full: the failure is put into the second timed region)
     assert res.returncode != 0 and time.time() - t0 < 110, res.stderr[-3000:]
     assert not [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
     assert 'IGRF' in res.stderr and 'SequenceError' in res.stderr, res.stderr[-3000:]

@@ -7,7 +7,7 @@ mkdir -p $O
 i=0
 for set in "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_STALL_sum TCC_EA0_WRREQ_DRAM_CREDIT_STALL_sum TCC_BUSY_sum GRBM_GUI_ACTIVE" "MemUnitStalled TA_BUSY_avr SQ_INSTS_VMEM_WR SQ_INST_CYCLES_VMEM_WR SQ_INSTS_SMEM SQ_WAIT_INST_ANY SQ_WAVE_CYCLES" "TCC_EA0_WRREQ_LEVEL_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_WRREQ_WRITE_DRAM_sum GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout -s INT 150 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/set$i -- python3 $R/bench.py --steps 12 --warmup 3 --spinup-ms 0 --cpu-rows 0 --no-variants > $O/set$i.log 2>&1 < /dev/null
+  timeout -s INT 150 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/set$i -- python3 $R/bench.py --full --steps 12 --warmup 3 --spinup-ms 0 --cpu-rows 0 --no-variants > $O/set$i.log 2>&1 < /dev/null
   echo "pmc set $i exit $?"
 done
 python3 - <<PY

@@ -1,6 +1,6 @@
 """
 Where a short timed region's time goes on the GPU side: reads the database of
-    rocprofv3 --kernel-trace -d DIR -o t -- python3 bench.py --steps 20 --warmup 5 --no-variants
+    rocprofv3 --kernel-trace -d DIR -o t -- python3 bench.py --full --steps 20 --warmup 5 --no-variants
 and prints, for every timed region (a call of 1 + 19 frames' launches: the first launch carries one frame), the big kernel's
 busy time, the gaps between its launches, the coarse pre-passes of the frames that have no finished neighbour yet (a repeated
 region starts the sequence again) and the tail after the last big kernel (the finalise kernels of the last launch).

@@ -1,6 +1,6 @@
 """The driver's invocation (20 frames): kernel trace of the timed region — every launch of the big kernel with its frames,
 duration and the gap to the one before, what runs after the last one — next to the host's own clock.
-usage (on the GPU box): rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 20 --warmup 5 --cpu-rows 0
+usage (on an MI355X): rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --steps 20 --warmup 5 --cpu-rows 0
 --no-variants;  python3 tools/short_run_timeline.py DIR"""
 import csv, glob, sys
 rows = []
