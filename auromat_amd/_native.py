@@ -107,7 +107,7 @@ class RunResult(C.Structure):
                 ('retried', C.c_int32), ('reserved2_', C.c_int32), ('uploaded_bytes', C.c_int64)]
 
 
-ABI_VERSION = 6          # include/auromat_hip.h AMT_ABI_VERSION
+ABI_VERSION = 7          # include/auromat_hip.h AMT_ABI_VERSION
 _I, _L, _D, _P = C.c_int, C.c_int64, C.c_double, C.c_void_p
 _SIGNATURES = {
     'amt_abi_version': ([], _I),
@@ -192,6 +192,8 @@ _SIGNATURES = {
                        C.POINTER(Axis), _I, _P], _I),
     'amt_bin_frame_finalize': ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),
     'amt_bin_frame_finalize_window': ([_P, _P] + [C.c_int32] * 8 + [_P, _P, _P, _P], _I),
+    'amt_median_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                          C.POINTER(Axis), _I, _P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
                            _P], _I),
     'amt_nearest_gather': ([_P, _P, _L, _P, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),

@@ -1,0 +1,712 @@
+// Median binning (auromat_amd.resample.resampleMedian): np.median of every channel over the pixels that
+// resample(method='mean') bins into a cell (reference auromat/resample.py:353-357 names the statistic and leaves it
+// unbuilt).  Exact and independent of scatter order: every result is an order statistic of the cell's keys.
+//
+//   k_med_count    cell of every pixel by the membership rule of k_bin_frame (histogram2d's edges), counts per cell;
+//                  a lane takes 4 consecutive pixels and a run of lanes with one cell issues one atomic
+//   k_med_scan_*   exclusive scan of the counts (block sums, one workgroup over the sums, block rescan)
+//   k_med_fill     scatter of the KEYS into contiguous per-cell segments, one plane per channel: u16 channel values,
+//                  elevation as an order-preserving u64 of its float64 bits; positions reserved per run of lanes
+//   k_med_small    one wave per cell: outputs of every cell (count, mask, empty cells) and, for cells of <= 64 pixels,
+//                  a 64-lane bitonic sort per plane; larger cells are listed for the two tiers below
+//   k_med_medium   one workgroup per cell of <= kLargeMin keys: radix select in LDS (8-bit digits: one pass for u8,
+//                  two for u16, eight for the elevation key)
+//   k_med_large_*  cells above kLargeMin: the same radix select over many workgroups per cell, digit histograms in
+//                  global memory (one launch pair per digit and plane)
+// Both tiers select k_lo = (n-1)/2 and get k_hi = n/2 from the same pass: it is k_lo's value when the keys <= that
+// value are more than k_hi, else the smallest key above it (one more pass).  Even counts average the two in float64.
+#include "amt_common.h"
+
+#include <cmath>
+
+namespace {
+
+using namespace amt;
+
+constexpr int kBlock = 256;
+constexpr int kPPT = 4;                 // consecutive pixels per lane in the count and fill passes
+constexpr int kSmallMax = 64;           // cells up to one wave's lanes are sorted in registers
+constexpr int kLargeMin = 16384;        // cells above this many keys are spread over several workgroups
+constexpr int kChunk = 4096;            // keys per workgroup of the large tier
+constexpr int kScanItems = 8;           // cells per thread of the scan
+
+inline dim3 grid_for(int64_t n) {
+    int64_t blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (blocks < 1) blocks = 1;
+    return dim3(static_cast<unsigned>(blocks));
+}
+
+struct med_args {
+    const double* lat_c;
+    const double* lon_c;
+    const double* elev;
+    const void* img;
+    const uint8_t* mask;
+    int64_t n;
+    double min_elev;
+    int use_elev_threshold;
+    int lon_wrap;
+    axis_dev ax, ay;
+    int nx, ny, nch, img_dtype;
+};
+
+// Flat cell (iy * nx + ix) of pixel i or -1: the membership of k_bin_frame (amt_binning.hip) — finite latitude,
+// elevation >= the threshold, centre mask 0, and inside the edges by histogram2d's rules (bin_index).
+__device__ __forceinline__ int pixel_cell(const med_args& A, int64_t i) {
+    const double la = A.lat_c[i];
+    if (!(la == la)) return -1;
+    if (A.use_elev_threshold && !(A.elev[i] >= A.min_elev)) return -1;
+    if (A.mask && A.mask[i]) return -1;
+    const double lo = A.lon_c[i];
+    const double xv = A.lon_wrap ? wrap180_shifted(lo) : lo;
+    const int bx = bin_index(A.ax, xv), by = bin_index(A.ay, la);
+    if (bx < 1 || bx > A.ax.nbin || by < 1 || by > A.ay.nbin) return -1;
+    return (by - 1) * A.nx + (bx - 1);
+}
+
+// order-preserving integer key of a float64 (NaN with the sign bit clear sorts above +inf)
+__device__ __forceinline__ unsigned long long elev_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double elev_of_key(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// One lane's 4 pixels as seen by the wave: the cell they share (-1: none valid, or `mixed` when they fall into
+// more than one cell) and how many are valid.
+struct lane_cells {
+    int c[kPPT];
+    int cell;
+    unsigned cnt;
+    bool mixed;
+};
+
+__device__ __forceinline__ void summarise(lane_cells& L) {
+    L.cell = -1;
+    L.cnt = 0;
+    L.mixed = false;
+#pragma unroll
+    for (int j = 0; j < kPPT; ++j) {
+        if (L.c[j] < 0) continue;
+        if (L.cell < 0) L.cell = L.c[j];
+        else if (L.c[j] != L.cell) L.mixed = true;
+        L.cnt += 1;
+    }
+    if (L.mixed) {
+        L.cell = -1;
+        L.cnt = 0;
+    }
+}
+
+// Runs of consecutive lanes with the same cell: for every lane the first lane of its run, and the number of
+// pixels of the run before this lane (excl) and in all of it (total).  Called by the whole wave.
+struct lane_run {
+    int head;
+    unsigned excl, total;
+};
+
+__device__ __forceinline__ lane_run run_of(int cell, unsigned cnt, int lane) {
+    unsigned incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    const int prev = __shfl_up(cell, 1);
+    const bool is_head = lane == 0 || prev != cell;
+    const unsigned long long heads = __ballot(is_head);
+    const unsigned long long upto = heads & (~0ull >> (63 - lane));
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+    lane_run r;
+    r.head = 63 - __clzll(upto);
+    const int last = above ? lane + __ffsll((long long)above) - 1 : 63;
+    const unsigned before_run = __shfl(incl, r.head) - __shfl(cnt, r.head);
+    r.excl = incl - cnt - before_run;
+    r.total = __shfl(incl, last) - before_run;
+    return r;
+}
+
+__global__ __launch_bounds__(kBlock) void k_med_count(med_args A, int* __restrict__ cell_of,
+                                                     unsigned* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT;
+    // whole waves stay in the loop together (the shuffles need every lane)
+    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride) {
+        const int64_t i0 = base + (int64_t)lane * kPPT;
+        lane_cells L;
+#pragma unroll
+        for (int j = 0; j < kPPT; ++j) {
+            const int64_t i = i0 + j;
+            L.c[j] = i < A.n ? pixel_cell(A, i) : -1;
+            if (i < A.n) cell_of[i] = L.c[j];
+        }
+        summarise(L);
+        if (L.mixed) {
+#pragma unroll
+            for (int j = 0; j < kPPT; ++j)
+                if (L.c[j] >= 0) atomicAdd(&count[L.c[j]], 1u);
+        }
+        const lane_run r = run_of(L.cell, L.cnt, lane);
+        if (r.head == lane && L.cell >= 0 && r.total) atomicAdd(&count[L.cell], r.total);
+    }
+}
+
+// ---- exclusive scan of the counts: offset[0..cells], offset[cells] = number of binned pixels ----
+constexpr int kScanTile = kBlock * kScanItems;
+
+__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* sWave, unsigned& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) sWave[wave] = incl;
+    __syncthreads();
+    unsigned before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) {
+        before += w < wave ? sWave[w] : 0u;
+        total += sWave[w];
+    }
+    __syncthreads();
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_med_scan_sums(const unsigned* __restrict__ count, int64_t cells,
+                                                         unsigned* __restrict__ bsum) {
+    __shared__ unsigned sWave[kBlock / 64];
+    const int64_t b0 = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+    unsigned s = 0;
+#pragma unroll
+    for (int q = 0; q < kScanItems; ++q) s += b0 + q < cells ? count[b0 + q] : 0u;
+    unsigned total;
+    (void)block_excl_scan(s, sWave, total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// one workgroup: exclusive scan of the nb block sums in place, bsum[nb] = the grand total
+__global__ __launch_bounds__(kBlock) void k_med_scan_blocks(unsigned* __restrict__ bsum, int nb) {
+    __shared__ unsigned sWave[kBlock / 64];
+    unsigned carry = 0;
+    for (int base = 0; base < nb; base += kBlock) {
+        const int i = base + threadIdx.x;
+        const unsigned v = i < nb ? bsum[i] : 0u;
+        unsigned total;
+        const unsigned e = block_excl_scan(v, sWave, total);
+        if (i < nb) bsum[i] = carry + e;
+        carry += total;
+    }
+    if (threadIdx.x == 0) bsum[nb] = carry;
+}
+
+__global__ __launch_bounds__(kBlock) void k_med_scan_apply(const unsigned* __restrict__ count, int64_t cells,
+                                                          const unsigned* __restrict__ bsum, int nb,
+                                                          unsigned* __restrict__ offset) {
+    __shared__ unsigned sWave[kBlock / 64];
+    const int64_t b0 = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+    unsigned v[kScanItems], s = 0;
+#pragma unroll
+    for (int q = 0; q < kScanItems; ++q) {
+        v[q] = b0 + q < cells ? count[b0 + q] : 0u;
+        s += v[q];
+    }
+    unsigned total;
+    unsigned run = bsum[blockIdx.x] + block_excl_scan(s, sWave, total);
+#pragma unroll
+    for (int q = 0; q < kScanItems; ++q) {
+        if (b0 + q < cells) offset[b0 + q] = run;
+        run += v[q];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) offset[cells] = bsum[nb];
+}
+
+// ---- scatter of the keys ----
+template <typename IMG_T>
+__global__ __launch_bounds__(kBlock) void k_med_fill(med_args A, const int* __restrict__ cell_of,
+                                                    const unsigned* __restrict__ offset, unsigned* __restrict__ cursor,
+                                                    uint16_t* __restrict__ keys16, unsigned long long* __restrict__ keys64) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT;
+    const IMG_T* img = static_cast<const IMG_T*>(A.img);
+    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride) {
+        const int64_t i0 = base + (int64_t)lane * kPPT;
+        lane_cells L;
+#pragma unroll
+        for (int j = 0; j < kPPT; ++j) L.c[j] = i0 + j < A.n ? cell_of[i0 + j] : -1;
+        summarise(L);
+        const lane_run r = run_of(L.cell, L.cnt, lane);
+        unsigned first = 0;
+        if (r.head == lane && L.cell >= 0 && r.total) first = offset[L.cell] + atomicAdd(&cursor[L.cell], r.total);
+        first = __shfl(first, r.head) + r.excl;
+#pragma unroll
+        for (int j = 0; j < kPPT; ++j) {
+            const int c = L.c[j];
+            if (c < 0) continue;
+            unsigned pos;
+            if (L.mixed) pos = offset[c] + atomicAdd(&cursor[c], 1u);
+            else pos = first++;
+            const int64_t i = i0 + j;
+            for (int ch = 0; ch < A.nch; ++ch) keys16[(int64_t)ch * A.n + pos] = (uint16_t)img[i * A.nch + ch];
+            if (keys64) keys64[pos] = elev_key(A.elev[i]);
+        }
+    }
+}
+
+// ---- outputs ----
+struct out_args {
+    int nx, ny, nch, img_dtype, has_elev;
+    int64_t n;                          // pixels: stride of the key planes
+    const unsigned* count;
+    const unsigned* offset;
+    const uint16_t* keys16;
+    const unsigned long long* keys64;
+    double* median;
+    void* out_img;
+    uint8_t* out_mask;
+    double* out_count;
+};
+
+__device__ __forceinline__ int64_t out_index(const out_args& O, int cell) {
+    const int iy = cell / O.nx, ix = cell - iy * O.nx;
+    return (int64_t)(O.ny - 1 - iy) * O.nx + ix;      // rows north to south (resample.py:339-349)
+}
+
+// plane p < nch: channel p; p == nch: elevation.  lo / hi: the keys of ranks (n-1)/2 and n/2.
+__device__ __forceinline__ void put_median(const out_args& O, int cell, int p, unsigned long long lo, unsigned long long hi) {
+    const int64_t o = out_index(O, cell);
+    if (p == O.nch) {
+        O.median[o * (O.nch + 1) + p] = (elev_of_key(lo) + elev_of_key(hi)) / 2.0;
+        return;
+    }
+    const double v = ((double)lo + (double)hi) / 2.0;       // np.median: mean of the middle pair in float64
+    O.median[o * (O.nch + 1) + p] = v;
+    if (O.out_img) {
+        if (O.img_dtype == 1) static_cast<uint8_t*>(O.out_img)[o * O.nch + p] = (uint8_t)rint(v);     // half to even
+        else static_cast<uint16_t*>(O.out_img)[o * O.nch + p] = (uint16_t)rint(v);
+    }
+}
+
+__device__ __forceinline__ int plane_bits(const out_args& O, int p) {
+    return p == O.nch ? 64 : (O.img_dtype == 1 ? 8 : 16);
+}
+
+__device__ __forceinline__ unsigned long long load_key(const out_args& O, int p, unsigned pos) {
+    return p == O.nch ? O.keys64[pos] : (unsigned long long)O.keys16[(int64_t)p * O.n + pos];
+}
+
+// ascending bitonic sort of one key per lane over the 64 lanes of a wave
+template <typename K>
+__device__ __forceinline__ K wave_sort(K key, int lane) {
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const K other = __shfl_xor(key, j);
+            const bool keep_min = ((lane & j) == 0) == ((lane & k) == 0);
+            key = keep_min ? (other < key ? other : key) : (other > key ? other : key);
+        }
+    }
+    return key;
+}
+
+struct tier_counters {
+    unsigned n_medium, n_large, max_large, pad;
+};
+
+// One wave per cell: every cell's count and mask, NaN / 0 for empty ones, the median of cells of <= 64 keys; the
+// others are appended to the medium or large list.
+__global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restrict__ medium, int* __restrict__ large,
+                                                     tier_counters* __restrict__ tiers) {
+    const int lane = threadIdx.x & 63;
+    const int64_t cells = (int64_t)O.nx * O.ny;
+    const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
+    const int nplane = O.nch + (O.has_elev ? 1 : 0);
+    for (int64_t w = blockIdx.x * (int64_t)(kBlock / 64) + (threadIdx.x >> 6); w < cells; w += waves) {
+        const int cell = (int)w;
+        const unsigned cnt = O.count[cell];
+        const int64_t o = out_index(O, cell);
+        if (lane == 0) {
+            if (O.out_count) O.out_count[o] = (double)cnt;
+            if (O.out_mask) O.out_mask[o] = cnt == 0;
+            if (cnt == 0 || !O.has_elev) O.median[o * (O.nch + 1) + O.nch] = NAN;
+            if (cnt == 0) {
+                for (int p = 0; p < O.nch; ++p) {
+                    O.median[o * (O.nch + 1) + p] = NAN;
+                    if (O.out_img) {
+                        if (O.img_dtype == 1) static_cast<uint8_t*>(O.out_img)[o * O.nch + p] = 0;
+                        else static_cast<uint16_t*>(O.out_img)[o * O.nch + p] = 0;
+                    }
+                }
+            } else if (cnt > (unsigned)kSmallMax) {
+                if (cnt > (unsigned)kLargeMin) {
+                    large[atomicAdd(&tiers->n_large, 1u)] = cell;
+                    atomicMax(&tiers->max_large, cnt);
+                } else {
+                    medium[atomicAdd(&tiers->n_medium, 1u)] = cell;
+                }
+            }
+        }
+        if (cnt == 0 || cnt > (unsigned)kSmallMax) continue;       // (wave-uniform)
+        const unsigned off = O.offset[cell];
+        const int klo = (int)(cnt - 1) / 2, khi = (int)cnt / 2;
+        for (int p = 0; p < nplane; ++p) {
+            unsigned long long lo, hi;
+            if (p == O.nch) {
+                const unsigned long long key = wave_sort(lane < (int)cnt ? O.keys64[off + lane] : ~0ull, lane);
+                lo = __shfl(key, klo);
+                hi = __shfl(key, khi);
+            } else {
+                const unsigned key = wave_sort(lane < (int)cnt ? (unsigned)O.keys16[(int64_t)p * O.n + off + lane] : ~0u, lane);
+                lo = (unsigned)__shfl(key, klo);
+                hi = (unsigned)__shfl(key, khi);
+            }
+            if (lane == 0) put_median(O, cell, p, lo, hi);
+        }
+    }
+}
+
+// Adds 1 to h[d] for every active lane; lanes that agree on d (the common case: the high digits of a cell's
+// keys are mostly equal) share one LDS / global atomic.  Called by the whole wave.
+__device__ __forceinline__ void hist_add(unsigned* h, int d, bool act, int lane) {
+    const unsigned long long m = __ballot(act);
+    if (!m) return;
+    const int first = __builtin_ctzll(m);
+    const int d0 = __shfl(d, first);
+    if (__ballot(act && d == d0) == m) {
+        if (lane == first) atomicAdd(&h[d0], (unsigned)__popcll(m));
+    } else if (act) {
+        atomicAdd(&h[d], 1u);
+    }
+}
+
+// The digit of the k-th smallest key (0-based) from a 256-bin histogram; run by one wave.
+// below: keys in lower bins; in_bin: keys in the digit's bin.
+struct digit_pick {
+    int d;
+    unsigned below, in_bin;
+};
+
+__device__ __forceinline__ digit_pick find_digit(const unsigned* h, unsigned k, int lane) {
+    unsigned b[4], s = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        b[q] = h[4 * lane + q];
+        s += b[q];
+    }
+    unsigned incl = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    const unsigned excl = incl - s;
+    const unsigned long long hit = __ballot(excl <= k && k < incl);
+    const int src = hit ? __builtin_ctzll(hit) : 63;
+    digit_pick r = {0, 0, 0};
+    unsigned acc = excl;
+    bool found = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (!found && k < acc + b[q]) {
+            r.d = 4 * lane + q;
+            r.below = acc;
+            r.in_bin = b[q];
+            found = true;
+        }
+        acc += b[q];
+    }
+    r.d = __shfl(r.d, src);
+    r.below = __shfl(r.below, src);
+    r.in_bin = __shfl(r.in_bin, src);
+    return r;
+}
+
+// does `key` share the digits above bit `shift + 8` with `prefix`?
+__device__ __forceinline__ bool prefix_match(unsigned long long key, unsigned long long prefix, int shift) {
+    return shift + 8 >= 64 || (key >> (shift + 8)) == (prefix >> (shift + 8));
+}
+
+// One workgroup per cell of 65 .. kLargeMin keys: radix select of k_lo per plane in LDS.
+__global__ __launch_bounds__(kBlock) void k_med_medium(out_args O, const int* __restrict__ medium) {
+    __shared__ unsigned sHist[256];
+    __shared__ digit_pick sPick;
+    __shared__ unsigned long long sMin;
+    const int lane = threadIdx.x & 63;
+    const int cell = medium[blockIdx.x];
+    const unsigned cnt = O.count[cell], off = O.offset[cell];
+    const unsigned klo = (cnt - 1) / 2, khi = cnt / 2;
+    const int nplane = O.nch + (O.has_elev ? 1 : 0);
+    for (int p = 0; p < nplane; ++p) {
+        unsigned long long prefix = 0;
+        unsigned k = klo, less = 0, eq = 0;
+        for (int shift = plane_bits(O, p) - 8; shift >= 0; shift -= 8) {
+            sHist[threadIdx.x] = 0;
+            __syncthreads();
+            for (unsigned b = 0; b < cnt; b += kBlock) {
+                const unsigned i = b + threadIdx.x;
+                const unsigned long long key = i < cnt ? load_key(O, p, off + i) : 0ull;
+                hist_add(sHist, (int)((key >> shift) & 255), i < cnt && prefix_match(key, prefix, shift), lane);
+            }
+            __syncthreads();
+            if (threadIdx.x < 64) {
+                const digit_pick r = find_digit(sHist, k, lane);
+                if (lane == 0) sPick = r;
+            }
+            __syncthreads();
+            const digit_pick r = sPick;
+            prefix |= (unsigned long long)r.d << shift;
+            k -= r.below;
+            less += r.below;
+            eq = r.in_bin;
+            __syncthreads();
+        }
+        unsigned long long hi = prefix;
+        if (khi >= less + eq) {
+            // the upper middle key is the smallest key above the lower one
+            if (threadIdx.x == 0) sMin = ~0ull;
+            __syncthreads();
+            unsigned long long m = ~0ull;
+            for (unsigned i = threadIdx.x; i < cnt; i += kBlock) {
+                const unsigned long long key = load_key(O, p, off + i);
+                if (key > prefix && key < m) m = key;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long t = __shfl_xor(m, o);
+                m = t < m ? t : m;
+            }
+            if (lane == 0) atomicMin(&sMin, m);
+            __syncthreads();
+            hi = sMin;
+        }
+        if (threadIdx.x == 0) put_median(O, cell, p, prefix, hi);
+        __syncthreads();
+    }
+}
+
+// ---- large tier: one plane at a time, one launch pair per digit ----
+struct large_state {
+    unsigned long long prefix, min_above;
+    unsigned k, less, eq, pad;
+};
+
+__global__ void k_med_large_init(const out_args O, const int* __restrict__ large, int n_large, large_state* __restrict__ st) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_large) return;
+    const unsigned cnt = O.count[large[l]];
+    large_state s;
+    s.prefix = 0;
+    s.min_above = ~0ull;
+    s.k = (cnt - 1) / 2;
+    s.less = s.eq = s.pad = 0;
+    st[l] = s;
+}
+
+// blockIdx.y: large cell, blockIdx.x: chunk of kChunk keys of its segment.  Digit histogram of the keys that match
+// the prefix so far, added into ghist[cell][256].
+__global__ __launch_bounds__(kBlock) void k_med_large_hist(const out_args O, const int* __restrict__ large, int p, int shift,
+                                                          const large_state* __restrict__ st, unsigned* __restrict__ ghist) {
+    __shared__ unsigned sHist[256];
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.y;
+    const int cell = large[l];
+    const unsigned cnt = O.count[cell], off = O.offset[cell];
+    const unsigned b0 = blockIdx.x * (unsigned)kChunk;
+    if (b0 >= cnt) return;                                          // (block-uniform)
+    const unsigned b1 = min(cnt, b0 + (unsigned)kChunk);
+    const unsigned long long prefix = st[l].prefix;
+    sHist[threadIdx.x] = 0;
+    __syncthreads();
+    for (unsigned b = b0; b < b1; b += kBlock) {
+        const unsigned i = b + threadIdx.x;
+        const unsigned long long key = i < b1 ? load_key(O, p, off + i) : 0ull;
+        hist_add(sHist, (int)((key >> shift) & 255), i < b1 && prefix_match(key, prefix, shift), lane);
+    }
+    __syncthreads();
+    const unsigned v = sHist[threadIdx.x];
+    if (v) atomicAdd(&ghist[(int64_t)l * 256 + threadIdx.x], v);
+}
+
+// one wave per large cell: pick the digit, advance the state, clear the histogram for the next pass
+__global__ __launch_bounds__(64) void k_med_large_digit(int shift, large_state* __restrict__ st, unsigned* __restrict__ ghist) {
+    const int lane = threadIdx.x;
+    const int l = blockIdx.x;
+    unsigned* h = ghist + (int64_t)l * 256;
+    const digit_pick r = find_digit(h, st[l].k, lane);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) h[4 * lane + q] = 0;
+    if (lane == 0) {
+        st[l].prefix |= (unsigned long long)r.d << shift;
+        st[l].k -= r.below;
+        st[l].less += r.below;
+        st[l].eq = r.in_bin;
+    }
+}
+
+// the smallest key above the selected one, where the upper middle key needs it
+__global__ __launch_bounds__(kBlock) void k_med_large_above(const out_args O, const int* __restrict__ large, int p,
+                                                           large_state* __restrict__ st) {
+    const int lane = threadIdx.x & 63;
+    const int l = blockIdx.y;
+    const unsigned cnt = O.count[large[l]], off = O.offset[large[l]];
+    const unsigned b0 = blockIdx.x * (unsigned)kChunk;
+    if (b0 >= cnt || cnt / 2 < st[l].less + st[l].eq) return;      // (block-uniform)
+    const unsigned b1 = min(cnt, b0 + (unsigned)kChunk);
+    const unsigned long long lo = st[l].prefix;
+    unsigned long long m = ~0ull;
+    for (unsigned i = b0 + threadIdx.x; i < b1; i += kBlock) {
+        const unsigned long long key = load_key(O, p, off + i);
+        if (key > lo && key < m) m = key;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long t = __shfl_xor(m, o);
+        m = t < m ? t : m;
+    }
+    if (lane == 0 && m != ~0ull) atomicMin(&st[l].min_above, m);
+}
+
+__global__ void k_med_large_put(const out_args O, const int* __restrict__ large, int n_large, int p,
+                                const large_state* __restrict__ st) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_large) return;
+    const int cell = large[l];
+    const unsigned cnt = O.count[cell];
+    const large_state s = st[l];
+    put_median(O, cell, p, s.prefix, cnt / 2 < s.less + s.eq ? s.prefix : s.min_above);
+}
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                     int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                     double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, double* median,
+                     void* out_img, uint8_t* out_mask, double* out_count) {
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && median, "NULL argument");
+    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, (int64_t)height * width < 2147483647LL, "frame too large for 32-bit pixel indices");
+    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
+    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    AMT_REQUIRE(ctx, (int64_t)xaxis->nbin * yaxis->nbin < 2147483647LL, "grid too large");
+    med_args A;
+    A.lat_c = lat_c;
+    A.lon_c = lon_c;
+    A.elev = elev;
+    A.img = img;
+    A.mask = center_mask;
+    A.n = (int64_t)height * width;
+    A.min_elev = min_elevation;
+    A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
+    A.lon_wrap = lon_wrap ? 1 : 0;
+    make_axis(xaxis, &A.ax);
+    make_axis(yaxis, &A.ay);
+    A.nx = xaxis->nbin;
+    A.ny = yaxis->nbin;
+    A.nch = nchan;
+    A.img_dtype = img_dtype;
+    const int64_t n = A.n, cells = (int64_t)A.nx * A.ny;
+    const int nb = (int)((cells + kScanTile - 1) / kScanTile);
+    const int64_t large_cap = n / (kLargeMin + 1) + 1;
+
+    // workspace: count, cursor [cells] | tier counters | offset [cells + 1] | block sums [nb + 1] | medium, large lists
+    // [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state [large_cap] and
+    // histograms [large_cap * 256]
+    size_t at = 0;
+    const size_t o_count = at;   at = align256(at + (size_t)2 * cells * sizeof(unsigned));
+    const size_t o_tiers = at;   at = align256(at + sizeof(tier_counters));
+    const size_t o_offset = at;  at = align256(at + (size_t)(cells + 1) * sizeof(unsigned));
+    const size_t o_bsum = at;    at = align256(at + (size_t)(nb + 1) * sizeof(unsigned));
+    const size_t o_medium = at;  at = align256(at + (size_t)cells * sizeof(int));
+    const size_t o_large = at;   at = align256(at + (size_t)cells * sizeof(int));
+    const size_t o_cellof = at;  at = align256(at + (size_t)n * sizeof(int));
+    const size_t o_keys16 = at;  at = align256(at + (size_t)nchan * n * sizeof(uint16_t));
+    const size_t o_keys64 = at;  at = align256(at + (elev ? (size_t)n * sizeof(unsigned long long) : 0));
+    const size_t o_state = at;   at = align256(at + (size_t)large_cap * sizeof(large_state));
+    const size_t o_ghist = at;   at = align256(at + (size_t)large_cap * 256 * sizeof(unsigned));
+    char* ws = static_cast<char*>(amt_workspace(ctx, at));
+    if (ws == nullptr) {
+        ctx->last_error = "amt_median_frame: workspace allocation failed";
+        return AMT_ENOMEM;
+    }
+    unsigned* count = reinterpret_cast<unsigned*>(ws + o_count);
+    unsigned* cursor = count + cells;
+    tier_counters* tiers = reinterpret_cast<tier_counters*>(ws + o_tiers);
+    unsigned* offset = reinterpret_cast<unsigned*>(ws + o_offset);
+    unsigned* bsum = reinterpret_cast<unsigned*>(ws + o_bsum);
+    int* medium = reinterpret_cast<int*>(ws + o_medium);
+    int* large = reinterpret_cast<int*>(ws + o_large);
+    int* cell_of = reinterpret_cast<int*>(ws + o_cellof);
+    uint16_t* keys16 = reinterpret_cast<uint16_t*>(ws + o_keys16);
+    unsigned long long* keys64 = elev ? reinterpret_cast<unsigned long long*>(ws + o_keys64) : nullptr;
+    large_state* state = reinterpret_cast<large_state*>(ws + o_state);
+    unsigned* ghist = reinterpret_cast<unsigned*>(ws + o_ghist);
+
+    // count, cursor and the tier counters are adjacent: one clear
+    AMT_HIP(ctx, hipMemsetAsync(ws, 0, o_offset, ctx->stream));
+    hipLaunchKernelGGL(k_med_count, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of, count);
+    hipLaunchKernelGGL(k_med_scan_sums, dim3(nb), dim3(kBlock), 0, ctx->stream, count, cells, bsum);
+    hipLaunchKernelGGL(k_med_scan_blocks, dim3(1), dim3(kBlock), 0, ctx->stream, bsum, nb);
+    hipLaunchKernelGGL(k_med_scan_apply, dim3(nb), dim3(kBlock), 0, ctx->stream, count, cells, bsum, nb, offset);
+    if (nchan == 0 || img_dtype == 1)
+        hipLaunchKernelGGL(k_med_fill<uint8_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of,
+                           offset, cursor, keys16, keys64);
+    else
+        hipLaunchKernelGGL(k_med_fill<uint16_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of,
+                           offset, cursor, keys16, keys64);
+    out_args O;
+    O.nx = A.nx;
+    O.ny = A.ny;
+    O.nch = nchan;
+    O.img_dtype = img_dtype;
+    O.has_elev = elev != nullptr;
+    O.n = n;
+    O.count = count;
+    O.offset = offset;
+    O.keys16 = keys16;
+    O.keys64 = keys64;
+    O.median = median;
+    O.out_img = nchan ? out_img : nullptr;
+    O.out_mask = out_mask;
+    O.out_count = out_count;
+    hipLaunchKernelGGL(k_med_small, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, medium, large, tiers);
+    AMT_LAUNCH_CHECK(ctx);
+    // the one device -> host read: how many cells the two upper tiers have
+    tier_counters t;
+    AMT_HIP(ctx, hipMemcpyAsync(&t, tiers, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int nplane = nchan + (elev ? 1 : 0);
+    if (t.n_medium > 0)
+        hipLaunchKernelGGL(k_med_medium, dim3(t.n_medium), dim3(kBlock), 0, ctx->stream, O, medium);
+    if (t.n_large > 0) {
+        AMT_REQUIRE(ctx, (int64_t)t.n_large <= large_cap, "internal: large-cell count out of range");
+        const int nl = (int)t.n_large;
+        const dim3 chunks((t.max_large + kChunk - 1) / kChunk, (unsigned)nl);
+        const dim3 per_cell((nl + kBlock - 1) / kBlock);
+        AMT_HIP(ctx, hipMemsetAsync(ghist, 0, (size_t)nl * 256 * sizeof(unsigned), ctx->stream));
+        for (int p = 0; p < nplane; ++p) {
+            hipLaunchKernelGGL(k_med_large_init, per_cell, dim3(kBlock), 0, ctx->stream, O, large, nl, state);
+            const int bits = p == nchan ? 64 : (img_dtype == 1 ? 8 : 16);
+            for (int shift = bits - 8; shift >= 0; shift -= 8) {
+                hipLaunchKernelGGL(k_med_large_hist, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, shift, state, ghist);
+                hipLaunchKernelGGL(k_med_large_digit, dim3(nl), dim3(64), 0, ctx->stream, shift, state, ghist);
+            }
+            hipLaunchKernelGGL(k_med_large_above, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, state);
+            hipLaunchKernelGGL(k_med_large_put, per_cell, dim3(kBlock), 0, ctx->stream, O, large, nl, p, state);
+        }
+    }
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+}  // extern "C"

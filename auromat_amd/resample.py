@@ -1,7 +1,7 @@
 """
 Resampling of mappings onto a regular latitude/longitude grid (plate carree), relative to either
 geodetic or MLat/MLT coordinates — mirror of the reference's auromat/resample.py for the
-``method='mean'`` binning.
+``method='mean'`` binning, plus the median binning the reference names but never built (:func:`resampleMedian`).
 
 Host side: the grid definition (global alignment, pole / discontinuity handling, bin edges —
 a few hundred scalars per frame, reference resample.py:159-299).  Device side: bin assignment with
@@ -184,6 +184,85 @@ def resample(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=No
                                  mayOverlap=mappingOrCollection.mayOverlap)
     raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
                      format(type(mappingOrCollection)))
+
+
+def resampleMedian(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+    """
+    Like :func:`resample` with ``method='mean'``, but every channel of a cell (image channels and elevation) is the
+    median of the cell's pixels instead of their mean: ``np.median`` of the same pixel set the mean bins, the mean of the
+    two middle values in float64 for an even count, then the image's rounding half to even and cast (reference
+    resample.py:128-136).  A star, a city light or a hot pixel among a cell's pixels moves its mean but not its median.
+    Same grid, box, pole and date-line rules as :func:`resample`; empty cells are masked where the mean masks them.
+
+    The reference names ``method='median'`` and raises NotImplementedError for it (resample.py:353-357);
+    ``resample(..., method='median')`` keeps doing so, as a drop-in for the reference must, so the median has a name of
+    its own.  It reads ``mapping.frame()`` like ``method='nearest'`` (any mapping with a device frame, MIRACLE and
+    direction arrays included) and runs on the device (``amt_median_frame``).
+
+    :param mappingOrCollection:
+    :param None|number|tuple pxPerDeg: tuple (latPxPerDeg, lonPxPerDeg) or a number if both are the same
+    :param None|number arcsecPerPx: spherical resolution, used to approximate pxPerDeg; has precedence
+    :param None|bool containsPole: specify True|False to skip the pole check
+    :rtype: a subclass of BaseMapping or MappingCollection
+    """
+    def doResample(mapping):
+        global last_plan
+        last_plan = None
+        pole = mapping.containsPole if containsPole is None else containsPole
+        ppd = plateCarreeResolution(mapping.boundingBox, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+        res = resample_frame_median(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd,
+                                    mapping.containsDiscontinuity, pole, outline=mapping.outline if pole else None)
+        img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
+        elevation = ma.masked_invalid(res['median'][:, :, -1], copy=False) if res['has_elev'] else None
+        return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
+
+    if isinstance(mappingOrCollection, BaseMapping):
+        return doResample(mappingOrCollection)
+    elif isinstance(mappingOrCollection, MappingCollection):
+        return MappingCollection([doResample(m) for m in mappingOrCollection.mappings], mappingOrCollection.identifier,
+                                 mayOverlap=mappingOrCollection.mayOverlap)
+    raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
+                     format(type(mappingOrCollection)))
+
+
+def resampleMedianMLatMLT(mapping, **kw):
+    """:func:`resampleMedian` such that MLat/MLT become regular grids (the path of :func:`resampleMLatMLT` through the
+    SM mapping: ``convertMappingToSM`` -> ``resampleMedian`` -> ``convertSMMappingToGeo``).
+
+    See :func:`resampleMedian` for parameters.
+    """
+    return convertSMMappingToGeo(resampleMedian(convertMappingToSM(mapping), **kw))
+
+
+def resample_frame_median(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,
+                          min_elevation=None, outline=None):
+    """
+    Median binning of a device-resident frame on the grid :func:`resample_frame` lays out (``amt_median_frame``).
+
+    :param outline: the mapping's outline, needed for the pole box as in :func:`resample_frame`
+    :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], median (ny,nx,C+1), img (ny,nx,C), mask (ny,nx),
+                  count (ny,nx), has_elev)
+    """
+    import torch
+    ctx = fd.ctx
+    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
+                                               min_elevation, outline, None)
+    xaxis, yaxis = grid.axes(ctx)
+    nch = fd.nchan
+    median = ctx.empty((grid.ny, grid.nx, nch + 1))
+    img = ctx.empty((grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd.img_dtype_code != 2 else torch.int16)
+    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
+    count = ctx.empty((grid.ny, grid.nx))
+    min_el = float('-inf') if min_elevation is None else float(min_elevation)
+    ctx.call('amt_median_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code or 1, nch,
+             ptr(fd.center_mask), fd.height, fd.width, min_el, C.byref(xaxis), C.byref(yaxis), lon_wrap, ptr(median),
+             ptr(img) if nch else None, ptr(mask), ptr(count))
+    out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
+               contains_discontinuity=bool(containsDiscontinuity), altitude=altitude)
+    out.update(grid_coordinates(out))
+    out.update(median=to_host(median), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
+               mask=to_host(mask).astype(bool), count=to_host(count))
+    return out
 
 
 def fixedGrid(pxPerDeg, latMin, latMax, lonMin, lonMax):
@@ -542,26 +621,10 @@ def nearest_indices(ctx, lat_c, lon_c, elev, center_mask, height, width, min_ele
     return index
 
 
-def resample_frame(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,
-                   min_elevation=None, keep_on_device=False, method='mean', outline=None, shard=None):
-    """
-    ``_resample`` + ``_resampleCenterData(method='mean')`` + the image finalisation of ``resample``
-    (reference resample.py:119-136,159-279,301-351) on a device-resident frame.
-
-    :param FrameData fd: centre lat/lon, elevation (optional), image and masks in HBM
-    :param min_elevation: fuse ``maskedByElevation(min_elevation)`` into the binning pass (the frame's
-                          own centre mask is applied in addition)
-    :param method: 'mean' (binning) or 'nearest' (closest pixel centre; needs `outline`)
-    :param outline: (n,2) [lat,lon] polygon of the mapping (``BaseMapping.outline``) for the interpolating methods:
-                    grid cells with a corner outside it are masked (reference resample.py:246-259)
-    :param shard: `fd` holds a band of rows of a frame whose other bands are on other ranks (see
-                  :func:`auromat_amd.sequence.resample_frame_sharded`): shard.box combines the reduction of the rotated
-                  corners, shard.acc sums the integer accumulators over the ranks before the means are taken
-    :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mean (ny,nx,C+1), img (ny,nx,C),
-                  mask (ny,nx), count (ny,nx) ['mean' only], has_elev)
-    """
+def _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole, min_elevation, outline, shard):
+    """The output grid of a device-resident frame and the centre coordinates to bin (reference resample.py:159-241):
+    ``(grid, lat_c, lon_c, lon_wrap)``, the pole rotated out of the data or the longitudes out of the date line."""
     import torch
-    _check_method(method)
     ctx = fd.ctx
     latMin, latMax = boundingBox.latSouth, boundingBox.latNorth
     lonMin, lonMax = boundingBox.lonWest, boundingBox.lonEast
@@ -597,7 +660,32 @@ def resample_frame(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=Fa
         lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
         lon_wrap = 1
 
-    grid = cached_grid(pxPerDeg, latMin, latMax, lonMin, lonMax)
+    return cached_grid(pxPerDeg, latMin, latMax, lonMin, lonMax), lat_c, lon_c, lon_wrap
+
+
+def resample_frame(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,
+                   min_elevation=None, keep_on_device=False, method='mean', outline=None, shard=None):
+    """
+    ``_resample`` + ``_resampleCenterData(method='mean')`` + the image finalisation of ``resample``
+    (reference resample.py:119-136,159-279,301-351) on a device-resident frame.
+
+    :param FrameData fd: centre lat/lon, elevation (optional), image and masks in HBM
+    :param min_elevation: fuse ``maskedByElevation(min_elevation)`` into the binning pass (the frame's
+                          own centre mask is applied in addition)
+    :param method: 'mean' (binning) or 'nearest' (closest pixel centre; needs `outline`)
+    :param outline: (n,2) [lat,lon] polygon of the mapping (``BaseMapping.outline``) for the interpolating methods:
+                    grid cells with a corner outside it are masked (reference resample.py:246-259)
+    :param shard: `fd` holds a band of rows of a frame whose other bands are on other ranks (see
+                  :func:`auromat_amd.sequence.resample_frame_sharded`): shard.box combines the reduction of the rotated
+                  corners, shard.acc sums the integer accumulators over the ranks before the means are taken
+    :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mean (ny,nx,C+1), img (ny,nx,C),
+                  mask (ny,nx), count (ny,nx) ['mean' only], has_elev)
+    """
+    import torch
+    _check_method(method)
+    ctx = fd.ctx
+    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
+                                               min_elevation, outline, shard)
     xaxis, yaxis = grid.axes(ctx)
     nch = fd.nchan
     if method in ('nearest', 'linear', 'cubic'):

@@ -38,7 +38,8 @@ extern "C" {
  *    sequence runner (amt_run_frame.img_host, amt_run_result.uploaded_bytes, amt_georef_image_rows, amt_malloc_host / amt_free_host)
  *    amt_pipe_launch_dirs_many, amt_host_threads, AMT_EDOMAIN; retired: amt_linear_gather, amt_cubic_gradients, amt_cubic_gather
  *    (round 6) */
-#define AMT_ABI_VERSION 6
+/* 7: amt_median_frame (median binning, auromat_amd.resample.resampleMedian) */
+#define AMT_ABI_VERSION 7
 
 #define AMT_OK 0
 #define AMT_EINVAL (-1)   /* bad argument (NULL pointer, negative size, unsupported dtype ...) */
@@ -486,6 +487,19 @@ int amt_bin_frame_finalize_window(amt_ctx* ctx, const uint64_t* acc, int32_t acc
                                   int32_t off_x, int32_t off_y, int32_t nx, int32_t ny, int32_t nchan,
                                   int32_t img_dtype, double* mean, void* out_img, uint8_t* out_mask,
                                   double* out_count);
+/* Median binning (auromat_amd.resample.resampleMedian; the reference names method='median' and leaves it unbuilt,
+ * auromat/resample.py:353-357): the pixels amt_bin_frame would bin into cell (ix, iy) — same arguments, same membership —
+ * and for every cell and channel np.median of their values: the order statistic of rank (n-1)/2, or for an even count n
+ * the float64 mean (a + b) / 2 of ranks n/2 - 1 and n/2.  Exact and deterministic for any cell size.  Channel c < nchan:
+ * the image channel; channel nchan: the elevation (NaN when elev is NULL).
+ * Outputs in the layout of amt_bin_frame_finalize (rows north to south): median (ny, nx, nchan+1) float64, NaN where
+ * empty; out_img (optional): (ny, nx, nchan) of img_dtype, round-half-even of the median (0 where empty); out_mask
+ * (optional): 1 where empty; out_count (optional): pixels per cell.  Uses the context's workspace (about 6 + 2*nchan
+ * (+8 with elev) bytes per pixel + 16 per cell).  Synchronises once: it reads how many cells hold more than 64 pixels. */
+int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                     int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                     double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, double* median,
+                     void* out_img, uint8_t* out_mask, double* out_count);
 /* Same for float accumulators of amt_hist2d_accumulate: mean[k] = sums[k]/count, NaN where empty,
  * transposed + flipped to (ny, nx, nweights). */
 int amt_hist2d_finalize_mean(amt_ctx* ctx, const double* count, const double* const* sums, int32_t nweights,
