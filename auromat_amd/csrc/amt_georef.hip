@@ -1,18 +1,19 @@
-// Fused per-frame georeferencing kernel (reference auromat/mapping/astrometry.py:49-212).
+// Fused per-frame georeferencing kernel k_georef_rows (reference auromat/mapping/astrometry.py:49-212): row marching,
+// no workgroup barriers.
 //
-// One workgroup owns a TW x TH tile of pixels:
-//   phase 1  every corner of the tile ((TW+1) x (TH+1), one thread per corner, strided):
-//            WCS pixel -> unit direction -> ray/ellipsoid hit -> [LDS: P, d]
-//            -> J2000->GEO rotation -> Bowring -> lat/lon (deg) written by the tile that owns the corner
-//   phase 2  every pixel of the tile: centre point = mean of the 4 corner hits read back from LDS
-//            (fast mode) or its own ray cast (exact mode) -> lat/lon, elevation, optional MLat/MLT;
-//            leaves a "valid above the elevation threshold" flag per pixel in LDS
-//   phase 3  (bounding box requested) every corner again, from registers: a corner counts when one of
-//            its in-tile neighbour centres is valid -> min/max of lat/lon -> one partial per workgroup
-// Each ray is cast once per tile (1.08x redundancy at 64x16), nothing but the final arrays touches
-// HBM, and all per-frame constants travel as kernel arguments (SGPRs), not through LDS.
+// One WAVE owns a strip of 63 pixel columns (64 corner columns, one per lane) and marches down
+// `rows` pixel rows.  Each lane casts the ray of its corner column once per corner row and keeps the
+// previous row's hit in registers; a pixel's four corners are then (own previous, own current) plus
+// the same two of lane+1, fetched with DPP wave shifts.  Redundancy: 64/63 horizontally, (rows+1)/rows
+// vertically.  The bounding box is accumulated from the corner side with a one-row delay (a corner
+// row is final once the centre row below it has been classified).
 //
-// The kernel is FP64-VALU bound; see the fm:: helpers in amt_common.h for the arithmetic budget.
+// All arithmetic is in fx:: (amt_common.h): explicit fma / mul / add in a fixed order, so that every variant of the
+// kernel gives the same bits (the two execution plans of the pipeline are tested for bit-identical grids).
+// What round 2 measured about this kernel (profiles/NOTEBOOK_r1-r3.md 4.1a): it is not FP64-issue bound any more; straight-line
+// "speculative" and per-phase wave-uniform variants of the row step (no NaN presets, no exec-mask regions) were
+// built and were SLOWER than this plain divergent form (register pressure, code size), so they were dropped.
+//
 // Algorithmic HBM bytes per frame: 16 B per corner + 24 B per pixel written, nothing read
 // ("WCS-fused" row of SURVEY.md §8d); with caller-supplied directions +24 B per corner read.
 #include "amt_common.h"
@@ -110,22 +111,18 @@ struct georef_args {
     double* mlt_c;
     double* bbox_partials;   // [nblocks][8] or NULL
     double bbox_min_elev;
-    // fused binning (row-marching kernel only)
+    // fused binning
     axis_dev bax, bay;       // full descriptions (rare paths: right-most edge rule, wrong first guess)
     axis_lin bxl, byl;       // what the common path needs: 5 scalars per axis
     const void* bin_img;
     unsigned long long* bin_acc;
     int bin_lon_wrap, bin_magnetic;
-    int item_order, chunk_stride;       // amt_georef_out.item_order; stride of the interleaved chunk order
-    // item_order 4 (two fronts): rows of work items [front_split, n) — the Earth side — are visited from front_split
-    // on, rows [0, front_split) — the sky side — from front_split - 1 backwards, front_e of the one for every front_s
-    // of the other; front_flip mirrors the frame first (Earth above the limb)
-    int front_split, front_e, front_s, front_flip;
+    int item_order;                     // amt_georef_out.item_order: 1 = rows of work items top to bottom, 2 = bottom to top
     // rows of work items that cannot see the shell (sky_bands(): rows [0, sky_top_end) and [sky_bottom_begin, n)); their
     // waves write NaN and cast no ray
     int sky_top_end, sky_bottom_begin;
     int bin_pole;                       // amt_georef_out.bin_pole: bin (and box) in the coordinates rotated by 90 deg about x
-    int row_layout;                     // amt_georef_out.row_layout: 0 = contiguous rows, 1 = strip-padded rows (k_georef_rows only)
+    int row_layout;                     // amt_georef_out.row_layout: 0 = contiguous rows, 1 = strip-padded rows
     pole_consts pole;
     bin_event* bin_events;      // optional list for on-edge pixels (amt_georef_out.bin_events)
     unsigned int* bin_event_count;
@@ -196,176 +193,6 @@ __device__ __forceinline__ void block_reduce8(double (&v)[8], double* __restrict
     }
 }
 
-template <int TW, int TH, bool FAST, bool DIRS_IN, bool MAG>
-__global__ __launch_bounds__(kThreads) void k_georef(georef_args A) {
-    constexpr int CW = TW + 1, CH = TH + 1, NC = CW * CH;
-    constexpr int NCI = (NC + kThreads - 1) / kThreads;       // corner iterations per thread
-    constexpr int NPI = TW * TH / kThreads;                   // pixel iterations per thread
-    static_assert(TW * TH % kThreads == 0, "tile must be a multiple of the workgroup");
-    __shared__ double sP[3][NC];
-    __shared__ double sD[3][NC];
-    __shared__ unsigned char sValid[TW * TH];
-    __shared__ double sRed[8][kThreads / 64];
-
-    const int tiles_x = (A.width + TW - 1) / TW;
-    const int tile_y = blockIdx.x / tiles_x;
-    const int tile_x = blockIdx.x - tile_y * tiles_x;
-    const int x0 = tile_x * TW, y0 = tile_y * TH;
-    const int W1 = A.width + 1;
-    const bool want_bbox = A.bbox_partials != nullptr;
-
-    // ---- phase 1: corners -------------------------------------------------------------
-    double cla[NCI], clo[NCI];
-#pragma unroll
-    for (int it = 0; it < NCI; ++it) {
-        const int c = threadIdx.x + it * kThreads;
-        cla[it] = NAN;
-        clo[it] = NAN;
-        if (c >= NC) continue;
-        const int cy = c / CW, cx = c - cy * CW;
-        const int gx = x0 + cx, gy = y0 + cy;
-        vec3 d = {NAN, NAN, NAN}, p = {NAN, NAN, NAN};
-        if (gx <= A.width && gy <= A.height) {
-            const int64_t gi = (int64_t)gy * W1 + gx;
-            if (DIRS_IN) {
-                d.x = A.dirs_in[3 * gi];
-                d.y = A.dirs_in[3 * gi + 1];
-                d.z = A.dirs_in[3 * gi + 2];
-            } else {
-                d = tan_direction_fast(A.wcs, gx - 0.5, gy - 0.5);
-            }
-            const double t = ray_param_fast(A.ray, d);
-            const bool hit = t == t;
-            const bool owner = (cx < TW || gx == A.width) && (cy < TH || gy == A.height);
-            double la = NAN, lo = NAN;
-            if (hit) {
-                p = ray_point(A.ray, d, t);
-                const vec3 g = mul(A.m_geo, p);
-                ecef_to_geodetic_deg_fast(A.bw, g.x, g.y, g.z, la, lo);
-            }
-            cla[it] = la;
-            clo[it] = lo;
-            if (owner) {
-                if (A.lat) A.lat[gi] = la;
-                if (A.lon) A.lon[gi] = lo;
-                if (MAG && A.mlat) {
-                    double ml = NAN, mt = NAN;
-                    if (hit) sm_to_mlat_mlt_fast(mul(A.m_sm, p), ml, mt);
-                    A.mlat[gi] = ml;
-                    A.mlt[gi] = mt;
-                }
-            }
-        }
-        sP[0][c] = p.x;
-        sP[1][c] = p.y;
-        sP[2][c] = p.z;
-        if (FAST) {
-            sD[0][c] = d.x;
-            sD[1][c] = d.y;
-            sD[2][c] = d.z;
-        }
-    }
-    __syncthreads();
-
-    // ---- phase 2: centres ---------------------------------------------------------------
-    double nvalid = 0;
-#pragma unroll
-    for (int it = 0; it < NPI; ++it) {
-        const int q = threadIdx.x + it * kThreads;
-        const int py = q / TW, px = q - py * TW;
-        const int gx = x0 + px, gy = y0 + py;
-        bool valid = false;
-        if (gx < A.width && gy < A.height) {
-            const int c00 = py * CW + px, c01 = c00 + 1, c10 = c00 + CW, c11 = c10 + 1;
-            vec3 p, d;
-            bool corners_ok = true;
-            if (FAST) {
-                // reference astrometry.py:154-160: ((c00 + c01) + c11) + c10, then /4
-                p.x = (((sP[0][c00] + sP[0][c01]) + sP[0][c11]) + sP[0][c10]) * 0.25;
-                p.y = (((sP[1][c00] + sP[1][c01]) + sP[1][c11]) + sP[1][c10]) * 0.25;
-                p.z = (((sP[2][c00] + sP[2][c01]) + sP[2][c11]) + sP[2][c10]) * 0.25;
-                d.x = (((sD[0][c00] + sD[0][c01]) + sD[0][c11]) + sD[0][c10]) * 0.25;
-                d.y = (((sD[1][c00] + sD[1][c01]) + sD[1][c11]) + sD[1][c10]) * 0.25;
-                d.z = (((sD[2][c00] + sD[2][c01]) + sD[2][c11]) + sD[2][c10]) * 0.25;
-            } else {
-                d = tan_direction_fast(A.wcs, (double)gx, (double)gy);
-                p = ray_point(A.ray, d, ray_param_fast(A.ray, d));
-                if (want_bbox) {
-                    // after sanitisation a centre also needs its 4 corners (reference mapping.py:1093-1101)
-                    const double s4 = (sP[0][c00] + sP[0][c01]) + (sP[0][c10] + sP[0][c11]);
-                    corners_ok = s4 == s4;
-                }
-            }
-            const int64_t gi = (int64_t)gy * A.width + gx;
-            double la = NAN, lo = NAN, el = NAN, ml = NAN, mt = NAN;
-            if (p.x == p.x) {
-                const vec3 g = mul(A.m_geo, p);
-                ecef_to_geodetic_deg_fast(A.bw, g.x, g.y, g.z, la, lo);
-                // reference astrometry.py:200-212, utils.py:33-46: 90 - angle(-d, P/|P|) = asin(-d.P/|P|)
-                double c = -(d.x * p.x + d.y * p.y + d.z * p.z) * fm::rsqrt(dot(p, p));
-                c = fmin(1.0, fmax(-1.0, c));
-                el = fm::asin_deg(c);
-                if (MAG && A.mlat_c) sm_to_mlat_mlt_fast(mul(A.m_sm, p), ml, mt);
-            }
-            if (A.lat_c) A.lat_c[gi] = la;
-            if (A.lon_c) A.lon_c[gi] = lo;
-            if (A.elev) A.elev[gi] = el;
-            if (MAG && A.mlat_c) {
-                A.mlat_c[gi] = ml;
-                A.mlt_c[gi] = mt;
-            }
-            valid = (el >= A.bbox_min_elev) && corners_ok;
-        }
-        if (want_bbox) {
-            sValid[q] = valid ? 1 : 0;
-            nvalid += valid ? 1.0 : 0.0;
-        }
-    }
-
-    // ---- phase 3: bounding box of the corners that keep a valid neighbour centre ----------------
-    // (reference mapping.py:845-864 maskedByElevation + 1063-1125 sanitisation + 693-743 boundingBox)
-    if (want_bbox) {
-        __syncthreads();
-        double v[8] = {kInf, -kInf, kInf, -kInf, kInf, -kInf, nvalid, 0};
-#pragma unroll
-        for (int it = 0; it < NCI; ++it) {
-            const int c = threadIdx.x + it * kThreads;
-            if (c >= NC) continue;
-            const int cy = c / CW, cx = c - cy * CW;
-            bool keep = false;
-            if (cy > 0 && cx > 0) keep |= sValid[(cy - 1) * TW + cx - 1] != 0;
-            if (cy > 0 && cx < TW) keep |= sValid[(cy - 1) * TW + cx] != 0;
-            if (cy < TH && cx > 0) keep |= sValid[cy * TW + cx - 1] != 0;
-            if (cy < TH && cx < TW) keep |= sValid[cy * TW + cx] != 0;
-            const double la = cla[it], lo = clo[it];
-            if (keep && la == la) {
-                v[0] = fmin(v[0], la);
-                v[1] = fmax(v[1], la);
-                v[2] = fmin(v[2], lo);
-                v[3] = fmax(v[3], lo);
-                if (lo > 0) v[4] = fmin(v[4], lo); else v[5] = fmax(v[5], lo);
-            }
-        }
-        block_reduce8<kThreads>(v, A.bbox_partials + (int64_t)blockIdx.x * 8, sRed);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Row-marching variant: no workgroup barriers.
-//
-// One WAVE owns a strip of 63 pixel columns (64 corner columns, one per lane) and marches down
-// `rows` pixel rows.  Each lane casts the ray of its corner column once per corner row and keeps the
-// previous row's hit in registers; a pixel's four corners are then (own previous, own current) plus
-// the same two of lane+1, fetched with DPP wave shifts.  Redundancy: 64/63 horizontally, (rows+1)/rows
-// vertically.  The bounding box is accumulated from the corner side with a one-row delay (a corner
-// row is final once the centre row below it has been classified).
-//
-// All arithmetic is in fx:: (amt_common.h): explicit fma / mul / add in a fixed order, so that every variant of the
-// kernel gives the same bits (the two execution plans of the pipeline are tested for bit-identical grids).
-// What round 2 measured about this kernel (profiles/NOTEBOOK_r1-r3.md 4.1a): it is not FP64-issue bound any more; straight-line
-// "speculative" and per-phase wave-uniform variants of the row step (no NaN presets, no exec-mask regions) were
-// built and were SLOWER than this plain divergent form (register pressure, code size), so they were dropped.
-// ------------------------------------------------------------------------------------------
 constexpr int kDppWaveShl1 = 0x130;   // lane i <- lane i+1
 constexpr int kDppWaveShr1 = 0x138;   // lane i <- lane i-1
 
@@ -494,25 +321,6 @@ constexpr int kBinW = 8, kBinCells = kBinW * kBinW;
 #ifndef AMT_ROWS_MIN_WAVES_MAGONLY
 #define AMT_ROWS_MIN_WAVES_MAGONLY 4
 #endif
-// item_order 4: the c-th row of work items in dispatch order -> its row of chunks.  The launch works on two fronts that
-// start at the limb and move apart: the Earth side (VALU-bound rows) and the sky side (rows that only store NaN), so that
-// both kinds are in flight together for most of the launch while each front keeps writing neighbouring rows (an order
-// that scatters the rows in flight over the whole frame, item_order 3, costs the stores their locality: a frame of sky
-// alone takes 113 instead of 96 us).  A bijection of [0, n) for any split in [0, n] and e, s >= 1.
-__host__ __device__ inline int two_front_chunk(int c, int n, int split, int e, int s, int flip) {
-    const int n_e = n - split, n_s = split;
-    const int full = min(n_e / e, n_s / s), per = e + s;
-    int chunk;
-    if (c < full * per) {
-        const int q = c / per, r = c - q * per;
-        chunk = r < e ? split + q * e + r : split - 1 - (q * s + (r - e));
-    } else {
-        const int r = c - full * per, rem_e = n_e - full * e;
-        chunk = r < rem_e ? split + full * e + r : split - 1 - (full * s + (r - rem_e));
-    }
-    return flip ? n - 1 - chunk : chunk;
-}
-
 template <bool FAST, bool DIRS_IN, int SECOND, int BIN>
 __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGONLY : (SECOND >= 2 ? AMT_ROWS_MIN_WAVES_POLE : (SECOND == 1 && BIN ? AMT_ROWS_MIN_WAVES_MAG : (BIN ? AMT_ROWS_MIN_WAVES_BIN : AMT_ROWS_MIN_WAVES)))) void k_georef_rows(georef_batch B, int rows_per_chunk, int strips_x,
                                                            int n_items, int n_frames) {
@@ -580,8 +388,6 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
     chunk = item / strips_x;
     strip = item - chunk * strips_x;
     if (A.item_order == 2) chunk = chunks_y - 1 - chunk;
-    if (A.item_order == 3) chunk = (int)(((long long)chunk * A.chunk_stride) % chunks_y);
-    if (A.item_order == 4) chunk = two_front_chunk(chunk, chunks_y, A.front_split, A.front_e, A.front_s, A.front_flip);
     const int x0 = strip * 63, y0 = chunk * rows_per_chunk;
     const int rows = min(rows_per_chunk, A.height - y0);
     const int gx = x0 + lane;
@@ -1290,7 +1096,6 @@ __global__ __launch_bounds__(kThreads) void k_bbox_fold(const double* __restrict
     block_reduce8<kThreads>(v, out + (int64_t)blockIdx.x * 8, sRed);
 }
 
-constexpr int kTW = 64, kTH = 8;
 constexpr int kFoldBlocks = 64;
 
 // The folds of up to kMaxBatch frames in one launch per stage (grid: blocks x frames; two launches behind a launch of three
@@ -1329,15 +1134,6 @@ __global__ __launch_bounds__(kThreads) void k_bbox_fold_batch(fold_batch Bf, int
 struct launch_events {
     hipEvent_t start, stop;
 };
-
-template <bool FAST, bool DIRS_IN>
-void launch_variant(amt_ctx* ctx, const georef_args& A, dim3 grid, bool mag, launch_events ev) {
-    const dim3 block(kThreads);
-    if (mag)
-        hipExtLaunchKernelGGL((k_georef<kTW, kTH, FAST, DIRS_IN, true>), grid, block, 0, ctx->stream, ev.start, ev.stop, 0, A);
-    else
-        hipExtLaunchKernelGGL((k_georef<kTW, kTH, FAST, DIRS_IN, false>), grid, block, 0, ctx->stream, ev.start, ev.stop, 0, A);
-}
 
 // second: 0 ... 4 as the kernel's SECOND
 template <bool FAST, bool DIRS_IN, int BIN>
@@ -1426,10 +1222,10 @@ __global__ __launch_bounds__(kThreads) void k_coarse_bbox(georef_args A, int str
     block_reduce8<kThreads>(v, partials + (int64_t)blockIdx.x * 8, sRed);
 }
 
-// amt_georef_out.item_order = 0: towards which side of the frame the nadir (the direction of the Earth's centre)
-// lies.  In-plane direction of the TAN projection of -cam: native vector v = rot^T d, intermediate coordinates
-// proportional to (v_y, -v_x) (no division by v_z, so it also works when the nadir is behind the image plane),
-// pixel offsets by the inverse CD matrix.
+// amt_georef_out.item_order automatic (any value but 1 and 2): towards which side of the frame the nadir (the direction
+// of the Earth's centre) lies.  In-plane direction of the TAN projection of -cam: native vector v = rot^T d, intermediate
+// coordinates proportional to (v_y, -v_x) (no division by v_z, so it also works when the nadir is behind the image
+// plane), pixel offsets by the inverse CD matrix.
 int nadir_side(const amt_frame_params* p) {
     const double d[3] = {-p->cam[0], -p->cam[1], -p->cam[2]};
     const double* r = p->rot;
@@ -1442,72 +1238,19 @@ int nadir_side(const amt_frame_params* p) {
     return (std::fabs(py) >= std::fabs(px) && py > 0) ? 2 : 1;
 }
 
-int forced_order_env() {
-    static const int forced_order = [] {
-        const char* e = std::getenv("AMT_ITEM_ORDER");
-        return e ? std::atoi(e) : 0;
-    }();
-    return forced_order;
-}
-
-// items (waves) of the row-marching launch / tiles of the tile kernel, and the rows per chunk
+// items (waves) of the row-marching launch, and the rows per chunk
 struct launch_shape {
-    bool use_tiles;
-    int rows_per_chunk, tiles_x, tiles_y, strips_x, chunks_y;
+    int rows_per_chunk, strips_x, chunks_y;
     int64_t n_items;
 };
 
 launch_shape shape_of(const amt_frame_params* p) {
-    // kernel selection: row-marching waves (default) or LDS tiles (AMT_GEOREF_KERNEL=tile), for A/B runs
-    static const bool use_tiles = [] {
-        const char* e = std::getenv("AMT_GEOREF_KERNEL");
-        return e != nullptr && std::strcmp(e, "tile") == 0;
-    }();
-    static const int rows_per_chunk = [] {
-        const char* e = std::getenv("AMT_GEOREF_ROWS");
-        const int v = e ? std::atoi(e) : 0;
-        return v > 0 ? v : 16;
-    }();
     launch_shape s;
-    s.use_tiles = use_tiles;
-    s.rows_per_chunk = rows_per_chunk;
-    s.tiles_x = (p->width + kTW - 1) / kTW;
-    s.tiles_y = (p->height + kTH - 1) / kTH;
+    s.rows_per_chunk = 16;
     s.strips_x = (p->width + 1 + 62) / 63;                       // 64 corner columns, 63 owned, per strip
-    s.chunks_y = (p->height + rows_per_chunk - 1) / rows_per_chunk;
-    s.n_items = use_tiles ? (int64_t)s.tiles_x * s.tiles_y : (int64_t)s.strips_x * s.chunks_y;
+    s.chunks_y = (p->height + s.rows_per_chunk - 1) / s.rows_per_chunk;
+    s.n_items = (int64_t)s.strips_x * s.chunks_y;
     return s;
-}
-
-// Stride s of the interleaved chunk order (item_order 3): rows of work items are visited in the order (k * s) mod n,
-// s coprime to n and close to n / golden ratio, so that any stretch of the launch samples the whole frame evenly.
-int interleave_stride(int n) {
-    if (n < 3) return 1;
-    auto gcd = [](int a, int b) {
-        while (b) {
-            const int t = a % b;
-            a = b;
-            b = t;
-        }
-        return a;
-    };
-    int s = (int)(n * 0.6180339887498949);
-    if (s < 1) s = 1;
-    while (gcd(s, n) != 1) ++s;
-    return s % n ? s % n : 1;
-}
-
-// Host copy of the kernel's hit test (shell_t >= 0) for the pixel-corner position (column x, row y).
-bool ray_hits_host(const affine_cam& c, const shell_ray& e, double x, double y) {
-    const double px = x + c.cx, py = y + c.cy;
-    const double ux = c.u0[0] + px * c.ux[0] + py * c.uy[0], uy = c.u0[1] + px * c.ux[1] + py * c.uy[1],
-                 uz = c.u0[2] + px * c.ux[2] + py * c.uy[2];
-    const double uu = ux * ux + uy * uy + uz * uz;
-    const double ku = ux * e.kx + uy * e.ky + uz * e.kz, uo = ux * e.ox + uy * e.oy + uz * e.oz;
-    const double a2 = e.qd * ku * ku + e.qa * uu, nb = -(e.qa * uo + e.qd_ko * ku);
-    const double disc = nb * nb - a2 * e.c0;
-    if (!(disc >= 0)) return false;
-    return (nb + e.root_sign * std::sqrt(disc)) / a2 >= 0;
 }
 
 // Which rows of work items cannot see the shell?  A corner (x, y) hits when disc(x, y) >= 0 and the root is in front of
@@ -1667,49 +1410,6 @@ void elevation_bands(const georef_args& A, const launch_shape& sh, double min_el
     if (t == n) *top_end = n, *bottom_begin = n;          // nothing above the threshold in the frame
 }
 
-// item_order 4: where the limb cuts the frame's rows of work items.  The middle row of every chunk is probed in three
-// columns; when the chunks that see the Earth are one run that reaches the first or the last row of chunks and the sky
-// takes at least an eighth of the frame, the launch works on two fronts from the limb (see two_front_chunk), the
-// Earth's rows and the sky's in the proportion that lets both fronts finish together.  Returns false when the frame is
-// not of that kind (all Earth, all sky, Earth to the left or right, a whole disc in view): the caller keeps its order.
-bool two_front_plan(const georef_args& A, const launch_shape& sh, int* split, int* n_e, int* n_s, int* flip) {
-    const int n = sh.chunks_y;
-    if (n < 16) return false;
-    int first = n, last = -1;
-    for (int c = 0; c < n; ++c) {
-        const double y = std::min((double)A.height, (c + 0.5) * sh.rows_per_chunk);
-        int hits = 0;
-        for (int k = 1; k <= 3; ++k) hits += ray_hits_host(A.cam, A.sray, 0.25 * k * A.width, y) ? 1 : 0;
-        if (hits >= 2) {
-            first = std::min(first, c);
-            last = c;
-        }
-    }
-    if (last < 0) return false;
-    // (the conic section that bounds the hits is convex: per column they are one interval)
-    const int earth = last - first + 1, sky = n - earth;
-    if (sky < n / 8 || earth < n / 8) return false;
-    if (last == n - 1) {
-        *flip = 0, *split = first;
-    } else if (first == 0) {
-        *flip = 1, *split = n - 1 - last;       // in the mirrored frame the Earth's chunks are [split, n)
-    } else {
-        return false;
-    }
-    // an Earth row of items costs about 1.6 times a sky row (all-Earth frame 150 us, frame of sky 96 us); small whole
-    // numbers whose ratio is close to (earth : sky) chunks weighted that way
-    const double want = (double)earth / sky;        // Earth rows per sky row so that both fronts end together
-    int best_e = 1, best_s = 1;
-    double best = 1e9;
-    for (int e = 1; e <= 4; ++e)
-        for (int s2 = 1; s2 <= 4; ++s2) {
-            const double d = std::fabs(std::log(((double)e / s2) / want));
-            if (d < best) best = d, best_e = e, best_s = s2;
-        }
-    *n_e = best_e, *n_s = best_s;
-    return true;
-}
-
 // One frame of a launch, validated and with its kernel arguments assembled
 struct prepared_frame {
     georef_args A;
@@ -1719,7 +1419,6 @@ struct prepared_frame {
     const amt_georef_out* out;
     const amt_georef_tail* tail;
     double* fold;       // scratch of the first fold stage (behind the partials)
-    bool mag;
     int second;         // k_georef_rows' SECOND
     int bin;
 };
@@ -1773,12 +1472,7 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
     A.bin_events = nullptr;
     A.bin_event_count = nullptr;
     A.bin_event_cap = 0;
-    // AMT_ITEM_ORDER = 1, 2, 3, 4 overrides the order for A/B runs
-    const int forced_order = forced_order_env();
-    A.item_order = out->item_order >= 1 && out->item_order <= 3 ? out->item_order : (dirs ? 1 : nadir_side(p));
-    if (forced_order >= 1 && forced_order <= 4) A.item_order = forced_order;
-    A.chunk_stride = 1;
-    A.front_split = 0, A.front_e = A.front_s = 1, A.front_flip = 0;
+    A.item_order = out->item_order == 1 || out->item_order == 2 ? out->item_order : (dirs ? 1 : nadir_side(p));
     std::memset(&A.bax, 0, sizeof(A.bax));
     std::memset(&A.bay, 0, sizeof(A.bay));
     std::memset(&A.bxl, 0, sizeof(A.bxl));
@@ -1822,33 +1516,12 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
         A.bin_magnetic = 1;
     }
     const launch_shape sh = shape_of(p);
-    A.chunk_stride = interleave_stride(sh.chunks_y);
     A.sky_top_end = 0, A.sky_bottom_begin = sh.chunks_y;
-    static const bool no_sky_path = std::getenv("AMT_NO_SKY_PATH") != nullptr;      // A/B runs
-    if (dirs == nullptr && !sh.use_tiles && !no_sky_path) sky_bands(A, sh, &A.sky_top_end, &A.sky_bottom_begin);
-    // two fronts from the limb (item_order 4; AMT_ITEM_ORDER=4, AMT_FRONT_RATIO = "e:s" overrides the proportion of the two
-    // fronts).  Measured (profiles/r3/x_ab_two_front_order.txt): 135 / 168 us (georef only / fused, kernel alone) against
-    // 126 / 153 us for the side-first order — sky rows (stores only) and Earth rows (VALU-bound) in flight TOGETHER are
-    // slower than one after the other, at every proportion; an option for A/B runs, not the default.
-    if (dirs == nullptr && !sh.use_tiles && (forced_order_env() == 4 || out->item_order == 4)) {
-        int split = 0, fe = 1, fs = 1, flip = 0;
-        if (two_front_plan(A, sh, &split, &fe, &fs, &flip)) {
-            A.item_order = 4;
-            A.front_split = split, A.front_e = fe, A.front_s = fs, A.front_flip = flip;
-            static const char* ratio = std::getenv("AMT_FRONT_RATIO");
-            if (ratio != nullptr) {
-                int e2 = 0, s2 = 0;
-                if (std::sscanf(ratio, "%d:%d", &e2, &s2) == 2 && e2 >= 1 && s2 >= 1) A.front_e = e2, A.front_s = s2;
-            }
-        } else if (A.item_order == 4) {
-            A.item_order = nadir_side(p);
-        }
-    }
-    const bool use_tiles = sh.use_tiles;
+    if (dirs == nullptr) sky_bands(A, sh, &A.sky_top_end, &A.sky_bottom_begin);
     const int64_t n_items = sh.n_items;
     AMT_REQUIRE(ctx, n_items < (1ll << 31), "frame too large");
     // the row-marching kernel addresses its arrays with 32-bit byte offsets
-    AMT_REQUIRE(ctx, use_tiles || ((int64_t)p->width + 1) * ((int64_t)p->height + 1) * 8 < (1ll << 32),
+    AMT_REQUIRE(ctx, ((int64_t)p->width + 1) * ((int64_t)p->height + 1) * 8 < (1ll << 32),
                 "frame too large (more than 2^29 pixel corners)");
     A.bbox_partials = nullptr;
     double* fold = nullptr;
@@ -1866,9 +1539,7 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
         }
         fold = A.bbox_partials + n_items * 8;
     }
-    AMT_REQUIRE(ctx, !(bin && use_tiles), "fused binning is implemented by the row-marching kernel only");
     AMT_REQUIRE(ctx, out->row_layout == AMT_ROWS_CONTIGUOUS || out->row_layout == AMT_ROWS_STRIP_PADDED, "unknown row_layout");
-    AMT_REQUIRE(ctx, !(A.row_layout && use_tiles), "strip-padded rows are written by the row-marching kernel only");
     AMT_REQUIRE(ctx, !A.row_layout || ((int64_t)p->height + 1) * sh.strips_x * 512 < (1ll << 32),
                 "frame too large for strip-padded rows (32-bit byte offsets)");
     F->sh = sh;
@@ -1877,20 +1548,17 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
     F->out = out;
     F->tail = tail;
     F->fold = fold;
-    F->mag = out->mlat != nullptr || out->mlat_c != nullptr || A.bin_magnetic;
-    AMT_REQUIRE(ctx, !(A.bin_pole && use_tiles), "bin_pole is implemented by the row-marching kernel only");
+    const bool mag = out->mlat != nullptr || out->mlat_c != nullptr || A.bin_magnetic;
     // (bin_pole on a geodetic grid with MLat / MLT outputs: the SECOND = 3 variant with the rotated pair taken from (lat, lon))
-    F->second = A.bin_pole ? (F->mag ? 3 : 2) : (F->mag ? 1 : 0);
+    F->second = A.bin_pole ? (mag ? 3 : 2) : (mag ? 1 : 0);
     // MLat / MLT only (SECOND = 4): a (MLat, SM longitude) grid without a pole plan whose caller wants none of the four
-    // geodetic arrays — what resampleMLatMLT consumes (reference mapping.py:1519-1547); AMT_NO_MAG_ONLY=1: A/B runs
-    static const bool no_mag_only = std::getenv("AMT_NO_MAG_ONLY") != nullptr;
+    // geodetic arrays — what resampleMLatMLT consumes (reference mapping.py:1519-1547)
     const bool no_geo_out = !A.lat && !A.lon && !A.lat_c && !A.lon_c;
-    if (F->second == 1 && dirs == nullptr && !use_tiles && no_geo_out) {
+    if (F->second == 1 && dirs == nullptr && no_geo_out) {
         // fused binning on the MLat / MLT grid; without binning: the box in (MLat, SM longitude) (bin_magnetic alone), or
         // MLat / MLT arrays and no box at all (what BaseAstrometryMapping.mLatMlt asks for)
-        if (bin ? (A.bin_magnetic && !no_mag_only) : (A.bin_magnetic || (!out->bbox && !no_mag_only))) F->second = 4;
+        if (bin ? A.bin_magnetic : (A.bin_magnetic || !out->bbox)) F->second = 4;
     }
-    AMT_REQUIRE(ctx, bin || !A.bin_magnetic || F->second == 4, "bin_magnetic without bin_acc needs the row-marching kernel");
     F->bin = bin;
     return AMT_OK;
 }
@@ -1901,7 +1569,7 @@ int launch_prepared(amt_ctx* ctx, int n, prepared_frame* F) {
     AMT_REQUIRE(ctx, n >= 1 && n <= kMaxBatch, "bad batch size");
     bool together = n > 1;
     for (int i = 1; i < n && together; ++i)
-        together = !F[0].sh.use_tiles && F[i].p->width == F[0].p->width && F[i].p->height == F[0].p->height &&
+        together = F[i].p->width == F[0].p->width && F[i].p->height == F[0].p->height &&
                    F[i].p->fast_center == F[0].p->fast_center && F[i].second == F[0].second && F[i].bin == F[0].bin &&
                    (F[i].dirs != nullptr) == (F[0].dirs != nullptr);
     if (n > 1 && !together) {
@@ -1909,14 +1577,12 @@ int launch_prepared(amt_ctx* ctx, int n, prepared_frame* F) {
             if (int rc = launch_prepared(ctx, 1, F + i)) return rc;
         return AMT_OK;
     }
-    const georef_args& A = F[0].A;
     const amt_frame_params* p = F[0].p;
     const double* dirs = F[0].dirs;
     const launch_shape& sh = F[0].sh;
-    const bool use_tiles = sh.use_tiles, mag = F[0].mag;
     const int bin = F[0].bin, rows_per_chunk = sh.rows_per_chunk, strips_x = sh.strips_x;
     const int64_t n_items = sh.n_items;
-    const int64_t nblocks = use_tiles ? n_items : ((int64_t)n * n_items + kRowsThreads / 64 - 1) / (kRowsThreads / 64);
+    const int64_t nblocks = ((int64_t)n * n_items + kRowsThreads / 64 - 1) / (kRowsThreads / 64);
     AMT_REQUIRE(ctx, (int64_t)n * n_items < (1ll << 31), "launch too large");
     const dim3 grid((unsigned)nblocks);
     // events ride on the dispatch packet itself: the timing pair when this launch is sampled, otherwise the
@@ -1925,26 +1591,16 @@ int launch_prepared(amt_ctx* ctx, int n, prepared_frame* F) {
     amt_timing_pair(ctx, AMT_KERNEL_GEOREF, n, &ev.start, &ev.stop);
     for (int i = 0; i < n && ev.stop == nullptr; ++i)
         if (F[i].tail != nullptr && F[i].out->bbox) ev.stop = F[i].tail->kernel_done;
-    if (use_tiles) {
-        if (dirs) {
-            launch_variant<true, true>(ctx, A, grid, mag, ev);
-        } else if (p->fast_center) {
-            launch_variant<true, false>(ctx, A, grid, mag, ev);
-        } else {
-            launch_variant<false, false>(ctx, A, grid, mag, ev);
-        }
+    georef_batch B;
+    ctx->last_second = F[0].second, ctx->last_bin = bin, ctx->last_frames = n;
+    for (int i = 0; i < kMaxBatch; ++i) B.f[i] = F[i < n ? i : 0].A;
+    B.math = fx::make_math_table();
+    if (dirs) {
+        launch_rows<true, true>(ctx, B, n, grid, F[0].second, bin, rows_per_chunk, strips_x, (int)n_items, ev);
+    } else if (p->fast_center) {
+        launch_rows<true, false>(ctx, B, n, grid, F[0].second, bin, rows_per_chunk, strips_x, (int)n_items, ev);
     } else {
-        georef_batch B;
-        ctx->last_second = F[0].second, ctx->last_bin = bin, ctx->last_frames = n;
-        for (int i = 0; i < kMaxBatch; ++i) B.f[i] = F[i < n ? i : 0].A;
-        B.math = fx::make_math_table();
-        if (dirs) {
-            launch_rows<true, true>(ctx, B, n, grid, F[0].second, bin, rows_per_chunk, strips_x, (int)n_items, ev);
-        } else if (p->fast_center) {
-            launch_rows<true, false>(ctx, B, n, grid, F[0].second, bin, rows_per_chunk, strips_x, (int)n_items, ev);
-        } else {
-            launch_rows<false, false>(ctx, B, n, grid, F[0].second, bin, rows_per_chunk, strips_x, (int)n_items, ev);
-        }
+        launch_rows<false, false>(ctx, B, n, grid, F[0].second, bin, rows_per_chunk, strips_x, (int)n_items, ev);
     }
     AMT_LAUNCH_CHECK(ctx);
     // the folds: one launch per stage for all frames whose folds run on the same stream (the frame drivers of a context

@@ -790,9 +790,6 @@ def _shared_stream(device, role):
     import torch
     key = (str(device), role)
     if key not in _STREAMS:
-        if not _STREAMS:
-            # AMT_STREAM_SHIFT=n (A/B runs): n streams made first, which moves the ones that follow to other hardware queues
-            _STREAMS[('shift', '')] = [torch.cuda.Stream(device=device) for _ in range(int(os.environ.get('AMT_STREAM_SHIFT', '0')))]
         _STREAMS[key] = torch.cuda.Stream(device=device)
     return _STREAMS[key]
 
@@ -1194,7 +1191,7 @@ class SequencePipeline(object):
         (amt_pipe_finalize_many), the others (general path, no valid pixel) go one by one through :meth:`_finish`."""
         import torch
         nb = len(self.pipes)
-        if not self.single_pass or os.environ.get('AMT_SEQ_FINISH_MANY') == '0':      # (the switch: A/B runs)
+        if not self.single_pass:
             return [self._finish(k0 + i, keep_on_device) for i in range(n)]
         qs = [self.pipes[(k0 + i) % nb] for i in range(n)]
         ready = [q.fused_ready(self.pxPerDeg, self.magnetic) for q in qs]
@@ -1222,8 +1219,7 @@ class SequencePipeline(object):
         """Device-resident images, header dicts, one launch stream; the single-pass plan or, for RGB frames with fast centres on
         a geodetic grid, the two-pass plan: what amt_run_process covers."""
         q = self.pipes[0]
-        two_pass_ok = (not self.single_pass and self.nchan == 3 and self.fast and not self.magnetic and
-                       os.environ.get('AMT_SEQ_NATIVE_TWO_PASS', '1') != '0')
+        two_pass_ok = not self.single_pass and self.nchan == 3 and self.fast and not self.magnetic
         if not ((self.single_pass or two_pass_ok) and self.s_alt is None and frames):
             return False
         # (the checks of FramePipeline.is_resident_image, inlined: this runs for every frame of every call)

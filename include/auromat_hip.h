@@ -184,10 +184,9 @@ typedef struct amt_georef_out {
                                     * Without bin_acc: only that — the box in (MLat, SM longitude); lat, lon, lat_c, lon_c
                                     * must then be NULL (MLat / MLT-only mode without binning) */
     /* Scheduling hint, no effect on results: order in which the frame's work items (strips of 63 columns x 16
-     * rows, row-major) are dispatched.  1 = rows top to bottom, 2 = bottom to top, 3 = interleaved (rows of items in
-     * the order (k * s) mod n with s near n / golden ratio; measured 7 % slower than 1 / 2 for a kernel run alone, equal
-     * inside the pipeline); 0 = automatic: bottom to top when the nadir lies below the frame centre (camera model;
-     * top to bottom for caller-supplied directions).  Rays that miss the shell are cheap, hits are expensive;
+     * rows, row-major) are dispatched.  1 = rows top to bottom, 2 = bottom to top; 0 or any other value = automatic:
+     * bottom to top when the nadir lies below the frame centre (camera model; top to bottom for caller-supplied
+     * directions).  Rays that miss the shell are cheap, hits are expensive;
      * starting with the rows where the Earth is lets the cheap items fill the end of the launch (4-5 % shorter
      * kernel; when the Earth is to the left or right every row mixes both kinds anyway).  amt_georef_coarse_bbox
      * reports the side from actual hits (bbox[7]). */
@@ -220,7 +219,7 @@ typedef struct amt_georef_out {
      *                              that no other wave writes (a measured 8-12 % of the kernel's time: DESIGN.md 4.1).  The 64th
      *                              double of a strip (and columns beyond the frame in the last strip) is padding with
      *                              unspecified content.  amt_unpad_rows compacts an array into contiguous rows, bit for bit the
-     *                              array the contiguous layout gives.  Row-marching kernel only (not AMT_GEOREF_KERNEL=tile);
+     *                              array the contiguous layout gives;
      *                              the two-pass binning (amt_bin_frame) and every other consumer read contiguous rows. */
     int32_t row_layout;
     double altitude;

@@ -51,7 +51,7 @@ def oracle_resample(g, img, min_elev, ppd, alt=110):
     (253, 171, 'iss030', True),    # not a multiple of 4 / 63 / 16: scalar bin path, partial strips and chunks
     (61, 35, 'iss029', True),      # narrower than one strip
     (130, 97, 'iss030', False),    # exact centres
-    (64, 16, 'iss030', True),      # exactly one tile of the LDS variant
+    (64, 16, 'iss030', True),      # exactly one strip wide plus one column, one chunk high
 ])
 def test_awkward_sizes_vs_oracle(width, height, pointing, fast):
     from auromat_amd.pipeline import FramePipeline
@@ -377,7 +377,7 @@ def test_item_order_is_a_pure_scheduling_hint():
     pipe = FramePipeline(w, h)
     img = frame_image(w, h, seed=3)
     base = None
-    for order in (1, 0, 2, 7):                    # 0 and out of range: decided from the camera model
+    for order in (1, 0, 2, 3, 4, 7):              # any value but 1 and 2: decided from the camera model
         pipe._out.item_order = order
         res = pipe.run(hdr, 110, cam, t, img=img, fast=True, min_elevation=10, pxPerDeg=10, fuse=False)
         arrays = dict(pipe.host_arrays(), mean=res['mean'], count=res['count'])

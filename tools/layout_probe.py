@@ -1,6 +1,6 @@
 """Round 6: the frame kernel ALONE (no binning; amt_georef_frame / amt_georef_frame_dirs on the bench frame) with contiguous and with
 strip-padded output rows, same process, passes interleaved; launches back to back (no host synchronisation inside a pass).
-usage: [AMT_ITEM_ORDER=..] layout_probe.py"""
+usage: layout_probe.py"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
