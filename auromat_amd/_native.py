@@ -86,7 +86,7 @@ class PipeResult(C.Structure):
 class RunConfig(C.Structure):
     """amt_run_config"""
     _fields_ = [(k, C.c_int32) for k in ('width', 'height', 'img_dtype', 'fast_center', 'magnetic', 'batch', 'use_hints',
-                                         'n_slots', 'two_pass', 'reserved_')] + \
+                                         'n_slots', 'two_pass', 'statistic')] + \
                [(k, C.c_double) for k in ('altitude', 'min_elevation', 'lat_px_per_deg', 'lon_px_per_deg')] + \
                [('slots', C.POINTER(GeorefOut)), ('arcsec_per_px', C.c_double)]
 
@@ -107,7 +107,7 @@ class RunResult(C.Structure):
                 ('retried', C.c_int32), ('reserved2_', C.c_int32), ('uploaded_bytes', C.c_int64)]
 
 
-ABI_VERSION = 7          # include/auromat_hip.h AMT_ABI_VERSION
+ABI_VERSION = 8          # include/auromat_hip.h AMT_ABI_VERSION
 _I, _L, _D, _P = C.c_int, C.c_int64, C.c_double, C.c_void_p
 _SIGNATURES = {
     'amt_abi_version': ([], _I),
@@ -194,6 +194,8 @@ _SIGNATURES = {
     'amt_bin_frame_finalize_window': ([_P, _P] + [C.c_int32] * 8 + [_P, _P, _P, _P], _I),
     'amt_median_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                           C.POINTER(Axis), _I, _P, _P, _P, _P], _I),
+    'amt_median_frame_async': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                                C.POINTER(Axis), _I, _I, _P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
                            _P], _I),
     'amt_nearest_gather': ([_P, _P, _L, _P, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),

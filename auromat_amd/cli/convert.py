@@ -20,6 +20,9 @@ What differs, and why:
   reference's flag and default) every frame's px/deg follows from its own bounding box (``plateCarreeResolution``, the
   box-first plan); ``--px-per-deg N`` (an addition) fixes the grid instead.  With several GPUs (``torchrun --nproc-per-node N
   -m auromat_amd.cli.convert``) the frames are sharded over the ranks and every rank writes the files of its own frames.
+* ``--statistic median`` (an addition; needs ``--resample``) bins every cell by the median of its pixels instead of their
+  mean (:func:`auromat_amd.resample.resampleMedian` / ``resampleMedianMLatMLT``), through the same two routes; the files
+  are written exactly as mean grids are.
 """
 from __future__ import print_function
 
@@ -93,6 +96,9 @@ def getParser():
                                    'runs through the single-pass frame pipeline')
     resampleArgs.add_argument('--grid', help='The grid which will be regular after resampling. Default is MLat/MLT grid. '
                                              'Use geo for geographical grid.', default=Grid.mag, choices=[Grid.geo, Grid.mag])
+    resampleArgs.add_argument('--statistic', choices=['mean', 'median'], default='mean',
+                              help='How the pixels of a grid cell are combined, default mean; median is robust to stars, city '
+                                   'lights and hot pixels (needs --resample)')
     outputArgs = parser.add_argument_group('output')
     outputArgs.add_argument('--out', help='Output directory, by default the "converted" subdirectory of --data')
     outputArgs.add_argument('--overwrite', help='Overwrites existing files.', action='store_true')
@@ -125,6 +131,8 @@ def parseargs(argv=None):
         args.out = os.path.join(args.data, 'converted')
     if args.overwrite and args.skip:
         parser.error('only one of --overwrite and --skip is allowed')
+    if args.statistic == 'median' and not args.resample:
+        parser.error('--statistic median needs --resample')
     if args.withoutGeo and args.format == Format.netcdf:
         parser.error('--without-geo is only usable with --format cdf')
     if args.format == Format.cdf:
@@ -215,7 +223,7 @@ def extension(args):
 def convert_with_classes(args, frames, export):
     """Frame by frame through the mapping classes: the reference's flow, its resolution rule included."""
     from ..mapping.spacecraft import getMapping
-    from ..resample import resample, resampleMLatMLT
+    from ..resample import resample, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT
     for identifier, hdr, img_path in frames:
         path = target_path(args, identifier)
         if path is None:
@@ -225,8 +233,12 @@ def convert_with_classes(args, frames, export):
         if args.resample:
             if args.minElevation >= 0:
                 mapping = mapping.maskedByElevation(args.minElevation)
-            fn = resample if args.grid == Grid.geo else resampleMLatMLT
-            mapping = fn(mapping, arcsecPerPx=args.resolution)
+            if args.statistic == 'median':
+                fn = resampleMedian if args.grid == Grid.geo else resampleMedianMLatMLT
+                mapping = fn(mapping, **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
+            else:
+                fn = resample if args.grid == Grid.geo else resampleMLatMLT
+                mapping = fn(mapping, arcsecPerPx=args.resolution)
         print('storing', path)
         export(path, mapping)
 
@@ -235,7 +247,7 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
     """The resampled grid of one frame (host arrays of the few hundred KB the pipeline returns) as the mapping that
     ``resample`` / ``resampleMLatMLT`` would have returned: a GenericMapping in geodetic coordinates; a grid that is
     regular in (MLat, SM longitude) goes through SM -> GEO like ``convertSMMappingToGeo`` (reference
-    mapping.py:1549-1559)."""
+    mapping.py:1549-1559).  The elevation comes from the 'mean' block or, for median grids, the 'median' block."""
     from ..coordinates.transform import smToLatLon
     from ..mapping.mapping import GenericMapping
     lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
@@ -243,7 +255,8 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
         lat, lon = smToLatLon(lat, lon, t)
         lat_c, lon_c = smToLatLon(lat_c, lon_c, t)
     img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    return GenericMapping(lat, lon, lat_c, lon_c, ma.masked_invalid(res['mean'][:, :, -1]), altitude, img, cam, t, identifier)
+    block = res['mean'] if 'mean' in res else res['median']
+    return GenericMapping(lat, lon, lat_c, lon_c, ma.masked_invalid(block[:, :, -1]), altitude, img, cam, t, identifier)
 
 
 def host_snapshot(mapping, with_mag):
@@ -302,7 +315,7 @@ def convert_with_pipeline(args, frames, export):
                                altitude=args.altitude, fast=not args.exactCenters,
                                min_elevation=args.minElevation if args.minElevation >= 0 else None,
                                pxPerDeg=args.pxPerDeg or 10, magnetic=magnetic, keep_coordinates=False,
-                               arcsecPerPx=None if args.pxPerDeg else args.resolution)
+                               arcsecPerPx=None if args.pxPerDeg else args.resolution, statistic=args.statistic)
 
         def feed():
             # decoding a 12 Mpx JPEG takes ~100 ms of host time, the GPU 0.2 ms per frame: images are read ahead on a
@@ -346,7 +359,9 @@ def convert_with_pipeline(args, frames, export):
                     continue
                 host = dict(res)
                 host.update(grid_coordinates(res))
-                host.update(mean=to_host(res['mean']), img=to_host(res['img'], dtype=first.dtype), mask=to_host(res['mask']).astype(bool))
+                stat = 'median' if args.statistic == 'median' else 'mean'
+                host[stat] = to_host(res[stat])
+                host.update(img=to_host(res['img'], dtype=first.dtype), mask=to_host(res['mask']).astype(bool))
                 print('storing', path)
                 mapping = grid_mapping(host, cam, t, args.altitude, identifier, magnetic)
                 if writers is None:

@@ -15,6 +15,16 @@
 
 namespace amt_gl {
 
+// astropy Angle.wrap_at(180 deg), as auromat_amd/mapping/mapping.py wrap_at_180 computes it (reference
+// resample.py:212-218): into [-180, 180)
+inline double wrap_at_180(double v) {
+    const double wraps = std::floor((v + 180.0) / 360.0);
+    double a = v - wraps * 360.0;
+    if (a >= 180.0) a -= 360.0;
+    if (a < -180.0) a += 360.0;
+    return a;
+}
+
 struct linspace {
     double start, stop, step;
     int64_t n;

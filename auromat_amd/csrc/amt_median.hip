@@ -13,10 +13,15 @@
 //                  two for u16, eight for the elevation key)
 //   k_med_large_*  cells above kLargeMin: the same radix select over many workgroups per cell, digit histograms in
 //                  global memory (one launch pair per digit and plane)
+// amt_median_frame_async enqueues the same passes without reading anything back: one launch of k_med_medium_walk, whose
+// fixed grid walks the device-side list of medium cells, and the large tier as k_med_large_step (one launch per digit
+// position, all planes and large cells in it; the last workgroup to finish a cell's histogram picks the digit) and
+// k_med_large_last.  Each of them reads the tier sizes from device memory and returns at once when its tier is empty.
 // Both tiers select k_lo = (n-1)/2 and get k_hi = n/2 from the same pass: it is k_lo's value when the keys <= that
 // value are more than k_hi, else the smallest key above it (one more pass).  Even counts average the two in float64.
 #include "amt_common.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -47,6 +52,7 @@ struct med_args {
     double min_elev;
     int use_elev_threshold;
     int lon_wrap;
+    int lon_from_mlt;                   // lon_c holds MLT hours: SM longitude as convertMappingToSM computes it
     axis_dev ax, ay;
     int nx, ny, nch, img_dtype;
 };
@@ -58,7 +64,8 @@ __device__ __forceinline__ int pixel_cell(const med_args& A, int64_t i) {
     if (!(la == la)) return -1;
     if (A.use_elev_threshold && !(A.elev[i] >= A.min_elev)) return -1;
     if (A.mask && A.mask[i]) return -1;
-    const double lo = A.lon_c[i];
+    double lo = A.lon_c[i];
+    if (A.lon_from_mlt) lo = (lo - 12.0) / (24.0 / 360.0);     // mltToSmLon (mapping/mapping.py convertMappingToSM)
     const double xv = A.lon_wrap ? wrap180_shifted(lo) : lo;
     const int bx = bin_index(A.ax, xv), by = bin_index(A.ay, la);
     if (bx < 1 || bx > A.ax.nbin || by < 1 || by > A.ay.nbin) return -1;
@@ -319,9 +326,11 @@ struct tier_counters {
 };
 
 // One wave per cell: every cell's count and mask, NaN / 0 for empty ones, the median of cells of <= 64 keys; the
-// others are appended to the medium or large list.
+// others are appended to the medium or large list.  CLEAR (amt_median_frame_async): the wave that lists a large cell
+// also zeroes that cell's digit histograms and tickets (nplane * 256 + nplane words from `lclear` on).
+template <bool CLEAR>
 __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restrict__ medium, int* __restrict__ large,
-                                                     tier_counters* __restrict__ tiers) {
+                                                     tier_counters* __restrict__ tiers, unsigned* __restrict__ lclear) {
     const int lane = threadIdx.x & 63;
     const int64_t cells = (int64_t)O.nx * O.ny;
     const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
@@ -330,6 +339,7 @@ __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restric
         const int cell = (int)w;
         const unsigned cnt = O.count[cell];
         const int64_t o = out_index(O, cell);
+        int listed = -1;
         if (lane == 0) {
             if (O.out_count) O.out_count[o] = (double)cnt;
             if (O.out_mask) O.out_mask[o] = cnt == 0;
@@ -344,12 +354,18 @@ __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restric
                 }
             } else if (cnt > (unsigned)kSmallMax) {
                 if (cnt > (unsigned)kLargeMin) {
-                    large[atomicAdd(&tiers->n_large, 1u)] = cell;
+                    listed = (int)atomicAdd(&tiers->n_large, 1u);
+                    large[listed] = cell;
                     atomicMax(&tiers->max_large, cnt);
                 } else {
                     medium[atomicAdd(&tiers->n_medium, 1u)] = cell;
                 }
             }
+        }
+        if (CLEAR && cnt > (unsigned)kLargeMin) {                  // (wave-uniform)
+            listed = __shfl(listed, 0);
+            const int words = nplane * 257;
+            for (int q = lane; q < words; q += 64) lclear[(int64_t)listed * words + q] = 0u;
         }
         if (cnt == 0 || cnt > (unsigned)kSmallMax) continue;       // (wave-uniform)
         const unsigned off = O.offset[cell];
@@ -431,13 +447,10 @@ __device__ __forceinline__ bool prefix_match(unsigned long long key, unsigned lo
     return shift + 8 >= 64 || (key >> (shift + 8)) == (prefix >> (shift + 8));
 }
 
-// One workgroup per cell of 65 .. kLargeMin keys: radix select of k_lo per plane in LDS.
-__global__ __launch_bounds__(kBlock) void k_med_medium(out_args O, const int* __restrict__ medium) {
-    __shared__ unsigned sHist[256];
-    __shared__ digit_pick sPick;
-    __shared__ unsigned long long sMin;
+// Radix select of k_lo per plane in LDS for one cell, by the whole workgroup.
+__device__ __forceinline__ void medium_cell(const out_args& O, int cell, unsigned* sHist, digit_pick& sPick,
+                                            unsigned long long& sMin) {
     const int lane = threadIdx.x & 63;
-    const int cell = medium[blockIdx.x];
     const unsigned cnt = O.count[cell], off = O.offset[cell];
     const unsigned klo = (cnt - 1) / 2, khi = cnt / 2;
     const int nplane = O.nch + (O.has_elev ? 1 : 0);
@@ -487,6 +500,24 @@ __global__ __launch_bounds__(kBlock) void k_med_medium(out_args O, const int* __
         if (threadIdx.x == 0) put_median(O, cell, p, prefix, hi);
         __syncthreads();
     }
+}
+
+// One workgroup per cell of 65 .. kLargeMin keys.
+__global__ __launch_bounds__(kBlock) void k_med_medium(out_args O, const int* __restrict__ medium) {
+    __shared__ unsigned sHist[256];
+    __shared__ digit_pick sPick;
+    __shared__ unsigned long long sMin;
+    medium_cell(O, medium[blockIdx.x], sHist, sPick, sMin);
+}
+
+// The same over a fixed grid: the workgroups walk the list of medium cells, whose length they read from device memory.
+__global__ __launch_bounds__(kBlock) void k_med_medium_walk(out_args O, const int* __restrict__ medium,
+                                                           const tier_counters* __restrict__ tiers) {
+    __shared__ unsigned sHist[256];
+    __shared__ digit_pick sPick;
+    __shared__ unsigned long long sMin;
+    const unsigned n_medium = tiers->n_medium;
+    for (unsigned i = blockIdx.x; i < n_medium; i += gridDim.x) medium_cell(O, medium[i], sHist, sPick, sMin);
 }
 
 // ---- large tier: one plane at a time, one launch pair per digit ----
@@ -581,17 +612,170 @@ __global__ void k_med_large_put(const out_args O, const int* __restrict__ large,
     put_median(O, cell, p, s.prefix, cnt / 2 < s.less + s.eq ? s.prefix : s.min_above);
 }
 
+// ---- large tier without a read-back (amt_median_frame_async) ----
+// Per large cell l and plane p: a large_state, a 256-bin histogram and a ticket, in `lh` as l * nplane * 257 words:
+// the histograms of its planes, then their tickets (zeroed by k_med_small<true> when it lists the cell).  A fixed grid
+// of workgroups; each one takes chunks blockIdx.x, blockIdx.x + gridDim.x, ... of every large cell.  After adding its
+// share to a histogram a workgroup takes a ticket; the one that draws the last ticket reads the histogram, advances the
+// state and clears both for the next launch.  Nothing waits for another workgroup.
+
+// adds the LDS histogram to the global one, then: is this the last workgroup to do so? (block-uniform result)
+__device__ __forceinline__ bool flush_and_ticket(const unsigned* sHist, unsigned* h, unsigned* tick, bool* sLast) {
+    if (h != nullptr) {
+        const unsigned v = sHist[threadIdx.x];
+        if (v) atomicAdd(&h[threadIdx.x], v);
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) *sLast = atomicAdd(tick, 1u) == gridDim.x - 1;
+    __syncthreads();
+    const bool last = *sLast;
+    if (last) __threadfence();
+    return last;
+}
+
+// one launch per digit position `shift` (56, 48, ..., 0): the digit of every plane whose keys have one there
+__global__ __launch_bounds__(kBlock) void k_med_large_step(const out_args O, const int* __restrict__ large,
+                                                          const tier_counters* __restrict__ tiers, int shift,
+                                                          large_state* __restrict__ st, unsigned* __restrict__ lh) {
+    __shared__ unsigned sHist[256];
+    __shared__ digit_pick sPick;
+    __shared__ bool sLast;
+    const int lane = threadIdx.x & 63;
+    const unsigned n_large = tiers->n_large;
+    const int nplane = O.nch + (O.has_elev ? 1 : 0);
+    for (unsigned l = 0; l < n_large; ++l) {
+        const int cell = large[l];
+        const unsigned cnt = O.count[cell], off = O.offset[cell];
+        for (int p = 0; p < nplane; ++p) {
+            const int bits = plane_bits(O, p);
+            if (shift >= bits) continue;                                    // (uniform)
+            const bool first = shift == bits - 8;
+            large_state* s = st + (int64_t)l * nplane + p;
+            const unsigned long long prefix = first ? 0ull : s->prefix;
+            sHist[threadIdx.x] = 0;
+            __syncthreads();
+            for (unsigned b0 = blockIdx.x * (unsigned)kChunk; b0 < cnt; b0 += gridDim.x * (unsigned)kChunk) {
+                const unsigned b1 = min(cnt, b0 + (unsigned)kChunk);
+                for (unsigned b = b0; b < b1; b += kBlock) {
+                    const unsigned i = b + threadIdx.x;
+                    const unsigned long long key = i < b1 ? load_key(O, p, off + i) : 0ull;
+                    hist_add(sHist, (int)((key >> shift) & 255), i < b1 && prefix_match(key, prefix, shift), lane);
+                }
+            }
+            __syncthreads();
+            unsigned* h = lh + (int64_t)l * nplane * 257 + p * 256;
+            unsigned* tick = lh + (int64_t)l * nplane * 257 + nplane * 256 + p;
+            if (!flush_and_ticket(sHist, h, tick, &sLast)) continue;
+            // the last workgroup: the whole histogram, the digit, the state for the next position
+            sHist[threadIdx.x] = __hip_atomic_load(&h[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            h[threadIdx.x] = 0;
+            __syncthreads();
+            if (threadIdx.x < 64) {
+                const unsigned k = first ? (cnt - 1) / 2 : s->k;
+                const digit_pick r = find_digit(sHist, k, lane);
+                if (lane == 0) {
+                    large_state n;
+                    n.prefix = prefix | ((unsigned long long)r.d << shift);
+                    n.min_above = ~0ull;
+                    n.k = k - r.below;
+                    n.less = (first ? 0u : s->less) + r.below;
+                    n.eq = r.in_bin;
+                    n.pad = 0;
+                    *s = n;
+                    *tick = 0;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// after the last digit: the smallest key above the selected one where the upper middle key needs it, then the medians
+__global__ __launch_bounds__(kBlock) void k_med_large_last(const out_args O, const int* __restrict__ large,
+                                                          const tier_counters* __restrict__ tiers,
+                                                          large_state* __restrict__ st, unsigned* __restrict__ lh) {
+    __shared__ bool sLast;
+    __shared__ unsigned long long sMin;
+    const int lane = threadIdx.x & 63;
+    const unsigned n_large = tiers->n_large;
+    const int nplane = O.nch + (O.has_elev ? 1 : 0);
+    for (unsigned l = 0; l < n_large; ++l) {
+        const int cell = large[l];
+        const unsigned cnt = O.count[cell], off = O.offset[cell];
+        for (int p = 0; p < nplane; ++p) {
+            large_state* s = st + (int64_t)l * nplane + p;
+            const unsigned long long lo = s->prefix;
+            const bool need = cnt / 2 >= s->less + s->eq;
+            if (threadIdx.x == 0) sMin = ~0ull;
+            __syncthreads();
+            if (need) {
+                unsigned long long m = ~0ull;
+                for (unsigned b0 = blockIdx.x * (unsigned)kChunk; b0 < cnt; b0 += gridDim.x * (unsigned)kChunk) {
+                    const unsigned b1 = min(cnt, b0 + (unsigned)kChunk);
+                    for (unsigned i = b0 + threadIdx.x; i < b1; i += kBlock) {
+                        const unsigned long long key = load_key(O, p, off + i);
+                        if (key > lo && key < m) m = key;
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const unsigned long long t = __shfl_xor(m, o);
+                    m = t < m ? t : m;
+                }
+                if (lane == 0 && m != ~0ull) atomicMin(&sMin, m);
+                __syncthreads();
+                if (threadIdx.x == 0 && sMin != ~0ull) atomicMin(&s->min_above, sMin);
+            }
+            unsigned* tick = lh + (int64_t)l * nplane * 257 + nplane * 256 + p;
+            if (!flush_and_ticket(nullptr, nullptr, tick, &sLast)) continue;
+            if (threadIdx.x == 0) {
+                const unsigned long long hi =
+                    need ? __hip_atomic_load(&s->min_above, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : lo;
+                put_median(O, cell, p, lo, hi);
+                *tick = 0;
+            }
+            __syncthreads();
+        }
+    }
+}
+
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-}  // namespace
 
-extern "C" {
+// compute units of the context's device (queried once per device)
+int64_t amt_cu_count(amt_ctx* ctx) {
+    static int cus[64];
+    const int d = ctx->device;
+    if (d < 0 || d >= 64) return 256;
+    if (cus[d] <= 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || v <= 0) {
+            (void)hipGetLastError();
+            v = 256;
+        }
+        cus[d] = v;
+    }
+    return cus[d];
+}
 
-int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
-                     int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
-                     double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, double* median,
-                     void* out_img, uint8_t* out_mask, double* out_count) {
-    AMT_CHECK_CTX(ctx);
+// What both entry points share: the arguments, the workspace and every pass up to the small tier (k_med_small); the
+// two upper tiers are enqueued by the callers.
+struct median_pass {
+    out_args O;
+    int64_t n, cells, large_cap;
+    int nplane;
+    tier_counters* tiers;
+    int* medium;
+    int* large;
+    large_state* state;
+    unsigned* lh;                       // amt_median_frame: the histograms; the async pass: histograms and tickets
+};
+
+int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                 int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                 double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int lon_from_mlt,
+                 double* median, void* out_img, uint8_t* out_mask, double* out_count, bool async, median_pass* M) {
     AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && median, "NULL argument");
     AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
     AMT_REQUIRE(ctx, (int64_t)height * width < 2147483647LL, "frame too large for 32-bit pixel indices");
@@ -609,6 +793,7 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     A.min_elev = min_elevation;
     A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
     A.lon_wrap = lon_wrap ? 1 : 0;
+    A.lon_from_mlt = lon_from_mlt ? 1 : 0;
     make_axis(xaxis, &A.ax);
     make_axis(yaxis, &A.ay);
     A.nx = xaxis->nbin;
@@ -618,10 +803,15 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     const int64_t n = A.n, cells = (int64_t)A.nx * A.ny;
     const int nb = (int)((cells + kScanTile - 1) / kScanTile);
     const int64_t large_cap = n / (kLargeMin + 1) + 1;
+    const int nplane = nchan + (elev ? 1 : 0);
+    // large-tier state and histograms per large cell: one plane at a time (amt_median_frame) or all of them (async; with
+    // a ticket per plane)
+    const int64_t per_large = async ? nplane : 1;
+    const int64_t lh_words = async ? (int64_t)nplane * 257 : 256;
 
     // workspace: count, cursor [cells] | tier counters | offset [cells + 1] | block sums [nb + 1] | medium, large lists
-    // [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state [large_cap] and
-    // histograms [large_cap * 256]
+    // [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state [large_cap * per_large] and
+    // histograms [large_cap * lh_words]
     size_t at = 0;
     const size_t o_count = at;   at = align256(at + (size_t)2 * cells * sizeof(unsigned));
     const size_t o_tiers = at;   at = align256(at + sizeof(tier_counters));
@@ -632,8 +822,8 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     const size_t o_cellof = at;  at = align256(at + (size_t)n * sizeof(int));
     const size_t o_keys16 = at;  at = align256(at + (size_t)nchan * n * sizeof(uint16_t));
     const size_t o_keys64 = at;  at = align256(at + (elev ? (size_t)n * sizeof(unsigned long long) : 0));
-    const size_t o_state = at;   at = align256(at + (size_t)large_cap * sizeof(large_state));
-    const size_t o_ghist = at;   at = align256(at + (size_t)large_cap * 256 * sizeof(unsigned));
+    const size_t o_state = at;   at = align256(at + (size_t)(large_cap * per_large) * sizeof(large_state));
+    const size_t o_ghist = at;   at = align256(at + (size_t)(large_cap * lh_words) * sizeof(unsigned));
     char* ws = static_cast<char*>(amt_workspace(ctx, at));
     if (ws == nullptr) {
         ctx->last_error = "amt_median_frame: workspace allocation failed";
@@ -641,16 +831,17 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     }
     unsigned* count = reinterpret_cast<unsigned*>(ws + o_count);
     unsigned* cursor = count + cells;
-    tier_counters* tiers = reinterpret_cast<tier_counters*>(ws + o_tiers);
     unsigned* offset = reinterpret_cast<unsigned*>(ws + o_offset);
     unsigned* bsum = reinterpret_cast<unsigned*>(ws + o_bsum);
-    int* medium = reinterpret_cast<int*>(ws + o_medium);
-    int* large = reinterpret_cast<int*>(ws + o_large);
     int* cell_of = reinterpret_cast<int*>(ws + o_cellof);
     uint16_t* keys16 = reinterpret_cast<uint16_t*>(ws + o_keys16);
     unsigned long long* keys64 = elev ? reinterpret_cast<unsigned long long*>(ws + o_keys64) : nullptr;
-    large_state* state = reinterpret_cast<large_state*>(ws + o_state);
-    unsigned* ghist = reinterpret_cast<unsigned*>(ws + o_ghist);
+    M->tiers = reinterpret_cast<tier_counters*>(ws + o_tiers);
+    M->medium = reinterpret_cast<int*>(ws + o_medium);
+    M->large = reinterpret_cast<int*>(ws + o_large);
+    M->state = reinterpret_cast<large_state*>(ws + o_state);
+    M->lh = reinterpret_cast<unsigned*>(ws + o_ghist);
+    M->n = n, M->cells = cells, M->large_cap = large_cap, M->nplane = nplane;
 
     // count, cursor and the tier counters are adjacent: one clear
     AMT_HIP(ctx, hipMemsetAsync(ws, 0, o_offset, ctx->stream));
@@ -664,7 +855,7 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     else
         hipLaunchKernelGGL(k_med_fill<uint16_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of,
                            offset, cursor, keys16, keys64);
-    out_args O;
+    out_args& O = M->O;
     O.nx = A.nx;
     O.ny = A.ny;
     O.nch = nchan;
@@ -679,17 +870,43 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     O.out_img = nchan ? out_img : nullptr;
     O.out_mask = out_mask;
     O.out_count = out_count;
-    hipLaunchKernelGGL(k_med_small, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, medium, large, tiers);
+    if (async)
+        hipLaunchKernelGGL(k_med_small<true>, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, M->medium, M->large,
+                           M->tiers, M->lh);
+    else
+        hipLaunchKernelGGL(k_med_small<false>, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, M->medium, M->large,
+                           M->tiers, nullptr);
     AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                     int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                     double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, double* median,
+                     void* out_img, uint8_t* out_mask, double* out_count) {
+    AMT_CHECK_CTX(ctx);
+    median_pass M;
+    if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
+                              yaxis, lon_wrap, 0, median, out_img, out_mask, out_count, false, &M))
+        return rc;
+    const out_args& O = M.O;
+    int* medium = M.medium;
+    int* large = M.large;
+    large_state* state = M.state;
+    unsigned* ghist = M.lh;
     // the one device -> host read: how many cells the two upper tiers have
     tier_counters t;
-    AMT_HIP(ctx, hipMemcpyAsync(&t, tiers, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipMemcpyAsync(&t, M.tiers, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
     AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int nplane = nchan + (elev ? 1 : 0);
+    const int nplane = M.nplane;
     if (t.n_medium > 0)
         hipLaunchKernelGGL(k_med_medium, dim3(t.n_medium), dim3(kBlock), 0, ctx->stream, O, medium);
     if (t.n_large > 0) {
-        AMT_REQUIRE(ctx, (int64_t)t.n_large <= large_cap, "internal: large-cell count out of range");
+        AMT_REQUIRE(ctx, (int64_t)t.n_large <= M.large_cap, "internal: large-cell count out of range");
         const int nl = (int)t.n_large;
         const dim3 chunks((t.max_large + kChunk - 1) / kChunk, (unsigned)nl);
         const dim3 per_cell((nl + kBlock - 1) / kBlock);
@@ -704,6 +921,36 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
             hipLaunchKernelGGL(k_med_large_above, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, state);
             hipLaunchKernelGGL(k_med_large_put, per_cell, dim3(kBlock), 0, ctx->stream, O, large, nl, p, state);
         }
+    }
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                           int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                           double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                           int lon_from_mlt, double* median, void* out_img, uint8_t* out_mask, double* out_count) {
+    AMT_CHECK_CTX(ctx);
+    median_pass M;
+    if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
+                              yaxis, lon_wrap, lon_from_mlt, median, out_img, out_mask, out_count, true, &M))
+        return rc;
+    // fixed grids from what the host knows: a medium cell has more than kSmallMax pixels, a large one more than kLargeMin;
+    // the workgroups read the tier sizes from device memory
+    const int64_t cu = amt_cu_count(ctx);
+    const int64_t medium_bound = std::min(M.cells, M.n / (kSmallMax + 1));
+    const int64_t medium_grid = std::max<int64_t>(1, std::min(medium_bound, 8 * cu));
+    hipLaunchKernelGGL(k_med_medium_walk, dim3((unsigned)medium_grid), dim3(kBlock), 0, ctx->stream, M.O, M.medium, M.tiers);
+    const int64_t large_grid = std::max<int64_t>(1, std::min(M.n / kChunk + 1, cu));
+    if (M.n > kLargeMin) {
+        int top = 0;
+        for (int p = 0; p < M.nplane; ++p) top = std::max(top, p == nchan ? 64 : (img_dtype == 1 ? 8 : 16));
+        for (int shift = top - 8; shift >= 0; shift -= 8)
+            hipLaunchKernelGGL(k_med_large_step, dim3((unsigned)large_grid), dim3(kBlock), 0, ctx->stream, M.O, M.large,
+                               M.tiers, shift, M.state, M.lh);
+        if (M.nplane > 0)
+            hipLaunchKernelGGL(k_med_large_last, dim3((unsigned)large_grid), dim3(kBlock), 0, ctx->stream, M.O, M.large,
+                               M.tiers, M.state, M.lh);
     }
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;

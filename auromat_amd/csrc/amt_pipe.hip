@@ -43,6 +43,7 @@ struct amt_pipe {
     // the two-pass plan on the driver's streams (amt_pipe_general_layout / _finalize): the frame's coordinate arrays, image
     // and size as the big kernel was given them
     bool two_pass;                 // amt_pipe_set_plan: never fuse the binning into the big kernel
+    bool box_in_grid;              // amt_pipe_set_plan(2): the box of a magnetic launch in (MLat, SM longitude)
     bool general_ready;            // amt_pipe_general_layout has laid out the exact grid of the frame in flight
     const double* g_lat_c;
     int g_row_layout;              // amt_georef_out.row_layout of the frame in flight (strip-padded arrays: no general path here)
@@ -91,15 +92,7 @@ int ensure_partials(amt_pipe* pipe, size_t bytes) {
     return AMT_OK;
 }
 
-// astropy Angle.wrap_at(180 deg), as auromat_amd/mapping/mapping.py wrap_at_180 computes it (reference
-// resample.py:212-218): into [-180, 180)
-double wrap_at_180(double v) {
-    const double wraps = std::floor((v + 180.0) / 360.0);
-    double a = v - wraps * 360.0;
-    if (a >= 180.0) a -= 360.0;
-    if (a < -180.0) a += 360.0;
-    return a;
-}
+using amt_gl::wrap_at_180;
 
 // Is the north or south pole of the mapping shell imaged by a valid pixel?  The pole point is projected
 // through the inverse TAN model; it counts when it falls inside the frame, is the first hit of its ray and
@@ -358,6 +351,7 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
     o.bin_xaxis = o.bin_yaxis = nullptr;
     o.bin_img = nullptr;
     o.bin_img_dtype = o.bin_lon_wrap = o.bin_magnetic = o.bin_pole = 0;
+    if (pipe->box_in_grid) o.bin_magnetic = magnetic;       // (without bin_acc: the box in the grid's coordinates)
     o.bin_events = nullptr;
     o.bin_event_count = nullptr;
     o.bin_event_capacity = 0;
@@ -730,6 +724,7 @@ int amt_pipe_finalize_many(amt_pipe* const* pipes, int32_t n, double* const* mea
 int amt_pipe_set_plan(amt_pipe* pipe, int two_pass) {
     if (pipe == nullptr) return AMT_EINVAL;
     pipe->two_pass = two_pass != 0;
+    pipe->box_in_grid = two_pass == 2;
     return AMT_OK;
 }
 

@@ -142,7 +142,8 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     AMT_REQUIRE(ctx, config->batch >= 1 && config->batch <= AMT_PIPE_MAX_BATCH, "batch out of range");
     AMT_REQUIRE(ctx, config->n_slots >= 2 * config->batch && config->slots != nullptr, "n_slots must be at least 2 * batch");
     AMT_REQUIRE(ctx, config->arcsec_per_px > 0 || (config->lat_px_per_deg > 0 && config->lon_px_per_deg > 0), "px per degree must be positive");
-    AMT_REQUIRE(ctx, !(config->arcsec_per_px > 0) || (!config->two_pass && config->n_slots >= 3 * config->batch),
+    AMT_REQUIRE(ctx, config->statistic == 0 || config->statistic == 1, "statistic must be 0 (mean) or 1 (median)");
+    AMT_REQUIRE(ctx, !(config->arcsec_per_px > 0) || ((config->statistic == 1 || !config->two_pass) && config->n_slots >= 3 * config->batch),
                 "arcsec_per_px: the box-first plan is a single-pass plan and needs n_slots >= 3 * batch");
     amt_run* run = new (std::nothrow) amt_run();
     if (run == nullptr) return AMT_ENOMEM;
@@ -177,7 +178,8 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     }
     for (int i = 0; i < ns; ++i) {
         int rc = amt_pipe_create(ctx, &run->pipes[i]);
-        if (rc == AMT_OK) rc = amt_pipe_set_plan(run->pipes[i], config->two_pass);
+        // (median: the big kernel writes the slot's arrays and bins nothing; its box in the grid's coordinates)
+        if (rc == AMT_OK) rc = amt_pipe_set_plan(run->pipes[i], config->statistic == 1 ? 2 : config->two_pass);
         if (rc != AMT_OK) {
             amt_run_destroy(run);
             return rc;
@@ -224,6 +226,30 @@ int amt_run_reset_hints(amt_run* run) {
 
 namespace {
 
+// Median sequences: the exact grid of a frame the big kernel has written the slot's arrays for (status 1 from amt_pipe_wait),
+// laid out as amt_pipe_general_layout and the single-pass plan lay it out — BaseMapping.boundingBox and the date-line branch
+// of _resample (reference mapping.py:711-741, resample.py:203-218), in (MLat, SM longitude) on a magnetic grid.  What the
+// median pass does not cover keeps status 1: a pole of the grid in view, exact centres, slots without the arrays.
+void median_layout(const amt_run* run, int slot, amt_pipe_result* pr) {
+    const amt_run_config& cfg = run->cfg;
+    const amt_georef_out& o = run->outs[slot];
+    const double* b = pr->bbox;
+    const bool have = cfg.magnetic ? (o.mlat_c && o.mlt_c) : (o.lat_c && o.lon_c);
+    if (pr->status != 1 || b[7] != 0 || !cfg.fast_center || !have || !o.elev || o.row_layout != 0 || !(b[6] > 0)) return;
+    const bool straddles = b[3] - b[2] > 180;
+    double lon_lo = b[2], lon_hi = b[3];
+    if (straddles) {
+        if (!(std::isfinite(b[4]) && std::isfinite(b[5]))) return;
+        lon_lo = amt_gl::wrap_at_180(b[4] + 180.0);
+        lon_hi = amt_gl::wrap_at_180(b[5] + 180.0);
+    }
+    amt_grid g;
+    if (!amt_gl::layout(run->ppd_lat[slot], run->ppd_lon[slot], b[0], b[1], lon_lo, lon_hi, &g)) return;
+    pr->grid = g;
+    pr->lon_wrapped = straddles ? 1 : 0;
+    pr->status = 0;
+}
+
 int run_finish(amt_run* run, int k0, int count) {
     amt_ctx* ctx = run->ctx;
     const amt_run_config& cfg = run->cfg;
@@ -265,14 +291,17 @@ int run_finish(amt_run* run, int k0, int count) {
             if (int rc = amt_pipe_wait(run->pipes[slot], &pr)) return rc;
             r.retried = 1;
         }
-        bool general = false;
-        if (pr.status == 1) {
+        bool general = false, median = false;
+        if (cfg.statistic == 1) {
+            median_layout(run, slot, &pr);
+            median = pr.status == 0;
+        } else if (pr.status == 1) {
             // the two-pass plan, natively, when the frame's coordinate arrays exist and nothing else is needed
             if (int rc = amt_pipe_general_layout(run->pipes[slot], &pr)) return rc;
             general = pr.status == 0;
         }
         r.status = pr.status;
-        r.two_pass = general ? 1 : 0;
+        r.two_pass = general || median ? 1 : 0;
         std::memcpy(r.bbox, pr.bbox, sizeof(r.bbox));
         r.edge_pixels = pr.edge_pixels;
         if (pr.status != 0) {
@@ -297,7 +326,21 @@ int run_finish(amt_run* run, int k0, int count) {
         double* f_mean = run->grids + run->grid_used;
         void* f_img = run->images + run->image_used;
         uint8_t* f_mask = reinterpret_cast<uint8_t*>(run->images + run->image_used + cells * 3 * (cfg.img_dtype == 2 ? 2 : 1));
-        if (general) {
+        if (median) {
+            // on the context's stream behind the frame's big kernel (and the batch launched after it): every median pass of the
+            // call runs in stream order, so they share the workspace of that stream
+            const amt_georef_out& o = run->outs[slot];
+            const bool mag = cfg.magnetic != 0;
+            if (int rc = amt_median_frame_async(ctx, mag ? o.mlat_c : o.lat_c, mag ? o.mlt_c : o.lon_c, o.elev, run->img[slot],
+                                                cfg.img_dtype, 3, nullptr, cfg.height, cfg.width, cfg.min_elevation,
+                                                &pr.grid.xaxis, &pr.grid.yaxis, pr.lon_wrapped, mag ? 1 : 0, f_mean, f_img, f_mask,
+                                                f_mean + 4 * cells))
+                return rc;
+            if (run->img[slot] == run->own_img[slot] && run->own_img[slot] != nullptr) {
+                AMT_HIP(ctx, hipEventRecord(run->img_free[slot], ctx->stream));
+                run->img_busy[slot] = 1;
+            }
+        } else if (general) {
             if (int rc = amt_pipe_general_finalize(run->pipes[slot], f_mean, f_img, f_mask, f_mean + 4 * cells)) return rc;
             if (run->img[slot] == run->own_img[slot] && run->own_img[slot] != nullptr) {
                 // the binning pass reads the slot's image buffer on the context's stream: the slot's next upload waits for it

@@ -32,7 +32,7 @@ import numpy as np
 from .frame import FrameData, PaddedFrameData, has_array
 from .mapping.astrometry import frame_params, pole_in_view, run_frame
 from .mapping.mapping import bounding_box_from_reduction, wrap_at_180
-from .resample import cached_grid, grid_coordinates, resample_frame
+from .resample import cached_grid, grid_coordinates, resample_frame, resample_frame_median
 from ._native import Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
 
 NEG_INF = float('-inf')
@@ -623,15 +623,18 @@ class FramePipeline(object):
             done.append(q._fused_wrap(*o, keep_on_device=keep_on_device))
         return done
 
-    def resample(self, pxPerDeg=10, containsPole=None, magnetic=False, keep_on_device=False):
-        """Stages 2 + 3.  magnetic=True bins on the (MLat, SM longitude) grid (resampleMLatMLT)."""
+    def resample(self, pxPerDeg=10, containsPole=None, magnetic=False, keep_on_device=False, statistic='mean'):
+        """Stages 2 + 3.  magnetic=True bins on the (MLat, SM longitude) grid (resampleMLatMLT).  statistic='median': the
+        median of every cell (resampleMedian / resampleMedianMLatMLT) by the two-pass plan; the result holds 'median'
+        in place of 'mean'."""
+        assert statistic in ('mean', 'median')
         try:
             _, _ = pxPerDeg
         except TypeError:
             pxPerDeg = (pxPerDeg, pxPerDeg)
         fd = self.fd
         Context.current(self.ctx.device)
-        if self._fused is not None and self._fused['pxPerDeg'] == tuple(pxPerDeg) and \
+        if statistic == 'mean' and self._fused is not None and self._fused['pxPerDeg'] == tuple(pxPerDeg) and \
                 self._fused['magnetic'] == bool(magnetic):
             res = self._wait_fused()
             # (a direction-array frame whose caller left the pole open and whose box reaches within 5 deg of a pole was handed
@@ -683,13 +686,17 @@ class FramePipeline(object):
             bb = self.bounding_box()
         pole = bb.containsPole if containsPole is None else containsPole
         self.last_plan = 'two-pass'
+        if statistic == 'median':
+            return resample_frame_median(fd, self.altitude, bb, pxPerDeg, bb.containsDiscontinuity, pole,
+                                         min_elevation=self.min_elevation, keep_on_device=keep_on_device)
         return resample_frame(fd, self.altitude, bb, pxPerDeg, bb.containsDiscontinuity, pole,
                               min_elevation=self.min_elevation, keep_on_device=keep_on_device, shard=self.shard)
 
     def run(self, wcsHeader, altitude, cameraPosGCRS, photoTime, img=None, fast=True, min_elevation=10.0,
             pxPerDeg=10, containsPole=None, magnetic=False, params=None, keep_on_device=False, fuse=False,
-            arcsecPerPx=None, dirs=None):
-        """One frame end to end; returns the dict of :func:`auromat_amd.resample.resample_frame`.  `arcsecPerPx` (has
+            arcsecPerPx=None, dirs=None, statistic='mean'):
+        """One frame end to end; returns the dict of :func:`auromat_amd.resample.resample_frame` (statistic='median': of
+        :func:`auromat_amd.resample.resample_frame_median`, never fused).  `arcsecPerPx` (has
         precedence over pxPerDeg, like the reference's resample()): the box-first plan — a box pass, px/deg from the frame's
         own bounding box, then the single-pass launch (``fuse``) or the two-pass plan; the px/deg pair used is in the
         result as 'pxPerDeg'."""
@@ -727,7 +734,7 @@ class FramePipeline(object):
         self.georef(wcsHeader, altitude, cameraPosGCRS, photoTime, fast, min_elevation, params=params,
                     fuse_pxPerDeg=pxPerDeg if fuse else None, fuse_magnetic=bool(magnetic), coarse_started=coarse_started,
                     dirs=dirs, pole_in_view=-1 if containsPole is None else int(bool(containsPole)))
-        res = self.resample(pxPerDeg, containsPole, magnetic, keep_on_device=keep_on_device)
+        res = self.resample(pxPerDeg, containsPole, magnetic, keep_on_device=keep_on_device, statistic=statistic)
         res['pxPerDeg'] = tuple(pxPerDeg)
         return res
 
@@ -899,6 +906,7 @@ class NativeResults(object):
         n = ny * nx
         o = r.grid_offset
         packed = self._grids[o:o + 5 * n]
+        stat = 'median' if seq.statistic == 'median' else 'mean'
         mean = self._grids[o:o + 4 * n].view(ny, nx, 4)
         count = self._grids[o + 4 * n:o + 5 * n].view(ny, nx)
         ob = r.image_offset
@@ -912,17 +920,19 @@ class NativeResults(object):
         out = dict(has_elev=True, grid=grid, contains_pole=pole, contains_discontinuity=wrapped or pole,
                    altitude=r.altitude, magnetic=seq.magnetic, pxPerDeg=ppd)
         if self._keep:
-            out.update(mean=mean, img=img, mask=mask, count=count, packed=packed)
+            out.update(img=img, mask=mask, count=count, packed=packed)
+            out[stat] = mean
             return out
         out.update(grid_coordinates(out))
-        out.update(mean=to_host(mean), img=to_host(img, dtype=fd.img_dtype), mask=to_host(mask).astype(bool),
-                   count=to_host(count))
+        out.update(img=to_host(img, dtype=fd.img_dtype), mask=to_host(mask).astype(bool), count=to_host(count))
+        out[stat] = to_host(mean)
         return out
 
     # ---- what the gather needs, without per-frame objects (auromat_amd.sequence) -----------------------------------
     def payload(self):
-        """(device tensor, length): mean | count of all frames back to back, or None when a frame took another path."""
-        if self._table is None or not self._keep or np.any(self._table['status'] == 1):
+        """(device tensor, length): mean | count of all frames back to back, or None when a frame took another path (or the
+        grids hold medians: the gather carries means)."""
+        if self._table is None or not self._keep or np.any(self._table['status'] == 1) or self._seq.statistic != 'mean':
             return None
         t = self._table
         used = int((5 * t['ny'].astype(np.int64) * t['nx']).sum())
@@ -965,9 +975,18 @@ class SequencePipeline(object):
     def __init__(self, width, height, nchan=3, img_dtype=np.uint16, device=None, altitude=110, fast=True,
                  min_elevation=10.0, pxPerDeg=10, plan='single-pass', bin_stream=True, shared_image=None,
                  magnetic=False, batch=3, own_image_buffers=True, keep_coordinates=True, launch_streams=1,
-                 geodetic_arrays=None, arcsecPerPx=None, padded=None):
+                 geodetic_arrays=None, arcsecPerPx=None, padded=None, statistic='mean'):
         import torch
         assert plan in ('single-pass', 'two-pass')
+        # statistic='median' (resampleMedian / resampleMedianMLatMLT): every frame through the native runner's median pass —
+        # the frame kernel writes the buffer's centre and elevation arrays (contiguous rows), the median kernels bin them
+        # (amt_run_config.statistic, amt_median_frame_async); the results carry 'median' in place of 'mean'
+        assert statistic in ('mean', 'median')
+        self.statistic = statistic
+        if statistic == 'median':
+            assert plan == 'single-pass' and nchan == 3, "statistic='median': RGB frames through the native runner"
+            padded = False
+            keep_coordinates = True
         try:
             _, _ = pxPerDeg
         except TypeError:
@@ -1242,7 +1261,8 @@ class SequencePipeline(object):
             q = self.pipes[0]
             cfg = RunConfig(width=q.width, height=q.height, img_dtype=1 if q.fd.img_dtype == np.uint8 else 2, fast_center=1 if self.fast else 0,
                             magnetic=1 if self.magnetic else 0, batch=self.batch, use_hints=1 if self.use_hints else 0,
-                            n_slots=nb, two_pass=0 if self.single_pass else 1, altitude=float(self.altitude),
+                            n_slots=nb, two_pass=0 if self.single_pass else 1,
+                            statistic=1 if self.statistic == 'median' else 0, altitude=float(self.altitude),
                             min_elevation=NEG_INF if self.min_elevation is None else float(self.min_elevation),
                             lat_px_per_deg=float(self.pxPerDeg[0]) if self.pxPerDeg else 0.0,
                             lon_px_per_deg=float(self.pxPerDeg[1]) if self.pxPerDeg else 0.0, slots=slots,
@@ -1353,13 +1373,14 @@ class SequencePipeline(object):
         fallbacks = {}
         max_cells = int((table['ny'].astype(np.int64) * table['nx']).max()) if n else 1
         names = {0: 'single-pass', 2: 'empty', 4: 'pole-without-resolution'}
+        median = self.statistic == 'median'
         if not status.any() and not table['two_pass'].any():
             self.plans.extend(['single-pass'] * n)
         else:
             for k in range(n):
                 st = int(status[k])
                 if st in names:
-                    self.plans.append('two-pass' if st == 0 and table['two_pass'][k] else names[st])
+                    self.plans.append(('median' if median else 'two-pass') if st == 0 and table['two_pass'][k] else names[st])
                     continue
                 f = frames[k]
                 q = self.pipes[0]
@@ -1370,8 +1391,11 @@ class SequencePipeline(object):
                 alt = f[4] if len(f) > 4 and f[4] is not None else self.altitude
                 try:
                     ppd = (table['lat_px_per_deg'][k], table['lon_px_per_deg'][k]) if self.arcsecPerPx else self.pxPerDeg
+                    # (median: the frames the runner's median pass does not cover — a pole in view, exact centres — by
+                    # resample_frame_median on the frame's arrays, what resampleMedian / resampleMedianMLatMLT run)
                     res = q.run(f[0], alt, f[1], f[2], fast=self.fast, min_elevation=self.min_elevation, pxPerDeg=ppd,
-                                magnetic=self.magnetic, keep_on_device=keep_on_device, fuse=False)
+                                magnetic=self.magnetic, keep_on_device=keep_on_device, fuse=False,
+                                statistic=self.statistic)
                     res['magnetic'] = self.magnetic
                 except EmptyFrame:
                     res = None
@@ -1512,6 +1536,40 @@ class SequencePipeline(object):
         self._frames_done += len(out)
         return out
 
+    def _process_median(self, frames, keep_on_device, on_batch):
+        """process() with statistic='median': the native runner, in pieces of up to `median_chunk` frames (an iterator — the
+        convert driver's generator of decoded host images — is consumed piece by piece).  Device-resident and pinned images
+        go to the runner as they are; any other image is copied to the device first, on the caller's stream."""
+        import torch
+        q = self.pipes[0]
+        dt, shape = q._img_torch_dtype, tuple(q._img_shape)
+        out = []
+        it = iter(frames)
+        while True:
+            chunk = []
+            for f in it:
+                img = f[3]
+                if not (hasattr(img, 'is_cuda') and img.dtype == dt and img.is_contiguous() and (img.is_cuda or img.is_pinned())):
+                    a = np.ascontiguousarray(img.cpu().numpy() if hasattr(img, 'is_cuda') else img)
+                    if a.dtype == np.uint16:
+                        a = a.view(np.int16)
+                    img = torch.from_numpy(a).to(self.ctx.device)
+                assert type(f[0]) is dict and tuple(img.shape) == shape, \
+                    "statistic='median': frames are (header dict, cameraPosGCRS, photoTime, image[, altitude])"
+                chunk.append((f[0], f[1], f[2], img) + tuple(f[4:]))
+                if len(chunk) == self.median_chunk:
+                    break
+            if not chunk:
+                break
+            got = list(self._process_native(chunk, keep_on_device))
+            if on_batch is not None:
+                on_batch(len(out), got)
+            out.extend(got)
+        return out
+
+    # frames per call of the runner in median sequences (the arenas and, for host images, their device copies)
+    median_chunk = 24
+
     def finalize_stream(self):
         """The stream the single-pass results are produced on (the drivers' finalise stream, shared by the pipeline's
         buffers): consumers that want to touch results before process() returns enqueue there."""
@@ -1533,6 +1591,8 @@ class SequencePipeline(object):
         del self.plans[:]
         self.hinted = 0
         self.uploaded_bytes = 0
+        if self.statistic == 'median':
+            return self._process_median(frames, keep_on_device, on_batch)
         if on_batch is None and self.native and isinstance(frames, (list, tuple)):
             # (an iterator — the convert driver's read-ahead generator of decoded host images — is consumed frame by frame
             # below: its images are not device-resident anyway, and materialising it would hold every decoded image of the

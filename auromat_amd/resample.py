@@ -235,11 +235,13 @@ def resampleMedianMLatMLT(mapping, **kw):
 
 
 def resample_frame_median(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,
-                          min_elevation=None, outline=None):
+                          min_elevation=None, outline=None, keep_on_device=False):
     """
     Median binning of a device-resident frame on the grid :func:`resample_frame` lays out (``amt_median_frame``).
 
     :param outline: the mapping's outline, needed for the pole box as in :func:`resample_frame`
+    :param keep_on_device: the arrays stay device tensors and no grid coordinates are computed (sequence mode, as
+                           :func:`resample_frame`)
     :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], median (ny,nx,C+1), img (ny,nx,C), mask (ny,nx),
                   count (ny,nx), has_elev)
     """
@@ -259,6 +261,9 @@ def resample_frame_median(fd, altitude, boundingBox, pxPerDeg, containsDiscontin
              ptr(img) if nch else None, ptr(mask), ptr(count))
     out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
                contains_discontinuity=bool(containsDiscontinuity), altitude=altitude)
+    if keep_on_device:
+        out.update(median=median, img=img, mask=mask, count=count)
+        return out
     out.update(grid_coordinates(out))
     out.update(median=to_host(median), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
                mask=to_host(mask).astype(bool), count=to_host(count))

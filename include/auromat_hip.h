@@ -39,7 +39,9 @@ extern "C" {
  *    amt_pipe_launch_dirs_many, amt_host_threads, AMT_EDOMAIN; retired: amt_linear_gather, amt_cubic_gradients, amt_cubic_gather
  *    (round 6) */
 /* 7: amt_median_frame (median binning, auromat_amd.resample.resampleMedian) */
-#define AMT_ABI_VERSION 7
+/* 8: amt_median_frame_async (the median pass without a read-back); amt_run_config.statistic (median sequences in the runner, in
+ *    place of reserved_); amt_pipe_set_plan(pipe, 2) */
+#define AMT_ABI_VERSION 8
 
 #define AMT_OK 0
 #define AMT_EINVAL (-1)   /* bad argument (NULL pointer, negative size, unsupported dtype ...) */
@@ -499,6 +501,20 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
                      int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                      double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, double* median,
                      void* out_img, uint8_t* out_mask, double* out_count);
+/* amt_median_frame that only enqueues work (ABI v8): the same bits, no read-back and no host wait.  Every kernel goes on the
+ * context's stream; the inputs must stay valid and the outputs untouched until the stream has run them, and the result is
+ * ready in stream order.  The pass uses the workspace of the context's current stream (about 18 bytes per pixel for uint16
+ * RGB plus elevation): passes enqueued one after the other on ONE stream may share it; passes that can run at the same time
+ * need contexts (or streams) of their own.  (A call that needs a larger workspace than the stream has grows it, which
+ * synchronises that stream once, as for every user of the workspace.)  The cells above 64 pixels are selected by one launch of a fixed grid that walks
+ * the device's list of them; cells above 16384 pixels by one launch per digit position of the widest key (8 with the
+ * elevation, 2 for uint16, 1 for uint8) plus one, which return at once when the frame has no such cell.
+ * lon_from_mlt != 0: lon_c holds MLT hours, binned at the SM longitude (lon_c - 12) / (24 / 360) in float64, which is what
+ * convertMappingToSM (auromat_amd/mapping/mapping.py) computes for resampleMedianMLatMLT. */
+int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                           int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                           double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                           int lon_from_mlt, double* median, void* out_img, uint8_t* out_mask, double* out_count);
 /* Same for float accumulators of amt_hist2d_accumulate: mean[k] = sums[k]/count, NaN where empty,
  * transposed + flipped to (ny, nx, nweights). */
 int amt_hist2d_finalize_mean(amt_ctx* ctx, const double* count, const double* const* sums, int32_t nweights,
@@ -732,7 +748,9 @@ int amt_pipe_join(amt_pipe* pipe);
  *                                  lon_wrapped, status 0 — unless the frame needs what only the caller has (a pole in view,
  *                                  exact centres, an MLat / MLT grid, no coordinate arrays): then status stays 1;
  *   amt_pipe_general_finalize      zeroes the accumulators, bins the frame's arrays (amt_bin_frame) and finalises into the
- *                                  caller's arrays (sized from result->grid), on the context's stream. */
+ *                                  caller's arrays (sized from result->grid), on the context's stream.
+ * amt_pipe_set_plan(pipe, 2) (ABI v8) is plan 1 whose box is reported in the grid's coordinates: (MLat, SM longitude) for a
+ * magnetic launch, as amt_pipe_launch_box does (the median sequences of the runner). */
 int amt_pipe_set_plan(amt_pipe* pipe, int two_pass);
 int amt_pipe_general_layout(amt_pipe* pipe, amt_pipe_result* result);
 int amt_pipe_general_finalize(amt_pipe* pipe, double* mean, void* out_img, uint8_t* out_mask, double* out_count);
@@ -759,7 +777,15 @@ int amt_pipe_general_finalize(amt_pipe* pipe, double* mean, void* out_img, uint8
  * arcsec_per_px > 0 — `resample(mapping, arcsecPerPx=R)`, what the reference's auromat-convert runs (cli/convert.py:176-185) —:
  * every frame's px/deg follows from its own bounding box (amt_plate_carree_resolution; lat / lon_px_per_deg of the config are
  * ignored, the frame's pair is in its result): the box-first plan (amt_pipe_launch_box), the box pass of a batch two batches
- * ahead of its single-pass launch; needs n_slots >= 3 * batch. */
+ * ahead of its single-pass launch; needs n_slots >= 3 * batch.
+ * Median sequences (statistic = 1, ABI v8; auromat_amd.resample.resampleMedian / resampleMedianMLatMLT): the big kernel
+ * writes the slot's centre and elevation arrays and bins nothing (the slots need lat_c / lon_c / elev, or mlat_c / mlt_c /
+ * elev for magnetic grids, in contiguous rows: row_layout 0); after the wait for the frame's exact box the runner lays out
+ * the same grid as for the mean and enqueues amt_median_frame_async on the context's stream, so the median passes of all
+ * frames run in stream order and share the context's workspace.  The arenas hold the same blocks: (ny, nx, 4) medians
+ * (elevation last, NaN where empty), count, the image rounded half to even and the mask.  status 1 for what the pass does
+ * not cover: a pole of the grid in view, exact centres (fast_center = 0); the caller finishes those.  two_pass is ignored;
+ * arcsec_per_px works as for the mean (box pass, then the launch that writes the arrays). */
 typedef struct amt_run amt_run;
 typedef struct amt_run_config {
     int32_t width, height;
@@ -770,7 +796,7 @@ typedef struct amt_run_config {
     int32_t use_hints;            /* 0: coarse pre-pass for every frame */
     int32_t n_slots;              /* frame slots, >= 2 * batch */
     int32_t two_pass;             /* 1: the two-pass plan for every frame (needs the slots' lat_c / lon_c / elev arrays) */
-    int32_t reserved_;
+    int32_t statistic;            /* ABI v8: 0 mean, 1 median (see "median sequences" below) */
     double altitude;              /* mapping shell [km] of frames that name none */
     double min_elevation;         /* maskedByElevation; -inf disables */
     double lat_px_per_deg, lon_px_per_deg;
