@@ -23,6 +23,7 @@ def sources():
 
 def _deps():
     return sources() + [os.path.join(CSRC, 'amt_common.h'), os.path.join(CSRC, 'amt_grid.h'), os.path.join(CSRC, 'amt_params.h'),
+                        os.path.join(CSRC, 'amt_bin_tile.h'),
                         os.path.join(os.path.dirname(PKG_DIR), 'include', 'auromat_hip.h')]
 
 

@@ -77,6 +77,12 @@ class SeqFrame(C.Structure):
                 ('reserved', C.c_int32), ('altitude', C.c_double), ('mean', C.c_void_p), ('count', C.c_void_p)]
 
 
+class MosaicMember(C.Structure):
+    """amt_mosaic_member"""
+    _fields_ = [(k, C.c_void_p) for k in ('lat_c', 'lon_c', 'elev', 'img', 'center_mask')] + \
+               [(k, C.c_int32) for k in ('height', 'width', 'win_x0', 'win_y0', 'win_nx', 'win_ny')]
+
+
 class PipeResult(C.Structure):
     """amt_pipe_result"""
     _fields_ = [('status', C.c_int32), ('fused', C.c_int32), ('lon_wrapped', C.c_int32), ('edge_pixels', C.c_int32),
@@ -107,7 +113,7 @@ class RunResult(C.Structure):
                 ('retried', C.c_int32), ('reserved2_', C.c_int32), ('uploaded_bytes', C.c_int64)]
 
 
-ABI_VERSION = 8          # include/auromat_hip.h AMT_ABI_VERSION
+ABI_VERSION = 9          # include/auromat_hip.h AMT_ABI_VERSION
 _I, _L, _D, _P = C.c_int, C.c_int64, C.c_double, C.c_void_p
 _SIGNATURES = {
     'amt_abi_version': ([], _I),
@@ -196,6 +202,8 @@ _SIGNATURES = {
                           C.POINTER(Axis), _I, _P, _P, _P, _P], _I),
     'amt_median_frame_async': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                                 C.POINTER(Axis), _I, _I, _P, _P, _P, _P], _I),
+    'amt_mosaic_frames': ([_P, C.POINTER(MosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis),
+                           _I, C.c_int32, _P, _P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
                            _P], _I),
     'amt_nearest_gather': ([_P, _P, _L, _P, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),

@@ -1,13 +1,12 @@
 // Histogram binning for resample(method='mean')
 // (reference auromat/util/histogram.py:57-282, auromat/resample.py:301-351).
 //
-// k_bin_frame: one workgroup bins a BW x BH tile of the image.  Neighbouring pixels fall into
-// neighbouring cells, so the tile's cells form a small window of the output grid: the window is
-// privatised in LDS (u32 count / channel sums, i64 fixed-point elevation), filled with LDS atomics
-// and flushed with one 64-bit global integer atomic per touched cell and plane.  Integer
+// k_bin_frame: one workgroup bins a BW x BH tile of the image into an LDS window of the output grid, flushed with
+// 64-bit global integer atomics (the tile body, shared with the mosaic binning: amt_bin_tile.h).  Integer
 // accumulation is exact and order independent, so the result is bit-reproducible.
 // Algorithmic HBM bytes: 24 B (lat, lon, elev) + nchan * sizeof(pixel) per pixel read; the grid is negligible.
 #include "amt_common.h"
+#include "amt_bin_tile.h"
 
 namespace {
 
@@ -58,243 +57,9 @@ __global__ void k_hist2d_finalize(const double* __restrict__ count, hist_args A,
 }
 
 // ------------------------------------------------------------------------------------------
-// fused frame binning
+// fused frame binning: k_bin_frame<IMG_T, NCH, VEC, false> (amt_bin_tile.h)
 // ------------------------------------------------------------------------------------------
-struct bin_args {
-    const double* lat_c;
-    const double* lon_c;
-    const double* elev;
-    const void* img;
-    const uint8_t* mask;
-    int height, width;
-    double min_elev;
-    int use_elev_threshold;
-    axis_dev ax, ay;
-    int lon_wrap;
-    unsigned long long* acc;
-};
-
-constexpr int kPPT = 4;                      // consecutive pixels (along x) per thread and row, loaded as two pairs
-constexpr int kBW = 64 * kPPT, kBH = kBlock / 64, kWCap = 1024;   // tile: 256 x 4 pixels, one image row per wave
-// Column of pixel j of lane l inside the tile row.  (A layout with the two pairs 128 pixels apart, which makes
-// every 16-byte wave load one contiguous 1 KiB segment, measured 25 % slower: 146 vs 118 us per frame.)
-__device__ __forceinline__ int tile_col(int lane, int j) { return kPPT * lane + j; }
-
-// Loads the thread's two pixel pairs of one row; `row` points at the tile's first pixel of that row, `n_row`
-// is the number of pixels of the tile row inside the image.  VEC promises 16-byte alignment of `row`.
-template <bool VEC>
-__device__ __forceinline__ void load_run(const double* __restrict__ row, int lane, int n_row, double (&v)[kPPT]) {
-#pragma unroll
-    for (int k = 0; k < kPPT / 2; ++k) {
-        const int c = tile_col(lane, 2 * k);
-        if (VEC && c + 1 < n_row) {
-            const double2 a = *reinterpret_cast<const double2*>(row + c);
-            v[2 * k] = a.x;
-            v[2 * k + 1] = a.y;
-        } else {
-            v[2 * k] = c < n_row ? row[c] : NAN;
-            v[2 * k + 1] = c + 1 < n_row ? row[c + 1] : NAN;
-        }
-    }
-}
-
-constexpr int kWX = 32, kWY = 32;            // LDS window of kWX x kWY cells centred on the tile's anchor cell
-constexpr int kRowIters = 4;                 // a workgroup walks kRowIters x kBH image rows (16) with one window
-static_assert(kWX * kWY == kWCap, "window size");
-
-template <typename IMG_T, int NCH, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_bin_frame(bin_args A) {
-    __shared__ unsigned int sCnt[kWCap];
-    __shared__ unsigned int sCh[NCH > 0 ? NCH : 1][kWCap];
-    __shared__ unsigned long long sEl[kWCap];
-    __shared__ int sCand[kBlock / 64];
-
-    const int tiles_x = (A.width + kBW - 1) / kBW;
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int gx0 = tile_x * kBW;
-    const int64_t ncell = (int64_t)A.ax.nbin * A.ay.nbin;
-    const IMG_T* img = static_cast<const IMG_T*>(A.img);
-
-    for (int i = threadIdx.x; i < kWCap; i += kBlock) {
-        sCnt[i] = 0;
-        sEl[i] = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) sCh[c][i] = 0;
-    }
-    // anchor cell (block-uniform): the window covers cells [ax0, ax0 + kWX) x [ay0, ay0 + kWY)
-    int ax0 = 0, ay0 = 0;
-    bool have_anchor = false;
-    __syncthreads();
-
-    for (int it = 0; it < kRowIters; ++it) {
-        const int gy = (tile_y * kRowIters + it) * kBH + wave;
-        const int n_row = (gy < A.height) ? min(kBW, A.width - gx0) : 0;   // pixels of this tile row inside the image
-
-        // ---- all loads first (one memory latency per row group), then arithmetic ---------------------
-        double la[kPPT], lo[kPPT], ev[kPPT];
-        unsigned int ch[kPPT][NCH > 0 ? NCH : 1];
-        unsigned char mk[kPPT];
-#pragma unroll
-        for (int j = 0; j < kPPT; ++j) {
-            la[j] = NAN; lo[j] = NAN; ev[j] = 0.0; mk[j] = 0;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) ch[j][c] = 0;
-        }
-        if (n_row > 0) {
-            const int64_t g0 = (int64_t)gy * A.width + gx0;
-            load_run<VEC>(A.lat_c + g0, lane, n_row, la);
-        }
-        // a pixel without a latitude is not binned (resample.py:315-321): where a wave's whole tile row has none — the sky
-        // above the limb, 30-40 % of an ISS frame — its longitudes, elevations and image bytes (22 of the 30 B per pixel)
-        // are not read at all
-        bool any_lat = false;
-#pragma unroll
-        for (int j = 0; j < kPPT; ++j) any_lat = any_lat || la[j] == la[j];
-        if (n_row > 0 && __any(any_lat)) {
-            const int64_t g0 = (int64_t)gy * A.width + gx0;
-            load_run<VEC>(A.lon_c + g0, lane, n_row, lo);
-            if (A.elev) load_run<VEC>(A.elev + g0, lane, n_row, ev);
-            if (A.mask) {
-#pragma unroll
-                for (int j = 0; j < kPPT; ++j) mk[j] = tile_col(lane, j) < n_row ? A.mask[g0 + tile_col(lane, j)] : 1;
-            }
-            if (NCH > 0) {
-                constexpr int kPairBytes = 2 * NCH * (int)sizeof(IMG_T);
-#pragma unroll
-                for (int k = 0; k < kPPT / 2; ++k) {
-                    const int c0 = tile_col(lane, 2 * k);
-                    const IMG_T* q = img + (g0 + c0) * NCH;
-                    if (VEC && kPairBytes % 4 == 0 && c0 + 1 < n_row) {
-                        // a pixel pair is kPairBytes contiguous, 4-byte aligned bytes (even column, even width)
-                        constexpr int kWords = kPairBytes / 4;
-                        const uint32_t* w = reinterpret_cast<const uint32_t*>(q);
-                        uint32_t buf[kWords > 0 ? kWords : 1];
-#pragma unroll
-                        for (int i = 0; i < kWords; ++i) buf[i] = w[i];
-#pragma unroll
-                        for (int e = 0; e < 2 * NCH; ++e) {
-                            const unsigned int val = sizeof(IMG_T) == 2 ? (buf[e >> 1] >> ((e & 1) * 16)) & 0xffffu
-                                                                        : (buf[e >> 2] >> ((e & 3) * 8)) & 0xffu;
-                            ch[2 * k + e / NCH][e % NCH] = val;
-                        }
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 2; ++e)
-#pragma unroll
-                            for (int c = 0; c < NCH; ++c) ch[2 * k + e][c] = c0 + e < n_row ? q[e * NCH + c] : 0;
-                    }
-                }
-            }
-        }
-
-        int cellx[kPPT], celly[kPPT];
-        int first = 0;                                  // first valid cell of this thread, packed (x << 16 | y) + 1
-#pragma unroll
-        for (int j = kPPT - 1; j >= 0; --j) {
-            bool ok = la[j] == la[j];                                          // resample.py:315-321
-            if (A.use_elev_threshold) ok = ok && (ev[j] >= A.min_elev);        // mapping.py:856
-            ok = ok && mk[j] == 0;
-            cellx[j] = 0;
-            celly[j] = 0;
-            if (ok) {
-                const double xv = A.lon_wrap ? wrap180_shifted(lo[j]) : lo[j];
-                const int bx = bin_index(A.ax, xv), by = bin_index(A.ay, la[j]);
-                if (bx >= 1 && bx <= A.ax.nbin && by >= 1 && by <= A.ay.nbin) {
-                    cellx[j] = bx;
-                    celly[j] = by;
-                    first = -1 - j;   // the loop runs downwards: the smallest valid j wins
-                }
-            }
-        }
-        if (!have_anchor) {
-            // elect the anchor: cell of the first valid pixel of the lowest wave that has one
-            const unsigned long long m = __ballot(first < 0);
-            int cand = 0;
-            if (m) {
-                const int src = __builtin_ctzll(m);
-                const int j = -1 - __shfl(first, src);
-                int cx = 0, cy = 0;
-#pragma unroll
-                for (int k = 0; k < kPPT; ++k) {
-                    cx = (k == j) ? cellx[k] : cx;
-                    cy = (k == j) ? celly[k] : cy;
-                }
-                cx = __shfl(cx, src);
-                cy = __shfl(cy, src);
-                cand = ((cx & 0xffff) << 16 | (cy & 0xffff)) + 1;     // grids have < 65535 bins per axis here
-            }
-            if (lane == 0) sCand[wave] = cand;
-            __syncthreads();
-            int chosen = 0;
-#pragma unroll
-            for (int w = kBlock / 64 - 1; w >= 0; --w) chosen = sCand[w] ? sCand[w] : chosen;
-            __syncthreads();
-            if (chosen) {
-                have_anchor = true;
-                ax0 = (((chosen - 1) >> 16) & 0xffff) - kWX / 2;
-                ay0 = ((chosen - 1) & 0xffff) - kWY / 2;
-            }
-        }
-
-        // consecutive pixels of a thread mostly share a cell: sum runs in registers, one atomic set per run.
-        // (a NaN elevation of a kept pixel contributes 0; the reference would poison the cell — the mask
-        //  invariants of mapping.py:299-316 make that unreachable)
-        int run_x = 0, run_y = 0;
-        unsigned int rcnt = 0, rch[NCH > 0 ? NCH : 1];
-        long long rel = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) rch[c] = 0;
-        auto flush = [&]() {
-            const int dx = run_x - ax0, dy = run_y - ay0;
-            if (dx >= 0 && dx < kWX && dy >= 0 && dy < kWY) {
-                const int wi = dx * kWY + dy;
-                atomicAdd(&sCnt[wi], rcnt);
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) atomicAdd(&sCh[c][wi], rch[c]);
-                atomicAdd(&sEl[wi], (unsigned long long)rel);
-            } else {
-                // outside the LDS window (very fine grids or strongly stretched tiles): global atomics
-                const int64_t cell = (int64_t)(run_x - 1) * A.ay.nbin + (run_y - 1);
-                atomicAdd(&A.acc[cell], (unsigned long long)rcnt);
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) atomicAdd(&A.acc[(int64_t)(1 + c) * ncell + cell], (unsigned long long)rch[c]);
-                atomicAdd(&A.acc[(int64_t)(1 + NCH) * ncell + cell], (unsigned long long)rel);
-            }
-        };
-#pragma unroll
-        for (int j = 0; j < kPPT; ++j) {
-            if (cellx[j] == 0) continue;
-            if (cellx[j] != run_x || celly[j] != run_y) {
-                if (run_x > 0) flush();
-                run_x = cellx[j];
-                run_y = celly[j];
-                rcnt = 0;
-                rel = 0;
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) rch[c] = 0;
-            }
-            rcnt += 1;
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) rch[c] += ch[j][c];
-            rel += (ev[j] == ev[j]) ? __double2ll_rn(ev[j] * kFix) : 0;
-        }
-        if (run_x > 0) flush();
-    }
-
-    if (!have_anchor) return;      // nothing of this tile landed on the grid (block-uniform)
-    __syncthreads();
-    for (int i = threadIdx.x; i < kWCap; i += kBlock) {
-        const unsigned int cnt = sCnt[i];
-        if (cnt == 0) continue;
-        const int dx = i / kWY, dy = i - dx * kWY;
-        const int64_t cell = (int64_t)(ax0 + dx - 1) * A.ay.nbin + (ay0 + dy - 1);
-        atomicAdd(&A.acc[cell], (unsigned long long)cnt);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) atomicAdd(&A.acc[(int64_t)(1 + c) * ncell + cell], (unsigned long long)sCh[c][i]);
-        atomicAdd(&A.acc[(int64_t)(1 + NCH) * ncell + cell], sEl[i]);
-    }
-}
+static_assert(kBlock == kBinBlock, "block size");
 
 template <typename IMG_T>
 __global__ void k_bin_finalize(unsigned long long* __restrict__ acc, int acc_nx, int acc_ny, int off_x,
@@ -306,19 +71,10 @@ __global__ void k_bin_finalize(unsigned long long* __restrict__ acc, int acc_nx,
         const int r = (int)(i / nx), c = (int)(i - (int64_t)r * nx);
         // transpose + flipud (resample.py:339-349), inside the [off_x, off_x+nx) x [off_y, off_y+ny) window
         const int64_t cell = (int64_t)(off_x + c) * acc_ny + (off_y + ny - 1 - r);
-        const unsigned long long cnt = acc[cell];
-        const double dc = (double)cnt;
-        for (int k = 0; k < nch; ++k) {
-            const double m = cnt ? (double)acc[(int64_t)(1 + k) * plane + cell] / dc : NAN;
-            if (mean) mean[i * (nch + 1) + k] = m;
-            if (out_img) out_img[i * nch + k] = cnt ? (IMG_T)rint(m) : (IMG_T)0;   // np.round: half to even
-        }
-        if (mean) {
-            const long long fx = (long long)acc[(int64_t)(1 + nch) * plane + cell];
-            mean[i * (nch + 1) + nch] = cnt ? ((double)fx / kFix) / dc : NAN;
-        }
-        if (out_mask) out_mask[i] = cnt ? 0 : 1;
-        if (out_count) out_count[i] = dc;
+        finalize_cell(acc[cell], [&](int k) { return acc[(int64_t)(1 + k) * plane + cell]; },
+                      [&]() { return (long long)acc[(int64_t)(1 + nch) * plane + cell]; }, nch, i, mean, out_img,
+                      out_mask, out_count, cell_wants{mean != nullptr, out_img != nullptr, out_mask != nullptr,
+                                                      out_count != nullptr});
     }
     if (clear) {
         // leave the whole accumulator grid zeroed for the next frame (every thread clears only cells whose
@@ -554,8 +310,8 @@ int amt_bin_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const 
     const bool vec = (width % 2 == 0) && aligned16(lat_c) && aligned16(lon_c) && (elev == nullptr || aligned16(elev));
 #define AMT_BIN_CASE(T, N)                                                                  \
     do {                                                                                    \
-        if (vec) hipExtLaunchKernelGGL((k_bin_frame<T, N, true>), grid, block, 0, ctx->stream, t0, t1, 0, A);  \
-        else hipExtLaunchKernelGGL((k_bin_frame<T, N, false>), grid, block, 0, ctx->stream, t0, t1, 0, A);     \
+        if (vec) hipExtLaunchKernelGGL((k_bin_frame<T, N, true, false>), grid, block, 0, ctx->stream, t0, t1, 0, A);  \
+        else hipExtLaunchKernelGGL((k_bin_frame<T, N, false, false>), grid, block, 0, ctx->stream, t0, t1, 0, A);     \
     } while (0)
     const bool u8 = img_dtype == 1;
     hipEvent_t t0, t1;

@@ -761,6 +761,24 @@ class GenericMapping(BaseMapping):
         return m
 
 
+class MosaicMapping(GenericMapping):
+    """
+    The members of a :class:`MappingCollection` binned onto one grid (``auromat_amd.resample.resampleMosaic``): a
+    :class:`GenericMapping` plus ``source``, a masked int32 (h, w) array holding the index of the member each cell's
+    value comes from (masked where the cell is empty), and ``members``, the members' identifiers in collection order.
+    """
+
+    def __init__(self, lats, lons, latsCenter, lonsCenter, elev, alti, img, cameraPosGCRS, photoTime, identifier, source,
+                 members, metadata=None):
+        GenericMapping.__init__(self, lats, lons, latsCenter, lonsCenter, elev, alti, img, cameraPosGCRS, photoTime,
+                                identifier, metadata=metadata)
+        self._source = source
+        self._members = list(members)
+
+    source = property(lambda self: self._source)
+    members = property(lambda self: self._members)
+
+
 class MappingCollection(object):
     def __init__(self, mappings, identifier, mayOverlap=True):
         """

@@ -24,7 +24,7 @@ from .mapping.mapping import (BaseMapping, MappingCollection, convertMappingToSM
                               wrap_at_180)
 from .coordinates.geodesic import angularDistanceOnParallel
 from .util.histogram import make_axis
-from ._native import Context, host9, ptr, to_host
+from ._native import Context, MosaicMember, host9, ptr, to_host
 
 
 def plateCarreeResolution(boundingBox, arcsecPerPx):
@@ -232,6 +232,191 @@ def resampleMedianMLatMLT(mapping, **kw):
     See :func:`resampleMedian` for parameters.
     """
     return convertSMMappingToGeo(resampleMedian(convertMappingToSM(mapping), **kw))
+
+
+def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+    """
+    Bins every member of a :class:`MappingCollection` onto ONE grid and returns ONE mapping (:class:`MosaicMapping`), where
+    :func:`resample` of a collection grids each member on its own box.
+
+    The grid is the one :func:`resample` lays out for a single mapping with the collection's box
+    (``collection.boundingBox``; ``arcsecPerPx``: ``plateCarreeResolution(collection.boundingBox, arcsecPerPx)``), with the
+    date-line rule for every member when that box contains the discontinuity.  When ``containsPole`` is True (or None and a
+    member contains a pole) every member's centres are rotated by +90 deg about x and the box is the union of the extents of
+    the members' rotated outlines.  A member's pixel counts in a cell when ``resample`` would bin it there on the common
+    grid and the cell meets the member's own bounding box (in the plan's coordinates).
+
+    Overlaps follow ``collection.mayOverlap``: False — the mean over every member's pixels in the cell; True — the member
+    with the highest mean elevation in the cell wins it whole (the reference's drawing rule for overlapping mappings,
+    draw_helpers.py:128-178), the earlier member on a tie.  ``source`` holds the winning member's index per cell
+    (``members`` their identifiers).  Members are read through ``mapping.frame()``.
+
+    :raises ValueError: for an empty collection, members of different altitudes or image dtypes / channel counts, and a
+                        member without elevation when ``mayOverlap`` is True
+    :rtype: MosaicMapping
+    """
+    res = mosaic_frames(collection, pxPerDeg, arcsecPerPx, containsPole)
+    return _mosaic_mapping(collection, res)
+
+
+def resampleMosaicMLatMLT(collection, **kw):
+    """:func:`resampleMosaic` such that MLat/MLT become regular grids: the members converted to SM coordinates
+    (``convertMappingToSM``), the mosaic, and back (``convertSMMappingToGeo``), as :func:`resampleMedianMLatMLT` does.
+
+    See :func:`resampleMosaic` for parameters.
+    """
+    from .mapping.mapping import MosaicMapping
+    sm = MappingCollection([convertMappingToSM(m) for m in collection.mappings], collection.identifier,
+                           mayOverlap=collection.mayOverlap)
+    mosaic = resampleMosaic(sm, **kw)
+    geo = convertSMMappingToGeo(mosaic)
+    return MosaicMapping(geo.lats, geo.lons, geo.latsCenter, geo.lonsCenter, geo.elevation, geo.altitude, geo.img,
+                         geo.cameraPosGCRS, geo.photoTime, geo.identifier, mosaic.source, mosaic.members)
+
+
+def _mosaic_mapping(collection, res):
+    from .mapping.mapping import MosaicMapping
+    members = collection.mappings
+    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
+    elevation = ma.masked_invalid(res['mean'][:, :, -1], copy=False) if res['has_elev'] else None
+    source = ma.masked_array(res['source'], mask=res['source'] < 0)
+    photoTime = collection.photoTime
+    first = next(m for m in members if m.photoTime == photoTime)
+    return MosaicMapping(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, res['altitude'], img,
+                         first.cameraPosGCRS, photoTime, collection.identifier, source, [m.identifier for m in members])
+
+
+def mosaic_axis_window(edges, lo, hi):
+    """(first, count) of the cells [edges[c], edges[c+1]] that meet [lo, hi]: edges[c + 1] >= lo and edges[c] <= hi (the
+    edges are np.linspace's, the numbers the device's bin_index compares with)."""
+    edges = np.asarray(edges, dtype=np.float64)
+    n = len(edges) - 1
+    if not (hi >= lo):
+        return 0, 0
+    c0 = int(np.searchsorted(edges[1:], lo, side='left'))        # first c with edges[c + 1] >= lo
+    c1 = int(np.searchsorted(edges[:-1], hi, side='right')) - 1  # last c with edges[c] <= hi
+    c0, c1 = max(c0, 0), min(c1, n - 1)
+    return (c0, c1 - c0 + 1) if c1 >= c0 else (0, 0)
+
+
+def mosaic_plan(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+    """The host side of :func:`resampleMosaic`: checks the members and lays out the common grid and every member's window
+    (:func:`mosaic_layout`).  Returns mosaic_layout's dict plus altitude, rule and the members' frames."""
+    members = list(collection.mappings)
+    if not members:
+        raise ValueError('resampleMosaic: the collection %r is empty' % (collection.identifier,))
+    altitudes = [m.altitude for m in members]
+    if any(a != altitudes[0] for a in altitudes):
+        raise ValueError('resampleMosaic: the members differ in altitude: %s' %
+                         ', '.join('%s: %s km' % (m.identifier, m.altitude) for m in members))
+    frames = [m.frame() for m in members]
+    kinds = [(fd.img_dtype_code or 0, fd.nchan) for fd in frames]
+    if any(k != kinds[0] for k in kinds):
+        raise ValueError('resampleMosaic: the members differ in image dtype or channel count: %s' %
+                         ', '.join('%s: %s x %d' % (m.identifier, fd.img_dtype, fd.nchan) for m, fd in zip(members, frames)))
+    rule = 1 if collection.mayOverlap else 0
+    if rule:
+        missing = [m.identifier for m, fd in zip(members, frames) if fd.elev is None]
+        if missing:
+            raise ValueError('resampleMosaic: mayOverlap=True (highest elevation wins) needs every member\'s elevation; '
+                             'without: %s' % ', '.join(str(i) for i in missing))
+    altitude = altitudes[0]
+    pole = any(m.containsPole for m in members) if containsPole is None else bool(containsPole)
+    poleBoxes = None
+    if pole:
+        poleBoxes = []
+        for m in members:
+            outline = np.asarray(m.outline, dtype=np.float64)
+            ola, olo = _rotate_pole_host(outline[:, 0], outline[:, 1], altitude, 90)
+            poleBoxes.append((ola.min(), ola.max(), olo.min(), olo.max()))
+    plan = mosaic_layout([m.boundingBox for m in members], pxPerDeg, arcsecPerPx, poleBoxes)
+    plan.update(altitude=altitude, rule=rule, frames=frames)
+    return plan
+
+
+def mosaic_layout(memberBoxes, pxPerDeg=25, arcsecPerPx=None, poleBoxes=None):
+    """The common grid and the member windows of a mosaic, on the host alone (see :func:`resampleMosaic`).
+
+    :param memberBoxes: every member's BoundingBox (the collection's box is their merged box)
+    :param poleBoxes: the pole plan: (latMin, latMax, lonMin, lonMax) of every member's rotated outline; None: the
+                      geodetic plan (with the date-line rule when the merged box contains the discontinuity)
+    :return: dict(grid, pole, discontinuity, lon_wrap, boxes [per member in the plan's coordinates; lonMin = None: all
+             longitudes], windows [(x0, y0, nx, ny) per member, cells of the grid; (0, 0, 0, 0) when empty])
+    """
+    from .mapping.mapping import BoundingBox
+    merged = BoundingBox.mergedBoundingBoxes(memberBoxes)
+    disc, lon_wrap = False, 0
+    if poleBoxes is not None:
+        boxes = [tuple(b) for b in poleBoxes]
+        latMin, latMax = min(b[0] for b in boxes), max(b[1] for b in boxes)
+        lonMin, lonMax = min(b[2] for b in boxes), max(b[3] for b in boxes)
+    else:
+        latMin, latMax, lonMin, lonMax = merged.latSouth, merged.latNorth, merged.lonWest, merged.lonEast
+        disc = merged.containsDiscontinuity
+        boxes = []
+        for b in memberBoxes:
+            west, east = b.lonWest, b.lonEast
+            if disc:
+                west, east = wrap_at_180(west + 180), wrap_at_180(east + 180)
+            # a member box that crosses the plan's discontinuity holds both ends of the longitude axis
+            boxes.append((b.latSouth, b.latNorth, west, east) if west <= east else (b.latSouth, b.latNorth, None, None))
+        if disc:
+            lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
+            lon_wrap = 1
+    ppd = plateCarreeResolution(merged, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+    grid = cached_grid(ppd, latMin, latMax, lonMin, lonMax)
+    windows = []
+    for la0, la1, lo0, lo1 in boxes:
+        x0, nx = (0, grid.nx) if lo0 is None else mosaic_axis_window(grid.xedges, lo0, lo1)
+        y0, ny = mosaic_axis_window(grid.yedges, la0, la1)
+        windows.append((x0, y0, nx, ny) if nx and ny else (0, 0, 0, 0))
+    return dict(grid=grid, pole=poleBoxes is not None, discontinuity=disc, lon_wrap=lon_wrap, boxes=boxes, windows=windows)
+
+
+def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+    """The mosaic of a collection's device frames on the common grid (``amt_mosaic_frames``): see :func:`resampleMosaic`.
+
+    :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mean (ny,nx,C+1), img (ny,nx,C), mask (ny,nx),
+                  count (ny,nx), source (ny,nx) int32 [-1: empty], has_elev, plan)
+    """
+    import torch
+    plan = mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole)
+    grid, frames, altitude = plan['grid'], plan['frames'], plan['altitude']
+    ctx = frames[0].ctx
+    fd0 = frames[0]
+    nch = fd0.nchan
+    keep = []                    # device arrays the call reads (the rotated centres of the pole plan)
+    table = (MosaicMember * len(frames))()
+    for i, (fd, (x0, y0, wnx, wny)) in enumerate(zip(frames, plan['windows'])):
+        lat_c, lon_c = fd.lat_c, fd.lon_c
+        if plan['pole']:
+            lat_c, lon_c = _rotate_pole_dev(ctx, fd.lat_c, fd.lon_c, altitude, 90)
+            keep.append((lat_c, lon_c))
+        t = table[i]
+        addr = [None if a is None else ptr(a).value for a in (lat_c, lon_c, fd.elev, fd.img if nch else None,
+                                                              fd.center_mask)]
+        t.lat_c, t.lon_c, t.elev, t.img, t.center_mask = addr
+        t.height, t.width = fd.height, fd.width
+        t.win_x0, t.win_y0, t.win_nx, t.win_ny = x0, y0, wnx, wny
+    xaxis, yaxis = grid.axes(ctx)
+    mean = ctx.empty((grid.ny, grid.nx, nch + 1))
+    img = ctx.empty((grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd0.img_dtype_code != 2 else torch.int16)
+    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
+    count = ctx.empty((grid.ny, grid.nx))
+    source = ctx.empty((grid.ny, grid.nx), torch.int32)
+    if not nch:
+        img.zero_()
+    ctx.call('amt_mosaic_frames', table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'), C.byref(xaxis),
+             C.byref(yaxis), plan['lon_wrap'], plan['rule'], ptr(mean), ptr(img) if nch else None, ptr(mask), ptr(count),
+             ptr(source))
+    has_elev = all(fd.elev is not None for fd in frames)
+    out = dict(has_elev=has_elev, grid=grid, contains_pole=plan['pole'], contains_discontinuity=plan['discontinuity'],
+               altitude=altitude, plan=plan)
+    out.update(grid_coordinates(out))
+    out.update(mean=to_host(mean), img=to_host(img, dtype=fd0.img_dtype if nch else np.uint8),
+               mask=to_host(mask).astype(bool), count=to_host(count), source=to_host(source, dtype=np.int32))
+    del keep                     # (after the read-back above: the kernels are done with them)
+    return out
 
 
 def resample_frame_median(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,

@@ -41,7 +41,8 @@ extern "C" {
 /* 7: amt_median_frame (median binning, auromat_amd.resample.resampleMedian) */
 /* 8: amt_median_frame_async (the median pass without a read-back); amt_run_config.statistic (median sequences in the runner, in
  *    place of reserved_); amt_pipe_set_plan(pipe, 2) */
-#define AMT_ABI_VERSION 8
+/* 9: amt_mosaic_frames, amt_mosaic_member (the members of a collection binned onto one grid, auromat_amd.resample.resampleMosaic) */
+#define AMT_ABI_VERSION 9
 
 #define AMT_OK 0
 #define AMT_EINVAL (-1)   /* bad argument (NULL pointer, negative size, unsupported dtype ...) */
@@ -515,6 +516,32 @@ int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_
                            int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                            double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
                            int lon_from_mlt, double* median, void* out_img, uint8_t* out_mask, double* out_count);
+/* Mosaics (ABI v9; auromat_amd.resample.resampleMosaic): the members of a collection binned onto ONE grid.  A pixel of member i
+ * counts in cell c when amt_bin_frame on the common axes would bin it into c (same bin_index, masks, NaN and right-edge rules)
+ * AND c lies in the member's window [win_x0, win_x0 + win_nx) x [win_y0, win_y0 + win_ny) (cells of the common grid, x along
+ * xaxis, y along the ascending yaxis; an empty window bins nothing).  Cell value by `rule`:
+ *   0 (union): the mean over every member's pixels in the cell (the integer sums added, then amt_bin_frame_finalize's
+ *     arithmetic); out_source: the lowest member index present;
+ *   1 (highest elevation wins, the reference's rule for overlapping mappings): of the members with pixels in the cell, the one
+ *     whose float64 mean elevation (computed as amt_bin_frame_finalize computes it) is largest, the lower index on a tie; the
+ *     cell takes that member's mean, image, count and mask bit for bit.  Every member needs `elev`.
+ * Outputs in the layout of amt_bin_frame_finalize (rows north to south): mean (ny, nx, nchan+1), out_img, out_mask, out_count
+ * (each optional) and out_source (optional): int32 (ny, nx), the member index, -1 where the cell is empty.
+ * A fixed number of launches whatever n_members is; the member table is uploaded from the host array and the accumulators
+ * ((nchan + 2) x 8 bytes per window cell of every member) live in the context's workspace.  The call only enqueues work: no
+ * read-back and no host wait; inputs and outputs as for amt_median_frame_async. */
+typedef struct amt_mosaic_member {
+    const double* lat_c;
+    const double* lon_c;
+    const double* elev;               /* may be NULL only for rule 0 */
+    const void* img;                  /* may be NULL when nchan == 0 */
+    const uint8_t* center_mask;       /* optional */
+    int32_t height, width;
+    int32_t win_x0, win_y0, win_nx, win_ny;   /* window in cells of the common grid */
+} amt_mosaic_member;
+int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype, int32_t nchan,
+                      double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int32_t rule,
+                      double* mean, void* out_img, uint8_t* out_mask, double* out_count, int32_t* out_source);
 /* Same for float accumulators of amt_hist2d_accumulate: mean[k] = sums[k]/count, NaN where empty,
  * transposed + flipped to (ny, nx, nweights). */
 int amt_hist2d_finalize_mean(amt_ctx* ctx, const double* count, const double* const* sums, int32_t nweights,

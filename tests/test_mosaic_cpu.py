@@ -1,0 +1,136 @@
+"""Mosaic binning without a GPU: the NumPy statement of the feature (tests/_mosaic_oracle.py) against the oracle's
+resample and histogram, the overlap rules, the host layout of the common grid and the member windows, and the C struct."""
+import ctypes as C
+
+import numpy as np
+
+import _mosaic_oracle as MO
+
+
+def _points(rng, lat0, lon0, n=20000, span=4.0):
+    lat = rng.uniform(lat0, lat0 + span, n)
+    lon = rng.uniform(lon0, lon0 + 2 * span, n)
+    lat[::991] = np.nan
+    img = rng.randint(0, 256, (n, 3)).astype(np.float64)
+    el = rng.uniform(5, 90, n)
+    return lat, lon, img, el
+
+
+def _edges(ppd, box):
+    from auromat_amd.resample import cached_grid
+    g = cached_grid((ppd, ppd), *box)
+    return g, g.xedges, g.yedges
+
+
+def test_one_member_equals_the_oracles_resample_mean():
+    from oracle import ref_numpy as O
+    rng = np.random.RandomState(0)
+    lat, lon, img, el = _points(rng, 60.0, 10.0)
+    box = (np.nanmin(lat), np.nanmax(lat), np.nanmin(lon), np.nanmax(lon))
+    g, xe, ye = _edges(10, box)
+    data = np.concatenate([img, el[:, None]], axis=1)
+    want = O.resample_mean(lat[:, None], lon[:, None], 110, data[:, None, :], None, (box[0], box[2], box[1], box[3]),
+                           (10, 10))
+    got = MO.mosaic([(lon, lat, ~np.isnan(lat), data, (0, 0, g.nx, g.ny))], xe, ye, 1, 3)
+    assert np.array_equal(got['count'], want['count'])
+    assert np.array_equal(got['mean'][..., :3], want['data'][..., :3], equal_nan=True)
+    assert np.allclose(got['mean'][..., 3], want['data'][..., 3], rtol=0, atol=1e-11, equal_nan=True)
+    assert np.array_equal(got['source'] >= 0, want['count'] > 0)
+
+
+def test_union_equals_the_histogram_of_the_concatenated_pixels():
+    from oracle import ref_numpy as O
+    rng = np.random.RandomState(1)
+    a, b = _points(rng, 60.0, 10.0), _points(rng, 61.5, 12.0)
+    g, xe, ye = _edges(10, (60.0, 65.5, 10.0, 20.0))
+    full = (0, 0, g.nx, g.ny)
+    members = [(m[1], m[0], ~np.isnan(m[0]), np.concatenate([m[2], m[3][:, None]], 1), full) for m in (a, b)]
+    got = MO.mosaic(members, xe, ye, 0, 3)
+    cat = [np.concatenate([m[k] for m in members]) for k in range(4)]
+    count, sums = MO.member_planes(cat[0], cat[1], cat[2], cat[3], xe, ye)
+    assert np.array_equal(got['count'], np.flipud(count.T))
+    with np.errstate(invalid='ignore'):
+        want = np.dstack([np.flipud(sp.T) for sp in sums]) / np.flipud(count.T)[..., None]
+    assert np.allclose(got['mean'], want, rtol=1e-13, atol=0, equal_nan=True)
+    # the source is the lowest member present: member 0 wherever it has pixels
+    assert np.array_equal(got['source'] == 0, MO.member_planes(*members[0][:4], xe, ye)[0].T[::-1] > 0)
+
+
+def test_planted_tie_goes_to_the_lower_index():
+    rng = np.random.RandomState(2)
+    lat, lon, img, el = _points(rng, 60.0, 10.0, n=5000)
+    g, xe, ye = _edges(10, (60.0, 64.0, 10.0, 18.0))
+    full = (0, 0, g.nx, g.ny)
+    data = np.concatenate([img, el[:, None]], 1)
+    other = np.concatenate([255 - img, el[:, None]], 1)        # the same elevations, other pixels
+    got = MO.mosaic([(lon, lat, ~np.isnan(lat), data, full), (lon, lat, ~np.isnan(lat), other, full)], xe, ye, 1, 3)
+    filled = got['count'] > 0
+    assert filled.any() and (got['source'][filled] == 0).all()
+    # one cell where member 1 is higher by a hair wins for member 1
+    higher = np.concatenate([img, el[:, None] + 1e-9], 1)
+    got = MO.mosaic([(lon, lat, ~np.isnan(lat), data, full), (lon, lat, ~np.isnan(lat), higher, full)], xe, ye, 1, 3)
+    assert (got['source'][filled] == 1).all()
+
+
+def test_window_edges_and_member_boxes_across_the_date_line():
+    from auromat_amd.mapping.mapping import BoundingBox as B
+    from auromat_amd.resample import mosaic_axis_window, mosaic_layout
+    e = np.linspace(0.0, 10.0, 11)
+    assert mosaic_axis_window(e, 2.0, 2.0) == (1, 2)          # on an interior edge: both cells meet it
+    assert mosaic_axis_window(e, 2.5, 3.5) == (2, 2)
+    assert mosaic_axis_window(e, -5, 20) == (0, 10)
+    assert mosaic_axis_window(e, 11, 12) == (0, 0)
+    west, east = B(-10, 170, 0, 179.5), B(-5, -179, 5, -170)
+    p = mosaic_layout([west, east], 10)
+    g = p['grid']
+    assert p['discontinuity'] and p['lon_wrap'] == 1
+    (x0, y0, nx, ny), (x1, y1, nx1, ny1) = p['windows']
+    # west of the date line -> the western part of the wrapped axis, east of it -> the eastern part
+    assert x0 == 0 and x0 + nx <= x1 and x1 + nx1 == g.nx
+    assert g.xedges[x0 + nx] >= -0.5 and g.xedges[x1] <= 1.0
+    assert y0 == 0 and y1 > 0
+
+
+def test_pole_plan_boxes_are_the_union_of_rotated_outline_extents():
+    from auromat_amd.mapping.mapping import BoundingBox as B
+    from auromat_amd.resample import mosaic_layout
+    p = mosaic_layout([B(80, -180, 90, 180), B(75, 10, 85, 40)], 10,
+                      poleBoxes=[(-5.0, 5.0, -20.0, 3.0), (-12.0, -2.0, 1.0, 14.0)])
+    g = p['grid']
+    assert p['pole'] and not p['discontinuity'] and p['lon_wrap'] == 0
+    # the grid resample lays out for the union box: global nodes around it, the outer half cells dropped
+    for lo, hi, edges in ((-12.0, 5.0, g.yedges), (-20.0, 14.0, g.xedges)):
+        assert abs(edges[0] - lo) <= 0.1 and abs(edges[-1] - hi) <= 0.1
+    (x0, y0, nx, ny), (x1, y1, nx1, ny1) = p['windows']
+    assert x0 == 0 and y1 == 0 and x1 + nx1 == g.nx and y0 + ny == g.ny
+
+
+def test_arcsec_resolution_comes_from_the_merged_box():
+    from auromat_amd.mapping.mapping import BoundingBox as B
+    from auromat_amd.resample import cached_grid, mosaic_layout, plateCarreeResolution
+    boxes = [B(60, 10, 70, 30), B(65, 20, 72, 40)]
+    p = mosaic_layout(boxes, arcsecPerPx=100)
+    lat_ppd, lon_ppd = plateCarreeResolution(B.mergedBoundingBoxes(boxes), 100)
+    g = p['grid']
+    want = cached_grid((lat_ppd, lon_ppd), 60, 72, 10, 40)
+    assert (g.nx, g.ny, g.lonStep, g.latStep, g.lon0, g.lat0) == (want.nx, want.ny, want.lonStep, want.latStep, want.lon0,
+                                                                  want.lat0)
+    for (x0, y0, nx, ny), b in zip(p['windows'], boxes):
+        # the cells whose extent meets the member's box: the neighbours outside do not
+        assert g.xedges[x0 + 1] >= b.lonWest and (x0 == 0 or g.xedges[x0] < b.lonWest)
+        assert g.xedges[x0 + nx - 1] <= b.lonEast and (x0 + nx == g.nx or g.xedges[x0 + nx] > b.lonEast)
+        assert g.yedges[y0 + 1] >= b.latSouth and (y0 == 0 or g.yedges[y0] < b.latSouth)
+        assert g.yedges[y0 + ny - 1] <= b.latNorth and (y0 + ny == g.ny or g.yedges[y0 + ny] > b.latNorth)
+
+
+def test_struct_size_matches_the_header():
+    from auromat_amd._native import ABI_VERSION, MosaicMember, _SIGNATURES
+    assert C.sizeof(MosaicMember) == 5 * 8 + 6 * 4
+    assert ABI_VERSION == 9 and 'amt_mosaic_frames' in _SIGNATURES
+
+
+def test_public_names():
+    from auromat_amd.mapping.mapping import GenericMapping, MosaicMapping
+    from auromat_amd.resample import resampleMosaic, resampleMosaicMLatMLT
+    assert issubclass(MosaicMapping, GenericMapping)
+    assert callable(resampleMosaic) and callable(resampleMosaicMLatMLT)
