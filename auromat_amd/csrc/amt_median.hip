@@ -8,7 +8,8 @@
 //   k_med_fill     scatter of the KEYS into contiguous per-cell segments, one plane per channel: u16 channel values,
 //                  elevation as an order-preserving u64 of its float64 bits; positions reserved per run of lanes
 //   k_med_small    one wave per cell: outputs of every cell (count, mask, empty cells) and, for cells of <= 64 pixels,
-//                  a 64-lane bitonic sort per plane; larger cells are listed for the two tiers below
+//                  a 64-lane bitonic sort per plane; larger cells are listed for the two tiers below (a large cell's
+//                  histograms and tickets are zeroed as it is listed)
 //   k_med_medium   one workgroup per cell of <= kLargeMin keys: radix select in LDS (8-bit digits: one pass for u8,
 //                  two for u16, eight for the elevation key)
 //   k_med_large_*  cells above kLargeMin: the same radix select over many workgroups per cell, digit histograms in
@@ -17,6 +18,9 @@
 // fixed grid walks the device-side list of medium cells, and the large tier as k_med_large_step (one launch per digit
 // position, all planes and large cells in it; the last workgroup to finish a cell's histogram picks the digit) and
 // k_med_large_last.  Each of them reads the tier sizes from device memory and returns at once when its tier is empty.
+// Same bits from both forms of the upper tiers, but neither replaces the other (profiles/REJECTED.md): every workgroup
+// of the ticket form visits the large cells one after the other (7 x the time of the launch pairs with 51 large cells),
+// and a workgroup of the walk waits for one more load than one of k_med_medium.
 // Both tiers select k_lo = (n-1)/2 and get k_hi = n/2 from the same pass: it is k_lo's value when the keys <= that
 // value are more than k_hi, else the smallest key above it (one more pass).  Even counts average the two in float64.
 #include "amt_common.h"
@@ -326,9 +330,8 @@ struct tier_counters {
 };
 
 // One wave per cell: every cell's count and mask, NaN / 0 for empty ones, the median of cells of <= 64 keys; the
-// others are appended to the medium or large list.  CLEAR (amt_median_frame_async): the wave that lists a large cell
-// also zeroes that cell's digit histograms and tickets (nplane * 256 + nplane words from `lclear` on).
-template <bool CLEAR>
+// others are appended to the medium or large list.  The wave that lists a large cell also zeroes that cell's digit
+// histograms and tickets (nplane * 256 + nplane words from `lclear` on).
 __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restrict__ medium, int* __restrict__ large,
                                                      tier_counters* __restrict__ tiers, unsigned* __restrict__ lclear) {
     const int lane = threadIdx.x & 63;
@@ -362,7 +365,7 @@ __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restric
                 }
             }
         }
-        if (CLEAR && cnt > (unsigned)kLargeMin) {                  // (wave-uniform)
+        if (cnt > (unsigned)kLargeMin) {                           // (wave-uniform)
             listed = __shfl(listed, 0);
             const int words = nplane * 257;
             for (int q = lane; q < words; q += 64) lclear[(int64_t)listed * words + q] = 0u;
@@ -521,6 +524,7 @@ __global__ __launch_bounds__(kBlock) void k_med_medium_walk(out_args O, const in
 }
 
 // ---- large tier: one plane at a time, one launch pair per digit ----
+// (ghist: 256 words per large cell from the start of `lh`, zero on entry and after every k_med_large_digit)
 struct large_state {
     unsigned long long prefix, min_above;
     unsigned k, less, eq, pad;
@@ -614,7 +618,7 @@ __global__ void k_med_large_put(const out_args O, const int* __restrict__ large,
 
 // ---- large tier without a read-back (amt_median_frame_async) ----
 // Per large cell l and plane p: a large_state, a 256-bin histogram and a ticket, in `lh` as l * nplane * 257 words:
-// the histograms of its planes, then their tickets (zeroed by k_med_small<true> when it lists the cell).  A fixed grid
+// the histograms of its planes, then their tickets (zeroed by k_med_small when it lists the cell).  A fixed grid
 // of workgroups; each one takes chunks blockIdx.x, blockIdx.x + gridDim.x, ... of every large cell.  After adding its
 // share to a histogram a workgroup takes a ticket; the one that draws the last ticket reads the histogram, advances the
 // state and clears both for the next launch.  Nothing waits for another workgroup.
@@ -769,13 +773,13 @@ struct median_pass {
     int* medium;
     int* large;
     large_state* state;
-    unsigned* lh;                       // amt_median_frame: the histograms; the async pass: histograms and tickets
+    unsigned* lh;                       // per large cell: the histograms of its planes, then their tickets
 };
 
 int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
                  int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                  double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int lon_from_mlt,
-                 double* median, void* out_img, uint8_t* out_mask, double* out_count, bool async, median_pass* M) {
+                 double* median, void* out_img, uint8_t* out_mask, double* out_count, median_pass* M) {
     AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && median, "NULL argument");
     AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
     AMT_REQUIRE(ctx, (int64_t)height * width < 2147483647LL, "frame too large for 32-bit pixel indices");
@@ -804,14 +808,11 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
     const int nb = (int)((cells + kScanTile - 1) / kScanTile);
     const int64_t large_cap = n / (kLargeMin + 1) + 1;
     const int nplane = nchan + (elev ? 1 : 0);
-    // large-tier state and histograms per large cell: one plane at a time (amt_median_frame) or all of them (async; with
-    // a ticket per plane)
-    const int64_t per_large = async ? nplane : 1;
-    const int64_t lh_words = async ? (int64_t)nplane * 257 : 256;
-
     // workspace: count, cursor [cells] | tier counters | offset [cells + 1] | block sums [nb + 1] | medium, large lists
-    // [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state [large_cap * per_large] and
-    // histograms [large_cap * lh_words]
+    // [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state [large_cap * nplane] and
+    // histograms with their tickets [large_cap * nplane * 257]: every plane of every large cell, as amt_median_frame_async
+    // has them in flight (733 cells x 4 planes x 1060 bytes = 3.1 MB at 12 Mpixel, beside ~18 bytes per pixel);
+    // amt_median_frame, one plane at a time, uses the first large_cap states and large_cap * 256 words.
     size_t at = 0;
     const size_t o_count = at;   at = align256(at + (size_t)2 * cells * sizeof(unsigned));
     const size_t o_tiers = at;   at = align256(at + sizeof(tier_counters));
@@ -822,8 +823,8 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
     const size_t o_cellof = at;  at = align256(at + (size_t)n * sizeof(int));
     const size_t o_keys16 = at;  at = align256(at + (size_t)nchan * n * sizeof(uint16_t));
     const size_t o_keys64 = at;  at = align256(at + (elev ? (size_t)n * sizeof(unsigned long long) : 0));
-    const size_t o_state = at;   at = align256(at + (size_t)(large_cap * per_large) * sizeof(large_state));
-    const size_t o_ghist = at;   at = align256(at + (size_t)(large_cap * lh_words) * sizeof(unsigned));
+    const size_t o_state = at;   at = align256(at + (size_t)(large_cap * nplane) * sizeof(large_state));
+    const size_t o_ghist = at;   at = align256(at + (size_t)(large_cap * nplane * 257) * sizeof(unsigned));
     char* ws = static_cast<char*>(amt_workspace(ctx, at));
     if (ws == nullptr) {
         ctx->last_error = "amt_median_frame: workspace allocation failed";
@@ -870,12 +871,8 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
     O.out_img = nchan ? out_img : nullptr;
     O.out_mask = out_mask;
     O.out_count = out_count;
-    if (async)
-        hipLaunchKernelGGL(k_med_small<true>, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, M->medium, M->large,
-                           M->tiers, M->lh);
-    else
-        hipLaunchKernelGGL(k_med_small<false>, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, M->medium, M->large,
-                           M->tiers, nullptr);
+    hipLaunchKernelGGL(k_med_small, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, M->medium, M->large, M->tiers,
+                       M->lh);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
@@ -891,7 +888,7 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     AMT_CHECK_CTX(ctx);
     median_pass M;
     if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
-                              yaxis, lon_wrap, 0, median, out_img, out_mask, out_count, false, &M))
+                              yaxis, lon_wrap, 0, median, out_img, out_mask, out_count, &M))
         return rc;
     const out_args& O = M.O;
     int* medium = M.medium;
@@ -910,7 +907,7 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
         const int nl = (int)t.n_large;
         const dim3 chunks((t.max_large + kChunk - 1) / kChunk, (unsigned)nl);
         const dim3 per_cell((nl + kBlock - 1) / kBlock);
-        AMT_HIP(ctx, hipMemsetAsync(ghist, 0, (size_t)nl * 256 * sizeof(unsigned), ctx->stream));
+        // (k_med_small has zeroed nplane * 257 >= 256 words of ghist for each of the nl cells it listed)
         for (int p = 0; p < nplane; ++p) {
             hipLaunchKernelGGL(k_med_large_init, per_cell, dim3(kBlock), 0, ctx->stream, O, large, nl, state);
             const int bits = p == nchan ? 64 : (img_dtype == 1 ? 8 : 16);
@@ -933,7 +930,7 @@ int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_
     AMT_CHECK_CTX(ctx);
     median_pass M;
     if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
-                              yaxis, lon_wrap, lon_from_mlt, median, out_img, out_mask, out_count, true, &M))
+                              yaxis, lon_wrap, lon_from_mlt, median, out_img, out_mask, out_count, &M))
         return rc;
     // fixed grids from what the host knows: a medium cell has more than kSmallMax pixels, a large one more than kLargeMin;
     // the workgroups read the tier sizes from device memory

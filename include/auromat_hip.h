@@ -497,7 +497,8 @@ int amt_bin_frame_finalize_window(amt_ctx* ctx, const uint64_t* acc, int32_t acc
  * Outputs in the layout of amt_bin_frame_finalize (rows north to south): median (ny, nx, nchan+1) float64, NaN where
  * empty; out_img (optional): (ny, nx, nchan) of img_dtype, round-half-even of the median (0 where empty); out_mask
  * (optional): 1 where empty; out_count (optional): pixels per cell.  Uses the context's workspace (about 6 + 2*nchan
- * (+8 with elev) bytes per pixel + 16 per cell).  Synchronises once: it reads how many cells hold more than 64 pixels. */
+ * (+8 with elev) bytes per pixel + 16 per cell, and 1060 bytes per channel for every 16385 pixels: the size
+ * amt_median_frame_async needs for the same arguments).  Synchronises once: it reads how many cells hold more than 64 pixels. */
 int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
                      int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                      double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, double* median,
