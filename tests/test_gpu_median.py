@@ -1,7 +1,9 @@
 """
 Median binning on the MI355X (auromat_amd.resample.resampleMedian, amt_median_frame) against the NumPy statement of the
 feature (tests/_median_oracle.py) applied to the mapping's own arrays: the same pixel set as the mean, np.median per cell
-and channel, exact — image channels equal, elevation bit-equal — for cells of one pixel up to more than a million.
+and channel, exact — image channels equal, elevation bit-equal — for cells of one pixel up to more than a million, as the
+camera frames happen to fill them.  The tier boundaries, the key patterns and the pixel orders that no frame controls are
+in tests/test_gpu_median_cells.py.
 """
 import os
 from datetime import datetime

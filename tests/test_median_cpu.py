@@ -85,3 +85,183 @@ def test_resample_median_method_still_raises():
         resample(None, method='median')
     with pytest.raises(ValueError):
         __import__('auromat_amd.resample', fromlist=['x']).resampleMedian(None)
+
+
+# ---- the constructed cases of tests/_median_cases.py: what the GPU tests (test_gpu_median_cells.py) rely on -------------
+import _median_cases as K
+
+
+def test_case_constants_are_the_sources():
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'auromat_amd', 'csrc', 'amt_median.hip')).read()
+    for name, value in (('kSmallMax', K.K_SMALL_MAX), ('kLargeMin', K.K_LARGE_MIN), ('kChunk', K.K_CHUNK),
+                        ('kBlock', K.K_BLOCK)):
+        found = re.findall(r'constexpr int %s = (\d+);' % name, src)
+        assert found == [str(value)], (name, found)
+    assert K.COUNTS == (0, 1, 2, 3, 63, 64, 65, 66, 255, 256, 257, 4095, 4096, 4097, 16383, 16384, 16385, 16386, 20480, 20481,
+                        65537)
+    assert K.BIG == 300001
+
+
+@pytest.mark.parametrize('dtype', [np.uint8, np.uint16])
+def test_tier_table_holds_what_it_promises(dtype):
+    case = K.tier_table(dtype, 4, True)
+    ny, nx = case.shape
+    assert (ny, nx) == (6, len(K.COUNTS) + 1)
+    # the frame: odd width, and a pixel count that is no multiple of 4 (a lane's quad) nor of 256
+    assert case.width % 2 == 1 and (case.height * case.width) % 4 != 0 and (case.height * case.width) % 256 != 0
+    want = K.table_expected(dtype, 4, True)
+    # every count in every row (the output's rows run north to south: row r of the table is output row ny - 1 - r)
+    count = want['count'][::-1]
+    for r in range(ny):
+        assert tuple(count[r, :-1].astype(int)) == K.COUNTS, r
+        assert count[r, -1] == (K.BIG if r == K.BIG_ROW else 0)
+    assert count.sum() > 1.41e6
+    # every pixel of a cell sits at the cell's centre; every plane meets every family at every count
+    ok = case.flat() >= 0
+    assert np.array_equal(case.lat[ok] % 1, np.full(ok.sum(), 0.5)) and np.array_equal(case.lon[ok] % 1, np.full(ok.sum(), 0.5))
+    assert not np.isnan(case.elev[ok]).any() and np.isnan(case.elev[~ok]).any()
+    assert (case.elev[ok] < 0).any() and (case.mask[~ok] == 1).any()
+    for plane in range(5):
+        assert sorted((r + plane) % 6 for r in range(6)) == list(range(6))
+    p = K.table_promises(dtype)
+    for tier in K.TIERS:
+        for kind in ('int', 'float64'):
+            assert p['equal'][kind, tier] >= 1, (kind, tier, p)
+            assert p['differ'][kind, tier] >= 1, (kind, tier, p)
+        assert p['odd_gap'][tier] > 0, (tier, p)
+    assert p['opposite_signs'] >= 1 and p['half_even_differs'] >= 1, p
+    # np.median per cell and the lexsort form agree on it
+    other = K.expected(case, loop=False)
+    for key in ('median', 'img', 'mask', 'count'):
+        assert np.array_equal(want[key], other[key], equal_nan=True), key
+    # fewer channels and no elevation are slices of the same result
+    sub = K.table_expected(dtype, 2, False)
+    assert sub['median'].shape == (ny, nx, 3) and np.isnan(sub['median'][..., 2]).all()
+    assert np.array_equal(sub['median'][..., :2], want['median'][..., :2], equal_nan=True)
+
+
+@pytest.mark.parametrize('dtype', [np.uint8, np.uint16])
+def test_tier_table_orders_are_permutations_of_one_multiset_per_cell(dtype):
+    base = K.tier_table(dtype, 4, True, 'sorted')
+    n = base.lat.size
+    for order in K.ORDERS:
+        assert np.array_equal(np.sort(K.table_order(order)), np.arange(n)), order
+
+    def per_cell(case):
+        """the cells of the binned pixels, and every plane's values sorted within each cell"""
+        flat = case.flat()
+        f = flat[flat >= 0]
+        planes = [case.img[:, ch] for ch in range(4)] + [case.elev]
+        return [np.sort(f)] + [v[flat >= 0][np.lexsort((v[flat >= 0], f))] for v in planes]
+
+    want = per_cell(base)
+    for order in ('shuffled', 'runs'):
+        got = per_cell(K.tier_table(dtype, 4, True, order))
+        for a, b in zip(got, want):
+            assert np.array_equal(a, b), order
+    # 'shuffled' leaves hardly a lane's quad in one cell; 'runs' has an excluded pixel in every 97th position
+    flat = K.tier_table(dtype, 4, True, 'shuffled').flat()
+    quads = flat[:n - n % 4].reshape(-1, 4)
+    assert ((quads != quads[:, :1]).any(axis=1)).mean() > 0.9
+    flat = K.tier_table(dtype, 4, True, 'runs').flat()
+    assert (flat[96:1000000:97] == -1).all()
+    lengths = np.diff(np.flatnonzero(np.diff(flat[:100000]) != 0))
+    assert set([1, 2, 3, 5, 7, 64]) <= set(lengths.tolist())
+
+
+@pytest.mark.parametrize('coord', ['plain', 'wrap', 'mlt'])
+@pytest.mark.parametrize('axis', ['uniform', 'nonuniform'])
+def test_membership_cases(axis, coord):
+    from oracle import ref_numpy as O
+    counts = {}
+    for mode in ('nothreshold', 'threshold', 'nomask'):
+        case = K.membership(np.uint8, axis, mode, coord)
+        assert case.height * case.width % 2 == 1 and case.lat.size > 20000 and case.shape == (6, 8)
+        flat, keep = case.flat(), case.keep()
+        assert not np.isnan(case.elev[flat >= 0]).any()
+        assert np.isnan(case.elev).sum() > 20 and np.isnan(case.lat).sum() > 15 and np.isnan(case.lon).sum() > 15
+        want = K.expected(case)
+        other = K.expected(case, loop=False)
+        for key in ('median', 'img', 'mask', 'count'):
+            assert np.array_equal(want[key], other[key], equal_nan=True), (mode, key)
+        # the membership is the oracle's histogram2d (pinned to the reference), edge points and all
+        H, _, _ = O.histogram2d(case.lon_binned[keep], case.lat[keep], [case.xedges, case.yedges])
+        assert np.array_equal(want['count'], H.T[::-1]), mode
+        counts[mode] = want['count'].sum()
+        assert (want['count'] > 0).all()
+    assert counts['threshold'] < counts['nothreshold'] * 0.95 and counts['threshold'] < counts['nomask'] * 0.95
+    case = K.membership(np.uint16, axis, 'threshold', coord)
+    assert case.img.dtype == np.uint16 and case.img.max() > 60000
+    if coord == 'plain':
+        # on every edge and one ulp to either side of it, the last edge included (the right-most-edge rule)
+        for v, edges in ((case.lon, case.xedges), (case.lat, case.yedges)):
+            for e in edges:
+                for p in (e, np.nextafter(e, -np.inf), np.nextafter(e, np.inf)):
+                    assert (v == p).any(), (e, p)
+        x_last = np.nextafter(case.xedges[-1], np.inf)
+        assert M.axis_index(np.array([x_last]), case.xedges)[0] == len(case.xedges) - 1
+        for lo, hi, v in ((case.xedges[0], case.xedges[-1], case.lon), (case.yedges[0], case.yedges[-1], case.lat)):
+            assert (v < lo - 0.1).any() and (v > hi + 0.1).any()
+    if coord == 'wrap':
+        assert np.nanmin(case.lon) < -350 and np.nanmax(case.lon) > 350
+        assert np.nanmin(case.lon_binned) >= -180 and np.nanmax(case.lon_binned) < 180
+    if coord == 'mlt':
+        # the device divides by 24 / 360 (mltToSmLon): the same cells as the multiplication by 15 that the case bins
+        assert np.nanmin(case.lon) >= 0 and np.nanmax(case.lon) <= 24
+        dev = O.wrap_at((case.lon - 12) / (24 / 360) + 180, 180)
+        assert np.array_equal(M.cell_index(dev, case.lat, case.xedges, case.yedges),
+                              M.cell_index(case.lon_binned, case.lat, case.xedges, case.yedges))
+
+
+def test_tail_cases():
+    assert K.TAIL_SIZES == ((1, 1), (1, 2), (1, 3), (1, 5), (3, 21), (1, 64), (5, 13), (1, 255), (257, 1), (7, 1021))
+    sizes = [h * w for h, w in K.TAIL_SIZES]
+    assert set(n % 4 for n in sizes) == {0, 1, 2, 3} and min(sizes) == 1 and sum(n < 64 for n in sizes) >= 5
+    for h, w in K.TAIL_SIZES:
+        for ncell in K.TAIL_CELLS:
+            case = K.tails(np.uint16, h, w, ncell)
+            want = K.expected(case)
+            other = K.expected(case, loop=False)
+            for key in ('median', 'img', 'mask', 'count'):
+                assert np.array_equal(want[key], other[key], equal_nan=True), (h, w, ncell, key)
+            assert want['count'].sum() == h * w and want['count'].shape == (1, ncell)
+            assert want['count'].max() - want['count'].min() <= 1
+
+
+def test_sparse_case():
+    case = K.sparse(np.uint8)
+    ny, nx = case.shape
+    assert (ny, nx) == (1000, 1100) and ny * nx > 256 * K.K_BLOCK * 8       # the scan's carry loop runs more than once
+    assert case.height * case.width % 4 != 0
+    want = K.expected(case)
+    assert (want['count'] > 0).sum() > K.LOOP_MAX_CELLS                     # (so `want` is the lexsort form)
+    # np.median itself in the three placed cells and in every 40th of the others (a loop over all 60 k takes half a minute)
+    flat = case.flat()
+    cells = K.sparse_placed_cells()
+    some = np.concatenate([np.unique(flat[flat >= 0])[::40], [(ny - 1 - iy) * nx + ix for iy, ix in cells]])
+    chosen = np.isin(flat, some)
+    planes = np.concatenate([case.img, case.elev[:, None]], axis=1)
+    loop = M.median_loop(case.lon, case.lat, planes, case.xedges, case.yedges, keep=chosen).reshape(ny * nx, 4)
+    assert len(some) > 1000 and np.array_equal(loop[some], want['median'].reshape(ny * nx, 4)[some])
+    assert want['count'].sum() == 60000 + sum(K.SPARSE_PLACED)
+    assert cells[0] == (0, 0) and cells[-1] == (ny - 1, nx - 1)
+    for (iy, ix), c in zip(cells, K.SPARSE_PLACED):
+        assert c <= want['count'][ny - 1 - iy, ix] <= c + 3
+    assert K.tier_of(K.SPARSE_PLACED).tolist() == [1, 1, 2]
+
+
+def test_one_large_cell_case():
+    case = K.one_large_cell(np.uint16)
+    assert K.HUGE % 2 == 0 and K.HUGE > 256 * K.K_CHUNK and case.height * case.width % 4 != 0
+    want = K.expected(case)
+    other = K.expected(case, loop=False)
+    for key in ('median', 'img', 'mask', 'count'):
+        assert np.array_equal(want[key], other[key], equal_nan=True), key
+    assert want['count'].tolist() == [[K.HUGE]]
+    flat = case.flat()
+    pairs = [K.middle_pairs(flat, v) for v in (case.img[:, 0], case.img[:, 1], case.img[:, 2], case.elev)]
+    differ = [bool(lo[0] != hi[0]) for _, _, lo, hi in pairs]
+    assert differ == [True, False, True, True]
+    assert np.signbit(pairs[3][2][0]) and not np.signbit(pairs[3][3][0])
