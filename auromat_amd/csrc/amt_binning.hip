@@ -306,8 +306,11 @@ int amt_bin_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const 
     const int tiles_x = (width + kBW - 1) / kBW, tiles_y = (height + kBH * kRowIters - 1) / (kBH * kRowIters);
     const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(kBlock);
     auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    // vector path: rows start 16-byte aligned (even width) so that every pixel pair is one aligned 16-byte load
-    const bool vec = (width % 2 == 0) && aligned16(lat_c) && aligned16(lon_c) && (elev == nullptr || aligned16(elev));
+    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
+    // vector path: rows start 16-byte aligned (even width) so that every pixel pair is one aligned 16-byte load, and
+    // the image starts 4-byte aligned so that a pixel pair's words are aligned 4-byte loads
+    const bool vec = (width % 2 == 0) && aligned16(lat_c) && aligned16(lon_c) && (elev == nullptr || aligned16(elev)) &&
+                     (nchan == 0 || aligned4(img));
 #define AMT_BIN_CASE(T, N)                                                                  \
     do {                                                                                    \
         if (vec) hipExtLaunchKernelGGL((k_bin_frame<T, N, true, false>), grid, block, 0, ctx->stream, t0, t1, 0, A);  \

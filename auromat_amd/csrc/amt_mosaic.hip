@@ -116,6 +116,7 @@ extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members,
     size_t acc_words = 0;
     bool vec = true;
     auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
     int64_t tiles = 0;
     for (int32_t i = 0; i < n_members; ++i) {
         const amt_mosaic_member& m = members[i];
@@ -141,7 +142,9 @@ extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members,
             tiles += tiles_x * tiles_y;
             acc_off[(size_t)i] = acc_words;
             acc_words += (size_t)(nchan + 2) * (size_t)m.win_nx * (size_t)m.win_ny;
-            vec = vec && (m.width % 2 == 0) && aligned16(m.lat_c) && aligned16(m.lon_c) && (m.elev == nullptr || aligned16(m.elev));
+            // (as amt_bin_frame: even width, 16-byte aligned coordinates and a 4-byte aligned image, of every member)
+            vec = vec && (m.width % 2 == 0) && aligned16(m.lat_c) && aligned16(m.lon_c) &&
+                  (m.elev == nullptr || aligned16(m.elev)) && (nchan == 0 || aligned4(m.img));
         }
         AMT_REQUIRE(ctx, tiles < (int64_t)1 << 31, "too many tiles");
     }

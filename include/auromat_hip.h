@@ -471,7 +471,10 @@ int amt_hist2d_accumulate(amt_ctx* ctx, const double* x, const double* y, int64_
  * acc: device uint64[(nchan+2) * nx*ny] workspace, zeroed by the caller:
  *   plane 0 = count, planes 1..nchan = exact integer channel sums,
  *   plane nchan+1 = elevation sum in signed 31.32 fixed point (|error| <= 2^-33 deg per sample;
- *   order independent, so results are bit-reproducible). */
+ *   order independent, so results are bit-reproducible; 2^63 / (90 * 2^32) = 2.38e7 pixels of 90 deg fit into one cell).
+ * The call ADDS to acc: several frames (or row bands of one frame) may be binned into one accumulator.
+ * Alignment: any.  The fast (vector) path needs an even width, lat_c / lon_c / elev 16-byte aligned and img 4-byte aligned;
+ * otherwise (e.g. img is a slice of a uint8 / uint16 array) the launch takes the scalar path.  Same results either way. */
 int amt_bin_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev,
                   const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask,
                   int32_t height, int32_t width, double min_elevation, const amt_axis* xaxis,
@@ -530,7 +533,9 @@ int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_
  * (each optional) and out_source (optional): int32 (ny, nx), the member index, -1 where the cell is empty.
  * A fixed number of launches whatever n_members is; the member table is uploaded from the host array and the accumulators
  * ((nchan + 2) x 8 bytes per window cell of every member) live in the context's workspace.  The call only enqueues work: no
- * read-back and no host wait; inputs and outputs as for amt_median_frame_async. */
+ * read-back and no host wait; inputs and outputs as for amt_median_frame_async.
+ * Alignment: any, as for amt_bin_frame; the vector path is taken when EVERY member with a window has an even width, 16-byte
+ * aligned lat_c / lon_c / elev and a 4-byte aligned img, the scalar path for the whole launch otherwise. */
 typedef struct amt_mosaic_member {
     const double* lat_c;
     const double* lon_c;
