@@ -113,7 +113,8 @@ class RunResult(C.Structure):
                 ('retried', C.c_int32), ('reserved2_', C.c_int32), ('uploaded_bytes', C.c_int64)]
 
 
-ABI_VERSION = 9          # include/auromat_hip.h AMT_ABI_VERSION
+ABI_VERSION = 10         # include/auromat_hip.h AMT_ABI_VERSION
+PIPE_MAX_EDGE_PIXELS = 16384     # AMT_PIPE_MAX_EDGE_PIXELS: a fused frame with more on-edge pixels is not launched again
 _I, _L, _D, _P = C.c_int, C.c_int64, C.c_double, C.c_void_p
 _SIGNATURES = {
     'amt_abi_version': ([], _I),
@@ -226,6 +227,10 @@ _SIGNATURES = {
     'amt_pipe_general_finalize': ([_P, _P, _P, _P, _P], _I),
     'amt_frame_params_from_wcs': ([C.POINTER(RunFrame), C.c_int32, C.c_int32, C.c_int32, _D, C.c_int32,
                                    C.POINTER(FrameParams)], _I),
+    'amt_pole_in_view': ([C.POINTER(FrameParams), _D, _I], _I),
+    'amt_frames_close': ([C.POINTER(FrameParams), C.POINTER(FrameParams)], _I),
+    'amt_box_hint': ([c_double_p, C.POINTER(FrameParams), _L, c_double_p, C.POINTER(FrameParams), _L, _L, C.POINTER(FrameParams),
+                      c_double_p], _I),
     'amt_run_create': ([_P, C.POINTER(RunConfig), c_void_pp], _I),
     'amt_run_destroy': ([_P], _I),
     'amt_run_process': ([_P, C.POINTER(RunFrame), C.c_int32, _P, _L, _P, _L, C.POINTER(RunResult), C.POINTER(C.c_int32)], _I),

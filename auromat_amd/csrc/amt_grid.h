@@ -113,6 +113,39 @@ inline bool layout(double lat_ppd, double lon_ppd, double lat_min, double lat_ma
     return true;
 }
 
+// The 8-number box reduction [lat_min, lat_max, lon_min, lon_max, lon_min_positive, lon_max_nonpositive, n, pole] of a frame
+// without a pole in view -> the BoundingBox of BaseMapping.boundingBox (reference mapping.py:711-741) and the range its grid
+// is laid out for.  A box wider than 180 deg straddles the 180 deg discontinuity (mappings are narrower than that,
+// mapping.py:722-737): west = the smallest positive, east = the largest non-positive longitude, and the grid is laid out
+// for longitudes shifted by 180 deg (the date-line branch of _resample, resample.py:203-218).
+struct box_range {
+    double lat_lo, lat_hi;
+    double west, east;          // BoundingBox.lonWest / lonEast
+    double lon_lo, lon_hi;      // the same two as the grid sees them: shifted by 180 deg when `wrapped`
+    bool wrapped;
+};
+
+// false: a straddling box without a finite west or east (nothing can be laid out; *r is filled with the plain box)
+inline bool range_of_box(const double* b, box_range* r) {
+    r->lat_lo = b[0], r->lat_hi = b[1];
+    r->west = r->lon_lo = b[2], r->east = r->lon_hi = b[3];
+    r->wrapped = b[3] - b[2] > 180;
+    if (!r->wrapped) return true;
+    if (!(std::isfinite(b[4]) && std::isfinite(b[5]))) return false;
+    r->west = b[4], r->east = b[5];
+    r->lon_lo = wrap_at_180(b[4] + 180.0);
+    r->lon_hi = wrap_at_180(b[5] + 180.0);
+    return true;
+}
+
+// ... and the exact grid of that box; *wrapped is written once the range is known (before the layout is tried)
+inline bool layout_of_box(double lat_ppd, double lon_ppd, const double* b, amt_grid* g, int32_t* wrapped) {
+    box_range r;
+    if (!range_of_box(b, &r)) return false;
+    *wrapped = r.wrapped ? 1 : 0;
+    return layout(lat_ppd, lon_ppd, r.lat_lo, r.lat_hi, r.lon_lo, r.lon_hi, g);
+}
+
 
 // ---- plateCarreeResolution (reference auromat/resample.py:36-61) ------------------------------------------------------
 // The same arithmetic as auromat_amd/coordinates/geodesic.py angularDistanceOnParallel + auromat_amd/resample.py

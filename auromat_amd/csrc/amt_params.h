@@ -4,7 +4,11 @@
 // wcs.py:133-139, igrf.py:25-58): the same operations in the same order; products of 3x3 matrices accumulate with fused
 // multiply-adds in the order k = 0, 1, 2, which is what the BLAS behind NumPy's `dot` does for these sizes on the build
 // host (tests/test_host_cpu.py compares the two: equal to the last bit on the dates tried, and in any case to 4e-16).
+// And the host rules on those scalars, each implemented here once for the frame drivers, the sequence runner and (through
+// amt_pole_in_view, amt_frames_close, amt_box_hint) Python: the pole test and the sequence coherence behind the box hints;
+// tests/test_host_rules_cpu.py compares them with the NumPy restatements of tests/_host_rules.py.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -188,6 +192,133 @@ inline int frame_params(const amt_run_frame* f, int32_t width, int32_t height, i
         std::memcpy(p->m_sm, sm.v, sizeof(sm.v));
     }
     return AMT_OK;
+}
+
+// ---- host rules on amt_frame_params ---------------------------------------------------------------------------------------
+
+// Is the north (+1) or south (-1) pole of the mapping shell imaged by a valid pixel (0: neither)?  The pole point is
+// projected through the inverse TAN model; it counts when it falls inside the frame, is the first hit of its ray and
+// lies above the elevation threshold (-inf: none).  Replaces the outline-based test of the reference, geodesic.py:183 /
+// mapping.py:705-721, for known camera models.
+inline int pole_in_view(const amt_frame_params* p, double min_elevation, int magnetic) {
+    const double* m = magnetic ? p->m_sm : p->m_geo;
+    const double* r = p->rot;
+    const double sc[3] = {1 / p->a, 1 / p->a, 1 / p->b};
+    for (int sign = 1; sign >= -1; sign -= 2) {
+        double u[3], pole[3], los[3], d[3], n2 = 0;
+        for (int i = 0; i < 3; ++i) u[i] = m[6 + i] * sign;              // m^T (0,0,sign): pole axis in J2000
+        for (int i = 0; i < 3; ++i) n2 += u[i] * sc[i] * u[i] * sc[i];
+        double dist2 = 0;
+        for (int i = 0; i < 3; ++i) {
+            pole[i] = u[i] / std::sqrt(n2);
+            los[i] = pole[i] - p->cam[i];
+            dist2 += los[i] * los[i];
+        }
+        const double dist = std::sqrt(dist2);
+        double d_o = 0, d_d = 0, o_o = 0;
+        for (int i = 0; i < 3; ++i) {
+            d[i] = los[i] / dist;
+            const double ds = d[i] * sc[i], os = -p->cam[i] * sc[i];
+            d_o += ds * os;
+            d_d += ds * ds;
+            o_o += os * os;
+        }
+        const double disc = d_o * d_o - o_o * d_d + d_d;
+        if (disc < 0) continue;
+        const double t = (o_o < 1 ? d_o + std::sqrt(disc) : d_o - std::sqrt(disc)) / d_d;
+        if (std::fabs(t - dist) > 1e-6 * dist) continue;                  // the pole is on the far side
+        double v[3];
+        for (int i = 0; i < 3; ++i) v[i] = r[i] * d[0] + r[3 + i] * d[1] + r[6 + i] * d[2];   // rot^T d
+        if (v[2] <= 0) continue;
+        const double k = 180.0 / M_PI, bx = k * v[1] / v[2], by = -k * v[0] / v[2];
+        const double det = p->cd[0] * p->cd[3] - p->cd[1] * p->cd[2];
+        const double px = (bx * p->cd[3] - p->cd[1] * by) / det, py = (p->cd[0] * by - p->cd[2] * bx) / det;
+        const double x = px + p->crpix[0] - 1, y = py + p->crpix[1] - 1;
+        if (!(x >= -0.5 && x <= p->width - 0.5 && y >= -0.5 && y <= p->height - 0.5)) continue;
+        if (!std::isinf(min_elevation)) {
+            double dp = 0, pp = 0;
+            for (int i = 0; i < 3; ++i) {
+                dp += d[i] * pole[i];
+                pp += pole[i] * pole[i];
+            }
+            double sn = -dp / std::sqrt(pp);
+            sn = sn < -1 ? -1 : (sn > 1 ? 1 : sn);
+            if (!(std::asin(sn) * k >= min_elevation)) continue;
+        }
+        return sign;
+    }
+    return 0;
+}
+
+inline bool all_within(const double* a, const double* b, int n, double tol) {
+    for (int i = 0; i < n; ++i)
+        if (std::fabs(a[i] - b[i]) > tol) return false;
+    return true;
+}
+
+// Neighbours in a sequence: same frame size, camera model within 1 % in scale (separately solved frames of one sequence
+// differ in the sixth digit of their CD matrix) and 5 px in the reference pixel, camera within 100 km, boresight and Earth
+// rotation within about half a degree, shell within 30 km — all of which move the box by far less than the superset's margin.
+inline bool close_frames(const amt_frame_params& a, const amt_frame_params& b) {
+    if (a.width != b.width || a.height != b.height || a.fast_center != b.fast_center) return false;
+    if (std::fabs(a.a - b.a) > 30.0 || std::fabs(a.b - b.b) > 30.0) return false;
+    double cd_max = 0;
+    for (int i = 0; i < 4; ++i) cd_max = std::max(cd_max, std::fabs(a.cd[i]));
+    return all_within(a.cam, b.cam, 3, 100.0) && all_within(a.rot, b.rot, 9, 0.01) && all_within(a.m_geo, b.m_geo, 9, 0.01) &&
+           all_within(a.m_sm, b.m_sm, 9, 0.01) && all_within(a.cd, b.cd, 4, 0.01 * cd_max) && all_within(a.crpix, b.crpix, 2, 5.0);
+}
+
+// Frames a, b (n_ab frames apart) and c (n_bc frames after b) of a steady sequence: same frame size, shell and reference pixel
+// as close_frames asks, c within 400 km of b, the same plate scale within 1 %, and CD matrix (it turns with the camera's
+// roll: 5e-4 per element over 20 s of the real ISS029 sequence), camera and boresight of c where the pace of a -> b puts them.
+inline bool steady_frames(const amt_frame_params& a, const amt_frame_params& b, const amt_frame_params& c, long long n_ab, long long n_bc) {
+    if (n_ab <= 0 || n_bc <= 0 || n_bc > 16) return false;
+    if (b.width != c.width || b.height != c.height || b.fast_center != c.fast_center) return false;
+    if (std::fabs(b.a - c.a) > 30.0 || std::fabs(b.b - c.b) > 30.0) return false;
+    if (!(all_within(b.cam, c.cam, 3, 400.0) && all_within(b.rot, c.rot, 9, 0.05) && all_within(b.m_geo, c.m_geo, 9, 0.05) &&
+          all_within(b.m_sm, c.m_sm, 9, 0.05) && all_within(b.crpix, c.crpix, 2, 5.0)))
+        return false;
+    const double scale_b = std::sqrt(std::fabs(b.cd[0] * b.cd[3] - b.cd[1] * b.cd[2]));
+    const double scale_c = std::sqrt(std::fabs(c.cd[0] * c.cd[3] - c.cd[1] * c.cd[2]));
+    if (!(scale_b > 0 && std::fabs(scale_c - scale_b) <= 0.01 * scale_b)) return false;
+    for (int i = 0; i < 4; ++i) {
+        const double step = (b.cd[i] - a.cd[i]) / n_ab;
+        if (std::fabs((c.cd[i] - b.cd[i]) - step * n_bc) > 0.3 * std::fabs(step * n_bc) + 0.01 * scale_b) return false;
+    }
+    for (int i = 0; i < 3; ++i) {
+        const double step = (b.cam[i] - a.cam[i]) / n_ab;
+        if (std::fabs((c.cam[i] - b.cam[i]) - step * n_bc) > 0.2 * std::fabs(step * n_bc) + 5.0) return false;
+    }
+    for (int i = 0; i < 9; ++i) {
+        const double step = (b.rot[i] - a.rot[i]) / n_ab;
+        if (std::fabs((c.rot[i] - b.rot[i]) - step * n_bc) > 0.3 * std::fabs(step * n_bc) + 2e-3) return false;
+    }
+    return true;
+}
+
+// Estimate of the box reduction of frame k (parameters p) from the latest frame the single-pass plan finished (its exact
+// reduction, parameters and running index) and the one finished before it (prev_box == nullptr: there is none), or false
+// (then the coarse pre-pass runs).  The latest frame's box as it is when that frame is a neighbour of this one; else, in a
+// steady sequence, the two boxes extrapolated linearly to this frame: a frame is prepared two batches ahead of the latest
+// finished one, 20 s of orbit at the ISS's 3 s cadence, which moves the box by more than the superset's margin, but
+// smoothly.  A poor estimate costs time (the frame is handed back), never correctness.
+inline bool box_hint(const double* last_box, const amt_frame_params& last_p, long long last_index, const double* prev_box,
+                     const amt_frame_params* prev_p, long long prev_index, long long k, const amt_frame_params& p, double* est) {
+    if (close_frames(last_p, p)) {
+        std::memcpy(est, last_box, 8 * sizeof(double));
+        return true;
+    }
+    if (prev_box == nullptr || prev_p == nullptr || !close_frames(*prev_p, last_p) ||
+        !steady_frames(*prev_p, last_p, p, last_index - prev_index, k - last_index))
+        return false;
+    if ((prev_box[7] != 0) != (last_box[7] != 0) || (last_box[3] - last_box[2] > 180) != (prev_box[3] - prev_box[2] > 180))
+        return false;                               // a pole or the date line came into view between the two
+    const double f = (double)(k - last_index) / (double)(last_index - prev_index);
+    for (int i = 0; i < 6; ++i) est[i] = last_box[i] + f * (last_box[i] - prev_box[i]);
+    est[6] = last_box[6], est[7] = last_box[7];
+    est[0] = std::max(est[0], -90.0), est[1] = std::min(est[1], 90.0);
+    for (int i = 2; i < 6; ++i) est[i] = std::min(std::max(est[i], -180.0), 180.0);
+    return true;
 }
 
 }  // namespace amt_prm

@@ -7,6 +7,7 @@
 
 #include "amt_common.h"
 #include "amt_grid.h"
+#include "amt_params.h"
 
 struct amt_pipe {
     amt_ctx* ctx;
@@ -56,7 +57,6 @@ struct amt_pipe {
 namespace {
 
 constexpr int kCoarseStride = 16;      // every 16th pixel corner at most; >= 128 lattice points on the short side
-constexpr long long kEventCapacity = 16384;   // on-edge pixels per frame (a few dozen in practice)
 constexpr double kMarginDeg = 1.0;     // safety margin around the coarse box (> 3 lattice steps on the ground)
 constexpr double kPoleGuardDeg = 85.0; // direction arrays, pole unknown: boxes that reach beyond this latitude are not fused
 
@@ -92,62 +92,6 @@ int ensure_partials(amt_pipe* pipe, size_t bytes) {
     return AMT_OK;
 }
 
-using amt_gl::wrap_at_180;
-
-// Is the north or south pole of the mapping shell imaged by a valid pixel?  The pole point is projected
-// through the inverse TAN model; it counts when it falls inside the frame, is the first hit of its ray and
-// lies above the elevation threshold (host mirror: auromat_amd/mapping/astrometry.py pole_in_view; replaces
-// the outline-based test of the reference, geodesic.py:183 / mapping.py:705-721, for known camera models).
-bool pole_visible(const amt_frame_params* p, double min_elevation, int magnetic) {
-    const double* m = magnetic ? p->m_sm : p->m_geo;
-    const double* r = p->rot;
-    const double sc[3] = {1 / p->a, 1 / p->a, 1 / p->b};
-    for (int sign = 1; sign >= -1; sign -= 2) {
-        double u[3], pole[3], los[3], d[3], n2 = 0;
-        for (int i = 0; i < 3; ++i) u[i] = m[6 + i] * sign;              // m^T (0,0,sign): pole axis in J2000
-        for (int i = 0; i < 3; ++i) n2 += u[i] * sc[i] * u[i] * sc[i];
-        double dist2 = 0;
-        for (int i = 0; i < 3; ++i) {
-            pole[i] = u[i] / std::sqrt(n2);
-            los[i] = pole[i] - p->cam[i];
-            dist2 += los[i] * los[i];
-        }
-        const double dist = std::sqrt(dist2);
-        double d_o = 0, d_d = 0, o_o = 0;
-        for (int i = 0; i < 3; ++i) {
-            d[i] = los[i] / dist;
-            const double ds = d[i] * sc[i], os = -p->cam[i] * sc[i];
-            d_o += ds * os;
-            d_d += ds * ds;
-            o_o += os * os;
-        }
-        const double disc = d_o * d_o - o_o * d_d + d_d;
-        if (disc < 0) continue;
-        const double t = (o_o < 1 ? d_o + std::sqrt(disc) : d_o - std::sqrt(disc)) / d_d;
-        if (std::fabs(t - dist) > 1e-6 * dist) continue;                  // the pole is on the far side
-        double v[3];
-        for (int i = 0; i < 3; ++i) v[i] = r[i] * d[0] + r[3 + i] * d[1] + r[6 + i] * d[2];   // rot^T d
-        if (v[2] <= 0) continue;
-        const double k = 180.0 / M_PI, bx = k * v[1] / v[2], by = -k * v[0] / v[2];
-        const double det = p->cd[0] * p->cd[3] - p->cd[1] * p->cd[2];
-        const double px = (bx * p->cd[3] - p->cd[1] * by) / det, py = (p->cd[0] * by - p->cd[2] * bx) / det;
-        const double x = px + p->crpix[0] - 1, y = py + p->crpix[1] - 1;
-        if (!(x >= -0.5 && x <= p->width - 0.5 && y >= -0.5 && y <= p->height - 0.5)) continue;
-        if (!std::isinf(min_elevation)) {
-            double dp = 0, pp = 0;
-            for (int i = 0; i < 3; ++i) {
-                dp += d[i] * pole[i];
-                pp += pole[i] * pole[i];
-            }
-            double sn = -dp / std::sqrt(pp);
-            sn = sn < -1 ? -1 : (sn > 1 ? 1 : sn);
-            if (!(std::asin(sn) * k >= min_elevation)) continue;
-        }
-        return true;
-    }
-    return false;
-}
-
 }  // namespace
 
 extern "C" {
@@ -166,6 +110,10 @@ int amt_plate_carree_resolution(double lat_south, double lon_west, double lat_no
     if (!amt_gl::plate_carree_resolution(lat_south, lon_west, lat_north, lon_east, arcsec_per_px, lat_px_per_deg, lon_px_per_deg))
         return AMT_EINVAL;
     return *lon_px_per_deg > 0 ? AMT_OK : AMT_EDOMAIN;
+}
+
+int amt_pole_in_view(const amt_frame_params* p, double min_elevation, int magnetic) {
+    return p == nullptr ? 0 : amt_prm::pole_in_view(p, min_elevation, magnetic ? 1 : 0);
 }
 
 int amt_pipe_create(amt_ctx* ctx, amt_pipe** out_pipe) {
@@ -190,7 +138,7 @@ int amt_pipe_create(amt_ctx* ctx, amt_pipe** out_pipe) {
               hipEventCreate(&pipe->kernel_done) == hipSuccess &&
               hipEventCreateWithFlags(&pipe->bbox_done, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&pipe->tail_done, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc(&pipe->events, kEventCapacity * 32) == hipSuccess &&
+              hipMalloc(&pipe->events, AMT_PIPE_MAX_EDGE_PIXELS * 32) == hipSuccess &&
               // (zeroed on the context's stream before the first fused launch, see pipe_prepare: a memset on the null stream
               // here is not ordered against the context's non-blocking stream and may run late when processes share the GPU)
               hipMalloc(reinterpret_cast<void**>(&pipe->event_count), sizeof(uint32_t)) == hipSuccess &&
@@ -266,7 +214,7 @@ int amt_pipe_coarse(amt_pipe* pipe, const amt_frame_params* p, double min_elevat
     amt_ctx* ctx = pipe->ctx;
     AMT_REQUIRE(ctx, p != nullptr, "NULL argument");
     // a frame with a pole of its grid in view is binned in rotated coordinates (the pole plans): its box is needed in those
-    const int mode = (magnetic ? 1 : 0) + (pole_visible(p, min_elevation, magnetic ? 1 : 0) ? 2 : 0);
+    const int mode = (magnetic ? 1 : 0) + (amt_prm::pole_in_view(p, min_elevation, magnetic ? 1 : 0) != 0 ? 2 : 0);
     return pipe_coarse(pipe, p, min_elevation, mode);
 }
 
@@ -291,7 +239,7 @@ int pipe_prepare(amt_pipe* pipe, const amt_frame_params* p, const amt_georef_out
     magnetic = magnetic ? 1 : 0;
     // (direction arrays: there is no camera model to project the pole through — the caller decides, or nobody does)
     pipe->pole_unknown = dirs != nullptr && pole_in_view < 0;
-    pipe->pole = pole_in_view < 0 ? (dirs == nullptr && pole_visible(p, min_elevation, magnetic) ? 1 : 0) : (pole_in_view ? 1 : 0);
+    pipe->pole = pole_in_view < 0 ? (dirs == nullptr && amt_prm::pole_in_view(p, min_elevation, magnetic) != 0 ? 1 : 0) : (pole_in_view ? 1 : 0);
     // frames with a pole of their grid in view take a pole plan (binned in rotated coordinates; a geodetic pole frame of
     // a caller that wants the MLat / MLT arrays as well runs the kernel variant of the magnetic pole plan with the
     // rotated pair taken from (lat, lon), see prepare_georef); direction arrays have none: their pole frames are not fused
@@ -374,17 +322,14 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
     bool fuse = !pipe->two_pass && c[6] > 0 && (!pipe->pole || pipe->pole_plan);
     if (pipe->pole_unknown && !(c[0] > -kPoleGuardDeg && c[1] < kPoleGuardDeg)) fuse = false;
     pipe->lon_wrap = 0;
-    double box_lo = c[2], box_hi = c[3];
-    if (fuse && pipe->pole_plan && c[3] - c[2] > 180) fuse = false;      // (cannot happen: the rotated frame sits at the equator)
-    if (fuse && c[3] - c[2] > 180) {
-        // the box straddles the 180 deg discontinuity (mappings are narrower than 180 deg, mapping.py:722-737):
-        // west = smallest positive, east = largest non-positive longitude; bin longitudes shifted by 180 deg
-        // (reference resample.py:203-218)
-        fuse = std::isfinite(c[4]) && std::isfinite(c[5]);
-        box_lo = wrap_at_180(c[4] + 180.0);
-        box_hi = wrap_at_180(c[5] + 180.0);
+    amt_gl::box_range r;
+    const bool ranged = amt_gl::range_of_box(c, &r);
+    const double box_lo = r.lon_lo, box_hi = r.lon_hi;
+    if (fuse && pipe->pole_plan && r.wrapped) fuse = false;      // (cannot happen: the rotated frame sits at the equator)
+    if (fuse && r.wrapped) {
+        // the box straddles the 180 deg discontinuity: longitudes are binned shifted by 180 deg
         pipe->lon_wrap = 1;
-        fuse = fuse && box_hi > box_lo;
+        fuse = ranged && box_hi > box_lo;
     }
     if (fuse) {
         const double lat_abs = std::fmax(std::fabs(c[0]), std::fabs(c[1]));
@@ -415,7 +360,7 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
         o.bin_lon_wrap = pipe->lon_wrap;
         o.bin_events = pipe->events;
         o.bin_event_count = pipe->event_count;
-        o.bin_event_capacity = kEventCapacity;
+        o.bin_event_capacity = AMT_PIPE_MAX_EDGE_PIXELS;
         pipe->fused = true;
         pipe->acc_zero = false;
     }
@@ -556,7 +501,7 @@ int amt_pipe_launch_box_many(amt_pipe* const* pipes, int32_t n, const amt_frame_
         // (an estimate that is still pending belongs to another plan of this frame: dropped)
         if (pipe->coarse_pending && !pipe->coarse_hinted) AMT_HIP(ctx, hipEventSynchronize(pipe->coarse_done));
         pipe->coarse_pending = pipe->coarse_hinted = false;
-        pipe->pole = pole_visible(p[i], min_elevation, magnetic) ? 1 : 0;
+        pipe->pole = amt_prm::pole_in_view(p[i], min_elevation, magnetic) != 0 ? 1 : 0;
         pipe->pole_unknown = false;
         pipe->pole_plan = false;
         pipe->lat_ppd = pipe->lon_ppd = 0;
@@ -620,7 +565,7 @@ int amt_pipe_wait(amt_pipe* pipe, amt_pipe_result* result) {
     pipe->n_events = pipe->fused ? (long long)b[7] : 0;        // the last fold put the counter into slot 7
     if (!pipe->fused || (pipe->pole && !pipe->pole_plan)) return AMT_OK;
     result->edge_pixels = (int32_t)(pipe->n_events > 2000000000ll ? 2000000000ll : pipe->n_events);
-    if (pipe->n_events > kEventCapacity) return AMT_OK;         // more on-edge pixels than records: general path
+    if (pipe->n_events > AMT_PIPE_MAX_EDGE_PIXELS) return AMT_OK;         // more on-edge pixels than records: general path
     // direction arrays whose caller left the pole open: a box that comes near a pole goes back to the caller (status 1)
     if (pipe->pole_unknown && !(b[0] > -kPoleGuardDeg && b[1] < kPoleGuardDeg)) return AMT_OK;
     const bool straddles = b[3] - b[2] > 180;
@@ -633,15 +578,8 @@ int amt_pipe_wait(amt_pipe* pipe, amt_pipe_result* result) {
         for (int i = 0; i < 4; ++i)
             if (!(std::fabs(v[i] - std::nearbyint(v[i])) > 1e-6)) return AMT_OK;
     }
-    double lon_lo = b[2], lon_hi = b[3];
-    if (straddles) {
-        if (!(std::isfinite(b[4]) && std::isfinite(b[5]))) return AMT_OK;
-        lon_lo = wrap_at_180(b[4] + 180.0);
-        lon_hi = wrap_at_180(b[5] + 180.0);
-    }
-    result->lon_wrapped = straddles ? 1 : 0;
     amt_grid& g = result->grid;
-    if (!amt_gl::layout(pipe->lat_ppd, pipe->lon_ppd, b[0], b[1], lon_lo, lon_hi, &g)) return AMT_OK;
+    if (!amt_gl::layout_of_box(pipe->lat_ppd, pipe->lon_ppd, b, &g, &result->lon_wrapped)) return AMT_OK;
     const amt_grid& s = pipe->super;
     // window of the exact grid inside the superset (same global nodes => integer offsets)
     const long off_x = std::lround((g.lon_center_first - s.lon_center_first) / s.lon_step);
@@ -698,7 +636,7 @@ int amt_pipe_finalize_many(amt_pipe* const* pipes, int32_t n, double* const* mea
         for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipe, "a driver can hold one frame of a call");
         AMT_REQUIRE(ctx, pipe->ready, "amt_pipe_wait has not returned status 0 for this frame");
         AMT_REQUIRE(ctx, pipe->img_dtype == pipes[0]->img_dtype, "frames of one call must share the image type");
-        AMT_REQUIRE(ctx, pipe->n_events <= kEventCapacity, "more on-edge pixels than records");
+        AMT_REQUIRE(ctx, pipe->n_events <= AMT_PIPE_MAX_EDGE_PIXELS, "more on-edge pixels than records");
         finish_frame& F = B.f[i];
         F.events = pipe->events;
         F.count = pipe->event_count;
@@ -740,22 +678,15 @@ int amt_pipe_general_layout(amt_pipe* pipe, amt_pipe_result* result) {
     if (pipe->pole || !pipe->g_fast || pipe->g_mode != 0 || !pipe->g_lat_c || !pipe->g_lon_c || !pipe->g_elev || pipe->g_row_layout != 0) return AMT_OK;
     const double* b = result->bbox;
     if (!(b[6] > 0)) return AMT_OK;
-    // BaseMapping.boundingBox + the date-line branch of _resample (reference mapping.py:711-741, resample.py:203-218)
-    const bool straddles = b[3] - b[2] > 180;
-    double lon_lo = b[2], lon_hi = b[3];
-    if (straddles) {
-        if (!(std::isfinite(b[4]) && std::isfinite(b[5]))) return AMT_OK;
-        lon_lo = wrap_at_180(b[4] + 180.0);
-        lon_hi = wrap_at_180(b[5] + 180.0);
-    }
     amt_grid g;
-    if (!amt_gl::layout(pipe->lat_ppd, pipe->lon_ppd, b[0], b[1], lon_lo, lon_hi, &g)) return AMT_OK;
+    int32_t wrapped = 0;
+    if (!amt_gl::layout_of_box(pipe->lat_ppd, pipe->lon_ppd, b, &g, &wrapped)) return AMT_OK;
     if (g.nx >= 65535 || g.ny >= 65535) return AMT_OK;
     result->grid = g;
-    result->lon_wrapped = straddles ? 1 : 0;
+    result->lon_wrapped = wrapped;
     result->status = 0;
     pipe->exact = g;
-    pipe->lon_wrap = straddles ? 1 : 0;
+    pipe->lon_wrap = wrapped;
     pipe->general_ready = true;
     return AMT_OK;
 }

@@ -56,67 +56,10 @@ struct amt_run {
 
 namespace {
 
-bool all_within(const double* a, const double* b, int n, double tol) {
-    for (int i = 0; i < n; ++i)
-        if (std::fabs(a[i] - b[i]) > tol) return false;
-    return true;
-}
-
-// neighbours in a sequence (auromat_amd/pipeline.py _close): same frame size, camera model within 1 % in scale, camera
-// within 100 km, boresight and Earth rotation within about half a degree, shell within 30 km
-bool close_frames(const amt_frame_params& a, const amt_frame_params& b) {
-    if (a.width != b.width || a.height != b.height || a.fast_center != b.fast_center) return false;
-    if (std::fabs(a.a - b.a) > 30.0 || std::fabs(a.b - b.b) > 30.0) return false;
-    double cd_max = 0;
-    for (int i = 0; i < 4; ++i) cd_max = std::max(cd_max, std::fabs(a.cd[i]));
-    return all_within(a.cam, b.cam, 3, 100.0) && all_within(a.rot, b.rot, 9, 0.01) && all_within(a.m_geo, b.m_geo, 9, 0.01) &&
-           all_within(a.m_sm, b.m_sm, 9, 0.01) && all_within(a.cd, b.cd, 4, 0.01 * cd_max) && all_within(a.crpix, b.crpix, 2, 5.0);
-}
-
-// frames a, b (n_ab apart) and c (n_bc after b): a steady sequence (auromat_amd/pipeline.py _steady)
-bool steady_frames(const amt_frame_params& a, const amt_frame_params& b, const amt_frame_params& c, long long n_ab, long long n_bc) {
-    if (n_ab <= 0 || n_bc <= 0 || n_bc > 16) return false;
-    if (b.width != c.width || b.height != c.height || b.fast_center != c.fast_center) return false;
-    if (std::fabs(b.a - c.a) > 30.0 || std::fabs(b.b - c.b) > 30.0) return false;
-    if (!(all_within(b.cam, c.cam, 3, 400.0) && all_within(b.rot, c.rot, 9, 0.05) && all_within(b.m_geo, c.m_geo, 9, 0.05) &&
-          all_within(b.m_sm, c.m_sm, 9, 0.05) && all_within(b.crpix, c.crpix, 2, 5.0)))
-        return false;
-    const double scale_b = std::sqrt(std::fabs(b.cd[0] * b.cd[3] - b.cd[1] * b.cd[2]));
-    const double scale_c = std::sqrt(std::fabs(c.cd[0] * c.cd[3] - c.cd[1] * c.cd[2]));
-    if (!(scale_b > 0 && std::fabs(scale_c - scale_b) <= 0.01 * scale_b)) return false;
-    for (int i = 0; i < 4; ++i) {
-        const double step = (b.cd[i] - a.cd[i]) / n_ab;
-        if (std::fabs((c.cd[i] - b.cd[i]) - step * n_bc) > 0.3 * std::fabs(step * n_bc) + 0.01 * scale_b) return false;
-    }
-    for (int i = 0; i < 3; ++i) {
-        const double step = (b.cam[i] - a.cam[i]) / n_ab;
-        if (std::fabs((c.cam[i] - b.cam[i]) - step * n_bc) > 0.2 * std::fabs(step * n_bc) + 5.0) return false;
-    }
-    for (int i = 0; i < 9; ++i) {
-        const double step = (b.rot[i] - a.rot[i]) / n_ab;
-        if (std::fabs((c.rot[i] - b.rot[i]) - step * n_bc) > 0.3 * std::fabs(step * n_bc) + 2e-3) return false;
-    }
-    return true;
-}
-
-// estimate of frame k's box reduction from finished frames (auromat_amd/pipeline.py SequencePipeline._box_hint)
+// estimate of frame k's box reduction from the frames the single-pass plan has finished (amt_prm::box_hint)
 bool box_hint(const amt_run* run, long long k, const amt_frame_params& p, double* est) {
     const amt_run::hint &last = run->last, &prev = run->prev;
-    if (!last.valid) return false;
-    if (close_frames(last.p, p)) {
-        std::memcpy(est, last.box, sizeof(last.box));
-        return true;
-    }
-    if (!prev.valid || !close_frames(prev.p, last.p) || !steady_frames(prev.p, last.p, p, last.index - prev.index, k - last.index))
-        return false;
-    if ((prev.box[7] != 0) != (last.box[7] != 0) || (last.box[3] - last.box[2] > 180) != (prev.box[3] - prev.box[2] > 180))
-        return false;                               // a pole or the date line came into view between the two
-    const double f = (double)(k - last.index) / (double)(last.index - prev.index);
-    for (int i = 0; i < 6; ++i) est[i] = last.box[i] + f * (last.box[i] - prev.box[i]);
-    est[6] = last.box[6], est[7] = last.box[7];
-    est[0] = std::max(est[0], -90.0), est[1] = std::min(est[1], 90.0);
-    for (int i = 2; i < 6; ++i) est[i] = std::min(std::max(est[i], -180.0), 180.0);
-    return true;
+    return last.valid && amt_prm::box_hint(last.box, last.p, last.index, prev.valid ? prev.box : nullptr, &prev.p, prev.index, k, p, est);
 }
 
 int64_t image_bytes(const amt_run* run, int64_t cells) {
@@ -131,6 +74,16 @@ int amt_frame_params_from_wcs(const amt_run_frame* frame, int32_t width, int32_t
                               double altitude, int32_t want_sm, amt_frame_params* out) {
     if (frame == nullptr || out == nullptr || width <= 0 || height <= 0) return AMT_EINVAL;
     return amt_prm::frame_params(frame, width, height, fast_center, altitude, want_sm, out);
+}
+
+int amt_frames_close(const amt_frame_params* a, const amt_frame_params* b) {
+    return a != nullptr && b != nullptr && amt_prm::close_frames(*a, *b) ? 1 : 0;
+}
+
+int amt_box_hint(const double* last_box, const amt_frame_params* last_p, int64_t last_index, const double* prev_box,
+                 const amt_frame_params* prev_p, int64_t prev_index, int64_t k, const amt_frame_params* p, double* est8) {
+    if (last_box == nullptr || last_p == nullptr || p == nullptr || est8 == nullptr) return 0;
+    return amt_prm::box_hint(last_box, *last_p, last_index, prev_box, prev_p, prev_index, k, *p, est8) ? 1 : 0;
 }
 
 int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run) {
@@ -227,26 +180,20 @@ int amt_run_reset_hints(amt_run* run) {
 namespace {
 
 // Median sequences: the exact grid of a frame the big kernel has written the slot's arrays for (status 1 from amt_pipe_wait),
-// laid out as amt_pipe_general_layout and the single-pass plan lay it out — BaseMapping.boundingBox and the date-line branch
-// of _resample (reference mapping.py:711-741, resample.py:203-218), in (MLat, SM longitude) on a magnetic grid.  What the
-// median pass does not cover keeps status 1: a pole of the grid in view, exact centres, slots without the arrays.
+// laid out as amt_pipe_general_layout and the single-pass plan lay it out (amt_gl::layout_of_box), in (MLat, SM longitude) on a
+// magnetic grid.  What the median pass does not cover keeps status 1: a pole of the grid in view, exact centres, slots without
+// the arrays.
 void median_layout(const amt_run* run, int slot, amt_pipe_result* pr) {
     const amt_run_config& cfg = run->cfg;
     const amt_georef_out& o = run->outs[slot];
     const double* b = pr->bbox;
     const bool have = cfg.magnetic ? (o.mlat_c && o.mlt_c) : (o.lat_c && o.lon_c);
     if (pr->status != 1 || b[7] != 0 || !cfg.fast_center || !have || !o.elev || o.row_layout != 0 || !(b[6] > 0)) return;
-    const bool straddles = b[3] - b[2] > 180;
-    double lon_lo = b[2], lon_hi = b[3];
-    if (straddles) {
-        if (!(std::isfinite(b[4]) && std::isfinite(b[5]))) return;
-        lon_lo = amt_gl::wrap_at_180(b[4] + 180.0);
-        lon_hi = amt_gl::wrap_at_180(b[5] + 180.0);
-    }
     amt_grid g;
-    if (!amt_gl::layout(run->ppd_lat[slot], run->ppd_lon[slot], b[0], b[1], lon_lo, lon_hi, &g)) return;
+    int32_t wrapped = 0;
+    if (!amt_gl::layout_of_box(run->ppd_lat[slot], run->ppd_lon[slot], b, &g, &wrapped)) return;
     pr->grid = g;
-    pr->lon_wrapped = straddles ? 1 : 0;
+    pr->lon_wrapped = wrapped;
     pr->status = 0;
 }
 
@@ -278,7 +225,7 @@ int run_finish(amt_run* run, int k0, int count) {
         }
         amt_pipe_result pr;
         if (int rc = amt_pipe_wait(run->pipes[slot], &pr)) return rc;
-        if (pr.status == 1 && pr.fused && !cfg.two_pass && pr.bbox[6] > 0 && pr.edge_pixels <= 16384) {
+        if (pr.status == 1 && pr.fused && !cfg.two_pass && pr.bbox[6] > 0 && pr.edge_pixels <= AMT_PIPE_MAX_EDGE_PIXELS) {
             // handed back although the launch was fused — the exact box does not fit the superset grid of a poor estimate,
             // the date line judged differently —: once more, with the exact box (in the coordinates of the plan: bbox[7])
             // as the estimate.  On the context's stream, behind the batch launched after this one; rare.
@@ -434,10 +381,10 @@ int run_resolve(amt_run* run, int k0, int count) {
             run->pre_status[slot] = 2;
             continue;
         }
-        const bool straddles = b[3] - b[2] > 180;
-        const double west = straddles ? b[4] : b[2], east = straddles ? b[5] : b[3];
+        amt_gl::box_range r;
         double la = 0, lo = 0;
-        if (b[7] != 0 || !amt_gl::plate_carree_resolution(b[0], west, b[1], east, cfg.arcsec_per_px, &la, &lo) || !(lo > 0)) {
+        if (b[7] != 0 || !amt_gl::range_of_box(b, &r) ||
+            !amt_gl::plate_carree_resolution(r.lat_lo, r.west, r.lat_hi, r.east, cfg.arcsec_per_px, &la, &lo) || !(lo > 0)) {
             run->pre_status[slot] = 4;
             continue;
         }
@@ -451,6 +398,14 @@ int run_resolve(amt_run* run, int k0, int count) {
 void pop_front(int (*q)[2], int* n) {
     q[0][0] = q[1][0], q[0][1] = q[1][1];
     --*n;
+}
+
+// the arenas ran full: frames that were only prepared are reported as not processed
+void mark_not_processed(amt_run* run, int k0, int count) {
+    for (int i = 0; i < count; ++i) {
+        std::memset(&run->results[k0 + i], 0, sizeof(amt_run_result));
+        run->results[k0 + i].status = 3;
+    }
 }
 
 // box-first plan: the oldest boxed batch -> resolutions, its single-pass launch; then at most one batch stays in flight
@@ -479,10 +434,7 @@ int run_batch_ready_box(amt_run* run, int k0, int count) {
     if (run->n_boxed == 2)
         if (int rc = run_launch_boxed(run)) return rc;
     if (run->full) {
-        for (int i = 0; i < count; ++i) {
-            std::memset(&run->results[k0 + i], 0, sizeof(amt_run_result));
-            run->results[k0 + i].status = 3;
-        }
+        mark_not_processed(run, k0, count);
         return AMT_OK;
     }
     if (int rc = run_box(run, k0, count)) return rc;
@@ -496,15 +448,10 @@ int run_batch_ready(amt_run* run, int k0, int count) {
     if (run->cfg.arcsec_per_px > 0) return run_batch_ready_box(run, k0, count);
     if (run->n_launched == 2) {
         if (int rc = run_finish(run, run->launched[0][0], run->launched[0][1])) return rc;
-        run->launched[0][0] = run->launched[1][0], run->launched[0][1] = run->launched[1][1];
-        run->n_launched = 1;
+        pop_front(run->launched, &run->n_launched);
     }
     if (run->full) {
-        // the arenas ran full: frames that were only prepared are reported as not processed
-        for (int i = 0; i < count; ++i) {
-            std::memset(&run->results[k0 + i], 0, sizeof(amt_run_result));
-            run->results[k0 + i].status = 3;
-        }
+        mark_not_processed(run, k0, count);
         return AMT_OK;
     }
     if (int rc = run_launch(run, k0, count)) return rc;

@@ -191,6 +191,15 @@ def bounding_box_from_reduction(red):
     return BoundingBox(latSouth, lonWest, latNorth, lonEast)
 
 
+def grid_box_from_reduction(red, wrapped):
+    """(lat_min, lat_max, lon_min, lon_max) the output grid of a frame without a pole in view is laid out for; `wrapped`
+    (its box straddles the 180 deg discontinuity): in longitudes shifted by 180 deg (reference resample.py:203-218; the
+    library's amt_gl::range_of_box)."""
+    if wrapped:
+        return red[0], red[1], wrap_at_180(red[4] + 180), wrap_at_180(red[5] + 180)
+    return red[0], red[1], red[2], red[3]
+
+
 @add_metaclass(ABCMeta)
 class BaseMapping(object):
     """

@@ -31,11 +31,12 @@ import numpy as np
 
 from .frame import FrameData, PaddedFrameData, has_array
 from .mapping.astrometry import frame_params, pole_in_view, run_frame
-from .mapping.mapping import bounding_box_from_reduction, wrap_at_180
+from .mapping.mapping import bounding_box_from_reduction, grid_box_from_reduction
 from .resample import cached_grid, grid_coordinates, resample_frame, resample_frame_median
-from ._native import Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
+from ._native import PIPE_MAX_EDGE_PIXELS, Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
 
 NEG_INF = float('-inf')
+_Box8 = C.c_double * 8                 # a box reduction as the library takes it
 
 
 class EmptyFrame(ValueError):
@@ -61,6 +62,27 @@ class _GridView(object):
         if self._full is None:
             self._full = cached_grid(self._pxPerDeg, *self._box)
         return getattr(self._full, name)
+
+
+def _frame_block(g, pxPerDeg, bbox, wrapped, pole, altitude, grids, o8, images, ob, img16):
+    """One finished frame as it lies in memory — mean | count from double `o8` of `grids`, image | mask from byte `ob` of
+    `images` — and its grid `g` (amt_grid, laid out from the reduction `bbox`) -> (result dict without the arrays, packed = mean
+    and count as one tensor, mean, count, img, mask, the byte behind the mask)."""
+    import torch
+    ny, nx = g.ny, g.nx
+    n = ny * nx
+    packed = grids[o8:o8 + 5 * n]
+    mean = grids[o8:o8 + 4 * n].view(ny, nx, 4)
+    count = grids[o8 + 4 * n:o8 + 5 * n].view(ny, nx)
+    om = ob + (6 if img16 else 3) * n
+    img = images[ob:om]
+    img = (img.view(torch.int16) if img16 else img).view(ny, nx, 3)
+    mask = images[om:om + n].view(ny, nx)
+    # (a pole plan's grid is in rotated coordinates; BoundingBox.containsDiscontinuity is true for every box with a pole in
+    # it, reference mapping.py:200-206)
+    out = dict(has_elev=True, grid=_GridView(g, pxPerDeg, grid_box_from_reduction(bbox, wrapped)), contains_pole=pole,
+               contains_discontinuity=wrapped or pole, altitude=altitude)
+    return out, packed, mean, count, img, mask, om + n
 
 
 def earth_rows_of(params, height, min_elevation=None):
@@ -298,7 +320,7 @@ class FramePipeline(object):
         `dirs`: the frame's corner directions come from the caller (amt_pipe_coarse_dirs samples that array).
         """
         if hint is not None:
-            self._pcall('amt_pipe_coarse_hint', (C.c_double * 8)(*hint), 1 if magnetic else 0)
+            self._pcall('amt_pipe_coarse_hint', hint if isinstance(hint, _Box8) else _Box8(*hint), 1 if magnetic else 0)
         elif dirs is not None:
             self._pcall('amt_pipe_coarse_dirs', C.byref(params), ptr(dirs),
                         NEG_INF if min_elevation is None else float(min_elevation), 1 if magnetic else 0)
@@ -533,39 +555,15 @@ class FramePipeline(object):
         the frames of a launch, this frame's part starting at byte `offset`) of a frame amt_pipe_wait has laid out ->
         (out dict without the arrays, packed, mean, count, img, mask)."""
         import torch
-        ctx, fd = self.ctx, self.fd
-        g = res.grid
-        b = res.bbox
-        wrapped = bool(res.lon_wrapped)
-        pole = bool(b[7])                                       # a pole plan: grid in rotated coordinates
-        if wrapped:
-            # straddles the 180 deg discontinuity: the grid is laid out for longitudes shifted by 180 deg
-            box = (b[0], b[1], wrap_at_180(b[4] + 180), wrap_at_180(b[5] + 180))
-        else:
-            box = (b[0], b[1], b[2], b[3])
-        grid = _GridView(g, pxPerDeg, box)
         if mem is None:
-            mem = self._fused_alloc(self._fused_nbytes(res), torch.cuda.current_stream(ctx.device))
-        buf, b64, bimg = mem
-        # (one allocation for the four arrays: mean | count | image | mask)
-        n = g.ny * g.nx
-        o8 = offset // 8
-        packed = b64[o8:o8 + 5 * n]
-        mean = b64[o8:o8 + 4 * n].view(g.ny, g.nx, 4)
-        count = b64[o8 + 4 * n:o8 + 5 * n].view(g.ny, g.nx)
-        if fd.img_dtype_code == 2:
-            o16 = offset // 2 + 20 * n
-            img = bimg[o16:o16 + 3 * n].view(g.ny, g.nx, 3)
-            om = offset + 46 * n
-        else:
-            img = buf[offset + 40 * n:offset + 43 * n].view(g.ny, g.nx, 3)
-            om = offset + 43 * n
-        mask = buf[om:om + n].view(g.ny, g.nx)
-        # (BoundingBox.containsDiscontinuity is true for every box with a pole in it, reference mapping.py:200-206)
-        out = dict(has_elev=True, grid=grid, contains_pole=pole, contains_discontinuity=wrapped or pole,
-                   altitude=self.altitude)
-        # (the frame's bytes as they lie in the allocation: mean | count | image | mask — one copy takes all four to the host)
-        out['_block'] = buf[offset:om + n]
+            mem = self._fused_alloc(self._fused_nbytes(res), torch.cuda.current_stream(self.ctx.device))
+        buf, b64, _ = mem
+        # (one allocation for the four arrays: mean | count | image | mask; bbox[7]: a pole plan)
+        out, packed, mean, count, img, mask, end = _frame_block(
+            res.grid, pxPerDeg, res.bbox, bool(res.lon_wrapped), bool(res.bbox[7]), self.altitude, b64, offset // 8, buf,
+            offset + 40 * res.grid.ny * res.grid.nx, self.fd.img_dtype_code == 2)
+        # (the frame's bytes as they lie in the allocation: one copy takes all four arrays to the host)
+        out['_block'] = buf[offset:end]
         return out, packed, mean, count, img, mask
 
     def _fused_wrap(self, out, packed, mean, count, img, mask, keep_on_device):
@@ -642,7 +640,7 @@ class FramePipeline(object):
             # refuses to fuse that box again —, its corner quads decide, below)
             pole_guard = self._dirs is not None and self._fused.get('pole_in_view', -1) < 0 and \
                 (res.bbox[0] <= -85.0 or res.bbox[1] >= 85.0)
-            if res.status == 1 and res.fused and res.bbox[6] > 0 and res.edge_pixels <= 16384 and not self._fused.get('retried') \
+            if res.status == 1 and res.fused and res.bbox[6] > 0 and res.edge_pixels <= PIPE_MAX_EDGE_PIXELS and not self._fused.get('retried') \
                     and self.shard is None and not pole_guard:
                 # handed back although the launch was fused (the exact box does not fit the superset grid of a poor estimate,
                 # the date line judged differently by the pre-pass): once more with the exact box — in the coordinates of
@@ -766,24 +764,6 @@ def fused_class_pipeline(width, height, img_dtype, magnetic=False):
     return pipe
 
 
-def _close(a, b):
-    """Are two amt_frame_params neighbours in a sequence: same frame size, camera model within 1 % in scale, camera
-    within 100 km, boresight and Earth rotation within about half a degree, shell within 30 km?"""
-    if (a.width, a.height, a.fast_center) != (b.width, b.height, b.fast_center):
-        return False
-    if abs(a.a - b.a) > 30.0 or abs(a.b - b.b) > 30.0:
-        return False
-    # (separately solved frames of one sequence differ in the sixth digit of their CD matrix: the plate scale within 1 %
-    # and the reference pixel within 5 px move the box by far less than the superset's margin)
-    cd_tol = 0.01 * max(abs(v) for v in a.cd)
-    for x, y, tol in ((a.cam, b.cam, 100.0), (a.rot, b.rot, 0.01), (a.m_geo, b.m_geo, 0.01), (a.m_sm, b.m_sm, 0.01),
-                      (a.cd, b.cd, cd_tol), (a.crpix, b.crpix, 5.0)):
-        for u, v in zip(x, y):
-            if abs(u - v) > tol:
-                return False
-    return True
-
-
 _STREAMS = {}
 
 
@@ -801,39 +781,15 @@ def _shared_stream(device, role):
     return _STREAMS[key]
 
 
-def _steady(a, b, c, n_ab, n_bc):
-    """Frames a, b (n_ab frames apart) and c (n_bc frames after b): same frame size, shell and camera model as `_close`
-    asks, c within 400 km of b, and the camera has moved from b to c as it did from a to b (20 % + 5 km)?"""
-    if n_ab <= 0 or n_bc <= 0 or n_bc > 16:
-        return False
-    if (b.width, b.height, b.fast_center) != (c.width, c.height, c.fast_center):
-        return False
-    if abs(b.a - c.a) > 30.0 or abs(b.b - c.b) > 30.0:
-        return False
-    for x, y, tol in ((b.cam, c.cam, 400.0), (b.rot, c.rot, 0.05), (b.m_geo, c.m_geo, 0.05), (b.m_sm, c.m_sm, 0.05),
-                      (b.crpix, c.crpix, 5.0)):
-        for u, v in zip(x, y):
-            if abs(u - v) > tol:
-                return False
-    # the CD matrix turns with the camera's roll (5e-4 per element over 20 s of the real ISS029 sequence): same plate scale
-    # within 1 %, and the elements where the pace of a -> b puts them
-    scale_b = abs(b.cd[0] * b.cd[3] - b.cd[1] * b.cd[2]) ** 0.5
-    scale_c = abs(c.cd[0] * c.cd[3] - c.cd[1] * c.cd[2]) ** 0.5
-    if not (scale_b > 0 and abs(scale_c - scale_b) <= 0.01 * scale_b):
-        return False
-    for i in range(4):
-        step = (b.cd[i] - a.cd[i]) / n_ab
-        if abs((c.cd[i] - b.cd[i]) - step * n_bc) > 0.3 * abs(step * n_bc) + 0.01 * scale_b:
-            return False
-    for i in range(3):
-        step = (b.cam[i] - a.cam[i]) / n_ab
-        if abs((c.cam[i] - b.cam[i]) - step * n_bc) > 0.2 * abs(step * n_bc) + 5.0:
-            return False
-    for i in range(9):
-        step = (b.rot[i] - a.rot[i]) / n_ab
-        if abs((c.rot[i] - b.rot[i]) - step * n_bc) > 0.3 * abs(step * n_bc) + 2e-3:
-            return False
-    return True
+def _runs(indices):
+    """Ascending indices -> [(first, end)] of their runs of consecutive values (the frames of a batch that are launched)."""
+    runs = []
+    for i in indices:
+        if runs and runs[-1][1] == i:
+            runs[-1] = (runs[-1][0], i + 1)
+        else:
+            runs.append((i, i + 1))
+    return runs
 
 
 _RUN_RESULT_DTYPE = []
@@ -886,7 +842,6 @@ class NativeResults(object):
         return list(self) * n
 
     def _build(self, i):
-        import torch
         r = self._rec[i]
         if r.status in (2, 4):
             return None
@@ -894,31 +849,12 @@ class NativeResults(object):
             return self._fallbacks[i]
         seq = self._seq
         fd = seq.pipes[0].fd
-        b = r.bbox
-        wrapped, pole = bool(r.lon_wrapped), bool(r.contains_pole)
-        if wrapped:
-            box = (b[0], b[1], wrap_at_180(b[4] + 180), wrap_at_180(b[5] + 180))
-        else:
-            box = (b[0], b[1], b[2], b[3])
         ppd = (r.lat_px_per_deg, r.lon_px_per_deg)
-        grid = _GridView(r.grid, ppd, box)
-        ny, nx = r.ny, r.nx
-        n = ny * nx
-        o = r.grid_offset
-        packed = self._grids[o:o + 5 * n]
         stat = 'median' if seq.statistic == 'median' else 'mean'
-        mean = self._grids[o:o + 4 * n].view(ny, nx, 4)
-        count = self._grids[o + 4 * n:o + 5 * n].view(ny, nx)
-        ob = r.image_offset
-        if fd.img_dtype != np.uint8:
-            img = self._images[ob:ob + 6 * n].view(torch.int16).view(ny, nx, 3)
-            om = ob + 6 * n
-        else:
-            img = self._images[ob:ob + 3 * n].view(ny, nx, 3)
-            om = ob + 3 * n
-        mask = self._images[om:om + n].view(ny, nx)
-        out = dict(has_elev=True, grid=grid, contains_pole=pole, contains_discontinuity=wrapped or pole,
-                   altitude=r.altitude, magnetic=seq.magnetic, pxPerDeg=ppd)
+        out, packed, mean, count, img, mask, _ = _frame_block(
+            r.grid, ppd, r.bbox, bool(r.lon_wrapped), bool(r.contains_pole), r.altitude, self._grids, r.grid_offset, self._images,
+            r.image_offset, fd.img_dtype != np.uint8)
+        out.update(magnetic=seq.magnetic, pxPerDeg=ppd)
         if self._keep:
             out.update(img=img, mask=mask, count=count, packed=packed)
             out[stat] = mean
@@ -1081,33 +1017,39 @@ class SequencePipeline(object):
     def _box_hint(self, k, p):
         """
         Estimate of frame k's bounding-box reduction from frames that are already finished, or None (then the coarse
-        pre-pass runs).  The latest finished frame's exact box as it is when that frame is a neighbour of this one
-        (`_close`: camera within 100 km); else, in a steady sequence — the two latest finished frames are neighbours
-        of each other and the camera has kept its pace — their boxes extrapolated linearly to this frame: a frame is
-        prepared two batches ahead of the latest finished one, 20 s of orbit at the ISS's 3 s cadence, which moves
-        the box by more than the superset's margin, but smoothly.  A poor estimate costs time (the frame falls back
-        to the two-pass plan), never correctness.
+        pre-pass runs): amt_box_hint, the rule of the native runner (csrc/amt_params.h box_hint) — the latest finished
+        frame's exact box when that frame is a neighbour of this one, else, in a steady sequence, the two latest boxes
+        extrapolated linearly to this frame.  A poor estimate costs time (the frame falls back to the two-pass plan),
+        never correctness.
         """
         last, prev = self._hint, self._hint_prev
         if last is None:
             return None
-        if _close(last[1], p):
-            return last[0]
-        if prev is None or not _close(prev[1], last[1]) or not _steady(prev[1], last[1], p, last[2] - prev[2], k - last[2]):
-            return None
-        if bool(prev[0][7]) != bool(last[0][7]) or (last[0][3] - last[0][2] > 180) != (prev[0][3] - prev[0][2] > 180):
-            return None                     # a pole or the date line came into view between the two
-        f = (k - last[2]) / float(last[2] - prev[2])
-        est = [b + f * (b - a) for a, b in zip(prev[0][:6], last[0][:6])] + list(last[0][6:])
-        est[0], est[1] = max(est[0], -90.0), min(est[1], 90.0)
-        for i in (2, 3, 4, 5):
-            est[i] = min(max(est[i], -180.0), 180.0)
-        return est
+        box, q, i = prev if prev is not None else (None, None, 0)
+        est = _Box8()
+        ok = self.ctx._lib.amt_box_hint(last[0], C.byref(last[1]), last[2], box, None if q is None else C.byref(q), i, k,
+                                        C.byref(p), est)
+        return est if ok else None
+
+    def _hint_record(self, bbox, params, k):
+        """A frame the single-pass plan has finished becomes the latest record behind the box hints."""
+        self._hint_prev = self._hint
+        self._hint = (_Box8(*bbox), params, self._frames_done + k)
+
+    def _altitude_of(self, f):
+        """The shell of a frame tuple (header dict | amt_frame_params, camera, time, image[, altitude]): its own, or the pipeline's."""
+        return f[4] if len(f) > 4 and f[4] is not None else self.altitude
+
+    def _prepared(self, f):
+        """A frame tuple -> (amt_frame_params, camera, time, image, altitude)."""
+        hdr, cam, t, img = f[:4]
+        alt = self._altitude_of(f)
+        p = hdr if not isinstance(hdr, dict) else frame_params(hdr, alt, cam, t, self.fast, magnetic=self.magnetic)
+        return p, cam, t, img, alt
 
     def _prepare(self, k, frame):
-        hdr, cam, t, img = frame[:4]
-        alt = frame[4] if len(frame) > 4 and frame[4] is not None else self.altitude     # per-frame shell
-        p = hdr if not isinstance(hdr, dict) else frame_params(hdr, alt, cam, t, self.fast, magnetic=self.magnetic)
+        prepared = self._prepared(frame)
+        p = prepared[0]
         if self.single_pass:
             # the superset grid needs an estimate of the frame's bounding box: the exact box of the latest finished
             # frame when this one is its neighbour in the sequence (no kernel at all), else a coarse pre-pass (a
@@ -1115,7 +1057,7 @@ class SequencePipeline(object):
             hint = self._box_hint(self._frames_done + k, p) if self.use_hints else None
             self.pipes[k % len(self.pipes)].start_coarse(p, self.min_elevation, self.magnetic, hint)
             self.hinted += hint is not None
-        return p, cam, t, img, alt
+        return prepared
 
     def _launch(self, k0, prepared, pxPerDeg=None):
         """Launch the frames k0, k0+1, ... (one batch; prepared = their _prepare results).  `pxPerDeg`: a list with one
@@ -1199,8 +1141,7 @@ class SequencePipeline(object):
                         self._bin_done[slot] = ev
         self.plans.append(q.last_plan)
         if q.last_plan == 'single-pass':
-            self._hint_prev = self._hint
-            self._hint = (list(q._fused['result'].bbox), q.params, self._frames_done + k)
+            self._hint_record(q._fused['result'].bbox, q.params, k)
         else:
             self._hint = self._hint_prev = None     # the next frame gets a real pre-pass
         return res
@@ -1228,8 +1169,7 @@ class SequencePipeline(object):
             r = done[i]
             r['magnetic'] = self.magnetic
             self.plans.append('single-pass')
-            self._hint_prev = self._hint
-            self._hint = (list(ready[i].bbox), qs[i].params, self._frames_done + k0 + i)
+            self._hint_record(ready[i].bbox, qs[i].params, k0 + i)
             out.append(r)
         return out
 
@@ -1320,7 +1260,7 @@ class SequencePipeline(object):
                 try:
                     # frame by frame: the library launches as soon as a batch is complete, the first after one frame
                     for f in frames[done_total:]:
-                        alt = f[4] if len(f) > 4 and f[4] is not None else 0.0
+                        alt = self._altitude_of(f)
                         im_f = f[3]
                         if im_f.is_cuda:
                             run_frame(f[0], f[1], f[2], alt, im_f.data_ptr(), out=one)
@@ -1388,7 +1328,7 @@ class SequencePipeline(object):
                     q.use_image(f[3])
                 else:
                     q.set_image(f[3])
-                alt = f[4] if len(f) > 4 and f[4] is not None else self.altitude
+                alt = self._altitude_of(f)
                 try:
                     ppd = (table['lat_px_per_deg'][k], table['lon_px_per_deg'][k]) if self.arcsecPerPx else self.pxPerDeg
                     # (median: the frames the runner's median pass does not cover — a pole in view, exact centres — by
@@ -1445,10 +1385,7 @@ class SequencePipeline(object):
                 f = next(it, None)
                 if f is None:
                     break
-                hdr, cam, t, img = f[:4]
-                alt = f[4] if len(f) > 4 and f[4] is not None else self.altitude
-                p = hdr if not isinstance(hdr, dict) else frame_params(hdr, alt, cam, t, self.fast, magnetic=self.magnetic)
-                prepared.append((p, cam, t, img, alt))
+                prepared.append(self._prepared(f))
             if prepared:
                 n = len(prepared)
                 qs = [self.pipes[(k0 + i) % nb] for i in range(n)]
@@ -1477,34 +1414,24 @@ class SequencePipeline(object):
                 q.start_coarse(pr[0], self.min_elevation, self.magnetic, hint=red)
                 ppd.append(v)
                 live.append(i)
-            # the frames of the batch that have a valid pixel, as consecutive runs (a launch takes consecutive buffers)
-            i = 0
-            while i < len(live):
-                j = i
-                while j + 1 < len(live) and live[j + 1] == live[j] + 1:
-                    j += 1
-                self._launch(k0 + live[i], [prepared[m] for m in live[i:j + 1]], pxPerDeg=[ppd[m] for m in live[i:j + 1]])
-                i = j + 1
+            # (a launch takes consecutive buffers)
+            for i, j in _runs(live):
+                self._launch(k0 + i, prepared[i:j], pxPerDeg=ppd[i:j])
             return ppd
 
         def finish(k0, ppd):
             res = []
-            i = 0
-            while i < len(ppd):
-                if ppd[i] is None or ppd[i] == 'pole':
-                    self.plans.append('empty' if ppd[i] is None else 'pole-without-resolution')
+            done = 0
+            for i, j in _runs([m for m, v in enumerate(ppd) if isinstance(v, tuple)]) + [(len(ppd), len(ppd))]:
+                for v in ppd[done:i]:
+                    self.plans.append('empty' if v is None else 'pole-without-resolution')
                     res.append(None)
-                    i += 1
-                    continue
-                j = i
-                while j + 1 < len(ppd) and isinstance(ppd[j + 1], tuple):
-                    j += 1
-                part = self._finish_batch(k0 + i, j - i + 1, keep_on_device)
-                for r, v in zip(part, ppd[i:j + 1]):
+                part = self._finish_batch(k0 + i, j - i, keep_on_device) if j > i else []
+                for r, v in zip(part, ppd[i:j]):
                     if r is not None:
                         r['pxPerDeg'] = v
                 res.extend(part)
-                i = j + 1
+                done = j
             return res
 
         batches = {0: box(0)}

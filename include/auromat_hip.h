@@ -42,7 +42,7 @@ extern "C" {
 /* 8: amt_median_frame_async (the median pass without a read-back); amt_run_config.statistic (median sequences in the runner, in
  *    place of reserved_); amt_pipe_set_plan(pipe, 2) */
 /* 9: amt_mosaic_frames, amt_mosaic_member (the members of a collection binned onto one grid, auromat_amd.resample.resampleMosaic) */
-#define AMT_ABI_VERSION 9
+#define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
 #define AMT_EINVAL (-1)   /* bad argument (NULL pointer, negative size, unsupported dtype ...) */
@@ -670,13 +670,16 @@ int amt_grid_layout(double lat_px_per_deg, double lon_px_per_deg, double lat_min
  * arrays and bbox are valid, nothing else;
  * 2 = no pixel above the elevation threshold (mapping.py:858-859 -> ValueError). */
 typedef struct amt_pipe amt_pipe;
+#define AMT_PIPE_MAX_EDGE_PIXELS 16384
 typedef struct amt_pipe_result {
     int32_t status;
     int32_t fused;          /* 1 when the fused kernel was launched for this frame */
     int32_t lon_wrapped;    /* 1: the frame straddles the 180 deg discontinuity; `grid` is laid out for longitudes
                              * shifted by 180 deg (wrap_at_180(lon + 180)) and the caller shifts the output
                              * coordinates back (reference resample.py:203-218,274-277) */
-    int32_t edge_pixels;    /* pixels on a bin edge (right-most-edge rule) that were resolved separately */
+    int32_t edge_pixels;    /* pixels on a bin edge (right-most-edge rule) that were resolved separately; a fused frame
+                             * with more than AMT_PIPE_MAX_EDGE_PIXELS of them (the driver's records) gets status 1, and
+                             * launching it again with its exact box as the estimate cannot help */
     double bbox[8];         /* exact reduction of amt_georef_frame; [7] = 1 when a pole (of the grid's coordinates) is in
                              * view: [0..5] are then in the rotated coordinates the grid is laid out in (amt_georef_out.
                              * bin_pole), and the caller rotates the output coordinates back (resample.py:262-273) */
@@ -872,6 +875,22 @@ typedef struct amt_run_result {
 /* The host scalars of one frame (no GPU call).  AMT_EINVAL: date outside the IGRF table with want_sm. */
 int amt_frame_params_from_wcs(const amt_run_frame* frame, int32_t width, int32_t height, int32_t fast_center,
                               double altitude, int32_t want_sm, amt_frame_params* out);
+/* The host rules of the frame drivers and the runner on those scalars (ABI v10; no context, no GPU call) — what the library
+ * itself decides with, so that a host with a frame loop of its own decides the same:
+ * amt_pole_in_view: +1 / -1 when the north / south pole of the mapping shell (magnetic != 0: of the SM frame; p->m_sm must be
+ * set) is imaged by a valid pixel of the camera model — inside the frame, the first hit of its ray, at or above min_elevation
+ * (-inf: no threshold) —, else 0; the decision of amt_pipe_launch(pole_in_view < 0) and of amt_pipe_launch_box.
+ * amt_frames_close: 1 when two frames are neighbours in a sequence (same size, camera within 100 km, pointing and Earth
+ * rotation within half a degree, plate scale within 1 %, shell within 30 km), else 0.
+ * amt_box_hint: the runner's estimate of the box reduction of frame k (parameters p) from the latest frame the single-pass
+ * plan finished — its exact reduction (amt_pipe_result.bbox), parameters and running index — and the one finished before it
+ * (prev_box = NULL: none): last_box itself when that frame and p are close; the two boxes extrapolated linearly to k when the
+ * sequence is steady (the camera keeps the pace of prev -> last, at most 16 frames ahead) and neither a pole nor the date line
+ * came into view between the two.  Returns 1 and fills est8 (for amt_pipe_coarse_hint), or 0: run amt_pipe_coarse. */
+int amt_pole_in_view(const amt_frame_params* p, double min_elevation, int magnetic);
+int amt_frames_close(const amt_frame_params* a, const amt_frame_params* b);
+int amt_box_hint(const double* last_box, const amt_frame_params* last_p, int64_t last_index, const double* prev_box,
+                 const amt_frame_params* prev_p, int64_t prev_index, int64_t k, const amt_frame_params* p, double* est8);
 int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run);
 int amt_run_destroy(amt_run* run);
 /* Processes frames[0 .. n) on the context's stream (+ the drivers' own streams); on return the context's stream is

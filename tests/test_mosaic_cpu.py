@@ -126,7 +126,7 @@ def test_arcsec_resolution_comes_from_the_merged_box():
 def test_struct_size_matches_the_header():
     from auromat_amd._native import ABI_VERSION, MosaicMember, _SIGNATURES
     assert C.sizeof(MosaicMember) == 5 * 8 + 6 * 4
-    assert ABI_VERSION == 9 and 'amt_mosaic_frames' in _SIGNATURES
+    assert ABI_VERSION == 10 and 'amt_mosaic_frames' in _SIGNATURES
 
 
 def test_public_names():

@@ -146,8 +146,10 @@ def test_real_sequence_headers_are_the_references():
     assert all(f[0]['IMAGEW'] == 4256 and f[0]['IMAGEH'] == 2832 for f in frames)
     # neighbouring real frames are neighbours for the box hints too (their separately solved CD matrices differ in the
     # sixth digit), frames 20 s apart are not
+    import ctypes as C
+    from auromat_amd import _native
     from auromat_amd.mapping.astrometry import frame_params
-    from auromat_amd.pipeline import _close
+    _close = lambda a, b: bool(_native.lib().amt_frames_close(C.byref(a), C.byref(b)))
     ps = [frame_params(h, 110, cam, t, True) for h, cam, t, _ in frames]
     assert all(_close(a, b) for a, b in zip(ps, ps[1:])) and _close(ps[0], ps[3]) and not _close(ps[0], ps[7])
 
