@@ -114,6 +114,7 @@ class RunResult(C.Structure):
 
 
 ABI_VERSION = 10         # include/auromat_hip.h AMT_ABI_VERSION
+QUANTILES_MAX = 8         # AMT_QUANTILES_MAX: quantiles per call of amt_quantile_frame[_async]
 PIPE_MAX_EDGE_PIXELS = 16384     # AMT_PIPE_MAX_EDGE_PIXELS: a fused frame with more on-edge pixels is not launched again
 _I, _L, _D, _P = C.c_int, C.c_int64, C.c_double, C.c_void_p
 _SIGNATURES = {
@@ -203,6 +204,11 @@ _SIGNATURES = {
                           C.POINTER(Axis), _I, _P, _P, _P, _P], _I),
     'amt_median_frame_async': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                                 C.POINTER(Axis), _I, _I, _P, _P, _P, _P], _I),
+    'amt_quantile_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                            C.POINTER(Axis), _I, c_double_p, _I, _P, _P, _P, _P], _I),
+    'amt_quantile_frame_async': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                                  C.POINTER(Axis), _I, _I, c_double_p, _I, _P, _P, _P, _P], _I),
+    'amt_quantile_rank': ([_L, _D, C.POINTER(_L), C.POINTER(_L), c_double_p], _I),
     'amt_mosaic_frames': ([_P, C.POINTER(MosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis),
                            _I, C.c_int32, _P, _P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
@@ -238,6 +244,7 @@ _SIGNATURES = {
     'amt_run_push': ([_P, C.POINTER(RunFrame)], _I),
     'amt_run_end': ([_P, C.POINTER(C.c_int32)], _I),
     'amt_run_reset_hints': ([_P], _I),
+    'amt_run_set_quantile': ([_P, _D], _I),
     'amt_seq_payload_size': ([C.POINTER(SeqFrame), C.c_int32, C.POINTER(_L)], _I),
     'amt_seq_pack': ([_P, C.POINTER(SeqFrame), C.c_int32, C.c_int32, _P, _L], _I),
     'amt_seq_unpack': ([_P, _L, C.c_int32, C.c_int32, C.POINTER(SeqFrame), C.c_int32, C.POINTER(C.c_int32)], _I),

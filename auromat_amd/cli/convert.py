@@ -22,7 +22,8 @@ What differs, and why:
   -m auromat_amd.cli.convert``) the frames are sharded over the ranks and every rank writes the files of its own frames.
 * ``--statistic median`` (an addition; needs ``--resample``) bins every cell by the median of its pixels instead of their
   mean (:func:`auromat_amd.resample.resampleMedian` / ``resampleMedianMLatMLT``), through the same two routes; the files
-  are written exactly as mean grids are.
+  are written exactly as mean grids are.  ``--statistic quantile --quantile Q`` bins by the quantile Q in [0, 1] of a cell's
+  pixels in the same way (:func:`auromat_amd.resample.resampleQuantile` / ``resampleQuantileMLatMLT``).
 """
 from __future__ import print_function
 
@@ -96,9 +97,12 @@ def getParser():
                                    'runs through the single-pass frame pipeline')
     resampleArgs.add_argument('--grid', help='The grid which will be regular after resampling. Default is MLat/MLT grid. '
                                              'Use geo for geographical grid.', default=Grid.mag, choices=[Grid.geo, Grid.mag])
-    resampleArgs.add_argument('--statistic', choices=['mean', 'median'], default='mean',
+    resampleArgs.add_argument('--statistic', choices=['mean', 'median', 'quantile'], default='mean',
                               help='How the pixels of a grid cell are combined, default mean; median is robust to stars, city '
-                                   'lights and hot pixels (needs --resample)')
+                                   'lights and hot pixels; quantile takes --quantile (both need --resample)')
+    resampleArgs.add_argument('--quantile', metavar='Q', type=float,
+                              help='the quantile of a cell\'s pixels, in [0, 1], for --statistic quantile (numpy.quantile, '
+                                   'method linear): 0.25 a background estimate, 0.9 a peak estimate')
     outputArgs = parser.add_argument_group('output')
     outputArgs.add_argument('--out', help='Output directory, by default the "converted" subdirectory of --data')
     outputArgs.add_argument('--overwrite', help='Overwrites existing files.', action='store_true')
@@ -131,8 +135,15 @@ def parseargs(argv=None):
         args.out = os.path.join(args.data, 'converted')
     if args.overwrite and args.skip:
         parser.error('only one of --overwrite and --skip is allowed')
-    if args.statistic == 'median' and not args.resample:
-        parser.error('--statistic median needs --resample')
+    if args.statistic != 'mean' and not args.resample:
+        parser.error('--statistic %s needs --resample' % args.statistic)
+    if args.statistic == 'quantile':
+        if args.quantile is None:
+            parser.error('--statistic quantile needs --quantile')
+        if not 0.0 <= args.quantile <= 1.0:
+            parser.error('--quantile must be in the range [0, 1]')
+    elif args.quantile is not None:
+        parser.error('--quantile is only usable with --statistic quantile')
     if args.withoutGeo and args.format == Format.netcdf:
         parser.error('--without-geo is only usable with --format cdf')
     if args.format == Format.cdf:
@@ -223,7 +234,8 @@ def extension(args):
 def convert_with_classes(args, frames, export):
     """Frame by frame through the mapping classes: the reference's flow, its resolution rule included."""
     from ..mapping.spacecraft import getMapping
-    from ..resample import resample, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT
+    from ..resample import (resample, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT, resampleQuantile,
+                            resampleQuantileMLatMLT)
     for identifier, hdr, img_path in frames:
         path = target_path(args, identifier)
         if path is None:
@@ -236,6 +248,10 @@ def convert_with_classes(args, frames, export):
             if args.statistic == 'median':
                 fn = resampleMedian if args.grid == Grid.geo else resampleMedianMLatMLT
                 mapping = fn(mapping, **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
+            elif args.statistic == 'quantile':
+                fn = resampleQuantile if args.grid == Grid.geo else resampleQuantileMLatMLT
+                mapping = fn(mapping, args.quantile,
+                             **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
             else:
                 fn = resample if args.grid == Grid.geo else resampleMLatMLT
                 mapping = fn(mapping, arcsecPerPx=args.resolution)
@@ -247,7 +263,7 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
     """The resampled grid of one frame (host arrays of the few hundred KB the pipeline returns) as the mapping that
     ``resample`` / ``resampleMLatMLT`` would have returned: a GenericMapping in geodetic coordinates; a grid that is
     regular in (MLat, SM longitude) goes through SM -> GEO like ``convertSMMappingToGeo`` (reference
-    mapping.py:1549-1559).  The elevation comes from the 'mean' block or, for median grids, the 'median' block."""
+    mapping.py:1549-1559).  The elevation comes from the 'mean' block or, for median and quantile grids, the 'median' / 'quantile' block."""
     from ..coordinates.transform import smToLatLon
     from ..mapping.mapping import GenericMapping
     lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
@@ -255,7 +271,7 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
         lat, lon = smToLatLon(lat, lon, t)
         lat_c, lon_c = smToLatLon(lat_c, lon_c, t)
     img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    block = res['mean'] if 'mean' in res else res['median']
+    block = res['mean'] if 'mean' in res else res['median'] if 'median' in res else res['quantile']
     return GenericMapping(lat, lon, lat_c, lon_c, ma.masked_invalid(block[:, :, -1]), altitude, img, cam, t, identifier)
 
 
@@ -315,7 +331,8 @@ def convert_with_pipeline(args, frames, export):
                                altitude=args.altitude, fast=not args.exactCenters,
                                min_elevation=args.minElevation if args.minElevation >= 0 else None,
                                pxPerDeg=args.pxPerDeg or 10, magnetic=magnetic, keep_coordinates=False,
-                               arcsecPerPx=None if args.pxPerDeg else args.resolution, statistic=args.statistic)
+                               arcsecPerPx=None if args.pxPerDeg else args.resolution, statistic=args.statistic,
+                               quantile=args.quantile)
 
         def feed():
             # decoding a 12 Mpx JPEG takes ~100 ms of host time, the GPU 0.2 ms per frame: images are read ahead on a
@@ -359,7 +376,7 @@ def convert_with_pipeline(args, frames, export):
                     continue
                 host = dict(res)
                 host.update(grid_coordinates(res))
-                stat = 'median' if args.statistic == 'median' else 'mean'
+                stat = args.statistic               # the name of the block: 'mean', 'median' or 'quantile'
                 host[stat] = to_host(res[stat])
                 host.update(img=to_host(res['img'], dtype=first.dtype), mask=to_host(res['mask']).astype(bool))
                 print('storing', path)

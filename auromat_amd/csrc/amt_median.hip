@@ -23,6 +23,10 @@
 // and a workgroup of the walk waits for one more load than one of k_med_medium.
 // Both tiers select k_lo = (n-1)/2 and get k_hi = n/2 from the same pass: it is k_lo's value when the keys <= that
 // value are more than k_hi, else the smallest key above it (one more pass).  Even counts average the two in float64.
+// Quantile binning (amt_quantile_frame[_async], auromat_amd.resample.resampleQuantile) is the same code under another rank
+// rule (rank_rule below): np.quantile's pair (k, k + 1) of method 'linear' and its lerp (put_quantile) in place of the
+// middle pair and its mean.  The count, scan and fill passes run once per call; the small tier sorts a plane once and
+// reads every quantile's pair from the sorted lanes, the two upper tiers select once per quantile of the call.
 #include "amt_common.h"
 
 #include <algorithm>
@@ -38,6 +42,45 @@ constexpr int kSmallMax = 64;           // cells up to one wave's lanes are sort
 constexpr int kLargeMin = 16384;        // cells above this many keys are spread over several workgroups
 constexpr int kChunk = 4096;            // keys per workgroup of the large tier
 constexpr int kScanItems = 8;           // cells per thread of the scan
+constexpr int kQuantilesMax = AMT_QUANTILES_MAX;
+
+// The rank rule: which two order statistics of a cell's n >= 1 sorted keys a result is made of (k2 is k or k + 1), and the
+// weight g that put_quantile gives them.
+//   median:  np.median's middle pair (n-1)/2 and n/2, combined as (a + b) / 2 (put_median; g is not used)
+//   else:    np.quantile(..., q) by method 'linear', operation by operation (numpy/lib/_function_base_impl.py: _quantile,
+//            _get_indexes, _get_gamma): vi = (n-1) * q in float64, k = floor(vi), g = vi - k; where vi >= n-1 (q = 1,
+//            n = 1) both ranks are n-1 and g = vi + 1, NumPy's index -1 for the last value taken literally: the lerp of
+//            the equal pair then leaves -0.0 as it is for n = 1 and gives +0.0 otherwise, as np.quantile does
+// One function for the device and for the host entry point amt_quantile_rank.
+struct rank_pair {
+    int64_t k, k2;
+    double g;
+};
+
+__host__ __device__ inline rank_pair rank_rule(int64_t n, double q, bool median) {
+#pragma clang fp contract(off)
+    rank_pair r;
+    __builtin_assume(n >= 1);
+    if (median) {
+        // (unsigned shifts: for the 32-bit counts of the kernels these stay 32-bit operations, as they were before this rule)
+        r.k = (int64_t)((uint64_t)(n - 1) >> 1);
+        r.k2 = (int64_t)((uint64_t)n >> 1);
+        r.g = 0.5;
+        return r;
+    }
+    const double top = (double)(n - 1);
+    const double vi = top * q;
+    const double fl = floor(vi);
+    if (vi >= top) {
+        r.k = r.k2 = n - 1;
+        r.g = vi + 1.0;
+    } else {
+        r.k = (int64_t)fl;
+        r.k2 = r.k + 1;
+        r.g = vi - fl;
+    }
+    return r;
+}
 
 inline dim3 grid_for(int64_t n) {
     int64_t blocks = (n + kBlock - 1) / kBlock;
@@ -276,11 +319,24 @@ struct out_args {
     const unsigned* offset;
     const uint16_t* keys16;
     const unsigned long long* keys64;
-    double* median;
-    void* out_img;
+    double* median;                     // median (ny, nx, nch+1), or quantile (nq, ny, nx, nch+1)
+    void* out_img;                      // (ny, nx, nch), or (nq, ny, nx, nch)
     uint8_t* out_mask;
     double* out_count;
+    int nq;                             // 0: the median; else the quantiles q[0 .. nq)
+    double q[kQuantilesMax];
 };
+
+// The kernels below that depend on the statistic are instantiated once per rank rule (QUANT false: the median, which then
+// compiles to what it was before the quantiles came: one result, constant ranks, no look at q).
+// results per cell and plane, and the ranks of result j for a cell of cnt keys
+template <bool QUANT>
+__device__ __forceinline__ int stat_count(const out_args& O) { return QUANT ? O.nq : 1; }
+
+template <bool QUANT>
+__device__ __forceinline__ rank_pair stat_rank(const out_args& O, int j, unsigned cnt) {
+    return rank_rule((int64_t)cnt, QUANT ? O.q[j] : 0.5, !QUANT);
+}
 
 __device__ __forceinline__ int64_t out_index(const out_args& O, int cell) {
     const int iy = cell / O.nx, ix = cell - iy * O.nx;
@@ -300,6 +356,38 @@ __device__ __forceinline__ void put_median(const out_args& O, int cell, int p, u
         if (O.img_dtype == 1) static_cast<uint8_t*>(O.out_img)[o * O.nch + p] = (uint8_t)rint(v);     // half to even
         else static_cast<uint16_t*>(O.out_img)[o * O.nch + p] = (uint16_t)rint(v);
     }
+}
+
+// np.quantile's lerp of the keys of ranks k and k2 into result j (numpy/lib/_function_base_impl.py: _lerp), every operation
+// rounded on its own.  Always evaluated: a + d * 0 turns -0.0 into +0.0, as NumPy does.  The image: round half to even.
+__device__ __forceinline__ void put_quantile(const out_args& O, int cell, int p, int j, unsigned long long lo,
+                                             unsigned long long hi, double g) {
+#pragma clang fp contract(off)
+    const int64_t o = (int64_t)j * O.nx * O.ny + out_index(O, cell);
+    const double a = p == O.nch ? elev_of_key(lo) : (double)lo;
+    const double b = p == O.nch ? elev_of_key(hi) : (double)hi;
+    const double d = b - a;
+    double v;
+    if (g >= 0.5) {
+        const double t = d * (1.0 - g);
+        v = b - t;
+    } else {
+        const double t = d * g;
+        v = a + t;
+    }
+    O.median[o * (O.nch + 1) + p] = v;
+    if (p < O.nch && O.out_img) {
+        if (O.img_dtype == 1) static_cast<uint8_t*>(O.out_img)[o * O.nch + p] = (uint8_t)rint(v);
+        else static_cast<uint16_t*>(O.out_img)[o * O.nch + p] = (uint16_t)rint(v);
+    }
+}
+
+// result j of plane p from the keys of its two ranks, by the call's statistic
+template <bool QUANT>
+__device__ __forceinline__ void put_stat(const out_args& O, int cell, int p, int j, unsigned long long lo,
+                                         unsigned long long hi, double g) {
+    if (!QUANT) put_median(O, cell, p, lo, hi);
+    else put_quantile(O, cell, p, j, lo, hi, g);
 }
 
 __device__ __forceinline__ int plane_bits(const out_args& O, int p) {
@@ -332,12 +420,14 @@ struct tier_counters {
 // One wave per cell: every cell's count and mask, NaN / 0 for empty ones, the median of cells of <= 64 keys; the
 // others are appended to the medium or large list.  The wave that lists a large cell also zeroes that cell's digit
 // histograms and tickets (nplane * 256 + nplane words from `lclear` on).
+template <bool QUANT>
 __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restrict__ medium, int* __restrict__ large,
                                                      tier_counters* __restrict__ tiers, unsigned* __restrict__ lclear) {
     const int lane = threadIdx.x & 63;
     const int64_t cells = (int64_t)O.nx * O.ny;
     const int64_t waves = (int64_t)gridDim.x * (kBlock / 64);
     const int nplane = O.nch + (O.has_elev ? 1 : 0);
+    const int nstat = stat_count<QUANT>(O);
     for (int64_t w = blockIdx.x * (int64_t)(kBlock / 64) + (threadIdx.x >> 6); w < cells; w += waves) {
         const int cell = (int)w;
         const unsigned cnt = O.count[cell];
@@ -346,16 +436,19 @@ __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restric
         if (lane == 0) {
             if (O.out_count) O.out_count[o] = (double)cnt;
             if (O.out_mask) O.out_mask[o] = cnt == 0;
-            if (cnt == 0 || !O.has_elev) O.median[o * (O.nch + 1) + O.nch] = NAN;
-            if (cnt == 0) {
+            for (int j = 0; j < nstat; ++j) {
+                const int64_t oj = j * cells + o;
+                if (cnt == 0 || !O.has_elev) O.median[oj * (O.nch + 1) + O.nch] = NAN;
+                if (cnt != 0) continue;
                 for (int p = 0; p < O.nch; ++p) {
-                    O.median[o * (O.nch + 1) + p] = NAN;
+                    O.median[oj * (O.nch + 1) + p] = NAN;
                     if (O.out_img) {
-                        if (O.img_dtype == 1) static_cast<uint8_t*>(O.out_img)[o * O.nch + p] = 0;
-                        else static_cast<uint16_t*>(O.out_img)[o * O.nch + p] = 0;
+                        if (O.img_dtype == 1) static_cast<uint8_t*>(O.out_img)[oj * O.nch + p] = 0;
+                        else static_cast<uint16_t*>(O.out_img)[oj * O.nch + p] = 0;
                     }
                 }
-            } else if (cnt > (unsigned)kSmallMax) {
+            }
+            if (cnt > (unsigned)kSmallMax) {
                 if (cnt > (unsigned)kLargeMin) {
                     listed = (int)atomicAdd(&tiers->n_large, 1u);
                     large[listed] = cell;
@@ -372,19 +465,23 @@ __global__ __launch_bounds__(kBlock) void k_med_small(out_args O, int* __restric
         }
         if (cnt == 0 || cnt > (unsigned)kSmallMax) continue;       // (wave-uniform)
         const unsigned off = O.offset[cell];
-        const int klo = (int)(cnt - 1) / 2, khi = (int)cnt / 2;
+        // a plane is sorted once; every result of the call reads its pair from the sorted lanes
         for (int p = 0; p < nplane; ++p) {
-            unsigned long long lo, hi;
             if (p == O.nch) {
                 const unsigned long long key = wave_sort(lane < (int)cnt ? O.keys64[off + lane] : ~0ull, lane);
-                lo = __shfl(key, klo);
-                hi = __shfl(key, khi);
+                for (int j = 0; j < nstat; ++j) {
+                    const rank_pair r = stat_rank<QUANT>(O, j, cnt);
+                    const unsigned long long lo = __shfl(key, (int)r.k), hi = __shfl(key, (int)r.k2);
+                    if (lane == 0) put_stat<QUANT>(O, cell, p, j, lo, hi, r.g);
+                }
             } else {
                 const unsigned key = wave_sort(lane < (int)cnt ? (unsigned)O.keys16[(int64_t)p * O.n + off + lane] : ~0u, lane);
-                lo = (unsigned)__shfl(key, klo);
-                hi = (unsigned)__shfl(key, khi);
+                for (int j = 0; j < nstat; ++j) {
+                    const rank_pair r = stat_rank<QUANT>(O, j, cnt);
+                    const unsigned lo = __shfl(key, (int)r.k), hi = __shfl(key, (int)r.k2);
+                    if (lane == 0) put_stat<QUANT>(O, cell, p, j, lo, hi, r.g);
+                }
             }
-            if (lane == 0) put_median(O, cell, p, lo, hi);
         }
     }
 }
@@ -450,16 +547,20 @@ __device__ __forceinline__ bool prefix_match(unsigned long long key, unsigned lo
     return shift + 8 >= 64 || (key >> (shift + 8)) == (prefix >> (shift + 8));
 }
 
-// Radix select of k_lo per plane in LDS for one cell, by the whole workgroup.
+// Radix select of the first rank per plane and result in LDS for one cell, by the whole workgroup.
+template <bool QUANT>
 __device__ __forceinline__ void medium_cell(const out_args& O, int cell, unsigned* sHist, digit_pick& sPick,
                                             unsigned long long& sMin) {
     const int lane = threadIdx.x & 63;
     const unsigned cnt = O.count[cell], off = O.offset[cell];
-    const unsigned klo = (cnt - 1) / 2, khi = cnt / 2;
     const int nplane = O.nch + (O.has_elev ? 1 : 0);
-    for (int p = 0; p < nplane; ++p) {
+    const int nstat = stat_count<QUANT>(O);
+    for (int p = 0; p < nplane; ++p)
+    for (int j = 0; j < nstat; ++j) {
+        const rank_pair rk = stat_rank<QUANT>(O, j, cnt);
+        const unsigned khi = (unsigned)rk.k2;
         unsigned long long prefix = 0;
-        unsigned k = klo, less = 0, eq = 0;
+        unsigned k = (unsigned)rk.k, less = 0, eq = 0;
         for (int shift = plane_bits(O, p) - 8; shift >= 0; shift -= 8) {
             sHist[threadIdx.x] = 0;
             __syncthreads();
@@ -483,7 +584,7 @@ __device__ __forceinline__ void medium_cell(const out_args& O, int cell, unsigne
         }
         unsigned long long hi = prefix;
         if (khi >= less + eq) {
-            // the upper middle key is the smallest key above the lower one
+            // the key of the second rank is the smallest key above the first one
             if (threadIdx.x == 0) sMin = ~0ull;
             __syncthreads();
             unsigned long long m = ~0ull;
@@ -500,45 +601,51 @@ __device__ __forceinline__ void medium_cell(const out_args& O, int cell, unsigne
             __syncthreads();
             hi = sMin;
         }
-        if (threadIdx.x == 0) put_median(O, cell, p, prefix, hi);
+        if (threadIdx.x == 0) put_stat<QUANT>(O, cell, p, j, prefix, hi, rk.g);
         __syncthreads();
     }
 }
 
 // One workgroup per cell of 65 .. kLargeMin keys.
+template <bool QUANT>
 __global__ __launch_bounds__(kBlock) void k_med_medium(out_args O, const int* __restrict__ medium) {
     __shared__ unsigned sHist[256];
     __shared__ digit_pick sPick;
     __shared__ unsigned long long sMin;
-    medium_cell(O, medium[blockIdx.x], sHist, sPick, sMin);
+    medium_cell<QUANT>(O, medium[blockIdx.x], sHist, sPick, sMin);
 }
 
 // The same over a fixed grid: the workgroups walk the list of medium cells, whose length they read from device memory.
+template <bool QUANT>
 __global__ __launch_bounds__(kBlock) void k_med_medium_walk(out_args O, const int* __restrict__ medium,
                                                            const tier_counters* __restrict__ tiers) {
     __shared__ unsigned sHist[256];
     __shared__ digit_pick sPick;
     __shared__ unsigned long long sMin;
     const unsigned n_medium = tiers->n_medium;
-    for (unsigned i = blockIdx.x; i < n_medium; i += gridDim.x) medium_cell(O, medium[i], sHist, sPick, sMin);
+    for (unsigned i = blockIdx.x; i < n_medium; i += gridDim.x) medium_cell<QUANT>(O, medium[i], sHist, sPick, sMin);
 }
 
 // ---- large tier: one plane at a time, one launch pair per digit ----
 // (ghist: 256 words per large cell from the start of `lh`, zero on entry and after every k_med_large_digit)
 struct large_state {
     unsigned long long prefix, min_above;
-    unsigned k, less, eq, pad;
+    unsigned k, less, eq, k2;           // k2: the second rank of the result being selected
 };
 
-__global__ void k_med_large_init(const out_args O, const int* __restrict__ large, int n_large, large_state* __restrict__ st) {
+template <bool QUANT>
+__global__ void k_med_large_init(const out_args O, const int* __restrict__ large, int n_large, int j,
+                                 large_state* __restrict__ st) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= n_large) return;
     const unsigned cnt = O.count[large[l]];
     large_state s;
     s.prefix = 0;
     s.min_above = ~0ull;
-    s.k = (cnt - 1) / 2;
-    s.less = s.eq = s.pad = 0;
+    const rank_pair r = stat_rank<QUANT>(O, j, cnt);
+    s.k = (unsigned)r.k;
+    s.k2 = (unsigned)r.k2;
+    s.less = s.eq = 0;
     st[l] = s;
 }
 
@@ -583,14 +690,14 @@ __global__ __launch_bounds__(64) void k_med_large_digit(int shift, large_state* 
     }
 }
 
-// the smallest key above the selected one, where the upper middle key needs it
+// the smallest key above the selected one, where the second rank needs it
 __global__ __launch_bounds__(kBlock) void k_med_large_above(const out_args O, const int* __restrict__ large, int p,
                                                            large_state* __restrict__ st) {
     const int lane = threadIdx.x & 63;
     const int l = blockIdx.y;
     const unsigned cnt = O.count[large[l]], off = O.offset[large[l]];
     const unsigned b0 = blockIdx.x * (unsigned)kChunk;
-    if (b0 >= cnt || cnt / 2 < st[l].less + st[l].eq) return;      // (block-uniform)
+    if (b0 >= cnt || st[l].k2 < st[l].less + st[l].eq) return;     // (block-uniform)
     const unsigned b1 = min(cnt, b0 + (unsigned)kChunk);
     const unsigned long long lo = st[l].prefix;
     unsigned long long m = ~0ull;
@@ -606,14 +713,15 @@ __global__ __launch_bounds__(kBlock) void k_med_large_above(const out_args O, co
     if (lane == 0 && m != ~0ull) atomicMin(&st[l].min_above, m);
 }
 
-__global__ void k_med_large_put(const out_args O, const int* __restrict__ large, int n_large, int p,
+template <bool QUANT>
+__global__ void k_med_large_put(const out_args O, const int* __restrict__ large, int n_large, int p, int j,
                                 const large_state* __restrict__ st) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= n_large) return;
     const int cell = large[l];
     const unsigned cnt = O.count[cell];
     const large_state s = st[l];
-    put_median(O, cell, p, s.prefix, cnt / 2 < s.less + s.eq ? s.prefix : s.min_above);
+    put_stat<QUANT>(O, cell, p, j, s.prefix, s.k2 < s.less + s.eq ? s.prefix : s.min_above, stat_rank<QUANT>(O, j, cnt).g);
 }
 
 // ---- large tier without a read-back (amt_median_frame_async) ----
@@ -638,9 +746,10 @@ __device__ __forceinline__ bool flush_and_ticket(const unsigned* sHist, unsigned
     return last;
 }
 
-// one launch per digit position `shift` (56, 48, ..., 0): the digit of every plane whose keys have one there
+// one launch per digit position `shift` (56, 48, ..., 0) and result j: the digit of every plane whose keys have one there
+template <bool QUANT>
 __global__ __launch_bounds__(kBlock) void k_med_large_step(const out_args O, const int* __restrict__ large,
-                                                          const tier_counters* __restrict__ tiers, int shift,
+                                                          const tier_counters* __restrict__ tiers, int shift, int j,
                                                           large_state* __restrict__ st, unsigned* __restrict__ lh) {
     __shared__ unsigned sHist[256];
     __shared__ digit_pick sPick;
@@ -676,7 +785,8 @@ __global__ __launch_bounds__(kBlock) void k_med_large_step(const out_args O, con
             h[threadIdx.x] = 0;
             __syncthreads();
             if (threadIdx.x < 64) {
-                const unsigned k = first ? (cnt - 1) / 2 : s->k;
+                const rank_pair rk = stat_rank<QUANT>(O, j, cnt);
+                const unsigned k = first ? (unsigned)rk.k : s->k;
                 const digit_pick r = find_digit(sHist, k, lane);
                 if (lane == 0) {
                     large_state n;
@@ -685,7 +795,7 @@ __global__ __launch_bounds__(kBlock) void k_med_large_step(const out_args O, con
                     n.k = k - r.below;
                     n.less = (first ? 0u : s->less) + r.below;
                     n.eq = r.in_bin;
-                    n.pad = 0;
+                    n.k2 = (unsigned)rk.k2;
                     *s = n;
                     *tick = 0;
                 }
@@ -695,9 +805,10 @@ __global__ __launch_bounds__(kBlock) void k_med_large_step(const out_args O, con
     }
 }
 
-// after the last digit: the smallest key above the selected one where the upper middle key needs it, then the medians
+// after the last digit: the smallest key above the selected one where the second rank needs it, then result j
+template <bool QUANT>
 __global__ __launch_bounds__(kBlock) void k_med_large_last(const out_args O, const int* __restrict__ large,
-                                                          const tier_counters* __restrict__ tiers,
+                                                          const tier_counters* __restrict__ tiers, int j,
                                                           large_state* __restrict__ st, unsigned* __restrict__ lh) {
     __shared__ bool sLast;
     __shared__ unsigned long long sMin;
@@ -710,7 +821,7 @@ __global__ __launch_bounds__(kBlock) void k_med_large_last(const out_args O, con
         for (int p = 0; p < nplane; ++p) {
             large_state* s = st + (int64_t)l * nplane + p;
             const unsigned long long lo = s->prefix;
-            const bool need = cnt / 2 >= s->less + s->eq;
+            const bool need = s->k2 >= s->less + s->eq;
             if (threadIdx.x == 0) sMin = ~0ull;
             __syncthreads();
             if (need) {
@@ -736,13 +847,20 @@ __global__ __launch_bounds__(kBlock) void k_med_large_last(const out_args O, con
             if (threadIdx.x == 0) {
                 const unsigned long long hi =
                     need ? __hip_atomic_load(&s->min_above, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : lo;
-                put_median(O, cell, p, lo, hi);
+                put_stat<QUANT>(O, cell, p, j, lo, hi, stat_rank<QUANT>(O, j, cnt).g);
                 *tick = 0;
             }
             __syncthreads();
         }
     }
 }
+
+// launch of a kernel that is instantiated per rank rule
+#define MED_LAUNCH(kernel, quant, grid, block, ...)                                                  \
+    do {                                                                                             \
+        if (quant) hipLaunchKernelGGL((kernel<true>), grid, block, 0, ctx->stream, __VA_ARGS__);     \
+        else hipLaunchKernelGGL((kernel<false>), grid, block, 0, ctx->stream, __VA_ARGS__);          \
+    } while (0)
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -779,7 +897,9 @@ struct median_pass {
 int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
                  int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                  double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int lon_from_mlt,
-                 double* median, void* out_img, uint8_t* out_mask, double* out_count, median_pass* M) {
+                 const double* q, int nq, double* median, void* out_img, uint8_t* out_mask, double* out_count,
+                 median_pass* M) {
+    // (nq == 0: the median; the callers have checked the quantiles)
     AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && median, "NULL argument");
     AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
     AMT_REQUIRE(ctx, (int64_t)height * width < 2147483647LL, "frame too large for 32-bit pixel indices");
@@ -871,8 +991,83 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
     O.out_img = nchan ? out_img : nullptr;
     O.out_mask = out_mask;
     O.out_count = out_count;
-    hipLaunchKernelGGL(k_med_small, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, O, M->medium, M->large, M->tiers,
-                       M->lh);
+    O.nq = nq;
+    for (int j = 0; j < kQuantilesMax; ++j) O.q[j] = j < nq ? q[j] : 0.0;
+    MED_LAUNCH(k_med_small, nq != 0, grid_for(cells * 64), dim3(kBlock), O, M->medium, M->large, M->tiers, M->lh);
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+// The quantiles of a call, checked before anything else looks at its arguments or touches the device: 1 .. AMT_QUANTILES_MAX
+// finite values in [0, 1].
+bool quantiles_ok(amt_ctx* ctx, const double* q, int nq) {
+    bool ok = q != nullptr && nq >= 1 && nq <= kQuantilesMax;
+    for (int j = 0; ok && j < nq; ++j) ok = q[j] >= 0.0 && q[j] <= 1.0;      // (false for NaN)
+    if (!ok && ctx != nullptr) ctx->last_error = "quantiles: 1..AMT_QUANTILES_MAX values in [0, 1]";
+    return ok;
+}
+
+// The two upper tiers with one read-back (amt_median_frame, amt_quantile_frame): one launch per medium cell, and launch
+// pairs per digit, plane and result for the large cells.
+int upper_tiers_sync(amt_ctx* ctx, const median_pass& M) {
+    const out_args& O = M.O;
+    int* medium = M.medium;
+    int* large = M.large;
+    large_state* state = M.state;
+    unsigned* ghist = M.lh;
+    // the one device -> host read: how many cells the two upper tiers have
+    tier_counters t;
+    AMT_HIP(ctx, hipMemcpyAsync(&t, M.tiers, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int nplane = M.nplane, nstat = O.nq ? O.nq : 1;
+    const bool quant = O.nq != 0;
+    if (t.n_medium > 0)
+        MED_LAUNCH(k_med_medium, quant, dim3(t.n_medium), dim3(kBlock), O, medium);
+    if (t.n_large > 0) {
+        AMT_REQUIRE(ctx, (int64_t)t.n_large <= M.large_cap, "internal: large-cell count out of range");
+        const int nl = (int)t.n_large;
+        const dim3 chunks((t.max_large + kChunk - 1) / kChunk, (unsigned)nl);
+        const dim3 per_cell((nl + kBlock - 1) / kBlock);
+        // (k_med_small has zeroed nplane * 257 >= 256 words of ghist for each of the nl cells it listed)
+        for (int p = 0; p < nplane; ++p)
+            for (int j = 0; j < nstat; ++j) {
+                MED_LAUNCH(k_med_large_init, quant, per_cell, dim3(kBlock), O, large, nl, j, state);
+                const int bits = p == O.nch ? 64 : (O.img_dtype == 1 ? 8 : 16);
+                for (int shift = bits - 8; shift >= 0; shift -= 8) {
+                    hipLaunchKernelGGL(k_med_large_hist, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, shift, state, ghist);
+                    hipLaunchKernelGGL(k_med_large_digit, dim3(nl), dim3(64), 0, ctx->stream, shift, state, ghist);
+                }
+                hipLaunchKernelGGL(k_med_large_above, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, state);
+                MED_LAUNCH(k_med_large_put, quant, per_cell, dim3(kBlock), O, large, nl, p, j, state);
+            }
+    }
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+// The two upper tiers without a read-back (amt_median_frame_async, amt_quantile_frame_async).
+int upper_tiers_async(amt_ctx* ctx, const median_pass& M) {
+    // fixed grids from what the host knows: a medium cell has more than kSmallMax pixels, a large one more than kLargeMin;
+    // the workgroups read the tier sizes from device memory
+    const out_args& O = M.O;
+    const int64_t cu = amt_cu_count(ctx);
+    const int64_t medium_bound = std::min(M.cells, M.n / (kSmallMax + 1));
+    const int64_t medium_grid = std::max<int64_t>(1, std::min(medium_bound, 8 * cu));
+    const bool quant = O.nq != 0;
+    MED_LAUNCH(k_med_medium_walk, quant, dim3((unsigned)medium_grid), dim3(kBlock), O, M.medium, M.tiers);
+    const int64_t large_grid = std::max<int64_t>(1, std::min(M.n / kChunk + 1, cu));
+    if (M.n > kLargeMin && M.nplane > 0) {
+        int top = 0;
+        for (int p = 0; p < M.nplane; ++p) top = std::max(top, p == O.nch ? 64 : (O.img_dtype == 1 ? 8 : 16));
+        // (every result starts from the first digit again: the states, histograms and tickets are left clean by the last one)
+        const int nstat = O.nq ? O.nq : 1;
+        for (int j = 0; j < nstat; ++j) {
+            for (int shift = top - 8; shift >= 0; shift -= 8)
+                MED_LAUNCH(k_med_large_step, quant, dim3((unsigned)large_grid), dim3(kBlock), O, M.large, M.tiers, shift, j,
+                           M.state, M.lh);
+            MED_LAUNCH(k_med_large_last, quant, dim3((unsigned)large_grid), dim3(kBlock), O, M.large, M.tiers, j, M.state, M.lh);
+        }
+    }
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
@@ -888,39 +1083,9 @@ int amt_median_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, con
     AMT_CHECK_CTX(ctx);
     median_pass M;
     if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
-                              yaxis, lon_wrap, 0, median, out_img, out_mask, out_count, &M))
+                              yaxis, lon_wrap, 0, nullptr, 0, median, out_img, out_mask, out_count, &M))
         return rc;
-    const out_args& O = M.O;
-    int* medium = M.medium;
-    int* large = M.large;
-    large_state* state = M.state;
-    unsigned* ghist = M.lh;
-    // the one device -> host read: how many cells the two upper tiers have
-    tier_counters t;
-    AMT_HIP(ctx, hipMemcpyAsync(&t, M.tiers, sizeof(t), hipMemcpyDeviceToHost, ctx->stream));
-    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int nplane = M.nplane;
-    if (t.n_medium > 0)
-        hipLaunchKernelGGL(k_med_medium, dim3(t.n_medium), dim3(kBlock), 0, ctx->stream, O, medium);
-    if (t.n_large > 0) {
-        AMT_REQUIRE(ctx, (int64_t)t.n_large <= M.large_cap, "internal: large-cell count out of range");
-        const int nl = (int)t.n_large;
-        const dim3 chunks((t.max_large + kChunk - 1) / kChunk, (unsigned)nl);
-        const dim3 per_cell((nl + kBlock - 1) / kBlock);
-        // (k_med_small has zeroed nplane * 257 >= 256 words of ghist for each of the nl cells it listed)
-        for (int p = 0; p < nplane; ++p) {
-            hipLaunchKernelGGL(k_med_large_init, per_cell, dim3(kBlock), 0, ctx->stream, O, large, nl, state);
-            const int bits = p == nchan ? 64 : (img_dtype == 1 ? 8 : 16);
-            for (int shift = bits - 8; shift >= 0; shift -= 8) {
-                hipLaunchKernelGGL(k_med_large_hist, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, shift, state, ghist);
-                hipLaunchKernelGGL(k_med_large_digit, dim3(nl), dim3(64), 0, ctx->stream, shift, state, ghist);
-            }
-            hipLaunchKernelGGL(k_med_large_above, chunks, dim3(kBlock), 0, ctx->stream, O, large, p, state);
-            hipLaunchKernelGGL(k_med_large_put, per_cell, dim3(kBlock), 0, ctx->stream, O, large, nl, p, state);
-        }
-    }
-    AMT_LAUNCH_CHECK(ctx);
-    return AMT_OK;
+    return upper_tiers_sync(ctx, M);
 }
 
 int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
@@ -930,26 +1095,42 @@ int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_
     AMT_CHECK_CTX(ctx);
     median_pass M;
     if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
-                              yaxis, lon_wrap, lon_from_mlt, median, out_img, out_mask, out_count, &M))
+                              yaxis, lon_wrap, lon_from_mlt, nullptr, 0, median, out_img, out_mask, out_count, &M))
         return rc;
-    // fixed grids from what the host knows: a medium cell has more than kSmallMax pixels, a large one more than kLargeMin;
-    // the workgroups read the tier sizes from device memory
-    const int64_t cu = amt_cu_count(ctx);
-    const int64_t medium_bound = std::min(M.cells, M.n / (kSmallMax + 1));
-    const int64_t medium_grid = std::max<int64_t>(1, std::min(medium_bound, 8 * cu));
-    hipLaunchKernelGGL(k_med_medium_walk, dim3((unsigned)medium_grid), dim3(kBlock), 0, ctx->stream, M.O, M.medium, M.tiers);
-    const int64_t large_grid = std::max<int64_t>(1, std::min(M.n / kChunk + 1, cu));
-    if (M.n > kLargeMin) {
-        int top = 0;
-        for (int p = 0; p < M.nplane; ++p) top = std::max(top, p == nchan ? 64 : (img_dtype == 1 ? 8 : 16));
-        for (int shift = top - 8; shift >= 0; shift -= 8)
-            hipLaunchKernelGGL(k_med_large_step, dim3((unsigned)large_grid), dim3(kBlock), 0, ctx->stream, M.O, M.large,
-                               M.tiers, shift, M.state, M.lh);
-        if (M.nplane > 0)
-            hipLaunchKernelGGL(k_med_large_last, dim3((unsigned)large_grid), dim3(kBlock), 0, ctx->stream, M.O, M.large,
-                               M.tiers, M.state, M.lh);
-    }
-    AMT_LAUNCH_CHECK(ctx);
+    return upper_tiers_async(ctx, M);
+}
+
+int amt_quantile_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                       int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                       double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, const double* q,
+                       int nq, double* quantile, void* out_img, uint8_t* out_mask, double* out_count) {
+    if (!quantiles_ok(ctx, q, nq)) return AMT_EINVAL;
+    AMT_CHECK_CTX(ctx);
+    median_pass M;
+    if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
+                              yaxis, lon_wrap, 0, q, nq, quantile, out_img, out_mask, out_count, &M))
+        return rc;
+    return upper_tiers_sync(ctx, M);
+}
+
+int amt_quantile_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                             int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                             double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                             int lon_from_mlt, const double* q, int nq, double* quantile, void* out_img, uint8_t* out_mask,
+                             double* out_count) {
+    if (!quantiles_ok(ctx, q, nq)) return AMT_EINVAL;
+    AMT_CHECK_CTX(ctx);
+    median_pass M;
+    if (int rc = median_front(ctx, lat_c, lon_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation, xaxis,
+                              yaxis, lon_wrap, lon_from_mlt, q, nq, quantile, out_img, out_mask, out_count, &M))
+        return rc;
+    return upper_tiers_async(ctx, M);
+}
+
+int amt_quantile_rank(int64_t n, double q, int64_t* k, int64_t* k2, double* g) {
+    if (n < 1 || !(q >= 0.0 && q <= 1.0) || k == nullptr || k2 == nullptr || g == nullptr) return AMT_EINVAL;
+    const rank_pair r = rank_rule(n, q, false);
+    *k = r.k, *k2 = r.k2, *g = r.g;
     return AMT_OK;
 }
 

@@ -29,6 +29,8 @@ struct amt_run {
         long long index;
     } last, prev;
     long long frames_done;
+    bool has_quantile;                      // amt_run_set_quantile: the median pass selects `quantile` instead
+    double quantile;
     // the call in progress (amt_run_begin ... amt_run_end)
     bool active, full;
     double* grids;
@@ -105,6 +107,8 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     run->entry = nullptr;
     run->last.valid = run->prev.valid = false;
     run->frames_done = 0;
+    run->has_quantile = false;
+    run->quantile = 0.5;
     const int ns = config->n_slots;
     run->outs.assign(config->slots, config->slots + ns);
     run->cfg.slots = nullptr;
@@ -161,6 +165,17 @@ int amt_run_destroy(amt_run* run) {
         if (e != nullptr) (void)hipEventDestroy(e);
     if (run->copy_stream) (void)hipStreamDestroy(run->copy_stream);
     delete run;
+    return AMT_OK;
+}
+
+int amt_run_set_quantile(amt_run* run, double q) {
+    if (run == nullptr) return AMT_EINVAL;
+    amt_ctx* ctx = run->ctx;
+    AMT_REQUIRE(ctx, run->cfg.statistic == 1, "the runner was not created with statistic = 1");
+    AMT_REQUIRE(ctx, !run->active && run->frames_done == 0, "to be called before the first push");
+    AMT_REQUIRE(ctx, q >= 0.0 && q <= 1.0, "the quantile must lie in [0, 1]");
+    run->has_quantile = true;
+    run->quantile = q;
     return AMT_OK;
 }
 
@@ -278,11 +293,17 @@ int run_finish(amt_run* run, int k0, int count) {
             // call runs in stream order, so they share the workspace of that stream
             const amt_georef_out& o = run->outs[slot];
             const bool mag = cfg.magnetic != 0;
-            if (int rc = amt_median_frame_async(ctx, mag ? o.mlat_c : o.lat_c, mag ? o.mlt_c : o.lon_c, o.elev, run->img[slot],
-                                                cfg.img_dtype, 3, nullptr, cfg.height, cfg.width, cfg.min_elevation,
-                                                &pr.grid.xaxis, &pr.grid.yaxis, pr.lon_wrapped, mag ? 1 : 0, f_mean, f_img, f_mask,
-                                                f_mean + 4 * cells))
-                return rc;
+            const int rc =
+                run->has_quantile
+                    ? amt_quantile_frame_async(ctx, mag ? o.mlat_c : o.lat_c, mag ? o.mlt_c : o.lon_c, o.elev, run->img[slot],
+                                               cfg.img_dtype, 3, nullptr, cfg.height, cfg.width, cfg.min_elevation,
+                                               &pr.grid.xaxis, &pr.grid.yaxis, pr.lon_wrapped, mag ? 1 : 0, &run->quantile, 1,
+                                               f_mean, f_img, f_mask, f_mean + 4 * cells)
+                    : amt_median_frame_async(ctx, mag ? o.mlat_c : o.lat_c, mag ? o.mlt_c : o.lon_c, o.elev, run->img[slot],
+                                             cfg.img_dtype, 3, nullptr, cfg.height, cfg.width, cfg.min_elevation,
+                                             &pr.grid.xaxis, &pr.grid.yaxis, pr.lon_wrapped, mag ? 1 : 0, f_mean, f_img, f_mask,
+                                             f_mean + 4 * cells);
+            if (rc) return rc;
             if (run->img[slot] == run->own_img[slot] && run->own_img[slot] != nullptr) {
                 AMT_HIP(ctx, hipEventRecord(run->img_free[slot], ctx->stream));
                 run->img_busy[slot] = 1;

@@ -32,7 +32,7 @@ import numpy as np
 from .frame import FrameData, PaddedFrameData, has_array
 from .mapping.astrometry import frame_params, pole_in_view, run_frame
 from .mapping.mapping import bounding_box_from_reduction, grid_box_from_reduction
-from .resample import cached_grid, grid_coordinates, resample_frame, resample_frame_median
+from .resample import cached_grid, grid_coordinates, quantile_list, resample_frame, resample_frame_median, resample_frame_quantile
 from ._native import PIPE_MAX_EDGE_PIXELS, Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
 
 NEG_INF = float('-inf')
@@ -621,11 +621,16 @@ class FramePipeline(object):
             done.append(q._fused_wrap(*o, keep_on_device=keep_on_device))
         return done
 
-    def resample(self, pxPerDeg=10, containsPole=None, magnetic=False, keep_on_device=False, statistic='mean'):
+    def resample(self, pxPerDeg=10, containsPole=None, magnetic=False, keep_on_device=False, statistic='mean', q=None):
         """Stages 2 + 3.  magnetic=True bins on the (MLat, SM longitude) grid (resampleMLatMLT).  statistic='median': the
         median of every cell (resampleMedian / resampleMedianMLatMLT) by the two-pass plan; the result holds 'median'
-        in place of 'mean'."""
-        assert statistic in ('mean', 'median')
+        in place of 'mean'.  statistic='quantile': the quantile(s) `q` of every cell (resampleQuantile /
+        resampleQuantileMLatMLT; a number or up to 8 numbers in [0, 1]) in the same way; the result is that of
+        :func:`auromat_amd.resample.resample_frame_quantile`, 'quantile' and 'img' with a leading axis over `q`."""
+        assert statistic in ('mean', 'median', 'quantile')
+        assert (q is not None) == (statistic == 'quantile'), "q goes with statistic='quantile'"
+        if statistic == 'quantile':
+            q = quantile_list(q)
         try:
             _, _ = pxPerDeg
         except TypeError:
@@ -687,14 +692,18 @@ class FramePipeline(object):
         if statistic == 'median':
             return resample_frame_median(fd, self.altitude, bb, pxPerDeg, bb.containsDiscontinuity, pole,
                                          min_elevation=self.min_elevation, keep_on_device=keep_on_device)
+        if statistic == 'quantile':
+            return resample_frame_quantile(fd, self.altitude, bb, pxPerDeg, q, bb.containsDiscontinuity, pole,
+                                           min_elevation=self.min_elevation, keep_on_device=keep_on_device)
         return resample_frame(fd, self.altitude, bb, pxPerDeg, bb.containsDiscontinuity, pole,
                               min_elevation=self.min_elevation, keep_on_device=keep_on_device, shard=self.shard)
 
     def run(self, wcsHeader, altitude, cameraPosGCRS, photoTime, img=None, fast=True, min_elevation=10.0,
             pxPerDeg=10, containsPole=None, magnetic=False, params=None, keep_on_device=False, fuse=False,
-            arcsecPerPx=None, dirs=None, statistic='mean'):
+            arcsecPerPx=None, dirs=None, statistic='mean', q=None):
         """One frame end to end; returns the dict of :func:`auromat_amd.resample.resample_frame` (statistic='median': of
-        :func:`auromat_amd.resample.resample_frame_median`, never fused).  `arcsecPerPx` (has
+        :func:`auromat_amd.resample.resample_frame_median`, statistic='quantile' with the quantile(s) `q`: of
+        :func:`auromat_amd.resample.resample_frame_quantile`; neither is fused).  `arcsecPerPx` (has
         precedence over pxPerDeg, like the reference's resample()): the box-first plan — a box pass, px/deg from the frame's
         own bounding box, then the single-pass launch (``fuse``) or the two-pass plan; the px/deg pair used is in the
         result as 'pxPerDeg'."""
@@ -732,7 +741,7 @@ class FramePipeline(object):
         self.georef(wcsHeader, altitude, cameraPosGCRS, photoTime, fast, min_elevation, params=params,
                     fuse_pxPerDeg=pxPerDeg if fuse else None, fuse_magnetic=bool(magnetic), coarse_started=coarse_started,
                     dirs=dirs, pole_in_view=-1 if containsPole is None else int(bool(containsPole)))
-        res = self.resample(pxPerDeg, containsPole, magnetic, keep_on_device=keep_on_device, statistic=statistic)
+        res = self.resample(pxPerDeg, containsPole, magnetic, keep_on_device=keep_on_device, statistic=statistic, q=q)
         res['pxPerDeg'] = tuple(pxPerDeg)
         return res
 
@@ -850,7 +859,7 @@ class NativeResults(object):
         seq = self._seq
         fd = seq.pipes[0].fd
         ppd = (r.lat_px_per_deg, r.lon_px_per_deg)
-        stat = 'median' if seq.statistic == 'median' else 'mean'
+        stat = seq.statistic            # 'mean', 'median' or 'quantile': the name of the block in the result
         out, packed, mean, count, img, mask, _ = _frame_block(
             r.grid, ppd, r.bbox, bool(r.lon_wrapped), bool(r.contains_pole), r.altitude, self._grids, r.grid_offset, self._images,
             r.image_offset, fd.img_dtype != np.uint8)
@@ -911,16 +920,24 @@ class SequencePipeline(object):
     def __init__(self, width, height, nchan=3, img_dtype=np.uint16, device=None, altitude=110, fast=True,
                  min_elevation=10.0, pxPerDeg=10, plan='single-pass', bin_stream=True, shared_image=None,
                  magnetic=False, batch=3, own_image_buffers=True, keep_coordinates=True, launch_streams=1,
-                 geodetic_arrays=None, arcsecPerPx=None, padded=None, statistic='mean'):
+                 geodetic_arrays=None, arcsecPerPx=None, padded=None, statistic='mean', quantile=None):
         import torch
         assert plan in ('single-pass', 'two-pass')
         # statistic='median' (resampleMedian / resampleMedianMLatMLT): every frame through the native runner's median pass —
         # the frame kernel writes the buffer's centre and elevation arrays (contiguous rows), the median kernels bin them
         # (amt_run_config.statistic, amt_median_frame_async); the results carry 'median' in place of 'mean'
-        assert statistic in ('mean', 'median')
+        # statistic='quantile', quantile=q (resampleQuantile / resampleQuantileMLatMLT): the same pass selecting ONE quantile
+        # (amt_run_set_quantile, amt_quantile_frame_async); the results carry 'quantile'
+        assert statistic in ('mean', 'median', 'quantile')
+        assert (quantile is not None) == (statistic == 'quantile'), "quantile goes with statistic='quantile'"
         self.statistic = statistic
-        if statistic == 'median':
-            assert plan == 'single-pass' and nchan == 3, "statistic='median': RGB frames through the native runner"
+        self.quantile = None
+        if statistic == 'quantile':
+            if np.ndim(quantile) != 0:
+                raise ValueError('a sequence pipeline takes one quantile, got {!r}'.format(quantile))
+            self.quantile = quantile_list(quantile)[0]
+        if statistic != 'mean':
+            assert plan == 'single-pass' and nchan == 3, "statistic='%s': RGB frames through the native runner" % statistic
             padded = False
             keep_coordinates = True
         try:
@@ -1202,7 +1219,7 @@ class SequencePipeline(object):
             cfg = RunConfig(width=q.width, height=q.height, img_dtype=1 if q.fd.img_dtype == np.uint8 else 2, fast_center=1 if self.fast else 0,
                             magnetic=1 if self.magnetic else 0, batch=self.batch, use_hints=1 if self.use_hints else 0,
                             n_slots=nb, two_pass=0 if self.single_pass else 1,
-                            statistic=1 if self.statistic == 'median' else 0, altitude=float(self.altitude),
+                            statistic=0 if self.statistic == 'mean' else 1, altitude=float(self.altitude),
                             min_elevation=NEG_INF if self.min_elevation is None else float(self.min_elevation),
                             lat_px_per_deg=float(self.pxPerDeg[0]) if self.pxPerDeg else 0.0,
                             lon_px_per_deg=float(self.pxPerDeg[1]) if self.pxPerDeg else 0.0, slots=slots,
@@ -1210,6 +1227,8 @@ class SequencePipeline(object):
             handle = C.c_void_p()
             self.ctx.call('amt_run_create', C.byref(cfg), C.byref(handle))
             self._run = handle
+            if self.statistic == 'quantile':
+                self.ctx.check(self.ctx._lib.amt_run_set_quantile(handle, self.quantile))
             self._run_hints = self.use_hints
         return self._run
 
@@ -1313,14 +1332,14 @@ class SequencePipeline(object):
         fallbacks = {}
         max_cells = int((table['ny'].astype(np.int64) * table['nx']).max()) if n else 1
         names = {0: 'single-pass', 2: 'empty', 4: 'pole-without-resolution'}
-        median = self.statistic == 'median'
+        ordered = self.statistic != 'mean'          # (the runner's median / quantile pass: named after the statistic)
         if not status.any() and not table['two_pass'].any():
             self.plans.extend(['single-pass'] * n)
         else:
             for k in range(n):
                 st = int(status[k])
                 if st in names:
-                    self.plans.append(('median' if median else 'two-pass') if st == 0 and table['two_pass'][k] else names[st])
+                    self.plans.append((self.statistic if ordered else 'two-pass') if st == 0 and table['two_pass'][k] else names[st])
                     continue
                 f = frames[k]
                 q = self.pipes[0]
@@ -1332,10 +1351,13 @@ class SequencePipeline(object):
                 try:
                     ppd = (table['lat_px_per_deg'][k], table['lon_px_per_deg'][k]) if self.arcsecPerPx else self.pxPerDeg
                     # (median: the frames the runner's median pass does not cover — a pole in view, exact centres — by
-                    # resample_frame_median on the frame's arrays, what resampleMedian / resampleMedianMLatMLT run)
+                    # resample_frame_median on the frame's arrays, what resampleMedian / resampleMedianMLatMLT run; quantile:
+                    # likewise by resample_frame_quantile, its one quantile without the leading axis)
                     res = q.run(f[0], alt, f[1], f[2], fast=self.fast, min_elevation=self.min_elevation, pxPerDeg=ppd,
                                 magnetic=self.magnetic, keep_on_device=keep_on_device, fuse=False,
-                                statistic=self.statistic)
+                                statistic=self.statistic, q=self.quantile)
+                    if self.statistic == 'quantile':
+                        res['quantile'], res['img'] = res['quantile'][0], res['img'][0]
                     res['magnetic'] = self.magnetic
                 except EmptyFrame:
                     res = None
@@ -1464,7 +1486,7 @@ class SequencePipeline(object):
         return out
 
     def _process_median(self, frames, keep_on_device, on_batch):
-        """process() with statistic='median': the native runner, in pieces of up to `median_chunk` frames (an iterator — the
+        """process() with statistic='median' or 'quantile': the native runner, in pieces of up to `median_chunk` frames (an iterator — the
         convert driver's generator of decoded host images — is consumed piece by piece).  Device-resident and pinned images
         go to the runner as they are; any other image is copied to the device first, on the caller's stream."""
         import torch
@@ -1482,7 +1504,7 @@ class SequencePipeline(object):
                         a = a.view(np.int16)
                     img = torch.from_numpy(a).to(self.ctx.device)
                 assert type(f[0]) is dict and tuple(img.shape) == shape, \
-                    "statistic='median': frames are (header dict, cameraPosGCRS, photoTime, image[, altitude])"
+                    "statistic='median' / 'quantile': frames are (header dict, cameraPosGCRS, photoTime, image[, altitude])"
                 chunk.append((f[0], f[1], f[2], img) + tuple(f[4:]))
                 if len(chunk) == self.median_chunk:
                     break
@@ -1518,7 +1540,7 @@ class SequencePipeline(object):
         del self.plans[:]
         self.hinted = 0
         self.uploaded_bytes = 0
-        if self.statistic == 'median':
+        if self.statistic != 'mean':
             return self._process_median(frames, keep_on_device, on_batch)
         if on_batch is None and self.native and isinstance(frames, (list, tuple)):
             # (an iterator — the convert driver's read-ahead generator of decoded host images — is consumed frame by frame

@@ -234,6 +234,77 @@ def resampleMedianMLatMLT(mapping, **kw):
     return convertSMMappingToGeo(resampleMedian(convertMappingToSM(mapping), **kw))
 
 
+def quantile_list(q):
+    """The quantiles of a call as a list of floats: a number or a sequence of 1 .. 8 numbers, each in [0, 1].  ValueError for
+    anything else (NaN, an empty sequence, more than ``amt_quantile_frame`` takes in one call) — before any device work."""
+    from ._native import QUANTILES_MAX
+    try:
+        qs = [float(q)] if np.ndim(q) == 0 else [float(v) for v in q]
+    except (TypeError, ValueError):
+        raise ValueError('q must be a number or a sequence of numbers, but is: {!r}'.format(q))
+    if not 1 <= len(qs) <= QUANTILES_MAX:
+        raise ValueError('between 1 and {} quantiles per call, got {}'.format(QUANTILES_MAX, len(qs)))
+    for v in qs:
+        if not 0.0 <= v <= 1.0:             # (False for NaN)
+            raise ValueError('quantiles must be in the range [0, 1], got {!r}'.format(v))
+    return qs
+
+
+def resampleQuantile(mappingOrCollection, q, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+    """
+    Like :func:`resampleMedian`, but every channel of a cell (image channels and elevation) is the quantile `q` of the
+    cell's pixels: ``np.quantile(values.astype(float64), q)`` with NumPy's default method ``'linear'``, bit for bit, then
+    the image's rounding half to even and cast.  The lower quartile of a cell is a background estimate, the 0.9 quantile a
+    peak estimate that single stars and city lights do not own, the difference of the quartiles a spread.
+
+    A number `q` gives what :func:`resampleMedian` gives (a mapping, or a collection for a collection); a sequence of up to
+    8 numbers gives a list with one such result per `q`, in order, from ONE device call per mapping
+    (``amt_quantile_frame``): the pixels are assigned to cells and sorted into them once.  ``q=0.5`` is the median for
+    the image; for the elevation ``np.quantile`` and ``np.median`` combine the middle pair differently and may differ in
+    the last bit.
+
+    :param number|sequence q: quantile(s) in [0, 1]; ValueError otherwise
+    :param mappingOrCollection, pxPerDeg, arcsecPerPx, containsPole: see :func:`resampleMedian`
+    :rtype: a subclass of BaseMapping or MappingCollection, or a list of them
+    """
+    qs = quantile_list(q)
+
+    def doResample(mapping):
+        global last_plan
+        last_plan = None
+        pole = mapping.containsPole if containsPole is None else containsPole
+        ppd = plateCarreeResolution(mapping.boundingBox, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+        res = resample_frame_quantile(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd, qs,
+                                      mapping.containsDiscontinuity, pole, outline=mapping.outline if pole else None)
+        out = []
+        for j in range(len(qs)):
+            img = ma.masked_array(res['img'][j], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[3], 2))
+            elevation = ma.masked_invalid(res['quantile'][j, :, :, -1], copy=False) if res['has_elev'] else None
+            out.append(mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img))
+        return out
+
+    if isinstance(mappingOrCollection, BaseMapping):
+        results = doResample(mappingOrCollection)
+    elif isinstance(mappingOrCollection, MappingCollection):
+        per_mapping = [doResample(m) for m in mappingOrCollection.mappings]
+        results = [MappingCollection([r[j] for r in per_mapping], mappingOrCollection.identifier,
+                                     mayOverlap=mappingOrCollection.mayOverlap) for j in range(len(qs))]
+    else:
+        raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
+                         format(type(mappingOrCollection)))
+    return results[0] if np.ndim(q) == 0 else results
+
+
+def resampleQuantileMLatMLT(mapping, q, **kw):
+    """:func:`resampleQuantile` such that MLat/MLT become regular grids (``convertMappingToSM`` -> ``resampleQuantile`` ->
+    ``convertSMMappingToGeo``, as :func:`resampleMedianMLatMLT`).
+
+    See :func:`resampleQuantile` for parameters.
+    """
+    res = resampleQuantile(convertMappingToSM(mapping), q, **kw)
+    return [convertSMMappingToGeo(r) for r in res] if isinstance(res, list) else convertSMMappingToGeo(res)
+
+
 def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
     """
     Bins every member of a :class:`MappingCollection` onto ONE grid and returns ONE mapping (:class:`MosaicMapping`), where
@@ -451,6 +522,43 @@ def resample_frame_median(fd, altitude, boundingBox, pxPerDeg, containsDiscontin
         return out
     out.update(grid_coordinates(out))
     out.update(median=to_host(median), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
+               mask=to_host(mask).astype(bool), count=to_host(count))
+    return out
+
+
+def resample_frame_quantile(fd, altitude, boundingBox, pxPerDeg, q, containsDiscontinuity=False, containsPole=False,
+                            min_elevation=None, outline=None, keep_on_device=False):
+    """
+    Quantile binning of a device-resident frame on the grid :func:`resample_frame` lays out: every quantile of `q` (a
+    number or up to 8 numbers in [0, 1]) from one call of ``amt_quantile_frame``.
+
+    :param outline, keep_on_device: as for :func:`resample_frame_median`
+    :return: the dict of :func:`resample_frame_median` with quantile (nq,ny,nx,C+1) and img (nq,ny,nx,C) in place of
+             median and img; mask and count are (ny,nx)
+    """
+    import torch
+    qs = quantile_list(q)
+    nq = len(qs)
+    ctx = fd.ctx
+    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
+                                               min_elevation, outline, None)
+    xaxis, yaxis = grid.axes(ctx)
+    nch = fd.nchan
+    quantile = ctx.empty((nq, grid.ny, grid.nx, nch + 1))
+    img = ctx.empty((nq, grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd.img_dtype_code != 2 else torch.int16)
+    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
+    count = ctx.empty((grid.ny, grid.nx))
+    min_el = float('-inf') if min_elevation is None else float(min_elevation)
+    ctx.call('amt_quantile_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code or 1, nch,
+             ptr(fd.center_mask), fd.height, fd.width, min_el, C.byref(xaxis), C.byref(yaxis), lon_wrap,
+             (C.c_double * nq)(*qs), nq, ptr(quantile), ptr(img) if nch else None, ptr(mask), ptr(count))
+    out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
+               contains_discontinuity=bool(containsDiscontinuity), altitude=altitude, q=qs)
+    if keep_on_device:
+        out.update(quantile=quantile, img=img, mask=mask, count=count)
+        return out
+    out.update(grid_coordinates(out))
+    out.update(quantile=to_host(quantile), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
                mask=to_host(mask).astype(bool), count=to_host(count))
     return out
 

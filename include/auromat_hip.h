@@ -42,6 +42,8 @@ extern "C" {
 /* 8: amt_median_frame_async (the median pass without a read-back); amt_run_config.statistic (median sequences in the runner, in
  *    place of reserved_); amt_pipe_set_plan(pipe, 2) */
 /* 9: amt_mosaic_frames, amt_mosaic_member (the members of a collection binned onto one grid, auromat_amd.resample.resampleMosaic) */
+/* 10, additions only (no struct changed, the number stays): quantile binning — amt_quantile_frame, amt_quantile_frame_async,
+ *    amt_quantile_rank, amt_run_set_quantile, AMT_QUANTILES_MAX (auromat_amd.resample.resampleQuantile) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -520,6 +522,33 @@ int amt_median_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_
                            int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                            double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
                            int lon_from_mlt, double* median, void* out_img, uint8_t* out_mask, double* out_count);
+/* Quantile binning (auromat_amd.resample.resampleQuantile): amt_median_frame's pixels, membership, workspace and output
+ * layouts, and for every cell with n >= 1 pixels, every plane (channel or elevation) and every q[j]
+ * np.quantile(values.astype(float64), q[j]) by NumPy's default method 'linear', bit for bit:
+ *     vi = (double)(n - 1) * q;  k = floor(vi);  g = vi - k;
+ *     if vi >= n - 1:  a = b = sorted[n-1], g = vi + 1 (NumPy's index -1 for the last value);  else a = sorted[k], b = sorted[k+1]
+ *     d = b - a;
+ *     r = g >= 0.5 ? b - d * (1 - g) : a + d * g          (every operation rounded on its own, always evaluated)
+ * q: HOST array of nq values, 1 <= nq <= AMT_QUANTILES_MAX, each finite and in [0, 1]; anything else is AMT_EINVAL, returned
+ * before the other arguments are looked at or the device is touched.  quantile: (nq, ny, nx, nchan+1) float64, NaN where a cell
+ * is empty (and in the elevation plane when elev is NULL); out_img (optional): (nq, ny, nx, nchan), r rounded half to even;
+ * out_mask, out_count (optional): (ny, nx) as for the median.  The count, scan and fill passes run once per call whatever nq is.
+ * q = 0.5 is np.quantile's b - d * 0.5, not np.median's (a + b) / 2: equal on the integer planes, not always on the elevation. */
+#define AMT_QUANTILES_MAX 8
+int amt_quantile_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                       int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                       double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, const double* q,
+                       int nq, double* quantile, void* out_img, uint8_t* out_mask, double* out_count);
+/* amt_quantile_frame that only enqueues work, as amt_median_frame_async does for the median (no read-back, no host wait, the
+ * same workspace for the same frame and grid, lon_from_mlt); the large tier takes its launches once per quantile. */
+int amt_quantile_frame_async(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                             int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                             double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                             int lon_from_mlt, const double* q, int nq, double* quantile, void* out_img, uint8_t* out_mask,
+                             double* out_count);
+/* The rank rule of the quantile kernels on the host (no device needed): k, k2 (k or k + 1) and g above for a cell of n >= 1
+ * pixels.  The kernels call the same function.  AMT_EINVAL for n < 1, q outside [0, 1] or NaN, NULL outputs. */
+int amt_quantile_rank(int64_t n, double q, int64_t* k, int64_t* k2, double* g);
 /* Mosaics (ABI v9; auromat_amd.resample.resampleMosaic): the members of a collection binned onto ONE grid.  A pixel of member i
  * counts in cell c when amt_bin_frame on the common axes would bin it into c (same bin_index, masks, NaN and right-edge rules)
  * AND c lies in the member's window [win_x0, win_x0 + win_nx) x [win_y0, win_y0 + win_ny) (cells of the common grid, x along
@@ -909,6 +938,11 @@ int amt_run_push(amt_run* run, const amt_run_frame* frame);
 int amt_run_end(amt_run* run, int32_t* frames_done);
 /* Forget the box hints (the next frame gets a coarse pre-pass). */
 int amt_run_reset_hints(amt_run* run);
+/* Quantile sequences: the median pass of a runner created with statistic = 1 becomes a one-quantile pass — the frames it covers
+ * go through amt_quantile_frame_async with nq = 1 on the same arena blocks, (ny, nx, 4) quantiles in place of the medians.
+ * Before the first push of the runner; AMT_EINVAL for another statistic, a call in progress, q outside [0, 1] or NaN.  A runner
+ * on which it was never called is a median runner, as before. */
+int amt_run_set_quantile(amt_run* run, double q);
 
 /* ---- sequences over several GPUs: packing of per-frame grids for the gather ------------------------------------
  * Whole frames are independent (reference mapping/spacecraft.py:326-332 iterates them with a plain `map`,
