@@ -211,6 +211,10 @@ _SIGNATURES = {
     'amt_quantile_rank': ([_L, _D, C.POINTER(_L), C.POINTER(_L), c_double_p], _I),
     'amt_mosaic_frames': ([_P, C.POINTER(MosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis),
                            _I, C.c_int32, _P, _P, _P, _P, _P], _I),
+    'amt_mosaic_median_frames': ([_P, C.POINTER(MosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                                  C.POINTER(Axis), _I, C.c_int32, _P, _P, _P, _P, _P], _I),
+    'amt_mosaic_quantile_frames': ([_P, C.POINTER(MosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                                    C.POINTER(Axis), _I, C.c_int32, c_double_p, _I, _P, _P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
                            _P], _I),
     'amt_nearest_gather': ([_P, _P, _L, _P, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),

@@ -94,6 +94,12 @@ int amt_bin_finalize_on(amt_ctx* ctx, hipStream_t stream, uint64_t* acc, int32_t
                         int32_t off_y, int32_t nx, int32_t ny, int32_t nchan, int32_t img_dtype, double* mean,
                         void* out_img, uint8_t* out_mask, double* out_count, int clear);
 
+// amt_mosaic_frames (amt_mosaic.hip) with `tail_bytes` of the workspace behind its own tables handed out through `tail`; with a
+// tail and no out_source, `source` is written to the head of the tail
+int amt_mosaic_run(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype, int32_t nchan,
+                   double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int32_t rule, double* mean,
+                   void* out_img, uint8_t* out_mask, double* out_count, int32_t* out_source, size_t tail_bytes, char** tail);
+
 // one frame of a batched finalise step (amt_pipe_finalize_many -> k_pipe_finish)
 struct finish_frame {
     const void* events;        // bin_event records

@@ -27,6 +27,10 @@
 // rule (rank_rule below): np.quantile's pair (k, k + 1) of method 'linear' and its lerp (put_quantile) in place of the
 // middle pair and its mean.  The count, scan and fill passes run once per call; the small tier sorts a plane once and
 // reads every quantile's pair from the sorted lanes, the two upper tiers select once per quantile of the call.
+// Median and quantile mosaics (amt_mosaic_median_frames, amt_mosaic_quantile_frames; resampleMosaic(statistic=...)) put another
+// front before the same tiers: k_med_count_members and k_med_fill_members run the bodies of the count and fill passes
+// (count_wave, fill_wave) over the concatenated pixels of a mosaic's members, one launch each whatever the member count; a
+// pixel counts inside its member's window and, under rule 1, where amt_mosaic_frames' election (k_mosaic_select) chose its member.
 #include "amt_common.h"
 
 #include <algorithm>
@@ -182,28 +186,131 @@ __device__ __forceinline__ lane_run run_of(int cell, unsigned cnt, int lane) {
     return r;
 }
 
+// ---- the member table of a mosaic (amt_mosaic_median_frames, amt_mosaic_quantile_frames) ----
+// The pixel index space of the count and fill passes is the concatenation of the members that have a window: member m's
+// pixel i is g0 + i.  Work is handed out in whole workgroups of kBlock * kPPT pixels of ONE member (block_start: the first
+// workgroup of every member, n + 1 entries), so a wave only ever sees one member and the run rule below carries over.
+struct med_member {
+    const double* lat_c;
+    const double* lon_c;
+    const double* elev;
+    const void* img;
+    const uint8_t* mask;
+    int n, g0;                          // pixels; index of pixel 0 in the concatenated space
+    int x0, y0, wnx, wny;               // window in cells of the common grid
+};
+struct member_table {
+    const med_member* __restrict__ members;
+    const int* __restrict__ block_start;
+    int n;
+    const int32_t* source;              // rule 1: the elected member of every OUTPUT cell (k_mosaic_select), else NULL
+    int* first;                         // rule 0: the lowest member index present per cell (atomicMin), or NULL
+};
+
+// What a wave of the count pass knows beside the frame: nothing (a frame alone), or its member of a mosaic.
+struct no_member {};
+struct member_view {
+    int m, x0, y0, wnx, wny;
+    const int32_t* source;
+    int* first;
+};
+
+// the cell a pixel counts in: for a member, only inside its window, and under rule 1 only where it was elected
+__device__ __forceinline__ int keep_cell(const med_args&, const no_member&, int c) { return c; }
+__device__ __forceinline__ int keep_cell(const med_args& A, const member_view& V, int c) {
+    if (c < 0) return -1;
+    const int iy = c / A.nx, ix = c - iy * A.nx;
+    if ((unsigned)(ix - V.x0) >= (unsigned)V.wnx || (unsigned)(iy - V.y0) >= (unsigned)V.wny) return -1;
+    if (V.source && V.source[(int64_t)(A.ny - 1 - iy) * A.nx + ix] != V.m) return -1;
+    return c;
+}
+__device__ __forceinline__ void note_member(const no_member&, int) {}
+__device__ __forceinline__ void note_member(const member_view& V, int c) {
+    if (V.first) atomicMin(&V.first[c], V.m);
+}
+
+// The last m with block_start[m] <= b (members without a window have no workgroups: equal entries), by wave-uniform loads.
+__device__ __forceinline__ int table_member(const member_table& T, unsigned b) {
+    int lo = 0, hi = T.n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)T.block_start[mid] <= b) lo = mid; else hi = mid;
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
+// The frame of a member as the kernels' argument: the call's common part A0 with the member's arrays.
+__device__ __forceinline__ med_args member_args(const med_args& A0, const med_member& D) {
+    med_args A = A0;
+    A.lat_c = D.lat_c;
+    A.lon_c = D.lon_c;
+    A.elev = D.elev;
+    A.img = D.img;
+    A.mask = D.mask;
+    A.n = D.n;
+    A.use_elev_threshold = A0.use_elev_threshold && D.elev != nullptr;
+    return A;
+}
+
+// One wave's kPPT * 64 pixels of frame A from pixel `base` on; the frame's pixel 0 is g0 in cell_of.  The body of the count
+// pass, shared by the frame kernel and the member-table kernel.  Called by the whole wave.
+template <typename VIEW>
+__device__ __forceinline__ void count_wave(const med_args& A, const VIEW& V, int64_t base, int64_t g0, int lane, int* cell_of,
+                                           unsigned* count) {
+    const int64_t i0 = base + (int64_t)lane * kPPT;
+    lane_cells L;
+#pragma unroll
+    for (int j = 0; j < kPPT; ++j) {
+        const int64_t i = i0 + j;
+        L.c[j] = i < A.n ? keep_cell(A, V, pixel_cell(A, i)) : -1;
+        if (i < A.n) cell_of[g0 + i] = L.c[j];
+    }
+    summarise(L);
+    if (L.mixed) {
+#pragma unroll
+        for (int j = 0; j < kPPT; ++j)
+            if (L.c[j] >= 0) {
+                atomicAdd(&count[L.c[j]], 1u);
+                note_member(V, L.c[j]);
+            }
+    }
+    const lane_run r = run_of(L.cell, L.cnt, lane);
+    if (r.head == lane && L.cell >= 0 && r.total) {
+        atomicAdd(&count[L.cell], r.total);
+        note_member(V, L.cell);
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void k_med_count(med_args A, int* __restrict__ cell_of,
                                                      unsigned* __restrict__ count) {
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT;
     // whole waves stay in the loop together (the shuffles need every lane)
-    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride) {
-        const int64_t i0 = base + (int64_t)lane * kPPT;
-        lane_cells L;
-#pragma unroll
-        for (int j = 0; j < kPPT; ++j) {
-            const int64_t i = i0 + j;
-            L.c[j] = i < A.n ? pixel_cell(A, i) : -1;
-            if (i < A.n) cell_of[i] = L.c[j];
-        }
-        summarise(L);
-        if (L.mixed) {
-#pragma unroll
-            for (int j = 0; j < kPPT; ++j)
-                if (L.c[j] >= 0) atomicAdd(&count[L.c[j]], 1u);
-        }
-        const lane_run r = run_of(L.cell, L.cnt, lane);
-        if (r.head == lane && L.cell >= 0 && r.total) atomicAdd(&count[L.cell], r.total);
+    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride)
+        count_wave(A, no_member{}, base, 0, lane, cell_of, count);
+}
+
+// The count pass over a member table: workgroup blockIdx.x takes kBlock * kPPT pixels of one member.  The member's
+// descriptor is copied into registers once (the atomics below may alias the table for all the compiler knows).
+__global__ __launch_bounds__(kBlock) void k_med_count_members(med_args A0, member_table T, int* __restrict__ cell_of,
+                                                             unsigned* __restrict__ count) {
+    const int lane = threadIdx.x & 63;
+    const int m = table_member(T, blockIdx.x);
+    const med_member D = T.members[m];
+    const med_args A = member_args(A0, D);
+    const member_view V = {m, D.x0, D.y0, D.wnx, D.wny, T.source, T.first};
+    const int64_t base = ((int64_t)(blockIdx.x - (unsigned)T.block_start[m]) * kBlock + (threadIdx.x & ~63)) * kPPT;
+    if (base >= A.n) return;                                        // (wave-uniform)
+    count_wave(A, V, base, D.g0, lane, cell_of, count);
+}
+
+// rule 0 of a mosaic: out_source of every cell from the lowest member index the count pass has seen there
+__global__ __launch_bounds__(kBlock) void k_med_source(const unsigned* __restrict__ count, const int* __restrict__ first, int nx,
+                                                      int ny, int32_t* __restrict__ out_source) {
+    const int64_t cells = (int64_t)nx * ny;
+    for (int64_t c = blockIdx.x * (int64_t)kBlock + threadIdx.x; c < cells; c += (int64_t)gridDim.x * kBlock) {
+        const int iy = (int)(c / nx), ix = (int)(c - (int64_t)iy * nx);
+        out_source[(int64_t)(ny - 1 - iy) * nx + ix] = count[c] ? first[c] : -1;
     }
 }
 
@@ -280,35 +387,59 @@ __global__ __launch_bounds__(kBlock) void k_med_scan_apply(const unsigned* __res
 }
 
 // ---- scatter of the keys ----
+// One wave's kPPT * 64 pixels of frame A from pixel `base` on (pixel 0 is g0 in cell_of; the key planes are `stride` keys
+// apart): the body of the fill pass, shared like count_wave.  Called by the whole wave.
+template <typename IMG_T>
+__device__ __forceinline__ void fill_wave(const med_args& A, int64_t base, int64_t g0, int64_t stride, int lane,
+                                          const int* cell_of, const unsigned* offset, unsigned* cursor, uint16_t* keys16,
+                                          unsigned long long* keys64) {
+    const IMG_T* img = static_cast<const IMG_T*>(A.img);
+    const int64_t i0 = base + (int64_t)lane * kPPT;
+    lane_cells L;
+#pragma unroll
+    for (int j = 0; j < kPPT; ++j) L.c[j] = i0 + j < A.n ? cell_of[g0 + i0 + j] : -1;
+    summarise(L);
+    const lane_run r = run_of(L.cell, L.cnt, lane);
+    unsigned first = 0;
+    if (r.head == lane && L.cell >= 0 && r.total) first = offset[L.cell] + atomicAdd(&cursor[L.cell], r.total);
+    first = __shfl(first, r.head) + r.excl;
+#pragma unroll
+    for (int j = 0; j < kPPT; ++j) {
+        const int c = L.c[j];
+        if (c < 0) continue;
+        unsigned pos;
+        if (L.mixed) pos = offset[c] + atomicAdd(&cursor[c], 1u);
+        else pos = first++;
+        const int64_t i = i0 + j;
+        for (int ch = 0; ch < A.nch; ++ch) keys16[(int64_t)ch * stride + pos] = (uint16_t)img[i * A.nch + ch];
+        if (keys64) keys64[pos] = elev_key(A.elev[i]);
+    }
+}
+
 template <typename IMG_T>
 __global__ __launch_bounds__(kBlock) void k_med_fill(med_args A, const int* __restrict__ cell_of,
                                                     const unsigned* __restrict__ offset, unsigned* __restrict__ cursor,
                                                     uint16_t* __restrict__ keys16, unsigned long long* __restrict__ keys64) {
     const int lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT;
-    const IMG_T* img = static_cast<const IMG_T*>(A.img);
-    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride) {
-        const int64_t i0 = base + (int64_t)lane * kPPT;
-        lane_cells L;
-#pragma unroll
-        for (int j = 0; j < kPPT; ++j) L.c[j] = i0 + j < A.n ? cell_of[i0 + j] : -1;
-        summarise(L);
-        const lane_run r = run_of(L.cell, L.cnt, lane);
-        unsigned first = 0;
-        if (r.head == lane && L.cell >= 0 && r.total) first = offset[L.cell] + atomicAdd(&cursor[L.cell], r.total);
-        first = __shfl(first, r.head) + r.excl;
-#pragma unroll
-        for (int j = 0; j < kPPT; ++j) {
-            const int c = L.c[j];
-            if (c < 0) continue;
-            unsigned pos;
-            if (L.mixed) pos = offset[c] + atomicAdd(&cursor[c], 1u);
-            else pos = first++;
-            const int64_t i = i0 + j;
-            for (int ch = 0; ch < A.nch; ++ch) keys16[(int64_t)ch * A.n + pos] = (uint16_t)img[i * A.nch + ch];
-            if (keys64) keys64[pos] = elev_key(A.elev[i]);
-        }
-    }
+    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride)
+        fill_wave<IMG_T>(A, base, 0, A.n, lane, cell_of, offset, cursor, keys16, keys64);
+}
+
+// The fill pass over a member table (the workgroups of k_med_count_members); total: the pixels of the concatenated space.
+template <typename IMG_T>
+__global__ __launch_bounds__(kBlock) void k_med_fill_members(med_args A0, member_table T, int64_t total,
+                                                            const int* __restrict__ cell_of,
+                                                            const unsigned* __restrict__ offset, unsigned* __restrict__ cursor,
+                                                            uint16_t* __restrict__ keys16,
+                                                            unsigned long long* __restrict__ keys64) {
+    const int lane = threadIdx.x & 63;
+    const int m = table_member(T, blockIdx.x);
+    const med_member D = T.members[m];
+    const med_args A = member_args(A0, D);
+    const int64_t base = ((int64_t)(blockIdx.x - (unsigned)T.block_start[m]) * kBlock + (threadIdx.x & ~63)) * kPPT;
+    if (base >= A.n) return;                                        // (wave-uniform)
+    fill_wave<IMG_T>(A, base, D.g0, total, lane, cell_of, offset, cursor, keys16, keys64);
 }
 
 // ---- outputs ----
@@ -347,7 +478,9 @@ __device__ __forceinline__ int64_t out_index(const out_args& O, int cell) {
 __device__ __forceinline__ void put_median(const out_args& O, int cell, int p, unsigned long long lo, unsigned long long hi) {
     const int64_t o = out_index(O, cell);
     if (p == O.nch) {
-        O.median[o * (O.nch + 1) + p] = (elev_of_key(lo) + elev_of_key(hi)) / 2.0;
+        // np.median is np.mean of the middle pair, whose sum starts from +0.0: a pair of -0.0 gives +0.0 (every other pair is
+        // untouched: 0.0 + a is a)
+        O.median[o * (O.nch + 1) + p] = ((0.0 + elev_of_key(lo)) + elev_of_key(hi)) / 2.0;
         return;
     }
     const double v = ((double)lo + (double)hi) / 2.0;       // np.median: mean of the middle pair in float64
@@ -894,6 +1027,98 @@ struct median_pass {
     unsigned* lh;                       // per large cell: the histograms of its planes, then their tickets
 };
 
+// The workspace of a pass over n pixels and `cells` cells: count, cursor [cells] | tier counters | offset [cells + 1] | block
+// sums [nb + 1] | medium, large lists [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state
+// [large_cap * nplane] and histograms with their tickets [large_cap * nplane * 257]: every plane of every large cell, as
+// amt_median_frame_async has them in flight (733 cells x 4 planes x 1060 bytes = 3.1 MB at 12 Mpixel, beside ~18 bytes per
+// pixel); amt_median_frame, one plane at a time, uses the first large_cap states and large_cap * 256 words.
+struct med_layout {
+    size_t count, tiers, offset, bsum, medium, large, cellof, keys16, keys64, state, ghist, bytes;
+    int nb;
+    int64_t large_cap;
+};
+
+med_layout median_layout(int64_t n, int64_t cells, int nchan, bool has_elev) {
+    med_layout L;
+    L.nb = (int)((cells + kScanTile - 1) / kScanTile);
+    L.large_cap = n / (kLargeMin + 1) + 1;
+    const int nplane = nchan + (has_elev ? 1 : 0);
+    size_t at = 0;
+    L.count = at;   at = align256(at + (size_t)2 * cells * sizeof(unsigned));
+    L.tiers = at;   at = align256(at + sizeof(tier_counters));
+    L.offset = at;  at = align256(at + (size_t)(cells + 1) * sizeof(unsigned));
+    L.bsum = at;    at = align256(at + (size_t)(L.nb + 1) * sizeof(unsigned));
+    L.medium = at;  at = align256(at + (size_t)cells * sizeof(int));
+    L.large = at;   at = align256(at + (size_t)cells * sizeof(int));
+    L.cellof = at;  at = align256(at + (size_t)n * sizeof(int));
+    L.keys16 = at;  at = align256(at + (size_t)nchan * n * sizeof(uint16_t));
+    L.keys64 = at;  at = align256(at + (has_elev ? (size_t)n * sizeof(unsigned long long) : 0));
+    L.state = at;   at = align256(at + (size_t)(L.large_cap * nplane) * sizeof(large_state));
+    L.ghist = at;   at = align256(at + (size_t)(L.large_cap * nplane * 257) * sizeof(unsigned));
+    L.bytes = at;
+    return L;
+}
+
+// the arrays of the count, scan and fill passes in a workspace laid out by median_layout
+struct med_buffers {
+    unsigned* count;
+    unsigned* cursor;
+    unsigned* offset;
+    unsigned* bsum;
+    int* cell_of;
+    uint16_t* keys16;
+    unsigned long long* keys64;
+};
+
+med_buffers median_bind(char* ws, const med_layout& L, int64_t n, int64_t cells, int nchan, bool has_elev, median_pass* M) {
+    med_buffers B;
+    B.count = reinterpret_cast<unsigned*>(ws + L.count);
+    B.cursor = B.count + cells;
+    B.offset = reinterpret_cast<unsigned*>(ws + L.offset);
+    B.bsum = reinterpret_cast<unsigned*>(ws + L.bsum);
+    B.cell_of = reinterpret_cast<int*>(ws + L.cellof);
+    B.keys16 = reinterpret_cast<uint16_t*>(ws + L.keys16);
+    B.keys64 = has_elev ? reinterpret_cast<unsigned long long*>(ws + L.keys64) : nullptr;
+    M->tiers = reinterpret_cast<tier_counters*>(ws + L.tiers);
+    M->medium = reinterpret_cast<int*>(ws + L.medium);
+    M->large = reinterpret_cast<int*>(ws + L.large);
+    M->state = reinterpret_cast<large_state*>(ws + L.state);
+    M->lh = reinterpret_cast<unsigned*>(ws + L.ghist);
+    M->n = n, M->cells = cells, M->large_cap = L.large_cap, M->nplane = nchan + (has_elev ? 1 : 0);
+    return B;
+}
+
+void median_scan(amt_ctx* ctx, const med_buffers& B, int64_t cells, int nb) {
+    hipLaunchKernelGGL(k_med_scan_sums, dim3(nb), dim3(kBlock), 0, ctx->stream, B.count, cells, B.bsum);
+    hipLaunchKernelGGL(k_med_scan_blocks, dim3(1), dim3(kBlock), 0, ctx->stream, B.bsum, nb);
+    hipLaunchKernelGGL(k_med_scan_apply, dim3(nb), dim3(kBlock), 0, ctx->stream, B.count, cells, B.bsum, nb, B.offset);
+}
+
+// the output arguments and the small tier (k_med_small), after the fill pass
+int median_small(amt_ctx* ctx, const med_buffers& B, const med_args& A, bool has_elev, const double* q, int nq, double* median,
+                 void* out_img, uint8_t* out_mask, double* out_count, median_pass* M) {
+    out_args& O = M->O;
+    O.nx = A.nx;
+    O.ny = A.ny;
+    O.nch = A.nch;
+    O.img_dtype = A.img_dtype;
+    O.has_elev = has_elev;
+    O.n = M->n;
+    O.count = B.count;
+    O.offset = B.offset;
+    O.keys16 = B.keys16;
+    O.keys64 = B.keys64;
+    O.median = median;
+    O.out_img = A.nch ? out_img : nullptr;
+    O.out_mask = out_mask;
+    O.out_count = out_count;
+    O.nq = nq;
+    for (int j = 0; j < kQuantilesMax; ++j) O.q[j] = j < nq ? q[j] : 0.0;
+    MED_LAUNCH(k_med_small, nq != 0, grid_for(M->cells * 64), dim3(kBlock), O, M->medium, M->large, M->tiers, M->lh);
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
 int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
                  int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                  double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int lon_from_mlt,
@@ -925,77 +1150,153 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
     A.nch = nchan;
     A.img_dtype = img_dtype;
     const int64_t n = A.n, cells = (int64_t)A.nx * A.ny;
-    const int nb = (int)((cells + kScanTile - 1) / kScanTile);
-    const int64_t large_cap = n / (kLargeMin + 1) + 1;
-    const int nplane = nchan + (elev ? 1 : 0);
-    // workspace: count, cursor [cells] | tier counters | offset [cells + 1] | block sums [nb + 1] | medium, large lists
-    // [cells] | cell_of [n] | u16 keys [nchan * n] | u64 elevation keys [n] | large-tier state [large_cap * nplane] and
-    // histograms with their tickets [large_cap * nplane * 257]: every plane of every large cell, as amt_median_frame_async
-    // has them in flight (733 cells x 4 planes x 1060 bytes = 3.1 MB at 12 Mpixel, beside ~18 bytes per pixel);
-    // amt_median_frame, one plane at a time, uses the first large_cap states and large_cap * 256 words.
-    size_t at = 0;
-    const size_t o_count = at;   at = align256(at + (size_t)2 * cells * sizeof(unsigned));
-    const size_t o_tiers = at;   at = align256(at + sizeof(tier_counters));
-    const size_t o_offset = at;  at = align256(at + (size_t)(cells + 1) * sizeof(unsigned));
-    const size_t o_bsum = at;    at = align256(at + (size_t)(nb + 1) * sizeof(unsigned));
-    const size_t o_medium = at;  at = align256(at + (size_t)cells * sizeof(int));
-    const size_t o_large = at;   at = align256(at + (size_t)cells * sizeof(int));
-    const size_t o_cellof = at;  at = align256(at + (size_t)n * sizeof(int));
-    const size_t o_keys16 = at;  at = align256(at + (size_t)nchan * n * sizeof(uint16_t));
-    const size_t o_keys64 = at;  at = align256(at + (elev ? (size_t)n * sizeof(unsigned long long) : 0));
-    const size_t o_state = at;   at = align256(at + (size_t)(large_cap * nplane) * sizeof(large_state));
-    const size_t o_ghist = at;   at = align256(at + (size_t)(large_cap * nplane * 257) * sizeof(unsigned));
-    char* ws = static_cast<char*>(amt_workspace(ctx, at));
+    const med_layout L = median_layout(n, cells, nchan, elev != nullptr);
+    char* ws = static_cast<char*>(amt_workspace(ctx, L.bytes));
     if (ws == nullptr) {
         ctx->last_error = "amt_median_frame: workspace allocation failed";
         return AMT_ENOMEM;
     }
-    unsigned* count = reinterpret_cast<unsigned*>(ws + o_count);
-    unsigned* cursor = count + cells;
-    unsigned* offset = reinterpret_cast<unsigned*>(ws + o_offset);
-    unsigned* bsum = reinterpret_cast<unsigned*>(ws + o_bsum);
-    int* cell_of = reinterpret_cast<int*>(ws + o_cellof);
-    uint16_t* keys16 = reinterpret_cast<uint16_t*>(ws + o_keys16);
-    unsigned long long* keys64 = elev ? reinterpret_cast<unsigned long long*>(ws + o_keys64) : nullptr;
-    M->tiers = reinterpret_cast<tier_counters*>(ws + o_tiers);
-    M->medium = reinterpret_cast<int*>(ws + o_medium);
-    M->large = reinterpret_cast<int*>(ws + o_large);
-    M->state = reinterpret_cast<large_state*>(ws + o_state);
-    M->lh = reinterpret_cast<unsigned*>(ws + o_ghist);
-    M->n = n, M->cells = cells, M->large_cap = large_cap, M->nplane = nplane;
+    const med_buffers B = median_bind(ws, L, n, cells, nchan, elev != nullptr, M);
 
     // count, cursor and the tier counters are adjacent: one clear
-    AMT_HIP(ctx, hipMemsetAsync(ws, 0, o_offset, ctx->stream));
-    hipLaunchKernelGGL(k_med_count, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of, count);
-    hipLaunchKernelGGL(k_med_scan_sums, dim3(nb), dim3(kBlock), 0, ctx->stream, count, cells, bsum);
-    hipLaunchKernelGGL(k_med_scan_blocks, dim3(1), dim3(kBlock), 0, ctx->stream, bsum, nb);
-    hipLaunchKernelGGL(k_med_scan_apply, dim3(nb), dim3(kBlock), 0, ctx->stream, count, cells, bsum, nb, offset);
+    AMT_HIP(ctx, hipMemsetAsync(ws, 0, L.offset, ctx->stream));
+    hipLaunchKernelGGL(k_med_count, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, B.cell_of, B.count);
+    median_scan(ctx, B, cells, L.nb);
     if (nchan == 0 || img_dtype == 1)
-        hipLaunchKernelGGL(k_med_fill<uint8_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of,
-                           offset, cursor, keys16, keys64);
+        hipLaunchKernelGGL(k_med_fill<uint8_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, B.cell_of,
+                           B.offset, B.cursor, B.keys16, B.keys64);
     else
-        hipLaunchKernelGGL(k_med_fill<uint16_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, cell_of,
-                           offset, cursor, keys16, keys64);
-    out_args& O = M->O;
-    O.nx = A.nx;
-    O.ny = A.ny;
-    O.nch = nchan;
-    O.img_dtype = img_dtype;
-    O.has_elev = elev != nullptr;
-    O.n = n;
-    O.count = count;
-    O.offset = offset;
-    O.keys16 = keys16;
-    O.keys64 = keys64;
-    O.median = median;
-    O.out_img = nchan ? out_img : nullptr;
-    O.out_mask = out_mask;
-    O.out_count = out_count;
-    O.nq = nq;
-    for (int j = 0; j < kQuantilesMax; ++j) O.q[j] = j < nq ? q[j] : 0.0;
-    MED_LAUNCH(k_med_small, nq != 0, grid_for(cells * 64), dim3(kBlock), O, M->medium, M->large, M->tiers, M->lh);
-    AMT_LAUNCH_CHECK(ctx);
-    return AMT_OK;
+        hipLaunchKernelGGL(k_med_fill<uint16_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, B.cell_of,
+                           B.offset, B.cursor, B.keys16, B.keys64);
+    return median_small(ctx, B, A, elev != nullptr, q, nq, median, out_img, out_mask, out_count, M);
+}
+
+// The front of a mosaic (amt_mosaic_median_frames, amt_mosaic_quantile_frames): the cells, windows and overlap rule of
+// amt_mosaic_frames, the segments of the passes above.  Rule 1 first runs amt_mosaic_frames' own binning and election for
+// `source` alone; the count pass then keeps a member's pixel only where that member was elected, and from there both rules are
+// the frame's problem over the concatenated pixels of the members.  One count and one fill launch whatever n_members is.
+// Workspace (one allocation): rule 1's member tables and accumulators | source or first-member plane [cells] | member table |
+// block prefix | the median workspace for the concatenated pixels.
+int mosaic_median_front(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype, int32_t nchan,
+                        double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int32_t rule,
+                        const double* q, int nq, double* median, void* out_img, uint8_t* out_mask, double* out_count,
+                        int32_t* out_source, median_pass* M) {
+    AMT_REQUIRE(ctx, members && xaxis && yaxis && median, "NULL argument");
+    AMT_REQUIRE(ctx, n_members >= 1, "no members");
+    AMT_REQUIRE(ctx, rule == 0 || rule == 1, "rule must be 0 (union) or 1 (highest elevation)");
+    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
+    AMT_REQUIRE(ctx, nchan == 0 || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
+    const int nx = xaxis->nbin, ny = yaxis->nbin;
+    const int64_t cells = (int64_t)nx * ny;
+    std::vector<med_member> table((size_t)n_members);
+    std::vector<int> block_start((size_t)n_members + 1, 0);
+    int64_t total = 0, all_pixels = 0, blocks = 0;
+    bool has_elev = true;
+    for (int32_t i = 0; i < n_members; ++i) {
+        const amt_mosaic_member& m = members[i];
+        AMT_REQUIRE(ctx, m.lat_c && m.lon_c && m.height > 0 && m.width > 0, "member without centres");
+        AMT_REQUIRE(ctx, nchan == 0 || m.img, "member image missing");
+        AMT_REQUIRE(ctx, rule == 0 || m.elev != nullptr, "rule 1 needs every member's elevation");
+        AMT_REQUIRE(ctx, m.win_nx >= 0 && m.win_ny >= 0, "bad window");
+        AMT_REQUIRE(ctx, m.win_nx == 0 || m.win_ny == 0 ||
+                         (m.win_x0 >= 0 && m.win_y0 >= 0 && m.win_x0 + m.win_nx <= nx && m.win_y0 + m.win_ny <= ny),
+                    "window outside the grid");
+        has_elev = has_elev && m.elev != nullptr;           // (the elevation plane: of every member, or NaN)
+        const int64_t n = (int64_t)m.height * m.width;
+        all_pixels += n;
+        AMT_REQUIRE(ctx, all_pixels < 2147483647LL, "the members' pixels together exceed 32-bit pixel indices");
+        const bool empty = m.win_nx == 0 || m.win_ny == 0;
+        med_member& d = table[(size_t)i];
+        d.lat_c = m.lat_c;
+        d.lon_c = m.lon_c;
+        d.elev = m.elev;
+        d.img = m.img;
+        d.mask = m.center_mask;
+        d.n = (int)n;
+        d.g0 = (int)total;
+        d.x0 = m.win_x0, d.y0 = m.win_y0;
+        d.wnx = empty ? 0 : m.win_nx, d.wny = empty ? 0 : m.win_ny;
+        block_start[(size_t)i] = (int)blocks;
+        if (!empty) {
+            total += n;
+            blocks += (n + kBlock * kPPT - 1) / (kBlock * kPPT);
+        }
+    }
+    block_start[(size_t)n_members] = (int)blocks;
+    if (amt_set_device(ctx)) return AMT_EHIP;
+
+    const med_layout L = median_layout(total, cells, nchan, has_elev);
+    const size_t o_plane = 0;
+    const size_t o_table = align256(o_plane + (size_t)cells * sizeof(int32_t));
+    const size_t o_bstart = align256(o_table + table.size() * sizeof(med_member));
+    const size_t o_med = align256(o_bstart + block_start.size() * sizeof(int));
+    const size_t bytes = o_med + L.bytes;
+    char* ws = nullptr;
+    if (rule == 1) {
+        // the windowed binning and the election; with no out_source of its own the elected member of every output cell goes
+        // to the head of the tail, where it stays until the count pass has read it
+        if (int rc = amt_mosaic_run(ctx, members, n_members, img_dtype, nchan, min_elevation, xaxis, yaxis, lon_wrap, 1, nullptr,
+                                    nullptr, nullptr, nullptr, nullptr, bytes, &ws))
+            return rc;
+    } else {
+        ws = static_cast<char*>(amt_workspace(ctx, bytes));
+    }
+    if (ws == nullptr) {
+        ctx->last_error = "amt_mosaic_median_frames: workspace allocation failed";
+        return AMT_ENOMEM;
+    }
+    int32_t* plane = reinterpret_cast<int32_t*>(ws + o_plane);
+    const med_buffers B = median_bind(ws + o_med, L, total, cells, nchan, has_elev, M);
+
+    med_args A;                         // the call's common part; the kernels put a member's arrays in
+    A.lat_c = A.lon_c = A.elev = nullptr;
+    A.img = nullptr;
+    A.mask = nullptr;
+    A.n = 0;
+    A.min_elev = min_elevation;
+    A.use_elev_threshold = !(std::isinf(min_elevation) && min_elevation < 0);
+    A.lon_wrap = lon_wrap ? 1 : 0;
+    A.lon_from_mlt = 0;
+    make_axis(xaxis, &A.ax);
+    make_axis(yaxis, &A.ay);
+    A.nx = nx;
+    A.ny = ny;
+    A.nch = nchan;
+    A.img_dtype = img_dtype;
+    member_table T;
+    T.members = reinterpret_cast<const med_member*>(ws + o_table);
+    T.block_start = reinterpret_cast<const int*>(ws + o_bstart);
+    T.n = n_members;
+    T.source = rule == 1 ? plane : nullptr;
+    T.first = rule == 0 && out_source ? plane : nullptr;
+
+    // member table and block prefix: one upload (pageable source: the copy has consumed `host` when the call returns)
+    std::vector<char> host(o_med - o_table, 0);
+    std::memcpy(host.data(), table.data(), table.size() * sizeof(med_member));
+    std::memcpy(host.data() + (o_bstart - o_table), block_start.data(), block_start.size() * sizeof(int));
+    AMT_HIP(ctx, hipMemcpyAsync(ws + o_table, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (T.first) AMT_HIP(ctx, hipMemsetAsync(plane, 0x7f, (size_t)cells * sizeof(int32_t), ctx->stream));
+    AMT_HIP(ctx, hipMemsetAsync(ws + o_med, 0, L.offset, ctx->stream));
+    if (blocks > 0)
+        hipLaunchKernelGGL(k_med_count_members, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, A, T, B.cell_of, B.count);
+    if (out_source) {
+        if (rule == 1)
+            AMT_HIP(ctx, hipMemcpyAsync(out_source, plane, (size_t)cells * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        else
+            hipLaunchKernelGGL(k_med_source, grid_for(cells), dim3(kBlock), 0, ctx->stream, B.count, plane, nx, ny, out_source);
+    }
+    median_scan(ctx, B, cells, L.nb);
+    if (blocks > 0) {
+        if (nchan == 0 || img_dtype == 1)
+            hipLaunchKernelGGL(k_med_fill_members<uint8_t>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, A, T, total,
+                               B.cell_of, B.offset, B.cursor, B.keys16, B.keys64);
+        else
+            hipLaunchKernelGGL(k_med_fill_members<uint16_t>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, A, T, total,
+                               B.cell_of, B.offset, B.cursor, B.keys16, B.keys64);
+    }
+    return median_small(ctx, B, A, has_elev, q, nq, median, out_img, out_mask, out_count, M);
 }
 
 // The quantiles of a call, checked before anything else looks at its arguments or touches the device: 1 .. AMT_QUANTILES_MAX
@@ -1125,6 +1426,31 @@ int amt_quantile_frame_async(amt_ctx* ctx, const double* lat_c, const double* lo
                               yaxis, lon_wrap, lon_from_mlt, q, nq, quantile, out_img, out_mask, out_count, &M))
         return rc;
     return upper_tiers_async(ctx, M);
+}
+
+int amt_mosaic_median_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                             int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                             int32_t rule, double* median, void* out_img, uint8_t* out_mask, double* out_count,
+                             int32_t* out_source) {
+    AMT_CHECK_CTX(ctx);
+    median_pass M;
+    if (int rc = mosaic_median_front(ctx, members, n_members, img_dtype, nchan, min_elevation, xaxis, yaxis, lon_wrap, rule,
+                                     nullptr, 0, median, out_img, out_mask, out_count, out_source, &M))
+        return rc;
+    return upper_tiers_sync(ctx, M);
+}
+
+int amt_mosaic_quantile_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                               int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                               int32_t rule, const double* q, int nq, double* quantile, void* out_img, uint8_t* out_mask,
+                               double* out_count, int32_t* out_source) {
+    if (!quantiles_ok(ctx, q, nq)) return AMT_EINVAL;
+    AMT_CHECK_CTX(ctx);
+    median_pass M;
+    if (int rc = mosaic_median_front(ctx, members, n_members, img_dtype, nchan, min_elevation, xaxis, yaxis, lon_wrap, rule, q,
+                                     nq, quantile, out_img, out_mask, out_count, out_source, &M))
+        return rc;
+    return upper_tiers_sync(ctx, M);
 }
 
 int amt_quantile_rank(int64_t n, double q, int64_t* k, int64_t* k2, double* g) {

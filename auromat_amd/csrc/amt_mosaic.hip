@@ -5,6 +5,7 @@
 // each member's window of the common grid) bins every member's tiles, and k_mosaic_select gives every output cell its value
 // by the overlap rule.
 // Integer sums and an ordered walk over the members make the result independent of the order in which tiles run.
+// The median and quantile mosaics (amt_median.hip) run the same binning and election for `source` alone (amt_mosaic_run).
 #include <algorithm>
 
 #include "amt_common.h"
@@ -78,11 +79,13 @@ __global__ __launch_bounds__(kSelTile * kSelTile) void k_mosaic_select(select_ar
 
 }  // namespace
 
-extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype,
-                                 int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis,
-                                 int lon_wrap, int32_t rule, double* mean, void* out_img, uint8_t* out_mask,
-                                 double* out_count, int32_t* out_source) {
-    AMT_CHECK_CTX(ctx);
+// amt_mosaic_frames; `tail_bytes` more bytes of the context's workspace behind the call's own tables and accumulators are
+// handed to the caller through `tail` (256-byte aligned): amt_mosaic_median_frames and amt_mosaic_quantile_frames
+// (amt_median.hip) keep the median workspace there, in the same allocation, so that one call sizes the workspace once; with a
+// tail and no out_source the elected member of every cell ((ny, nx) int32) is written to the tail's first bytes.
+int amt_mosaic_run(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype, int32_t nchan,
+                   double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int32_t rule, double* mean,
+                   void* out_img, uint8_t* out_mask, double* out_count, int32_t* out_source, size_t tail_bytes, char** tail) {
     AMT_REQUIRE(ctx, members && xaxis && yaxis, "NULL argument");
     AMT_REQUIRE(ctx, n_members >= 1, "no members");
     AMT_REQUIRE(ctx, rule == 0 || rule == 1, "rule must be 0 (union) or 1 (highest elevation)");
@@ -169,11 +172,13 @@ extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members,
     const size_t o_list = o_lstart + up(list_start.size() * sizeof(int));
     const size_t o_acc = o_list + up(std::max<size_t>(list.size(), 1) * sizeof(int));
     const size_t bytes = o_acc + std::max<size_t>(acc_words, 1) * sizeof(unsigned long long);
-    char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
+    const size_t o_tail = up(bytes);
+    char* ws = static_cast<char*>(amt_workspace(ctx, tail_bytes ? o_tail + tail_bytes : bytes));
     if (ws == nullptr) {
         ctx->last_error = "amt_mosaic_frames: workspace allocation failed";
         return AMT_ENOMEM;
     }
+    if (tail != nullptr) *tail = ws + o_tail;
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + o_acc);
     for (int32_t i = 0; i < n_members; ++i) dev[(size_t)i].A.acc = acc + acc_off[(size_t)i];
     std::vector<char> host(o_acc, 0);
@@ -221,7 +226,7 @@ extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members,
     S.img = out_img;
     S.mask = out_mask;
     S.count = out_count;
-    S.source = out_source;
+    S.source = out_source ? out_source : (tail ? reinterpret_cast<int32_t*>(ws + o_tail) : nullptr);
     const dim3 sgrid((unsigned)n_sel), sblock(kSelTile * kSelTile);
     if (img_dtype == 2)
         hipLaunchKernelGGL(k_mosaic_select<uint16_t>, sgrid, sblock, 0, ctx->stream, S);
@@ -229,4 +234,13 @@ extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members,
         hipLaunchKernelGGL(k_mosaic_select<uint8_t>, sgrid, sblock, 0, ctx->stream, S);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
+}
+
+extern "C" int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                                 int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis,
+                                 int lon_wrap, int32_t rule, double* mean, void* out_img, uint8_t* out_mask,
+                                 double* out_count, int32_t* out_source) {
+    AMT_CHECK_CTX(ctx);
+    return amt_mosaic_run(ctx, members, n_members, img_dtype, nchan, min_elevation, xaxis, yaxis, lon_wrap, rule, mean, out_img,
+                          out_mask, out_count, out_source, 0, nullptr);
 }

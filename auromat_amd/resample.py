@@ -305,7 +305,24 @@ def resampleQuantileMLatMLT(mapping, q, **kw):
     return [convertSMMappingToGeo(r) for r in res] if isinstance(res, list) else convertSMMappingToGeo(res)
 
 
-def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+MOSAIC_STATISTICS = ('mean', 'median', 'quantile')
+
+
+def mosaic_statistic(statistic, q):
+    """The quantiles of a mosaic call as a list (None for 'mean' and 'median').  ValueError for an unknown statistic, `q` given
+    with 'mean' or 'median', 'quantile' without `q`, and what :func:`quantile_list` refuses — before any member is looked at."""
+    if statistic not in MOSAIC_STATISTICS:
+        raise ValueError('statistic must be one of {}, but is: {!r}'.format(', '.join(MOSAIC_STATISTICS), statistic))
+    if statistic != 'quantile':
+        if q is not None:
+            raise ValueError('q={!r} goes with statistic=\'quantile\', not with {!r}'.format(q, statistic))
+        return None
+    if q is None:
+        raise ValueError('statistic=\'quantile\' needs q: a number or a sequence of up to 8 numbers in [0, 1]')
+    return quantile_list(q)
+
+
+def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, statistic='mean', q=None):
     """
     Bins every member of a :class:`MappingCollection` onto ONE grid and returns ONE mapping (:class:`MosaicMapping`), where
     :func:`resample` of a collection grids each member on its own box.
@@ -322,34 +339,58 @@ def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None)
     draw_helpers.py:128-178), the earlier member on a tie.  ``source`` holds the winning member's index per cell
     (``members`` their identifiers).  Members are read through ``mapping.frame()``.
 
-    :raises ValueError: for an empty collection, members of different altitudes or image dtypes / channel counts, and a
-                        member without elevation when ``mayOverlap`` is True
-    :rtype: MosaicMapping
+    ``statistic`` names what a cell holds: ``'mean'`` (the default), ``'median'`` (``np.median`` as :func:`resampleMedian`
+    computes it) or ``'quantile'`` (``np.quantile(..., q)`` as :func:`resampleQuantile`) — over every member's pixels in the
+    cell (mayOverlap False), or over the winning member's pixels alone (True; the winner is the mean mosaic's).  A cell that a
+    pass of frames or a network of cameras sees many times keeps its median when one star, one city light or one saturated frame
+    moves its mean.  With ``'quantile'`` a number `q` gives one mapping, a sequence of 1 to 8 a list with one mapping per `q`
+    from ONE device call (:func:`resampleQuantile`'s convention).
+
+    :param str statistic: 'mean' | 'median' | 'quantile'
+    :param None|number|sequence q: the quantile(s), for statistic='quantile' only
+    :raises ValueError: for an unknown statistic, `q` with 'mean' or 'median', 'quantile' without `q` (all before the
+                        collection is looked at); for an empty collection, members of different altitudes or image dtypes /
+                        channel counts, and a member without elevation when ``mayOverlap`` is True
+    :rtype: MosaicMapping, or a list of them
     """
-    res = mosaic_frames(collection, pxPerDeg, arcsecPerPx, containsPole)
-    return _mosaic_mapping(collection, res)
+    qs = mosaic_statistic(statistic, q)
+    res = mosaic_frames(collection, pxPerDeg, arcsecPerPx, containsPole, statistic=statistic, q=qs)
+    if statistic == 'mean':
+        return _mosaic_mapping(collection, res)
+    if statistic == 'median':
+        return _mosaic_mapping(collection, res, res['median'], res['img'])
+    out = [_mosaic_mapping(collection, res, res['quantile'][j], res['img'][j]) for j in range(len(qs))]
+    return out[0] if np.ndim(q) == 0 else out
 
 
 def resampleMosaicMLatMLT(collection, **kw):
     """:func:`resampleMosaic` such that MLat/MLT become regular grids: the members converted to SM coordinates
     (``convertMappingToSM``), the mosaic, and back (``convertSMMappingToGeo``), as :func:`resampleMedianMLatMLT` does.
 
-    See :func:`resampleMosaic` for parameters.
+    See :func:`resampleMosaic` for parameters; a list result (several quantiles) is mapped element by element.
     """
     from .mapping.mapping import MosaicMapping
+    mosaic_statistic(kw.get('statistic', 'mean'), kw.get('q'))
     sm = MappingCollection([convertMappingToSM(m) for m in collection.mappings], collection.identifier,
                            mayOverlap=collection.mayOverlap)
+
+    def toGeo(mosaic):
+        geo = convertSMMappingToGeo(mosaic)
+        return MosaicMapping(geo.lats, geo.lons, geo.latsCenter, geo.lonsCenter, geo.elevation, geo.altitude, geo.img,
+                             geo.cameraPosGCRS, geo.photoTime, geo.identifier, mosaic.source, mosaic.members)
+
     mosaic = resampleMosaic(sm, **kw)
-    geo = convertSMMappingToGeo(mosaic)
-    return MosaicMapping(geo.lats, geo.lons, geo.latsCenter, geo.lonsCenter, geo.elevation, geo.altitude, geo.img,
-                         geo.cameraPosGCRS, geo.photoTime, geo.identifier, mosaic.source, mosaic.members)
+    return [toGeo(m) for m in mosaic] if isinstance(mosaic, list) else toGeo(mosaic)
 
 
-def _mosaic_mapping(collection, res):
+def _mosaic_mapping(collection, res, planes=None, image=None):
+    """The MosaicMapping of a mosaic_frames result; planes (ny,nx,C+1) / image (ny,nx,C): the statistic's, default the mean's."""
     from .mapping.mapping import MosaicMapping
     members = collection.mappings
-    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    elevation = ma.masked_invalid(res['mean'][:, :, -1], copy=False) if res['has_elev'] else None
+    planes = res['mean'] if planes is None else planes
+    image = res['img'] if image is None else image
+    img = ma.masked_array(image, mask=np.repeat(res['mask'][:, :, None], image.shape[2], 2))
+    elevation = ma.masked_invalid(planes[:, :, -1], copy=False) if res['has_elev'] else None
     source = ma.masked_array(res['source'], mask=res['source'] < 0)
     photoTime = collection.photoTime
     first = next(m for m in members if m.photoTime == photoTime)
@@ -444,13 +485,17 @@ def mosaic_layout(memberBoxes, pxPerDeg=25, arcsecPerPx=None, poleBoxes=None):
     return dict(grid=grid, pole=poleBoxes is not None, discontinuity=disc, lon_wrap=lon_wrap, boxes=boxes, windows=windows)
 
 
-def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
-    """The mosaic of a collection's device frames on the common grid (``amt_mosaic_frames``): see :func:`resampleMosaic`.
+def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, statistic='mean', q=None):
+    """The mosaic of a collection's device frames on the common grid (``amt_mosaic_frames``; ``amt_mosaic_median_frames`` /
+    ``amt_mosaic_quantile_frames`` for the other statistics): see :func:`resampleMosaic`.
 
     :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mean (ny,nx,C+1), img (ny,nx,C), mask (ny,nx),
-                  count (ny,nx), source (ny,nx) int32 [-1: empty], has_elev, plan)
+                  count (ny,nx), source (ny,nx) int32 [-1: empty], has_elev, plan); with statistic='median' ``median`` in place
+                  of ``mean``, with 'quantile' ``quantile`` (nq,ny,nx,C+1) and img (nq,ny,nx,C), as
+                  :func:`resample_frame_median` / :func:`resample_frame_quantile` return them, and ``q``
     """
     import torch
+    qs = mosaic_statistic(statistic, q)
     plan = mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole)
     grid, frames, altitude = plan['grid'], plan['frames'], plan['altitude']
     ctx = frames[0].ctx
@@ -470,21 +515,30 @@ def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
         t.height, t.width = fd.height, fd.width
         t.win_x0, t.win_y0, t.win_nx, t.win_ny = x0, y0, wnx, wny
     xaxis, yaxis = grid.axes(ctx)
-    mean = ctx.empty((grid.ny, grid.nx, nch + 1))
-    img = ctx.empty((grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd0.img_dtype_code != 2 else torch.int16)
+    lead = (len(qs),) if qs else ()
+    mean = ctx.empty(lead + (grid.ny, grid.nx, nch + 1))
+    img = ctx.empty(lead + (grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd0.img_dtype_code != 2 else torch.int16)
     mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
     count = ctx.empty((grid.ny, grid.nx))
     source = ctx.empty((grid.ny, grid.nx), torch.int32)
     if not nch:
         img.zero_()
-    ctx.call('amt_mosaic_frames', table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'), C.byref(xaxis),
-             C.byref(yaxis), plan['lon_wrap'], plan['rule'], ptr(mean), ptr(img) if nch else None, ptr(mask), ptr(count),
-             ptr(source))
+    head = [table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'), C.byref(xaxis), C.byref(yaxis), plan['lon_wrap'],
+            plan['rule']]
+    tail = [ptr(mean), ptr(img) if nch else None, ptr(mask), ptr(count), ptr(source)]
+    if statistic == 'mean':
+        ctx.call('amt_mosaic_frames', *(head + tail))
+    elif statistic == 'median':
+        ctx.call('amt_mosaic_median_frames', *(head + tail))
+    else:
+        ctx.call('amt_mosaic_quantile_frames', *(head + [(C.c_double * len(qs))(*qs), len(qs)] + tail))
     has_elev = all(fd.elev is not None for fd in frames)
     out = dict(has_elev=has_elev, grid=grid, contains_pole=plan['pole'], contains_discontinuity=plan['discontinuity'],
                altitude=altitude, plan=plan)
+    if qs:
+        out.update(q=qs)
     out.update(grid_coordinates(out))
-    out.update(mean=to_host(mean), img=to_host(img, dtype=fd0.img_dtype if nch else np.uint8),
+    out.update({statistic: to_host(mean)}, img=to_host(img, dtype=fd0.img_dtype if nch else np.uint8),
                mask=to_host(mask).astype(bool), count=to_host(count), source=to_host(source, dtype=np.int32))
     del keep                     # (after the read-back above: the kernels are done with them)
     return out

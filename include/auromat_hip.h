@@ -577,6 +577,30 @@ typedef struct amt_mosaic_member {
 int amt_mosaic_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype, int32_t nchan,
                       double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, int32_t rule,
                       double* mean, void* out_img, uint8_t* out_mask, double* out_count, int32_t* out_source);
+/* Median and quantile mosaics (additions to ABI v10; auromat_amd.resample.resampleMosaic(statistic='median' | 'quantile')):
+ * amt_mosaic_frames' member table, cells, windows and rules with amt_median_frame's / amt_quantile_frame's statistic in place of
+ * the mean.  A pixel of member i belongs to cell c when amt_median_frame on the common axes would put it into c and c lies in
+ * the member's window.
+ *   rule 0: every plane (image channels, elevation) is the statistic over the union of all members' pixels in the cell;
+ *     out_count: the union's count; out_source (may be NULL): the lowest member index present;
+ *   rule 1: the member amt_mosaic_frames elects (highest mean elevation as amt_bin_frame_finalize computes it, the lower index
+ *     on a tie) takes the cell whole: every plane is the statistic over that member's pixels alone; out_count, out_mask and
+ *     out_source are bit for bit those of amt_mosaic_frames on the same arguments.  Every member needs `elev`.
+ * The elevation plane is NaN unless every member has `elev`.  Outputs as for amt_median_frame / amt_quantile_frame (median
+ * (ny, nx, nchan+1), or quantile (nq, ny, nx, nchan+1) and out_img (nq, ny, nx, nchan)) plus out_source int32 (ny, nx), -1 where
+ * empty.  Results are order statistics: two runs, and the members in any order, give the same bits (except out_source, and
+ * exact ties of rule 1).  The members' pixels together must stay below 2^31 (AMT_EINVAL otherwise).  One count and one fill
+ * launch whatever n_members is; synchronises once, as amt_median_frame does.  The quantile form checks q / nq before anything
+ * else, as amt_quantile_frame does.  Workspace: amt_median_frame's for the members' pixels together, 4 bytes per cell, and for
+ * rule 1 amt_mosaic_frames' accumulators. */
+int amt_mosaic_median_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                             int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                             int32_t rule, double* median, void* out_img, uint8_t* out_mask, double* out_count,
+                             int32_t* out_source);
+int amt_mosaic_quantile_frames(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                               int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                               int32_t rule, const double* q, int nq, double* quantile, void* out_img, uint8_t* out_mask,
+                               double* out_count, int32_t* out_source);
 /* Same for float accumulators of amt_hist2d_accumulate: mean[k] = sums[k]/count, NaN where empty,
  * transposed + flipped to (ny, nx, nweights). */
 int amt_hist2d_finalize_mean(amt_ctx* ctx, const double* count, const double* const* sums, int32_t nweights,

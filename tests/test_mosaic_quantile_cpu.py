@@ -1,0 +1,210 @@
+"""
+Median and quantile mosaics without a GPU: the constructed cases of tests/_mosaic_quantile_cases.py keep their promises, the
+oracle of tests/_mosaic_quantile_oracle.py (a literal np.median / np.quantile per cell) equals its restatement through
+``_quantile_oracle.quantile_bins`` / ``_median_oracle.median_bins`` on the concatenated, filtered pixels bit for bit, the
+keyword checks of ``resampleMosaic(statistic=, q=)`` raise before the collection is looked at, and the two entry points are
+declared in the header and in ``_native._SIGNATURES``.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import _bin_cases as K
+import _bin_oracle as B
+import _median_cases as MC
+import _mosaic_quantile_cases as X
+import _mosaic_quantile_oracle as OR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+QS = (0.0, 1.0, 0.5, 0.25, 0.75, 1.0 / 3.0, 0.999, 1e-9)
+U8_U16 = pytest.mark.parametrize('dtype', [np.uint8, np.uint16], ids=['uint8', 'uint16'])
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype.kind == 'f' else a
+
+
+def same(a, b, what):
+    for key in a:
+        assert a[key].shape == b[key].shape and a[key].dtype == b[key].dtype, (what, key)
+        assert np.array_equal(_bits(a[key]), _bits(b[key])), (what, key)
+
+
+def counts_per_member(mosaic, rule):
+    """(members, ny, nx) pixels of every member that count in every cell"""
+    flats, mean = OR.member_flats(mosaic, rule)
+    ny, nx = mosaic.shape
+    return np.array([np.bincount(f[f >= 0], minlength=nx * ny).reshape(ny, nx) for f in flats]), mean
+
+
+# ---- the constants the cases are built on --------------------------------------------------------------------------------------
+def test_constants_are_the_sources():
+    import re
+    src = open(os.path.join(ROOT, 'auromat_amd', 'csrc', 'amt_median.hip')).read()
+    value = lambda name: int(re.search(r'constexpr int %s = (\d+);' % name, src).group(1))
+    assert value('kPPT') == X.K_PPT and value('kBlock') == MC.K_BLOCK
+    assert value('kSmallMax') == MC.K_SMALL_MAX and value('kLargeMin') == MC.K_LARGE_MIN
+    assert X.WORKGROUP_PIXELS == 1024
+
+
+# ---- promises ----------------------------------------------------------------------------------------------------------------
+@U8_U16
+def test_union_tiers_promises(dtype):
+    m = X.union_tiers(dtype)
+    per, mean = counts_per_member(m, 0)
+    total = per.sum(0)
+    # rows north to south: family f is output row ny - 1 - f; every row holds TOTALS
+    assert all(total[r].tolist() == list(X.TOTALS) for r in range(len(X.FAMILIES)))
+    assert np.array_equal(total, mean['count'])
+    # two or three members per cell beyond one pixel, and wherever the union reaches a higher tier no member reaches it alone
+    fed = (per > 0).sum(0)
+    assert ((fed >= 2) | (total < 2)).all() and (fed == 3).any() and (fed == 2).any()
+    for t in (MC.K_SMALL_MAX + 1, MC.K_SMALL_MAX + 2, MC.K_LARGE_MIN + 1, MC.K_LARGE_MIN + 2):
+        col = X.TOTALS.index(t)
+        assert (MC.tier_of(per[:, :, col]) < MC.tier_of(t)).all(), t
+    assert X.split(64) == (32, 32, 0) and X.split(65) == (32, 33, 0)
+    assert X.split(16384) == (8192, 8192, 0) and X.split(16385) == (8192, 8193, 0)
+    assert set(MC.tier_of(np.array(X.TOTALS)).tolist()) == {0, 1, 2}
+    # the value families, from the oracle's side: all-equal cells, equal and differing middle pairs, the digit carry, -0.0
+    want = OR.expected(m, 0)
+    ny = len(X.FAMILIES)
+    flats, _ = OR.member_flats(m, 0)
+    flat, v = np.concatenate(flats), OR.values(m)
+    row = lambda f: ny - 1 - f
+    for col in range(len(X.TOTALS)):
+        mine = v[flat == row(0) * len(X.TOTALS) + col]
+        assert (mine == mine[0]).all()
+    _, n, lo, hi = MC.middle_pairs(flat, v[:, 0])
+    even = n % 2 == 0
+    assert (even & (lo == hi)).any() and (even & (lo != hi)).any()
+    carry = 0x10 if np.dtype(dtype) == np.uint8 else 0x100
+    assert (even & (lo == carry - 1) & (hi == carry)).any()
+    zero = v[(flat >= row(3) * len(X.TOTALS)) & (flat < (row(3) + 1) * len(X.TOTALS)), -1]
+    assert ((zero == 0) & np.signbit(zero)).any() and (zero < 0).any() and (zero > 0).any()
+    assert not ((zero == 0) & ~np.signbit(zero)).any()
+    med = want['stat'][0, row(3), :, -1]
+    assert (med == 0).any()
+
+
+@U8_U16
+def test_winner_tiers_promises(dtype):
+    m = X.winner_tiers(dtype)
+    per1, mean1 = counts_per_member(m, 1)
+    per0, mean0 = counts_per_member(m, 0)
+    p = m.promises()
+    assert mean1['source'][0].tolist() == list(p['winners'])
+    assert per0[:, 0, :].T.tolist() == [list(s) for s in p['shares']]
+    union, winner = per0.sum(0)[0], per1.sum(0)[0]
+    assert winner[0] == 40 and union[0] == 70 and MC.tier_of(40) == 0 and MC.tier_of(70) == 1
+    assert winner[1] == MC.K_LARGE_MIN + 1 and union[1] == MC.K_LARGE_MIN + 101
+    assert winner[2] == 1 and union[2] == MC.K_LARGE_MIN + 2
+    assert (MC.tier_of(winner) != MC.tier_of(union)).sum() >= 3
+    # the election is exact: every elevation is a multiple of 2**-32, and the last cell is a tie of members 0 and 1
+    for c in m.members:
+        e = c.elev[~np.isnan(c.elev)] * 2.0 ** 32
+        assert np.array_equal(e, np.rint(e))
+    own = mean1['members']
+    assert own[0]['fx'][0, -1] == own[1]['fx'][0, -1] and own[0]['count'][0, -1] == own[1]['count'][0, -1]
+
+
+@U8_U16
+def test_seams_promises(dtype):
+    m = X.seams(dtype)
+    sizes = [c.height * c.width for c in m.members]
+    assert sizes == [n for n, _ in X.SEAM_MEMBERS] and all(c.height == 1 for c in m.members)
+    whole = [n for n, kind in X.SEAM_MEMBERS if kind == 'whole']
+    assert whole == [1, 3, 255, 257, 1023, 1025] and all(n % 2 == 1 and n % 4 for n in whole)
+    assert whole[-2] < X.WORKGROUP_PIXELS < whole[-1]
+    assert m.windows[0] == (0, 0, 0, 0) and m.windows[4] == (0, 0, 0, 0) and X.SEAM_MEMBERS[4][1] == 'empty'
+    per, mean = counts_per_member(m, 0)
+    kinds = [k for _, k in X.SEAM_MEMBERS]
+    for i, kind in enumerate(kinds):
+        assert (per[i].sum() == sizes[i]) == (kind == 'whole'), i
+        if kind != 'whole':
+            assert per[i].sum() == 0
+    # the last pixel of a member and the first pixel of the next member with pixels share a cell
+    flats, _ = OR.member_flats(m, 0)
+    live = [f for f, kind in zip(flats, kinds) if kind == 'whole']
+    shared = sum(int(a[-1] == b[0]) for a, b in zip(live[:-1], live[1:]))
+    assert shared == len(live) - 1, shared
+    assert B.cells(m.members[7], None).min() >= 0 and per[7].sum() == 0      # in the grid, outside the window
+
+
+# ---- the oracle and its restatement ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('rule', [0, 1])
+@U8_U16
+@pytest.mark.parametrize('make', [X.union_tiers, X.winner_tiers, X.seams], ids=['union', 'winner', 'seams'])
+def test_oracle_equals_restatement_on_constructed_cases(make, dtype, rule):
+    m = make(dtype)
+    mean = B.mosaic(m.members, m.windows, rule)
+    same(OR.expected(m, rule, QS, mean), OR.restated(m, rule, QS, mean), (m.name, rule, 'quantiles'))
+    same(OR.expected(m, rule, None, mean), OR.restated(m, rule, None, mean), (m.name, rule, 'median'))
+
+
+@pytest.mark.parametrize('rule', [0, 1])
+@pytest.mark.parametrize('name', sorted(K.MOSAIC_CASES))
+def test_oracle_equals_restatement_on_the_mosaic_cases(name, rule):
+    for dtype, nch, thr in ((np.uint8, 3, -np.inf), (np.uint16, 0, 'threshold')):
+        if thr == 'threshold':
+            thr = K.TIES_THRESHOLD if name == 'ties' else 0.0
+        m = K.MOSAIC_CASES[name](dtype, nch, thr)
+        mean = B.mosaic(m.members, m.windows, rule)
+        same(OR.expected(m, rule, QS, mean), OR.restated(m, rule, QS, mean), (m.name, rule))
+        same(OR.expected(m, rule, None, mean), OR.restated(m, rule, None, mean), (m.name, rule, 'median'))
+
+
+def test_rule_1_keeps_the_winner_alone():
+    m = K.mosaic_ties(np.uint8, 1)
+    want = OR.expected(m, 1, (0.0, 1.0))
+    assert want['source'].tolist() == [list(K.TIES_WINNERS)]
+    for col, w in enumerate(K.TIES_WINNERS):
+        c = m.members[w]
+        mine = c.img[B.cells(c, m.windows[w]) == col, 0]
+        assert want['stat'][0, 0, col, 0] == mine.min() and want['stat'][1, 0, col, 0] == mine.max()
+        assert want['count'][0, col] == len(mine)
+
+
+# ---- the keywords ----------------------------------------------------------------------------------------------------------------
+class _Untouchable(object):
+    def __getattr__(self, name):
+        raise AssertionError('the collection was looked at (%s)' % name)
+
+
+@pytest.mark.parametrize('kw', [dict(statistic='mode'), dict(statistic=None), dict(q=0.5), dict(statistic='mean', q=0.5),
+                                dict(statistic='median', q=(0.25, 0.75)), dict(statistic='quantile'),
+                                dict(statistic='quantile', q=()), dict(statistic='quantile', q=[0.1] * 9),
+                                dict(statistic='quantile', q=1.5), dict(statistic='quantile', q=float('nan'))],
+                         ids=lambda kw: '-'.join('%s=%s' % i for i in sorted(kw.items())))
+def test_bad_keywords_raise_before_the_collection_is_looked_at(kw):
+    from auromat_amd import resample as R
+    for fn in (R.resampleMosaic, R.resampleMosaicMLatMLT, R.mosaic_frames):
+        with pytest.raises(ValueError):
+            fn(_Untouchable(), **kw)
+
+
+def test_keywords_default_to_the_mean():
+    import inspect
+    from auromat_amd import resample as R
+    for fn in (R.resampleMosaic, R.mosaic_frames):
+        p = inspect.signature(fn).parameters
+        assert p['statistic'].default == 'mean' and p['q'].default is None
+        assert list(p)[:4] == ['collection', 'pxPerDeg', 'arcsecPerPx', 'containsPole']
+    assert R.mosaic_statistic('mean', None) is None and R.mosaic_statistic('median', None) is None
+    assert R.mosaic_statistic('quantile', 0.25) == [0.25] and R.mosaic_statistic('quantile', (0, 1)) == [0.0, 1.0]
+
+
+# ---- the ABI -----------------------------------------------------------------------------------------------------------------------
+def test_entry_points_are_declared():
+    import ctypes as C
+    from auromat_amd import _native as N
+    header = open(os.path.join(ROOT, 'include', 'auromat_hip.h')).read()
+    sig = N._SIGNATURES
+    for name in ('amt_mosaic_median_frames', 'amt_mosaic_quantile_frames'):
+        assert name in sig and ('int %s(amt_ctx* ctx, const amt_mosaic_member* members' % name) in header
+        assert sig[name][1] is C.c_int
+    mean, med, quant = (sig[k][0] for k in ('amt_mosaic_frames', 'amt_mosaic_median_frames', 'amt_mosaic_quantile_frames'))
+    assert med == mean                                  # the member table, axes, lon_wrap, min_elevation, rule; five outputs
+    assert quant[:10] == mean[:10] and quant[12:] == mean[10:] and quant[10:12] == [N.c_double_p, C.c_int]
+    assert N.ABI_VERSION == 10 and '#define AMT_ABI_VERSION 10' in header
