@@ -248,6 +248,7 @@ _SIGNATURES = {
     'amt_run_push': ([_P, C.POINTER(RunFrame)], _I),
     'amt_run_end': ([_P, C.POINTER(C.c_int32)], _I),
     'amt_run_reset_hints': ([_P], _I),
+    'amt_run_fill_stats': ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _I),
     'amt_run_set_quantile': ([_P, _D], _I),
     'amt_seq_payload_size': ([C.POINTER(SeqFrame), C.c_int32, C.POINTER(_L)], _I),
     'amt_seq_pack': ([_P, C.POINTER(SeqFrame), C.c_int32, C.c_int32, _P, _L], _I),

@@ -81,8 +81,21 @@ int amt_georef_launch(amt_ctx* ctx, const amt_frame_params* p, const double* dir
                       const amt_georef_tail* tail);
 // n <= AMT_MAX_BATCH equally sized frames in ONE launch of the big kernel (falls back to n launches otherwise)
 #define AMT_MAX_BATCH 3
+// sky (optional, n entries): the sky rows of each frame that its arrays already hold as NaN and need not be written again
+// (amt_prm::sky_fill, amt_params.h).  In: rows [0, known_top_end) and [known_bottom_begin, number of rows) of work items hold
+// NaN in every output array of the frame (amt_prm::sky_known_empty(): none).  Out: the same two for the arrays as
+// the launch leaves them — the frame's own sky rows, amt_georef_sky_rows — and how many sky rows of work items it wrote and
+// left alone.  Without it every sky row is written.
+struct amt_sky_state {
+    int known_top_end, known_bottom_begin;
+    int bands_filled, bands_skipped;
+};
 int amt_georef_launch_many(amt_ctx* ctx, int n, const amt_frame_params* const* p, const amt_georef_out* const* out,
-                           const amt_georef_tail* const* tail);
+                           const amt_georef_tail* const* tail, amt_sky_state* sky = nullptr);
+// amt_pipe_launch_many_res (amt_pipe.hip) with the sky state of each frame's arrays, as above; the sequence runner's launch
+int amt_pipe_launch_many_sky(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, const amt_georef_out* const* out,
+                             const void* const* img, int32_t img_dtype, double min_elevation, const double* lat_px_per_deg,
+                             const double* lon_px_per_deg, int pole_in_view, int magnetic, amt_sky_state* sky);
 // the same with caller-supplied corner directions, one array per frame (all frames or none)
 int amt_georef_launch_many_dirs(amt_ctx* ctx, int n, const amt_frame_params* const* p, const double* const* dirs,
                                 const amt_georef_out* const* out, const amt_georef_tail* const* tail);

@@ -17,6 +17,7 @@
 // Algorithmic HBM bytes per frame: 16 B per corner + 24 B per pixel written, nothing read
 // ("WCS-fused" row of SURVEY.md §8d); with caller-supplied directions +24 B per corner read.
 #include "amt_common.h"
+#include "amt_params.h"
 
 namespace {
 
@@ -121,6 +122,9 @@ struct georef_args {
     // rows of work items that cannot see the shell (sky_bands(): rows [0, sky_top_end) and [sky_bottom_begin, n)); their
     // waves write NaN and cast no ray
     int sky_top_end, sky_bottom_begin;
+    // the part of those rows that is still to be written: [fill_top_begin, sky_top_end) and [sky_bottom_begin, fill_bottom_end);
+    // the rest already holds NaN (amt_prm::sky_fill; 0 and the number of rows: everything is written)
+    int fill_top_begin, fill_bottom_end;
     int bin_pole;                       // amt_georef_out.bin_pole: bin (and box) in the coordinates rotated by 90 deg about x
     int row_layout;                     // amt_georef_out.row_layout: 0 = contiguous rows, 1 = strip-padded rows
     pole_consts pole;
@@ -402,6 +406,9 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         // The rows of a whole row of items are one contiguous range of each array, so the strips_x waves of the row
         // share it as contiguous pieces written with 16-byte stores (the pattern of a plain fill: 6 TB/s where the
         // 504-byte runs of the row-marching pattern reach 5).
+        // Rows the arrays are known to hold NaN in already (the sequence runner: the frame this slot held before had them in
+        // its sky) are not written again; the box partial is.
+        const bool fill = (chunk >= A.fill_top_begin && chunk < A.sky_top_end) || (chunk >= A.sky_bottom_begin && chunk < A.fill_bottom_end);
         const int n_corner_rows = rows + (y0 + rows == A.height ? 1 : 0);           // the image's last corner row too
         auto fill_nan = [&](double* base, int64_t first, int64_t count) {
             if (base == nullptr) return;
@@ -421,12 +428,14 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         const int64_t cpitch = A.row_layout ? (int64_t)strips_x * 64 : W1, ppitch = A.row_layout ? (int64_t)strips_x * 64 : A.width;
         const int64_t c0 = (int64_t)y0 * cpitch, cn = (int64_t)n_corner_rows * cpitch;
         const int64_t p0 = (int64_t)y0 * ppitch, pn = (int64_t)rows * ppitch;
-        fill_nan(A.lat, c0, cn);
-        fill_nan(A.lon, c0, cn);
-        fill_nan(A.lat_c, p0, pn);
-        fill_nan(A.lon_c, p0, pn);
-        fill_nan(A.elev, p0, pn);
-        if (mag_out) {
+        if (fill) {
+            fill_nan(A.lat, c0, cn);
+            fill_nan(A.lon, c0, cn);
+            fill_nan(A.lat_c, p0, pn);
+            fill_nan(A.lon_c, p0, pn);
+            fill_nan(A.elev, p0, pn);
+        }
+        if (fill && mag_out) {
             fill_nan(A.mlat, c0, cn);
             fill_nan(A.mlt, c0, cn);
             fill_nan(A.mlat_c, p0, pn);
@@ -1423,8 +1432,10 @@ struct prepared_frame {
     int bin;
 };
 
+// sky (optional): what the frame's arrays already hold as NaN on entry, the frame's own sky rows and what was written of
+// them on return (amt_sky_state); without it every sky row is written
 int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, const amt_georef_out* out,
-                   const amt_georef_tail* tail, prepared_frame* F) {
+                   const amt_georef_tail* tail, prepared_frame* F, amt_sky_state* sky = nullptr) {
     AMT_REQUIRE(ctx, p && out, "NULL argument");
     AMT_REQUIRE(ctx, p->width > 0 && p->height > 0, "empty frame");
     AMT_REQUIRE(ctx, p->a > 0 && p->b > 0 && p->a0 > 0 && p->b0 > 0, "ellipsoid axes must be positive");
@@ -1518,6 +1529,16 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
     const launch_shape sh = shape_of(p);
     A.sky_top_end = 0, A.sky_bottom_begin = sh.chunks_y;
     if (dirs == nullptr) sky_bands(A, sh, &A.sky_top_end, &A.sky_bottom_begin);
+    {
+        amt_prm::sky_known known = amt_prm::sky_known_empty();
+        if (sky != nullptr) known.top_end = sky->known_top_end, known.bottom_begin = sky->known_bottom_begin;
+        known = amt_prm::sky_fill(known, sh.chunks_y, A.sky_top_end, A.sky_bottom_begin, &A.fill_top_begin, &A.fill_bottom_end);
+        if (sky != nullptr) {
+            sky->known_top_end = known.top_end, sky->known_bottom_begin = known.bottom_begin;
+            sky->bands_filled = (A.sky_top_end - A.fill_top_begin) + (A.fill_bottom_end - A.sky_bottom_begin);
+            sky->bands_skipped = A.sky_top_end + (sh.chunks_y - A.sky_bottom_begin) - sky->bands_filled;
+        }
+    }
     const int64_t n_items = sh.n_items;
     AMT_REQUIRE(ctx, n_items < (1ll << 31), "frame too large");
     // the row-marching kernel addresses its arrays with 32-bit byte offsets
@@ -1648,12 +1669,12 @@ int amt_georef_launch(amt_ctx* ctx, const amt_frame_params* p, const double* dir
 }
 
 int amt_georef_launch_many(amt_ctx* ctx, int n, const amt_frame_params* const* p, const amt_georef_out* const* out,
-                           const amt_georef_tail* const* tail) {
+                           const amt_georef_tail* const* tail, amt_sky_state* sky) {
     AMT_CHECK_CTX(ctx);
     AMT_REQUIRE(ctx, n >= 1 && n <= kMaxBatch && p && out && tail, "bad batch");
     prepared_frame F[kMaxBatch];
     for (int i = 0; i < n; ++i)
-        if (int rc = prepare_georef(ctx, p[i], nullptr, out[i], tail[i], &F[i])) return rc;
+        if (int rc = prepare_georef(ctx, p[i], nullptr, out[i], tail[i], &F[i], sky ? sky + i : nullptr)) return rc;
     return launch_prepared(ctx, n, F);
 }
 

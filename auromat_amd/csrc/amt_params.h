@@ -321,4 +321,26 @@ inline bool box_hint(const double* last_box, const amt_frame_params& last_p, lon
     return true;
 }
 
+// ---- sky rows a frame's arrays already hold as NaN ----------------------------------------------------------------------------
+// The big kernel writes NaN into the rows of work items ("bands", n of them) that cannot see the shell: the frame's sky,
+// [0, t) and [b, n).  A slot of the sequence runner takes a new frame every n_slots frames, and what its arrays hold then is
+// known: the sky of the frame before is NaN, everything else is data.  `known` says so as [0, top_end) and [bottom_begin, n); a
+// bottom_begin beyond n counts as n, so that "nothing known" has one form whatever the number of bands: sky_known_empty().
+struct sky_known {
+    int top_end, bottom_begin;
+};
+constexpr int kSkyNoBottom = 0x7fffffff;
+inline sky_known sky_known_empty() { return sky_known{0, kSkyNoBottom}; }
+
+// The one rule: which sky bands of a frame still have to be written, [*fill_top_begin, t) and [b, *fill_bottom_end), when
+// its arrays hold `known`; returns what they hold after the launch: the frame's own sky (every sky band NaN — written now or
+// before —, every other band data).  The two ranges may hold more than is needed (known bottom bands inside a growing top
+// range, say), never less: known plus filled covers the sky.  Nothing known gives the fill range (0, n): every sky band is written.
+inline sky_known sky_fill(const sky_known& known, int n, int t, int b, int* fill_top_begin, int* fill_bottom_end) {
+    const int kt = std::min(std::max(known.top_end, 0), n), kb = std::min(std::max(known.bottom_begin, 0), n);
+    *fill_top_begin = std::min(kt, t);
+    *fill_bottom_end = std::max(kb, b);
+    return sky_known{t, b};
+}
+
 }  // namespace amt_prm

@@ -382,6 +382,33 @@ int pipe_after_launch(amt_pipe* pipe) {
 
 }  // namespace
 
+// amt_pipe_launch_many_res with the sky state of each frame's arrays (amt_common.h); not part of the C ABI
+int amt_pipe_launch_many_sky(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, const amt_georef_out* const* out,
+                             const void* const* img, int32_t img_dtype, double min_elevation, const double* lat_px_per_deg,
+                             const double* lon_px_per_deg, int pole_in_view, int magnetic, amt_sky_state* sky) {
+    if (pipes == nullptr || n < 1 || pipes[0] == nullptr) return AMT_EINVAL;
+    amt_ctx* ctx = pipes[0]->ctx;
+    AMT_REQUIRE(ctx, n <= AMT_MAX_BATCH, "at most AMT_PIPE_MAX_BATCH frames per launch");
+    AMT_REQUIRE(ctx, p && out && img && lat_px_per_deg && lon_px_per_deg, "NULL argument");
+    amt_georef_out o[AMT_MAX_BATCH];
+    amt_georef_tail tails[AMT_MAX_BATCH];
+    const amt_georef_out* op[AMT_MAX_BATCH];
+    const amt_georef_tail* tp[AMT_MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        AMT_REQUIRE(ctx, pipes[i] != nullptr && pipes[i]->ctx == ctx, "drivers of one launch must share the context");
+        for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipes[i], "a driver can hold one frame of a launch");
+        if (int rc = pipe_prepare(pipes[i], p[i], out[i], img[i], img_dtype, min_elevation, lat_px_per_deg[i],
+                                  lon_px_per_deg[i], pole_in_view, magnetic, &o[i], &tails[i]))
+            return rc;
+        op[i] = &o[i];
+        tp[i] = &tails[i];
+    }
+    if (int rc = amt_georef_launch_many(ctx, n, p, op, tp, sky)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (int rc = pipe_after_launch(pipes[i])) return rc;
+    return AMT_OK;
+}
+
 extern "C" {
 
 int amt_pipe_coarse_hint(amt_pipe* pipe, const double* bbox, int magnetic) {
@@ -414,27 +441,9 @@ int amt_pipe_launch_many_res(amt_pipe* const* pipes, int32_t n, const amt_frame_
                              const amt_georef_out* const* out, const void* const* img, int32_t img_dtype,
                              double min_elevation, const double* lat_px_per_deg, const double* lon_px_per_deg,
                              int pole_in_view, int magnetic) {
-    if (pipes == nullptr || n < 1 || pipes[0] == nullptr) return AMT_EINVAL;
-    amt_ctx* ctx = pipes[0]->ctx;
-    AMT_REQUIRE(ctx, n <= AMT_MAX_BATCH, "at most AMT_PIPE_MAX_BATCH frames per launch");
-    AMT_REQUIRE(ctx, p && out && img && lat_px_per_deg && lon_px_per_deg, "NULL argument");
-    amt_georef_out o[AMT_MAX_BATCH];
-    amt_georef_tail tails[AMT_MAX_BATCH];
-    const amt_georef_out* op[AMT_MAX_BATCH];
-    const amt_georef_tail* tp[AMT_MAX_BATCH];
-    for (int i = 0; i < n; ++i) {
-        AMT_REQUIRE(ctx, pipes[i] != nullptr && pipes[i]->ctx == ctx, "drivers of one launch must share the context");
-        for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipes[i], "a driver can hold one frame of a launch");
-        if (int rc = pipe_prepare(pipes[i], p[i], out[i], img[i], img_dtype, min_elevation, lat_px_per_deg[i],
-                                  lon_px_per_deg[i], pole_in_view, magnetic, &o[i], &tails[i]))
-            return rc;
-        op[i] = &o[i];
-        tp[i] = &tails[i];
-    }
-    if (int rc = amt_georef_launch_many(ctx, n, p, op, tp)) return rc;
-    for (int i = 0; i < n; ++i)
-        if (int rc = pipe_after_launch(pipes[i])) return rc;
-    return AMT_OK;
+    // (nothing is known about what the caller's arrays hold: every sky row is written)
+    return amt_pipe_launch_many_sky(pipes, n, p, out, img, img_dtype, min_elevation, lat_px_per_deg, lon_px_per_deg, pole_in_view,
+                                    magnetic, nullptr);
 }
 
 int amt_pipe_launch_dirs(amt_pipe* pipe, const amt_frame_params* p, const double* corner_dirs, const amt_georef_out* out,

@@ -1,6 +1,7 @@
 // Native sequence runner (include/auromat_hip.h, "native sequence runner"): the per-frame host loop of a sequence —
 // host scalars, box hints, launches, waits, grid layouts, finalise kernels — in one C call.  Host orchestration only;
-// it drives the single-pass frame drivers of amt_pipe.hip through their public entry points.
+// it drives the single-pass frame drivers of amt_pipe.hip through their public entry points and, for the launches, through
+// amt_pipe_launch_many_sky (amt_common.h: amt_pipe_launch_many_res with the sky state of each frame's slot).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -54,6 +55,15 @@ struct amt_run {
     std::vector<char> upload_pending, img_busy;
     std::vector<int64_t> uploaded_bytes;
     hipStream_t copy_stream;
+    // Sky rows of work items that a slot's arrays already hold as NaN (amt_prm::sky_fill): [0, known_top_end) and
+    // [known_bottom_begin, n), the sky of the frame the slot held before.  The launch of the slot's next frame does not write
+    // them again.  Valid only inside one call, begin ... end, while the runner is the only writer of the slots' arrays — a caller
+    // may do what it likes with them between calls —, kept per slot index and nowhere else; forgotten (forget_sky) when a call
+    // begins, when a push or the end of a call fails, and when the context's stream changes under the call: the big kernels of
+    // all frames, retries included, go on that one stream, and its order is what makes a slot's previous writer finished.
+    std::vector<int> known_top_end, known_bottom_begin;
+    hipStream_t launch_stream;
+    int64_t bands_filled, bands_skipped;    // amt_run_fill_stats: since the last amt_run_begin
 };
 
 namespace {
@@ -62,6 +72,13 @@ namespace {
 bool box_hint(const amt_run* run, long long k, const amt_frame_params& p, double* est) {
     const amt_run::hint &last = run->last, &prev = run->prev;
     return last.valid && amt_prm::box_hint(last.box, last.p, last.index, prev.valid ? prev.box : nullptr, &prev.p, prev.index, k, p, est);
+}
+
+// nothing is known about what the slots' arrays hold: the next frame of every slot writes all of its sky rows
+void forget_sky(amt_run* run) {
+    const amt_prm::sky_known none = amt_prm::sky_known_empty();
+    std::fill(run->known_top_end.begin(), run->known_top_end.end(), none.top_end);
+    std::fill(run->known_bottom_begin.begin(), run->known_bottom_begin.end(), none.bottom_begin);
 }
 
 int64_t image_bytes(const amt_run* run, int64_t cells) {
@@ -126,6 +143,10 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     run->img_busy.assign(ns, 0);
     run->uploaded_bytes.assign(ns, 0);
     run->copy_stream = nullptr;
+    run->known_top_end.assign(ns, amt_prm::sky_known_empty().top_end);
+    run->known_bottom_begin.assign(ns, amt_prm::sky_known_empty().bottom_begin);
+    run->launch_stream = nullptr;
+    run->bands_filled = run->bands_skipped = 0;
     run->active = run->full = false;
     run->n_launched = 0, run->batch_count = 0, run->n_boxed = 0;
     run->pipes.assign(ns, nullptr);
@@ -176,6 +197,13 @@ int amt_run_set_quantile(amt_run* run, double q) {
     AMT_REQUIRE(ctx, q >= 0.0 && q <= 1.0, "the quantile must lie in [0, 1]");
     run->has_quantile = true;
     run->quantile = q;
+    return AMT_OK;
+}
+
+int amt_run_fill_stats(amt_run* run, int64_t* bands_filled, int64_t* bands_skipped) {
+    if (run == nullptr) return AMT_EINVAL;
+    if (bands_filled) *bands_filled = run->bands_filled;
+    if (bands_skipped) *bands_skipped = run->bands_skipped;
     return AMT_OK;
 }
 
@@ -247,9 +275,16 @@ int run_finish(amt_run* run, int k0, int count) {
             const int mag = cfg.magnetic ? 1 : 0;
             run->outs[slot].altitude = run->alt[slot];
             if (int rc = amt_pipe_coarse_hint(run->pipes[slot], pr.bbox, mag)) return rc;
-            if (int rc = amt_pipe_launch(run->pipes[slot], &run->prm[slot], &run->outs[slot], run->img[slot], cfg.img_dtype,
-                                         cfg.min_elevation, run->ppd_lat[slot], run->ppd_lon[slot], -1, mag))
+            // (it writes every sky row again — nothing known —, and the slot then holds this frame's sky)
+            const amt_frame_params* rp = &run->prm[slot];
+            const amt_georef_out* ro = &run->outs[slot];
+            amt_sky_state sky = {amt_prm::sky_known_empty().top_end, amt_prm::sky_known_empty().bottom_begin, 0, 0};
+            if (ctx->stream != run->launch_stream) forget_sky(run), run->launch_stream = ctx->stream;
+            if (int rc = amt_pipe_launch_many_sky(&run->pipes[slot], 1, &rp, &ro, &run->img[slot], cfg.img_dtype, cfg.min_elevation,
+                                                  &run->ppd_lat[slot], &run->ppd_lon[slot], -1, mag, &sky))
                 return rc;
+            run->known_top_end[slot] = sky.known_top_end, run->known_bottom_begin[slot] = sky.known_bottom_begin;
+            run->bands_filled += sky.bands_filled, run->bands_skipped += sky.bands_skipped;
             if (int rc = amt_pipe_wait(run->pipes[slot], &pr)) return rc;
             r.retried = 1;
         }
@@ -342,6 +377,10 @@ int run_launch(amt_run* run, int k0, int count) {
     const amt_georef_out* oo[AMT_PIPE_MAX_BATCH];
     const void* ii[AMT_PIPE_MAX_BATCH];
     double la[AMT_PIPE_MAX_BATCH], lo[AMT_PIPE_MAX_BATCH];
+    amt_sky_state sky[AMT_PIPE_MAX_BATCH];
+    int slots[AMT_PIPE_MAX_BATCH];
+    // what the slots hold is known as long as every launch goes on one stream (amt_run.known_top_end)
+    if (ctx->stream != run->launch_stream) forget_sky(run), run->launch_stream = ctx->stream;
     // the frames of the batch that are launched (box-first plan: not those without a valid pixel or with a pole in view),
     // as runs of consecutive frames
     int i = 0;
@@ -356,6 +395,9 @@ int run_launch(amt_run* run, int k0, int count) {
             run->outs[slot].altitude = run->alt[slot];
             pp[m] = run->pipes[slot], prm[m] = &run->prm[slot], oo[m] = &run->outs[slot], ii[m] = run->img[slot];
             la[m] = run->ppd_lat[slot], lo[m] = run->ppd_lon[slot];
+            slots[m] = slot;
+            sky[m].known_top_end = run->known_top_end[slot], sky[m].known_bottom_begin = run->known_bottom_begin[slot];
+            sky[m].bands_filled = sky[m].bands_skipped = 0;
             if (ii[m] == nullptr) {
                 ctx->last_error = "amt_run: a frame has no image";
                 return AMT_EINVAL;
@@ -367,8 +409,13 @@ int run_launch(amt_run* run, int k0, int count) {
             }
             ++m, ++i;
         }
-        if (int rc = amt_pipe_launch_many_res(pp, m, prm, oo, ii, cfg.img_dtype, cfg.min_elevation, la, lo, -1, cfg.magnetic ? 1 : 0))
+        // each frame's launch leaves the sky rows alone that its slot holds as NaN already and says which the slot holds now
+        if (int rc = amt_pipe_launch_many_sky(pp, m, prm, oo, ii, cfg.img_dtype, cfg.min_elevation, la, lo, -1, cfg.magnetic ? 1 : 0, sky))
             return rc;
+        for (int j = 0; j < m; ++j) {
+            run->known_top_end[slots[j]] = sky[j].known_top_end, run->known_bottom_begin[slots[j]] = sky[j].known_bottom_begin;
+            run->bands_filled += sky[j].bands_filled, run->bands_skipped += sky[j].bands_skipped;
+        }
     }
     return AMT_OK;
 }
@@ -504,6 +551,9 @@ int amt_run_begin(amt_run* run, double* grids, int64_t grids_capacity, void* ima
     run->grid_used = run->image_used = 0;
     run->full = false;
     run->n_pushed = 0, run->batch_k0 = 0, run->batch_count = 0, run->n_launched = 0, run->n_boxed = 0;
+    forget_sky(run);                                // whatever the caller did with the slots' arrays since the last call
+    run->launch_stream = ctx->stream;
+    run->bands_filled = run->bands_skipped = 0;
     run->active = true;
     return AMT_OK;
 }
@@ -553,6 +603,8 @@ int amt_run_push(amt_run* run, const amt_run_frame* f) {
     const int rc = run_push_impl(run, f);
     //  a failed push leaves no hints behind whose indices refer to frames that were never counted
     if (rc != AMT_OK) run->last.valid = run->prev.valid = false;
+    // a launch or a wait failed somewhere in the queue: what the slots hold is anybody's guess
+    if (rc != AMT_OK) forget_sky(run);
     return rc;
 }
 
@@ -653,6 +705,7 @@ int amt_run_end(amt_run* run, int32_t* frames_done) {
     if (rc_all != AMT_OK) {
         //  a failed call leaves no half-valid state behind: no hints, nothing counted
         run->last.valid = run->prev.valid = false;
+        forget_sky(run);
         if (frames_done) *frames_done = 0;
         return rc_all;
     }

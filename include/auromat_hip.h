@@ -960,6 +960,13 @@ int amt_run_begin(amt_run* run, double* grids, int64_t grids_capacity, void* ima
                   amt_run_result* results, int32_t max_frames);
 int amt_run_push(amt_run* run, const amt_run_frame* frame);
 int amt_run_end(amt_run* run, int32_t* frames_done);
+/* Sky rows: a frame's rows of work items that cannot see the shell (amt_georef_sky_rows) are NaN in every array of its slot.
+ * A slot takes a new frame every n_slots frames; the rows of the new frame's sky that the frame before left as NaN are not
+ * written again.  The runner knows what a slot holds only between amt_run_begin and amt_run_end of one call, while it is the
+ * only writer of the slots' arrays; every call begins knowing nothing, so the arrays are the caller's between calls.
+ * amt_run_fill_stats: sky rows of work items (per frame launched; a frame launched twice counts twice) that the launches since
+ * the last amt_run_begin wrote / left alone.  Either pointer may be NULL. */
+int amt_run_fill_stats(amt_run* run, int64_t* bands_filled, int64_t* bands_skipped);
 /* Forget the box hints (the next frame gets a coarse pre-pass). */
 int amt_run_reset_hints(amt_run* run);
 /* Quantile sequences: the median pass of a runner created with statistic = 1 becomes a one-quantile pass — the frames it covers
