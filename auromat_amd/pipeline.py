@@ -32,7 +32,8 @@ import numpy as np
 from .frame import FrameData, PaddedFrameData, has_array
 from .mapping.astrometry import frame_params, pole_in_view, run_frame
 from .mapping.mapping import bounding_box_from_reduction, grid_box_from_reduction
-from .resample import cached_grid, grid_coordinates, quantile_list, resample_frame, resample_frame_median, resample_frame_quantile
+from .resample import (_px_per_deg, cached_grid, grid_coordinates, quantile_list, resample_frame, resample_frame_median,
+                       resample_frame_quantile)
 from ._native import PIPE_MAX_EDGE_PIXELS, Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
 
 NEG_INF = float('-inf')
@@ -631,10 +632,7 @@ class FramePipeline(object):
         assert (q is not None) == (statistic == 'quantile'), "q goes with statistic='quantile'"
         if statistic == 'quantile':
             q = quantile_list(q)
-        try:
-            _, _ = pxPerDeg
-        except TypeError:
-            pxPerDeg = (pxPerDeg, pxPerDeg)
+        pxPerDeg = _px_per_deg(pxPerDeg)
         fd = self.fd
         Context.current(self.ctx.device)
         if statistic == 'mean' and self._fused is not None and self._fused['pxPerDeg'] == tuple(pxPerDeg) and \
@@ -734,10 +732,7 @@ class FramePipeline(object):
             if fuse and not red[7]:
                 self.start_coarse(params, min_elevation, magnetic, hint=red)
                 coarse_started = True
-        try:
-            _, _ = pxPerDeg
-        except TypeError:
-            pxPerDeg = (pxPerDeg, pxPerDeg)
+        pxPerDeg = _px_per_deg(pxPerDeg)
         self.georef(wcsHeader, altitude, cameraPosGCRS, photoTime, fast, min_elevation, params=params,
                     fuse_pxPerDeg=pxPerDeg if fuse else None, fuse_magnetic=bool(magnetic), coarse_started=coarse_started,
                     dirs=dirs, pole_in_view=-1 if containsPole is None else int(bool(containsPole)))
@@ -940,19 +935,14 @@ class SequencePipeline(object):
             assert plan == 'single-pass' and nchan == 3, "statistic='%s': RGB frames through the native runner" % statistic
             padded = False
             keep_coordinates = True
-        try:
-            _, _ = pxPerDeg
-        except TypeError:
-            pxPerDeg = (pxPerDeg, pxPerDeg)
-        self.pxPerDeg = tuple(pxPerDeg)
         # arcsecPerPx (has precedence over pxPerDeg, like the reference's resample(); what `auromat-convert --resample
         # --resolution R` passes, cli/convert.py:176-185): every frame's px/deg follows from its own bounding box
         # (plateCarreeResolution, resample.py:36-61) — the box-first plan: a box pass of the frame kernel two batches ahead of
         # the frame's single-pass launch, which takes the exact box as its estimate (process -> _process_box_first)
         self.arcsecPerPx = float(arcsecPerPx) if arcsecPerPx else None
+        self.pxPerDeg = None if self.arcsecPerPx else _px_per_deg(pxPerDeg)
         if self.arcsecPerPx:
             assert plan == 'single-pass' and nchan == 3, 'arcsecPerPx: the box-first plan is a single-pass plan (RGB images)'
-            self.pxPerDeg = None
         self.altitude, self.fast, self.min_elevation = altitude, fast, min_elevation
         self.single_pass = plan == 'single-pass' and nchan == 3
         self.nchan = nchan

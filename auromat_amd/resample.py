@@ -89,8 +89,7 @@ def resampleMLatMLT(mapping, **kw):
                     arcsecPerPx=arcsec)
         if res is not None:
             last_plan = res['plan']
-            img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-            elevation = ma.masked_invalid(res['mean'][:, :, -1], copy=False)
+            img, elevation = _masked_image_and_elevation(res['mask'], res['mean'], res['img'], True)
             # convertSMMappingToGeo (reference mapping.py:1549-1559) on the grid's arrays as they are: building the SM mapping
             # first would send the grid to the device and back through its properties, for the same numbers
             from .coordinates.transform import smToLatLon
@@ -119,6 +118,45 @@ def _px_per_deg(pxPerDeg):
     return tuple(pxPerDeg)
 
 
+def _min_elevation(min_elevation):
+    """The elevation threshold as the device calls take it: -inf for none."""
+    return float('-inf') if min_elevation is None else float(min_elevation)
+
+
+def _members(mappingOrCollection):
+    """``(mappings, rebuild)``: the mappings to work on, and what makes the result out of the list of theirs (the one result
+    for a mapping; for a collection a collection with its identifier and ``mayOverlap``).  ValueError for anything else."""
+    if isinstance(mappingOrCollection, BaseMapping):
+        return [mappingOrCollection], lambda done: done[0]
+    if isinstance(mappingOrCollection, MappingCollection):
+        # (the reference forgets the identifier here and raises TypeError, resample.py:151)
+        return mappingOrCollection.mappings, lambda done: MappingCollection(done, mappingOrCollection.identifier,
+                                                                           mayOverlap=mappingOrCollection.mayOverlap)
+    raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
+                     format(type(mappingOrCollection)))
+
+
+def _masked_image_and_elevation(mask, planes, image, has_elev):
+    """``(img, elevation)`` as the mapping classes take them: image (ny,nx,C) masked where `mask` (ny,nx) is set, and the
+    last plane of `planes` (ny,nx,C+1) masked where it is NaN (None without an elevation)."""
+    img = ma.masked_array(image, mask=np.repeat(mask[:, :, None], image.shape[2], 2))
+    elevation = ma.masked_invalid(planes[:, :, -1], copy=False) if has_elev else None
+    return img, elevation
+
+
+def _created(mapping, res, planes, image, has_elev):
+    """``mapping.createResampled`` on the grid of the frame result `res`, with its `planes` and `image` of one statistic."""
+    img, elevation = _masked_image_and_elevation(res['mask'], planes, image, has_elev)
+    return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
+
+
+def _pole_and_resolution(mapping, pxPerDeg, arcsecPerPx, containsPole):
+    """``(containsPole, (latPxPerDeg, lonPxPerDeg))``: the caller's word or the mapping's; `arcsecPerPx` before `pxPerDeg`."""
+    pole = mapping.containsPole if containsPole is None else containsPole
+    ppd = plateCarreeResolution(mapping.boundingBox, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+    return pole, ppd
+
+
 def resample(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, method='mean'):
     """
     Returns a new mapping (or collection) where the colors and elevation are resampled into a
@@ -144,7 +182,7 @@ def resample(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=No
     """
     _check_method(method)
 
-    def doResample(mapping, pxPerDeg, arcsecPerPx, containsPole):
+    def doResample(mapping):
         global last_plan
         last_plan = None
         fused = getattr(mapping, '_fused_resample', None)
@@ -155,35 +193,15 @@ def resample(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=No
             res = fused(None if arcsecPerPx else _px_per_deg(pxPerDeg), containsPole, arcsecPerPx=arcsecPerPx)
             if res is not None:
                 last_plan = res['plan']
-                img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-                elevation = ma.masked_invalid(res['mean'][:, :, -1], copy=False)
-                return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
-        if containsPole is None:
-            containsPole = mapping.containsPole
-        if arcsecPerPx:
-            pxPerDeg = plateCarreeResolution(mapping.boundingBox, arcsecPerPx)
-        else:
-            try:
-                _, _ = pxPerDeg
-            except TypeError:
-                assert pxPerDeg is not None
-                pxPerDeg = (pxPerDeg, pxPerDeg)
-        res = resample_frame(mapping.frame(), mapping.altitude, mapping.boundingBox, pxPerDeg,
-                             mapping.containsDiscontinuity, containsPole, method=method,
-                             outline=mapping.outline if (method != 'mean' or containsPole) else None)
-        img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-        elevation = ma.masked_invalid(res['mean'][:, :, -1], copy=False) if res['has_elev'] else None
-        return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
+                return _created(mapping, res, res['mean'], res['img'], True)
+        pole, ppd = _pole_and_resolution(mapping, pxPerDeg, arcsecPerPx, containsPole)
+        res = resample_frame(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd,
+                             mapping.containsDiscontinuity, pole, method=method,
+                             outline=mapping.outline if (method != 'mean' or pole) else None)
+        return _created(mapping, res, res['mean'], res['img'], res['has_elev'])
 
-    if isinstance(mappingOrCollection, BaseMapping):
-        return doResample(mappingOrCollection, pxPerDeg, arcsecPerPx, containsPole)
-    elif isinstance(mappingOrCollection, MappingCollection):
-        mappings = [doResample(m, pxPerDeg, arcsecPerPx, containsPole) for m in mappingOrCollection.mappings]
-        # (the reference forgets the identifier here and raises TypeError, resample.py:151)
-        return MappingCollection(mappings, mappingOrCollection.identifier,
-                                 mayOverlap=mappingOrCollection.mayOverlap)
-    raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
-                     format(type(mappingOrCollection)))
+    members, rebuild = _members(mappingOrCollection)
+    return rebuild([doResample(m) for m in members])
 
 
 def resampleMedian(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
@@ -208,21 +226,13 @@ def resampleMedian(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsP
     def doResample(mapping):
         global last_plan
         last_plan = None
-        pole = mapping.containsPole if containsPole is None else containsPole
-        ppd = plateCarreeResolution(mapping.boundingBox, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+        pole, ppd = _pole_and_resolution(mapping, pxPerDeg, arcsecPerPx, containsPole)
         res = resample_frame_median(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd,
                                     mapping.containsDiscontinuity, pole, outline=mapping.outline if pole else None)
-        img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-        elevation = ma.masked_invalid(res['median'][:, :, -1], copy=False) if res['has_elev'] else None
-        return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
+        return _created(mapping, res, res['median'], res['img'], res['has_elev'])
 
-    if isinstance(mappingOrCollection, BaseMapping):
-        return doResample(mappingOrCollection)
-    elif isinstance(mappingOrCollection, MappingCollection):
-        return MappingCollection([doResample(m) for m in mappingOrCollection.mappings], mappingOrCollection.identifier,
-                                 mayOverlap=mappingOrCollection.mayOverlap)
-    raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
-                     format(type(mappingOrCollection)))
+    members, rebuild = _members(mappingOrCollection)
+    return rebuild([doResample(m) for m in members])
 
 
 def resampleMedianMLatMLT(mapping, **kw):
@@ -272,26 +282,15 @@ def resampleQuantile(mappingOrCollection, q, pxPerDeg=25, arcsecPerPx=None, cont
     def doResample(mapping):
         global last_plan
         last_plan = None
-        pole = mapping.containsPole if containsPole is None else containsPole
-        ppd = plateCarreeResolution(mapping.boundingBox, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+        pole, ppd = _pole_and_resolution(mapping, pxPerDeg, arcsecPerPx, containsPole)
         res = resample_frame_quantile(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd, qs,
                                       mapping.containsDiscontinuity, pole, outline=mapping.outline if pole else None)
-        out = []
-        for j in range(len(qs)):
-            img = ma.masked_array(res['img'][j], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[3], 2))
-            elevation = ma.masked_invalid(res['quantile'][j, :, :, -1], copy=False) if res['has_elev'] else None
-            out.append(mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img))
-        return out
+        return [_created(mapping, res, res['quantile'][j], res['img'][j], res['has_elev']) for j in range(len(qs))]
 
-    if isinstance(mappingOrCollection, BaseMapping):
-        results = doResample(mappingOrCollection)
-    elif isinstance(mappingOrCollection, MappingCollection):
-        per_mapping = [doResample(m) for m in mappingOrCollection.mappings]
-        results = [MappingCollection([r[j] for r in per_mapping], mappingOrCollection.identifier,
-                                     mayOverlap=mappingOrCollection.mayOverlap) for j in range(len(qs))]
-    else:
-        raise ValueError('First argument must be a mapping or a mapping collection, but is: {}'.
-                         format(type(mappingOrCollection)))
+    members, rebuild = _members(mappingOrCollection)
+    per_mapping = [doResample(m) for m in members]
+    # one result per quantile: of a collection, one collection per quantile with every member's mapping for it
+    results = [rebuild([r[j] for r in per_mapping]) for j in range(len(qs))]
     return results[0] if np.ndim(q) == 0 else results
 
 
@@ -389,8 +388,7 @@ def _mosaic_mapping(collection, res, planes=None, image=None):
     members = collection.mappings
     planes = res['mean'] if planes is None else planes
     image = res['img'] if image is None else image
-    img = ma.masked_array(image, mask=np.repeat(res['mask'][:, :, None], image.shape[2], 2))
-    elevation = ma.masked_invalid(planes[:, :, -1], copy=False) if res['has_elev'] else None
+    img, elevation = _masked_image_and_elevation(res['mask'], planes, image, res['has_elev'])
     source = ma.masked_array(res['source'], mask=res['source'] < 0)
     photoTime = collection.photoTime
     first = next(m for m in members if m.photoTime == photoTime)
@@ -515,32 +513,90 @@ def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, 
         t.height, t.width = fd.height, fd.width
         t.win_x0, t.win_y0, t.win_nx, t.win_ny = x0, y0, wnx, wny
     xaxis, yaxis = grid.axes(ctx)
-    lead = (len(qs),) if qs else ()
-    mean = ctx.empty(lead + (grid.ny, grid.nx, nch + 1))
-    img = ctx.empty(lead + (grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd0.img_dtype_code != 2 else torch.int16)
-    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
-    count = ctx.empty((grid.ny, grid.nx))
+    planes, img, mask, count = _bin_outputs(ctx, grid, nch, fd0.img_dtype_code, (len(qs),) if qs else ())
     source = ctx.empty((grid.ny, grid.nx), torch.int32)
     if not nch:
         img.zero_()
     head = [table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'), C.byref(xaxis), C.byref(yaxis), plan['lon_wrap'],
             plan['rule']]
-    tail = [ptr(mean), ptr(img) if nch else None, ptr(mask), ptr(count), ptr(source)]
+    tail = [ptr(planes), ptr(img) if nch else None, ptr(mask), ptr(count), ptr(source)]
     if statistic == 'mean':
         ctx.call('amt_mosaic_frames', *(head + tail))
     elif statistic == 'median':
         ctx.call('amt_mosaic_median_frames', *(head + tail))
     else:
         ctx.call('amt_mosaic_quantile_frames', *(head + [(C.c_double * len(qs))(*qs), len(qs)] + tail))
-    has_elev = all(fd.elev is not None for fd in frames)
-    out = dict(has_elev=has_elev, grid=grid, contains_pole=plan['pole'], contains_discontinuity=plan['discontinuity'],
-               altitude=altitude, plan=plan)
+    out = _result(grid, plan['pole'], plan['discontinuity'], altitude, all(fd.elev is not None for fd in frames),
+                  {statistic: planes, 'img': img, 'mask': mask, 'count': count, 'source': source}, False,
+                  fd0.img_dtype if nch else None)
+    del keep                     # (after the read-back above: the kernels are done with them)
+    out.update(plan=plan)
     if qs:
         out.update(q=qs)
+    return out
+
+
+def _bin_outputs(ctx, grid, nch, img_dtype_code, lead=(), count=True):
+    """The device outputs of a binning call on `grid`, uninitialised: planes `lead` + (ny,nx,nch+1) float64, image `lead` +
+    (ny,nx,max(nch,1)) uint8 (int16 holding the bits of a uint16 image), mask (ny,nx) uint8 and count (ny,nx) float64 (None
+    with ``count=False``).  `lead`: ``()`` or ``(nq,)``, one set of planes and one image per quantile."""
+    import torch
+    planes = ctx.empty(lead + (grid.ny, grid.nx, nch + 1))
+    img = ctx.empty(lead + (grid.ny, grid.nx, max(nch, 1)), torch.uint8 if img_dtype_code != 2 else torch.int16)
+    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
+    return planes, img, mask, ctx.empty((grid.ny, grid.nx)) if count else None
+
+
+def _result(grid, contains_pole, contains_discontinuity, altitude, has_elev, tensors, keep_on_device, img_dtype=None):
+    """
+    The result dict of the frame-level functions: what describes the grid, and the outputs of the device calls.
+
+    :param tensors: dict name -> device tensor, in the order they are read back ('sweeps': a number, passed through)
+    :param keep_on_device: the tensors go into the result as they are and no grid coordinates are computed (sequence mode: the
+                           grid is described by `grid`, first centre + step; coordinate arrays on demand, :func:`grid_coordinates`)
+    :param img_dtype: NumPy dtype of the frame's image (None: no image, 'img' is read back as uint8)
+    :return: dict(has_elev, grid, contains_pole, contains_discontinuity, altitude) plus either the tensors or lat, lon, lat_c,
+             lon_c [grid coordinates] and the tensors as host arrays: 'img' as `img_dtype`, 'mask' as bool, 'source' as int32,
+             'index' and 'triangles' as int64, everything else as it is (float64)
+    """
+    out = dict(has_elev=has_elev, grid=grid, contains_pole=contains_pole, contains_discontinuity=contains_discontinuity,
+               altitude=altitude)
+    if keep_on_device:
+        out.update(tensors)
+        return out
     out.update(grid_coordinates(out))
-    out.update({statistic: to_host(mean)}, img=to_host(img, dtype=fd0.img_dtype if nch else np.uint8),
-               mask=to_host(mask).astype(bool), count=to_host(count), source=to_host(source, dtype=np.int32))
-    del keep                     # (after the read-back above: the kernels are done with them)
+    dtypes = dict(img=np.uint8 if img_dtype is None else img_dtype, source=np.int32, index=np.int64, triangles=np.int64)
+    for name, t in tensors.items():
+        if name == 'sweeps':
+            out[name] = t
+        elif name == 'mask':
+            out[name] = to_host(t).astype(bool)
+        else:
+            out[name] = to_host(t, dtype=dtypes.get(name))
+    return out
+
+
+def _resample_frame_ordered(fd, altitude, boundingBox, pxPerDeg, qs, containsDiscontinuity, containsPole, min_elevation,
+                            outline, keep_on_device):
+    """Median (`qs` None: ``amt_median_frame``) or quantile binning (`qs` a list of 1 .. 8 quantiles: ``amt_quantile_frame``,
+    with a leading axis over them on the planes and the image) of a device-resident frame: the body of
+    :func:`resample_frame_median` and :func:`resample_frame_quantile`."""
+    ctx = fd.ctx
+    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
+                                               min_elevation, outline, None)
+    xaxis, yaxis = grid.axes(ctx)
+    nch = fd.nchan
+    planes, img, mask, count = _bin_outputs(ctx, grid, nch, fd.img_dtype_code, (len(qs),) if qs else ())
+    quantiles = [(C.c_double * len(qs))(*qs), len(qs)] if qs else []
+    ctx.call('amt_quantile_frame' if qs else 'amt_median_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img),
+             fd.img_dtype_code or 1, nch, ptr(fd.center_mask), fd.height, fd.width, _min_elevation(min_elevation),
+             C.byref(xaxis), C.byref(yaxis), lon_wrap, *(quantiles + [ptr(planes), ptr(img) if nch else None, ptr(mask),
+                                                                      ptr(count)]))
+    out = _result(grid, bool(containsPole), bool(containsDiscontinuity), altitude, fd.elev is not None,
+                  {'quantile' if qs else 'median': planes, 'img': img, 'mask': mask, 'count': count}, keep_on_device,
+                  fd.img_dtype if nch else None)
+    if qs:
+        out.update(q=qs)
     return out
 
 
@@ -555,29 +611,8 @@ def resample_frame_median(fd, altitude, boundingBox, pxPerDeg, containsDiscontin
     :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], median (ny,nx,C+1), img (ny,nx,C), mask (ny,nx),
                   count (ny,nx), has_elev)
     """
-    import torch
-    ctx = fd.ctx
-    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
-                                               min_elevation, outline, None)
-    xaxis, yaxis = grid.axes(ctx)
-    nch = fd.nchan
-    median = ctx.empty((grid.ny, grid.nx, nch + 1))
-    img = ctx.empty((grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd.img_dtype_code != 2 else torch.int16)
-    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
-    count = ctx.empty((grid.ny, grid.nx))
-    min_el = float('-inf') if min_elevation is None else float(min_elevation)
-    ctx.call('amt_median_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code or 1, nch,
-             ptr(fd.center_mask), fd.height, fd.width, min_el, C.byref(xaxis), C.byref(yaxis), lon_wrap, ptr(median),
-             ptr(img) if nch else None, ptr(mask), ptr(count))
-    out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
-               contains_discontinuity=bool(containsDiscontinuity), altitude=altitude)
-    if keep_on_device:
-        out.update(median=median, img=img, mask=mask, count=count)
-        return out
-    out.update(grid_coordinates(out))
-    out.update(median=to_host(median), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
-               mask=to_host(mask).astype(bool), count=to_host(count))
-    return out
+    return _resample_frame_ordered(fd, altitude, boundingBox, pxPerDeg, None, containsDiscontinuity, containsPole,
+                                   min_elevation, outline, keep_on_device)
 
 
 def resample_frame_quantile(fd, altitude, boundingBox, pxPerDeg, q, containsDiscontinuity=False, containsPole=False,
@@ -588,33 +623,10 @@ def resample_frame_quantile(fd, altitude, boundingBox, pxPerDeg, q, containsDisc
 
     :param outline, keep_on_device: as for :func:`resample_frame_median`
     :return: the dict of :func:`resample_frame_median` with quantile (nq,ny,nx,C+1) and img (nq,ny,nx,C) in place of
-             median and img; mask and count are (ny,nx)
+             median and img, and ``q`` (the quantiles as a list); mask and count are (ny,nx)
     """
-    import torch
-    qs = quantile_list(q)
-    nq = len(qs)
-    ctx = fd.ctx
-    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
-                                               min_elevation, outline, None)
-    xaxis, yaxis = grid.axes(ctx)
-    nch = fd.nchan
-    quantile = ctx.empty((nq, grid.ny, grid.nx, nch + 1))
-    img = ctx.empty((nq, grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd.img_dtype_code != 2 else torch.int16)
-    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
-    count = ctx.empty((grid.ny, grid.nx))
-    min_el = float('-inf') if min_elevation is None else float(min_elevation)
-    ctx.call('amt_quantile_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code or 1, nch,
-             ptr(fd.center_mask), fd.height, fd.width, min_el, C.byref(xaxis), C.byref(yaxis), lon_wrap,
-             (C.c_double * nq)(*qs), nq, ptr(quantile), ptr(img) if nch else None, ptr(mask), ptr(count))
-    out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
-               contains_discontinuity=bool(containsDiscontinuity), altitude=altitude, q=qs)
-    if keep_on_device:
-        out.update(quantile=quantile, img=img, mask=mask, count=count)
-        return out
-    out.update(grid_coordinates(out))
-    out.update(quantile=to_host(quantile), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
-               mask=to_host(mask).astype(bool), count=to_host(count))
-    return out
+    return _resample_frame_ordered(fd, altitude, boundingBox, pxPerDeg, quantile_list(q), containsDiscontinuity, containsPole,
+                                   min_elevation, outline, keep_on_device)
 
 
 def fixedGrid(pxPerDeg, latMin, latMax, lonMin, lonMax):
@@ -967,9 +979,8 @@ def nearest_indices(ctx, lat_c, lon_c, elev, center_mask, height, width, min_ele
     xaxis, yaxis = grid.axes(ctx)
     tlat, tlon = grid.device_centers(ctx)
     index = ctx.empty((grid.ny, grid.nx), torch.int64)
-    min_el = float('-inf') if min_elevation is None else float(min_elevation)
-    ctx.call('amt_nearest_frame', ptr(lat_c), ptr(lon_c), ptr(elev), ptr(center_mask), height, width, min_el,
-             C.byref(xaxis), C.byref(yaxis), lon_wrap, ptr(tlat), ptr(tlon), ptr(target_mask), ptr(index))
+    ctx.call('amt_nearest_frame', ptr(lat_c), ptr(lon_c), ptr(elev), ptr(center_mask), height, width,
+             _min_elevation(min_elevation), C.byref(xaxis), C.byref(yaxis), lon_wrap, ptr(tlat), ptr(tlon), ptr(target_mask), ptr(index))
     return index
 
 
@@ -1024,115 +1035,107 @@ def resample_frame(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=Fa
     :param FrameData fd: centre lat/lon, elevation (optional), image and masks in HBM
     :param min_elevation: fuse ``maskedByElevation(min_elevation)`` into the binning pass (the frame's
                           own centre mask is applied in addition)
-    :param method: 'mean' (binning) or 'nearest' (closest pixel centre; needs `outline`)
+    :param method: 'mean' (binning: :func:`_bin_mean_frame`) or 'nearest', 'linear', 'cubic' (interpolation between the pixel
+                   centres: :func:`_interpolate_frame`; needs `outline`)
     :param outline: (n,2) [lat,lon] polygon of the mapping (``BaseMapping.outline``) for the interpolating methods:
                     grid cells with a corner outside it are masked (reference resample.py:246-259)
     :param shard: `fd` holds a band of rows of a frame whose other bands are on other ranks (see
                   :func:`auromat_amd.sequence.resample_frame_sharded`): shard.box combines the reduction of the rotated
                   corners, shard.acc sums the integer accumulators over the ranks before the means are taken
+    :param keep_on_device: the arrays stay device tensors and no grid coordinates are computed (sequence mode, :func:`_result`)
     :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mean (ny,nx,C+1), img (ny,nx,C),
-                  mask (ny,nx), count (ny,nx) ['mean' only], has_elev)
+                  mask (ny,nx), count (ny,nx) ['mean' only], has_elev); 'nearest': also index (ny,nx), 'linear' and 'cubic':
+                  triangles (ny,nx,3), 'cubic': sweeps
     """
-    import torch
     _check_method(method)
-    ctx = fd.ctx
     grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
                                                min_elevation, outline, shard)
-    xaxis, yaxis = grid.axes(ctx)
+    axes = grid.axes(fd.ctx)
+    if method == 'mean':
+        tensors = _bin_mean_frame(fd, grid, axes, lat_c, lon_c, lon_wrap, min_elevation, shard)
+    else:
+        tensors = _interpolate_frame(fd, grid, lat_c, lon_c, lon_wrap, altitude, containsDiscontinuity, containsPole,
+                                     min_elevation, method, outline, shard)
+    return _result(grid, bool(containsPole), bool(containsDiscontinuity), altitude, fd.elev is not None, tensors,
+                   keep_on_device, fd.img_dtype if fd.nchan else None)
+
+
+def _bin_mean_frame(fd, grid, axes, lat_c, lon_c, lon_wrap, min_elevation, shard):
+    """method='mean' of :func:`resample_frame` on the grid and centre coordinates of :func:`_frame_grid`: integer accumulation
+    (``amt_bin_frame``), the sum over the ranks of a sharded frame, means and image (``amt_bin_frame_finalize``).  Returns the
+    device tensors mean, img, mask, count."""
+    import torch
+    ctx = fd.ctx
+    xaxis, yaxis = axes
     nch = fd.nchan
-    if method in ('nearest', 'linear', 'cubic'):
-        assert outline is not None, "method='%s' needs the outline of the mapping" % method
-        assert shard is None, "rows of one frame over several ranks: method='mean' only"
-        outline = np.array(outline, dtype=np.float64)
-        if containsPole:
-            outline[:, 0], outline[:, 1] = _rotate_pole_host(outline[:, 0], outline[:, 1], altitude, 90)
-        elif containsDiscontinuity:
-            outline[:, 1] = wrap_at_180(outline[:, 1] + 180)
-        target_mask = outside_outline_mask(ctx, grid, outline)
-        mean = ctx.empty((grid.ny, grid.nx, nch + 1))
-        img = ctx.empty((grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd.img_dtype_code != 2 else torch.int16)
-        mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
-        extra = {}
-        index = None
-        if method == 'nearest':
-            index = nearest_indices(ctx, lat_c, lon_c, fd.elev, fd.center_mask, fd.height, fd.width, min_elevation, grid,
-                                    lon_wrap, target_mask)
-            ctx.call('amt_nearest_gather', ptr(index), grid.nx * grid.ny, ptr(fd.img), fd.img_dtype_code or 1, nch,
-                     ptr(fd.elev), ptr(mean), ptr(img) if nch else None, ptr(mask))
-        else:
-            tri = ctx.empty((grid.ny, grid.nx, 3), torch.int64)
-            min_el = float('-inf') if min_elevation is None else float(min_elevation)
-            # scipy's griddata(method='linear' | 'cubic') on its own triangulation, in its own order (cubic_exact): image
-            # channels and elevation as float64 channels of the valid pixels, then numpy's rounding and cast of the image
-            assert fd.elev is not None, "method='%s' on a frame needs the elevation" % method
-            la, lo = lat_c.reshape(-1), lon_c.reshape(-1)
-            if lon_wrap:
-                lo = wrap_at_180_t(lo + 180)
-            valid = ~(torch.isnan(la) | torch.isnan(lo)) & (fd.elev.reshape(-1) >= min_el)
-            if fd.center_mask is not None:
-                valid &= fd.center_mask.reshape(-1) == 0
-            chans = [fd.elev.reshape(-1, 1)]
-            if nch:
-                pix = fd.img.reshape(-1, nch)
-                if fd.img_dtype_code == 2:
-                    pix = pix.to(torch.int32) & 0xffff            # uint16 bits kept as int16
-                chans.insert(0, pix.to(torch.float64))
-            tri_out = []
-            vals, sweeps = cubic_exact(ctx, la, lo, valid, torch.cat(chans, dim=1), fd.height, fd.width, grid, target_mask,
-                                       method=method, vertices_out=tri_out)
-            mean.copy_(vals.reshape(grid.ny, grid.nx, nch + 1))
-            empty = torch.isnan(mean[..., 0])
-            mask.copy_(empty.to(torch.uint8))
-            if nch:
-                # np.round + astype of the interpolated floats (reference resample.py:128-136); an overshoot wraps
-                rounded = torch.round(torch.nan_to_num(mean[..., :nch], nan=0.0)).to(torch.int64)
-                if fd.img_dtype_code == 2:
-                    img.copy_((rounded & 0xffff).to(torch.int32).to(torch.int16))
-                else:
-                    img.copy_((rounded & 0xff).to(torch.uint8))
-            tri.copy_(tri_out[0].reshape(grid.ny, grid.nx, 3))
-            extra = dict(triangles=tri)
-            if method == 'cubic':
-                extra['sweeps'] = max(sweeps)
-        out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
-                   contains_discontinuity=bool(containsDiscontinuity), altitude=altitude)
-        if keep_on_device:
-            out.update(mean=mean, img=img, mask=mask, **extra)
-            if index is not None:
-                out['index'] = index
-            return out
-        out.update(grid_coordinates(out))
-        out.update(mean=to_host(mean), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
-                   mask=to_host(mask).astype(bool))
-        if index is not None:
-            out['index'] = to_host(index, dtype=np.int64)
-        if extra:
-            out.update(triangles=to_host(extra['triangles'], dtype=np.int64))
-            if 'sweeps' in extra:
-                out['sweeps'] = extra['sweeps']
-        return out
     acc = ctx.zeros((nch + 2, grid.nx * grid.ny), torch.int64)
-    min_el = float('-inf') if min_elevation is None else float(min_elevation)
     ctx.call('amt_bin_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code, nch,
-             ptr(fd.center_mask), fd.height, fd.width, min_el, C.byref(xaxis), C.byref(yaxis), lon_wrap, ptr(acc))
+             ptr(fd.center_mask), fd.height, fd.width, _min_elevation(min_elevation), C.byref(xaxis), C.byref(yaxis), lon_wrap,
+             ptr(acc))
     if shard is not None:
         shard.acc(acc)          # integer counts and sums: the order of the ranks does not matter
-    mean = ctx.empty((grid.ny, grid.nx, nch + 1))
-    img = ctx.empty((grid.ny, grid.nx, max(nch, 1)), torch.uint8 if fd.img_dtype_code != 2 else torch.int16)
-    mask = ctx.empty((grid.ny, grid.nx), torch.uint8)
-    count = ctx.empty((grid.ny, grid.nx))
+    mean, img, mask, count = _bin_outputs(ctx, grid, nch, fd.img_dtype_code)
     ctx.call('amt_bin_frame_finalize', ptr(acc), grid.nx, grid.ny, nch, fd.img_dtype_code or 1, ptr(mean),
              ptr(img) if nch else None, ptr(mask), ptr(count))
+    return dict(mean=mean, img=img, mask=mask, count=count)
 
-    out = dict(has_elev=fd.elev is not None, grid=grid, contains_pole=bool(containsPole),
-               contains_discontinuity=bool(containsDiscontinuity), altitude=altitude)
-    if keep_on_device:
-        # sequence mode: the grid is described by `grid` (first centre + step); coordinate arrays on demand
-        out.update(mean=mean, img=img, mask=mask, count=count)
-        return out
-    out.update(grid_coordinates(out))
-    out.update(mean=to_host(mean), img=to_host(img, dtype=fd.img_dtype if nch else np.uint8),
-               mask=to_host(mask).astype(bool), count=to_host(count))
+
+def _interpolate_frame(fd, grid, lat_c, lon_c, lon_wrap, altitude, containsDiscontinuity, containsPole, min_elevation, method,
+                       outline, shard):
+    """method='nearest', 'linear' and 'cubic' of :func:`resample_frame` on the grid and centre coordinates of
+    :func:`_frame_grid`.  Returns the device tensors mean, img, mask and index ('nearest') or triangles ('linear', 'cubic';
+    'cubic' also the number ``sweeps``)."""
+    import torch
+    ctx = fd.ctx
+    nch = fd.nchan
+    assert outline is not None, "method='%s' needs the outline of the mapping" % method
+    assert shard is None, "rows of one frame over several ranks: method='mean' only"
+    outline = np.array(outline, dtype=np.float64)
+    if containsPole:
+        outline[:, 0], outline[:, 1] = _rotate_pole_host(outline[:, 0], outline[:, 1], altitude, 90)
+    elif containsDiscontinuity:
+        outline[:, 1] = wrap_at_180(outline[:, 1] + 180)
+    target_mask = outside_outline_mask(ctx, grid, outline)
+    mean, img, mask, _ = _bin_outputs(ctx, grid, nch, fd.img_dtype_code, count=False)
+    if method == 'nearest':
+        index = nearest_indices(ctx, lat_c, lon_c, fd.elev, fd.center_mask, fd.height, fd.width, min_elevation, grid,
+                                lon_wrap, target_mask)
+        ctx.call('amt_nearest_gather', ptr(index), grid.nx * grid.ny, ptr(fd.img), fd.img_dtype_code or 1, nch,
+                 ptr(fd.elev), ptr(mean), ptr(img) if nch else None, ptr(mask))
+        return dict(mean=mean, img=img, mask=mask, index=index)
+    tri = ctx.empty((grid.ny, grid.nx, 3), torch.int64)
+    # scipy's griddata(method='linear' | 'cubic') on its own triangulation, in its own order (cubic_exact): image
+    # channels and elevation as float64 channels of the valid pixels, then numpy's rounding and cast of the image
+    assert fd.elev is not None, "method='%s' on a frame needs the elevation" % method
+    la, lo = lat_c.reshape(-1), lon_c.reshape(-1)
+    if lon_wrap:
+        lo = wrap_at_180_t(lo + 180)
+    valid = ~(torch.isnan(la) | torch.isnan(lo)) & (fd.elev.reshape(-1) >= _min_elevation(min_elevation))
+    if fd.center_mask is not None:
+        valid &= fd.center_mask.reshape(-1) == 0
+    chans = [fd.elev.reshape(-1, 1)]
+    if nch:
+        pix = fd.img.reshape(-1, nch)
+        if fd.img_dtype_code == 2:
+            pix = pix.to(torch.int32) & 0xffff            # uint16 bits kept as int16
+        chans.insert(0, pix.to(torch.float64))
+    tri_out = []
+    vals, sweeps = cubic_exact(ctx, la, lo, valid, torch.cat(chans, dim=1), fd.height, fd.width, grid, target_mask,
+                               method=method, vertices_out=tri_out)
+    mean.copy_(vals.reshape(grid.ny, grid.nx, nch + 1))
+    empty = torch.isnan(mean[..., 0])
+    mask.copy_(empty.to(torch.uint8))
+    if nch:
+        # np.round + astype of the interpolated floats (reference resample.py:128-136); an overshoot wraps
+        rounded = torch.round(torch.nan_to_num(mean[..., :nch], nan=0.0)).to(torch.int64)
+        if fd.img_dtype_code == 2:
+            img.copy_((rounded & 0xffff).to(torch.int32).to(torch.int16))
+        else:
+            img.copy_((rounded & 0xff).to(torch.uint8))
+    tri.copy_(tri_out[0].reshape(grid.ny, grid.nx, 3))
+    out = dict(mean=mean, img=img, mask=mask, triangles=tri)
+    if method == 'cubic':
+        out['sweeps'] = max(sweeps)
     return out
 
 
@@ -1217,16 +1220,11 @@ def _resample(latsCenter, lonsCenter, altitude, data, outlineLatLonFn, boundingB
                 lo = wrap_at_180_t(lo + 180)
             picked, _ = cubic_exact(ctx, la, lo, ~(torch.isnan(la) | torch.isnan(lo)), flat, h, w, grid, target_mask, method='linear')
         mean = to_host(picked.reshape(grid.ny, grid.nx, d.shape[2]))
-    lat, lon, lat_gc, lon_gc = grid.lat, grid.lon, grid.lat_c, grid.lon_c
-    if containsPole:
-        lat, lon = _rotate_pole_host(lat, lon, altitude, -90)
-        lat_gc, lon_gc = _rotate_pole_host(lat_gc, lon_gc, altitude, -90)
-    elif containsDiscontinuity:
-        lon = wrap_at_180(lon + 180)
-        lon_gc = wrap_at_180(lon_gc + 180)
+    coords = grid_coordinates(dict(grid=grid, contains_pole=containsPole, contains_discontinuity=containsDiscontinuity,
+                                   altitude=altitude))
     if scalar:
         mean = mean.reshape(mean.shape[0], mean.shape[1])
-    return lat, lon, lat_gc, lon_gc, mean
+    return coords['lat'], coords['lon'], coords['lat_c'], coords['lon_c'], mean
 
 
 def _resampleCenterData(lat_c, lon_c, centerData, grid, lon_wrap):
