@@ -1,0 +1,359 @@
+// Area-weighted (conservative) binning: a pixel is the quadrilateral of its four corners, and every cell of the output
+// grid that the quadrilateral overlaps receives the pixel's values with the integer weight
+//     W = rint(|area(quadrilateral ∩ cell)| / area(cell) * 2^32).
+// No counterpart in the reference: resample(method='mean') puts a pixel into the one cell that holds its centre and
+// leaves holes where the cells are smaller than the pixels.
+//
+// k_area_frame: one pixel per lane.  The accumulators have the layout of amt_bin_frame (int64, (nch + 2) planes of
+// nx * ny cells, cell ix * ny + iy): plane 0 sum(W), plane 1 + k sum(W * v_k), the last plane sum(W * E) with
+// E = rint(elev * 2^16).  Every accumulation is a 64-bit integer atomic, so the result is exact, independent of the
+// order and bit-reproducible; tests/_area_oracle.py restates cell_weight() operation for operation in NumPy.
+//
+// Three regimes by the number of candidate cells of a pixel (the cells its bounding box meets):
+//   * one cell (cells much larger than pixels) and a few cells (cells about as large as pixels): the lane walks its
+//     own cells, at most kLaneCells of them, through the same cell_weight() — one code path, the same bits;
+//   * many cells (a pixel near the limb on a fine grid covers thousands): such pixels are collected by ballot, their
+//     quadrilaterals broadcast one at a time, and the wave's 64 lanes stride over the cells of each.
+//
+// No LDS privatisation.  Where it would find sharing — cells much larger than pixels, every pixel one cell — the mean
+// binning does not leave holes and the area weights add little; the regime this pass exists for is the fine grid,
+// where a (pixel, cell) pair is nearly unique (a cell meets about as many quadrilaterals as a quadrilateral meets
+// cells), a window of u64 LDS counters (W has 33 bits, so the u32 window of amt_bin_tile.h does not do) would be
+// filled and flushed with one global atomic per LDS atomic, and the large quadrilaterals fall outside any window.
+// The global atomics of a wave go to neighbouring cells of one or two grid columns (iy runs fastest).
+#include "amt_common.h"
+
+namespace {
+
+using namespace amt;
+
+constexpr int kAreaBlock = 256;
+constexpr int kLaneCells = 16;                   // a pixel with more candidate cells is walked by the whole wave
+constexpr double kWeightOne = 4294967296.0;      // 2^32: the weight of a cell that a pixel covers whole
+constexpr double kElevFix = 65536.0;             // 2^16: E = rint(elev * 2^16)
+constexpr unsigned long long kWeightLimit = 1ull << 40;   // a cell covered more than 256 times over: AMT_EDOMAIN
+
+struct area_args {
+    const double* lat;       // corners, (height + 1) x (width + 1)
+    const double* lon;
+    const double* lat_c;     // centres, height x width (the NaN test only)
+    const double* elev;
+    const void* img;
+    const uint8_t* mask;
+    int height, width, nch;
+    double min_elev;
+    int use_elev_threshold;
+    axis_dev ax, ay;
+    int lon_wrap;
+    unsigned long long* acc;
+};
+
+// Edge i of an axis: the double bin_index compares against.
+__device__ __forceinline__ double axis_edge(const axis_dev& ax, int i) {
+    return ax.uniform ? linspace_edge(ax, i) : ax.edges[i];
+}
+
+__device__ __forceinline__ double clamp_to(double v, double hi) { return fmin(fmax(v, 0.0), hi); }
+
+// W of the quadrilateral (X[i], Y[i]), i = 0..3 in order, and the cell [x0, x1] x [y0, y1].
+//
+// The signed area of quadrilateral ∩ cell is the boundary integral of clamp(y, 0, b) d clamp(x, 0, a) over the
+// quadrilateral's edges in cell-relative coordinates (the change of variables (x, y) -> (clamp x, clamp y) maps the
+// polygon onto its clipped self, winding included, so concave and self-intersecting quadrilaterals need no case).
+// Every edge is split at its at most four crossings with the lines x = 0, x = a, y = 0, y = b; on each piece both
+// clamped coordinates are linear, and the piece contributes one trapezoid.  Only + - * /, min, max, |.| and rint, each
+// rounded on its own (no contraction): NumPy computes the same bits.
+__device__ __forceinline__ unsigned long long cell_weight(const double (&X)[4], const double (&Y)[4], double x0, double x1,
+                                                          double y0, double y1) {
+#pragma clang fp contract(off)
+    const double a = x1 - x0, b = y1 - y0;
+    double px[4], py[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        px[i] = X[i] - x0;
+        py[i] = Y[i] - y0;
+    }
+    double S = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double ax_ = px[i], ay_ = py[i], bx_ = px[(i + 1) & 3], by_ = py[(i + 1) & 3];
+        const double dx = bx_ - ax_, dy = by_ - ay_;
+        // parameters of the crossings, 0 where the edge is parallel to the line (that piece then adds nothing new)
+        double t0 = dx != 0.0 ? (0.0 - ax_) / dx : 0.0;
+        double t1 = dx != 0.0 ? (a - ax_) / dx : 0.0;
+        double t2 = dy != 0.0 ? (0.0 - ay_) / dy : 0.0;
+        double t3 = dy != 0.0 ? (b - ay_) / dy : 0.0;
+        t0 = clamp_to(t0, 1.0);
+        t1 = clamp_to(t1, 1.0);
+        t2 = clamp_to(t2, 1.0);
+        t3 = clamp_to(t3, 1.0);
+        // sorting network of four: (0,1) (2,3) (0,2) (1,3) (1,2)
+        double lo, hi;
+        lo = fmin(t0, t1); hi = fmax(t0, t1); t0 = lo; t1 = hi;
+        lo = fmin(t2, t3); hi = fmax(t2, t3); t2 = lo; t3 = hi;
+        lo = fmin(t0, t2); hi = fmax(t0, t2); t0 = lo; t2 = hi;
+        lo = fmin(t1, t3); hi = fmax(t1, t3); t1 = lo; t3 = hi;
+        lo = fmin(t1, t2); hi = fmax(t1, t2); t1 = lo; t2 = hi;
+        const double ts[4] = {t0, t1, t2, t3};
+        double ux = clamp_to(ax_, a), uy = clamp_to(ay_, b);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            double x, y;
+            if (k < 4) {
+                const double mx = ts[k] * dx, my = ts[k] * dy;
+                x = ax_ + mx;
+                y = ay_ + my;
+            } else {
+                x = bx_;        // the edge ends at its end point exactly: the boundary closes
+                y = by_;
+            }
+            const double vx = clamp_to(x, a), vy = clamp_to(y, b);
+            const double w = vx - ux, h = uy + vy;
+            const double piece = w * h;
+            S = S + piece;
+            ux = vx;
+            uy = vy;
+        }
+    }
+    const double A = fabs(S) * 0.5;
+    const double cell = a * b;
+    const double f = A / cell;
+    const double scaled = f * kWeightOne;
+    return (unsigned long long)rint(scaled);
+}
+
+struct area_pixel {
+    double X[4], Y[4];
+    int ix0, iy0, nxr, nyr;          // candidate cells [ix0, ix0 + nxr) x [iy0, iy0 + nyr); nxr = 0: the pixel takes no part
+    unsigned int ch[4];
+    long long E;
+};
+
+// Adds the pixel's share of candidate cell (jx, jy) of its range to the accumulators.
+__device__ __forceinline__ void add_cell(const area_args& A, const area_pixel& P, int jx, int jy, int64_t plane) {
+    const int ix = P.ix0 + jx, iy = P.iy0 + jy;
+    const unsigned long long W = cell_weight(P.X, P.Y, axis_edge(A.ax, ix), axis_edge(A.ax, ix + 1), axis_edge(A.ay, iy),
+                                             axis_edge(A.ay, iy + 1));
+    if (W == 0) return;
+    const int64_t cell = (int64_t)ix * A.ay.nbin + iy;
+    atomicAdd(&A.acc[cell], W);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < A.nch) atomicAdd(&A.acc[(int64_t)(1 + c) * plane + cell], W * (unsigned long long)P.ch[c]);
+    atomicAdd(&A.acc[(int64_t)(1 + A.nch) * plane + cell], (unsigned long long)((long long)W * P.E));
+}
+
+__device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }     // false for NaN
+
+template <typename IMG_T>
+__global__ __launch_bounds__(kAreaBlock) void k_area_frame(area_args A) {
+    const int64_t npix = (int64_t)A.height * A.width, plane = (int64_t)A.ax.nbin * A.ay.nbin;
+    const int lane = threadIdx.x & 63;
+    const IMG_T* img = static_cast<const IMG_T*>(A.img);
+    // (whole waves run every iteration: the cooperative part below needs all 64 lanes)
+    const int64_t per_sweep = (int64_t)gridDim.x * kAreaBlock;
+    for (int64_t base = (int64_t)blockIdx.x * kAreaBlock + (threadIdx.x & ~63); base < npix; base += per_sweep) {
+        const int64_t p = base + lane;
+        area_pixel P;
+        P.nxr = P.nyr = 0;
+        P.ix0 = P.iy0 = 0;
+        P.E = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            P.X[i] = P.Y[i] = 0.0;
+            P.ch[i] = 0;
+        }
+        if (p < npix) {
+            const int r = (int)(p / A.width), c = (int)(p - (int64_t)r * A.width);
+            const double ev = A.elev ? A.elev[p] : 0.0;
+            bool ok = finite(A.lat_c[p]);
+            if (A.use_elev_threshold) ok = ok && (ev >= A.min_elev);
+            if (A.mask) ok = ok && A.mask[p] == 0;
+            if (ok) {
+                // corners (r, c), (r, c + 1), (r + 1, c + 1), (r + 1, c)
+                const int64_t q = (int64_t)r * (A.width + 1) + c;
+                const int64_t at[4] = {q, q + 1, q + A.width + 2, q + A.width + 1};
+                double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
+                bool fin = true;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double lo = A.lon[at[i]], la = A.lat[at[i]];
+                    fin = fin && finite(lo) && finite(la);
+                    const double x = A.lon_wrap ? wrap180_shifted(lo) : lo;
+                    P.X[i] = x;
+                    P.Y[i] = la;
+                    xmin = fmin(xmin, x); xmax = fmax(xmax, x);
+                    ymin = fmin(ymin, la); ymax = fmax(ymax, la);
+                }
+                // (a quadrilateral as wide as half the globe straddles the seam of the longitudes)
+                if (fin && xmax - xmin < 180.0 && xmax > A.ax.e0 && xmin < A.ax.e_last && ymax > A.ay.e0 &&
+                    ymin < A.ay.e_last) {
+                    // edges[g] <= v < edges[g + 1] for the bin g + 1 of bin_index: no cell below that of the minimum or
+                    // above that of the maximum meets the quadrilateral
+                    const int nbx = A.ax.nbin, nby = A.ay.nbin;
+                    const int ix0 = min(max(bin_index(A.ax, xmin) - 1, 0), nbx - 1);
+                    const int ix1 = min(max(bin_index(A.ax, xmax) - 1, 0), nbx - 1);
+                    const int iy0 = min(max(bin_index(A.ay, ymin) - 1, 0), nby - 1);
+                    const int iy1 = min(max(bin_index(A.ay, ymax) - 1, 0), nby - 1);
+                    P.ix0 = ix0;
+                    P.iy0 = iy0;
+                    P.nxr = ix1 - ix0 + 1;
+                    P.nyr = iy1 - iy0 + 1;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (k < A.nch) P.ch[k] = img[p * A.nch + k];
+                    // (a NaN elevation of an admitted pixel contributes 0, as in amt_bin_tile.h)
+                    P.E = (ev == ev) ? (long long)rint(ev * kElevFix) : 0;
+                }
+            }
+        }
+        const long long ncells = (long long)P.nxr * P.nyr;
+        const bool wide = ncells > kLaneCells;
+        if (!wide)
+            for (int jx = 0; jx < P.nxr; ++jx)
+                for (int jy = 0; jy < P.nyr; ++jy) add_cell(A, P, jx, jy, plane);
+        // the wide quadrilaterals of this wave, one at a time over all 64 lanes
+        unsigned long long todo = __ballot(wide);
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            area_pixel Q;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                Q.X[i] = __shfl(P.X[i], src);
+                Q.Y[i] = __shfl(P.Y[i], src);
+                Q.ch[i] = __shfl(P.ch[i], src);
+            }
+            Q.ix0 = __shfl(P.ix0, src);
+            Q.iy0 = __shfl(P.iy0, src);
+            Q.nxr = __shfl(P.nxr, src);
+            Q.nyr = __shfl(P.nyr, src);
+            Q.E = __shfl(P.E, src);
+            // lane l takes cells l, l + 64, ... of the range in the order jx * nyr + jy; the step of 64 cells is split into
+            // whole columns and a rest once per quadrilateral, so that no cell costs a division
+            const int step_x = 64 / Q.nyr, step_y = 64 - step_x * Q.nyr;
+            int jx = lane / Q.nyr, jy = lane - jx * Q.nyr;
+            while (jx < Q.nxr) {
+                add_cell(A, Q, jx, jy, plane);
+                jx += step_x;
+                jy += step_y;
+                if (jy >= Q.nyr) {
+                    jy -= Q.nyr;
+                    jx += 1;
+                }
+            }
+        }
+    }
+}
+
+// Transpose + flipud as k_bin_finalize; a cell is valid when its total weight reaches min_weight.
+template <typename IMG_T>
+__global__ void k_area_finalize(const unsigned long long* __restrict__ acc, int nx, int ny, int nch,
+                                unsigned long long min_weight, double* __restrict__ area, IMG_T* __restrict__ out_img,
+                                uint8_t* __restrict__ out_mask, double* __restrict__ out_coverage,
+                                unsigned int* __restrict__ over) {
+#pragma clang fp contract(off)
+    const int64_t n = (int64_t)nx * ny;
+    bool too_much = false;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int r = (int)(i / nx), c = (int)(i - (int64_t)r * nx);
+        const int64_t cell = (int64_t)c * ny + (ny - 1 - r);
+        const unsigned long long w = acc[cell];
+        too_much = too_much || w > kWeightLimit;
+        const bool valid = w >= min_weight;
+        const double dw = (double)w;
+        for (int k = 0; k < nch; ++k) {
+            const double m = valid ? (double)acc[(int64_t)(1 + k) * n + cell] / dw : NAN;
+            if (area) area[i * (nch + 1) + k] = m;
+            if (out_img) out_img[i * nch + k] = valid ? (IMG_T)rint(m) : (IMG_T)0;
+        }
+        if (area) {
+            const double e = (double)(long long)acc[(int64_t)(1 + nch) * n + cell] / dw;
+            area[i * (nch + 1) + nch] = valid ? e / kElevFix : NAN;
+        }
+        if (out_mask) out_mask[i] = valid ? 0 : 1;
+        if (out_coverage) out_coverage[i] = dw / kWeightOne;
+    }
+    if (too_much) atomicOr(over, 1u);
+}
+
+inline dim3 blocks_for(int64_t n) {
+    int64_t blocks = (n + kAreaBlock - 1) / kAreaBlock;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (blocks < 1) blocks = 1;
+    return dim3(static_cast<unsigned>(blocks));
+}
+
+}  // namespace
+
+extern "C" {
+
+int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const double* lat_c, const double* elev, const void* img,
+                   int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                   double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, uint64_t* acc) {
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, lat && lon && lat_c && xaxis && yaxis && acc, "NULL argument");
+    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, (int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31), "frames below 2^31 pixels");
+    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
+    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
+    area_args A;
+    A.lat = lat;
+    A.lon = lon;
+    A.lat_c = lat_c;
+    A.elev = elev;
+    A.img = img;
+    A.mask = center_mask;
+    A.height = height;
+    A.width = width;
+    A.nch = nchan;
+    A.min_elev = min_elevation;
+    A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
+    make_axis(xaxis, &A.ax);
+    make_axis(yaxis, &A.ay);
+    A.lon_wrap = lon_wrap ? 1 : 0;
+    A.acc = reinterpret_cast<unsigned long long*>(acc);
+    const dim3 grid = blocks_for((int64_t)height * width), block(kAreaBlock);
+    if (img_dtype == 2)
+        hipLaunchKernelGGL((k_area_frame<uint16_t>), grid, block, 0, ctx->stream, A);
+    else
+        hipLaunchKernelGGL((k_area_frame<uint8_t>), grid, block, 0, ctx->stream, A);
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32_t ny, int32_t nchan, int32_t img_dtype,
+                            uint64_t min_weight, double* area, void* out_img, uint8_t* out_mask, double* out_coverage) {
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, acc != nullptr, "NULL argument");
+    AMT_REQUIRE(ctx, nx > 0 && ny > 0 && nchan >= 0 && nchan <= 4, "bad shape");
+    AMT_REQUIRE(ctx, out_img == nullptr || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
+    unsigned int* over = static_cast<unsigned int*>(amt_workspace(ctx, sizeof(unsigned int)));
+    if (over == nullptr) {
+        ctx->last_error = "amt_area_frame_finalize: no device memory for the workspace";
+        return AMT_ENOMEM;
+    }
+    AMT_HIP(ctx, hipMemsetAsync(over, 0, sizeof(unsigned int), ctx->stream));
+    const unsigned long long least = min_weight < 1 ? 1ull : (unsigned long long)min_weight;
+    const dim3 grid = blocks_for((int64_t)nx * ny), block(kAreaBlock);
+    const unsigned long long* a = reinterpret_cast<const unsigned long long*>(acc);
+    if (img_dtype == 2)
+        hipLaunchKernelGGL((k_area_finalize<uint16_t>), grid, block, 0, ctx->stream, a, nx, ny, nchan, least, area,
+                           static_cast<uint16_t*>(out_img), out_mask, out_coverage, over);
+    else
+        hipLaunchKernelGGL((k_area_finalize<uint8_t>), grid, block, 0, ctx->stream, a, nx, ny, nchan, least, area,
+                           static_cast<uint8_t*>(out_img), out_mask, out_coverage, over);
+    AMT_LAUNCH_CHECK(ctx);
+    unsigned int flag = 0;
+    AMT_HIP(ctx, hipMemcpyAsync(&flag, over, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag) {
+        ctx->last_error = "amt_area_frame_finalize: a cell's total weight exceeds 2^40 (covered more than 256 times over)";
+        return AMT_EDOMAIN;
+    }
+    return AMT_OK;
+}
+
+}  // extern "C"

@@ -304,6 +304,64 @@ def resampleQuantileMLatMLT(mapping, q, **kw):
     return [convertSMMappingToGeo(r) for r in res] if isinstance(res, list) else convertSMMappingToGeo(res)
 
 
+def min_coverage_weight(minCoverage):
+    """The least total weight of a valid cell of the area-weighted binning, ``max(1, rint(minCoverage * 2^32))``; ValueError for
+    a `minCoverage` outside [0, 1] (or NaN) — before any device work."""
+    try:
+        v = float(minCoverage)
+    except (TypeError, ValueError):
+        raise ValueError('minCoverage must be a number in [0, 1], but is: {!r}'.format(minCoverage))
+    if not 0.0 <= v <= 1.0:                 # (False for NaN)
+        raise ValueError('minCoverage must be in the range [0, 1], got {!r}'.format(minCoverage))
+    return max(1, int(np.rint(v * 4294967296.0)))
+
+
+def resampleArea(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, minCoverage=0.5):
+    """
+    Area-weighted (conservative) resampling: like :func:`resample` with ``method='mean'`` on the same grid, but a pixel is the
+    quadrilateral of its four corners and every cell it overlaps receives its colours and elevation, weighted with the
+    fraction of the cell that the overlap covers.  A cell's value is the weighted mean over everything that overlaps it.
+
+    ``resample(method='mean')`` puts a pixel into the one cell that holds its centre: where cells are smaller than pixels (low
+    elevation angles, high resolutions) cells between the centres stay empty.  Here every cell that the pixels cover at least
+    `minCoverage` of is filled, and what the pixels saw is conserved rather than interpolated between centres; where cells are
+    larger than pixels, small pixels no longer count as much as large ones.  The weights are integers (``rint(fraction *
+    2^32)``) summed with integer atomics on the device (``amt_area_frame``), so the result is exact, independent of the order
+    of the pixels and the same bits on every run.  No counterpart in the reference; ``resample(method=...)`` keeps the
+    reference's method list.
+
+    A pixel takes part when its centre is unmasked (as for 'mean': mask the mapping by elevation first), its four corners are
+    finite and it does not straddle the seam of the longitudes (after the pole rotation or the date-line shift).
+
+    :param mappingOrCollection, pxPerDeg, arcsecPerPx, containsPole: see :func:`resample`
+    :param number minCoverage: a cell is masked unless the pixels cover at least this fraction of it, in [0, 1]
+                               (0: any overlap at all); ValueError otherwise
+    :rtype: a subclass of BaseMapping or MappingCollection
+    """
+    min_coverage_weight(minCoverage)
+
+    def doResample(mapping):
+        global last_plan
+        last_plan = None
+        pole, ppd = _pole_and_resolution(mapping, pxPerDeg, arcsecPerPx, containsPole)
+        res = resample_frame_area(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd, mapping.containsDiscontinuity,
+                                  pole, outline=mapping.outline if pole else None, minCoverage=minCoverage)
+        return _created(mapping, res, res['area'], res['img'], res['has_elev'])
+
+    members, rebuild = _members(mappingOrCollection)
+    return rebuild([doResample(m) for m in members])
+
+
+def resampleAreaMLatMLT(mapping, **kw):
+    """:func:`resampleArea` such that MLat/MLT become regular grids (``convertMappingToSM`` -> ``resampleArea`` ->
+    ``convertSMMappingToGeo``, as :func:`resampleMedianMLatMLT`).
+
+    See :func:`resampleArea` for parameters.
+    """
+    min_coverage_weight(kw.get('minCoverage', 0.5))
+    return convertSMMappingToGeo(resampleArea(convertMappingToSM(mapping), **kw))
+
+
 MOSAIC_STATISTICS = ('mean', 'median', 'quantile')
 
 
@@ -627,6 +685,50 @@ def resample_frame_quantile(fd, altitude, boundingBox, pxPerDeg, q, containsDisc
     """
     return _resample_frame_ordered(fd, altitude, boundingBox, pxPerDeg, quantile_list(q), containsDiscontinuity, containsPole,
                                    min_elevation, outline, keep_on_device)
+
+
+def resample_frame_area(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,
+                        min_elevation=None, keep_on_device=False, outline=None, minCoverage=0.5):
+    """
+    Area-weighted binning of a device-resident frame on the grid :func:`resample_frame` lays out (``amt_area_frame`` +
+    ``amt_area_frame_finalize``): see :func:`resampleArea`.  The corner arrays get the treatment the centre arrays get: rotated
+    with the pole, or wrapped out of the date line in the kernel.
+
+    :param outline, keep_on_device, min_elevation: as for :func:`resample_frame`
+    :param minCoverage: a cell is valid when the pixels cover at least this fraction of it
+    :raises ValueError: for `minCoverage` outside [0, 1]; when a cell is covered more than 256 times over (``AMT_EDOMAIN``:
+                        the integer sums could wrap)
+    :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], area (ny,nx,C+1) [weighted means, NaN where masked],
+                  img (ny,nx,C), mask (ny,nx), coverage (ny,nx) [fraction of the cell that the pixels cover, every cell],
+                  has_elev)
+    """
+    import torch
+    least = min_coverage_weight(minCoverage)
+    ctx = fd.ctx
+    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
+                                               min_elevation, outline, None)
+    lat, lon = fd.lat, fd.lon
+    if containsPole:
+        # (without an outline _frame_grid has rotated the corners once already, for the box, and keeps only the centres; the
+        #  class API always has the outline)
+        lat, lon = _rotate_pole_dev(ctx, fd.lat, fd.lon, altitude, 90)
+    xaxis, yaxis = grid.axes(ctx)
+    nch = fd.nchan
+    acc = ctx.zeros((nch + 2, grid.nx * grid.ny), torch.int64)
+    ctx.call('amt_area_frame', ptr(lat), ptr(lon), ptr(lat_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code or 1, nch,
+             ptr(fd.center_mask), fd.height, fd.width, _min_elevation(min_elevation), C.byref(xaxis), C.byref(yaxis), lon_wrap,
+             ptr(acc))
+    area, img, mask, coverage = _bin_outputs(ctx, grid, nch, fd.img_dtype_code)
+    rc = ctx._lib.amt_area_frame_finalize(ctx.handle, ptr(acc), grid.nx, grid.ny, nch, fd.img_dtype_code or 1, least, ptr(area),
+                                          ptr(img) if nch else None, ptr(mask), ptr(coverage))
+    if rc == -5:                            # AMT_EDOMAIN
+        raise ValueError('resampleArea: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
+                         'fit (is the resolution far too low for this mapping?)')
+    ctx.check(rc)
+    if not nch:
+        img.zero_()                         # (ny,nx,1) so that the result has an image; no kernel writes it without channels
+    return _result(grid, bool(containsPole), bool(containsDiscontinuity), altitude, fd.elev is not None,
+                   dict(area=area, img=img, mask=mask, coverage=coverage), keep_on_device, fd.img_dtype if nch else None)
 
 
 def fixedGrid(pxPerDeg, latMin, latMax, lonMin, lonMax):

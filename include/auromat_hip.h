@@ -43,7 +43,8 @@ extern "C" {
  *    place of reserved_); amt_pipe_set_plan(pipe, 2) */
 /* 9: amt_mosaic_frames, amt_mosaic_member (the members of a collection binned onto one grid, auromat_amd.resample.resampleMosaic) */
 /* 10, additions only (no struct changed, the number stays): quantile binning — amt_quantile_frame, amt_quantile_frame_async,
- *    amt_quantile_rank, amt_run_set_quantile, AMT_QUANTILES_MAX (auromat_amd.resample.resampleQuantile) */
+ *    amt_quantile_rank, amt_run_set_quantile, AMT_QUANTILES_MAX (auromat_amd.resample.resampleQuantile); the median and quantile
+ *    mosaics; area-weighted binning — amt_area_frame, amt_area_frame_finalize (auromat_amd.resample.resampleArea) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -494,6 +495,27 @@ int amt_bin_frame_finalize_window(amt_ctx* ctx, const uint64_t* acc, int32_t acc
                                   int32_t off_x, int32_t off_y, int32_t nx, int32_t ny, int32_t nchan,
                                   int32_t img_dtype, double* mean, void* out_img, uint8_t* out_mask,
                                   double* out_count);
+/* Area-weighted (conservative) binning (auromat_amd.resample.resampleArea; no counterpart in the reference): a pixel is the
+ * quadrilateral of its corners (r, c), (r, c+1), (r+1, c+1), (r+1, c) of the corner arrays lat / lon ((height+1) x (width+1),
+ * x = lon, y = lat; lon_wrap as for amt_bin_frame, applied to every corner), and every cell that it overlaps receives it with
+ * the integer weight W = rint(A / cell area * 2^32), A the absolute signed (winding) area of quadrilateral and cell rectangle
+ * (the rectangle between the axis's own edge values); a cell with W = 0 receives nothing.  A pixel takes part when lat_c is
+ * finite, elev >= min_elevation (-inf: no threshold; elev may be NULL), center_mask == 0 (may be NULL), all eight corner values
+ * are finite and the quadrilateral's x extent (after the wrap) is below 180.  The cell that holds the centre plays no role.
+ * acc: the layout of amt_bin_frame, zeroed by the caller, ADDED to: plane 0 = sum(W), planes 1..nchan = sum(W * channel),
+ * plane nchan+1 = sum(W * E), E = rint(elev * 2^16) (0 for a NaN elevation).  64-bit integer atomics: exact, order
+ * independent, bit-reproducible.  Alignment: any. */
+int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const double* lat_c, const double* elev, const void* img,
+                   int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                   double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, uint64_t* acc);
+/* Weighted means in the layout of amt_bin_frame_finalize.  A cell is valid when sum(W) >= max(1, min_weight) (min_weight =
+ * rint(minimum coverage * 2^32)).  area (optional): (ny, nx, nchan+1) float64, sum(W * v) / sum(W), the elevation
+ * sum(W * E) / sum(W) / 65536, NaN where invalid; out_img (optional): round-half-even of the value, 0 where invalid; out_mask
+ * (optional): 1 where invalid; out_coverage (optional): sum(W) / 2^32 for every cell.  Reads one device flag back
+ * (synchronises): AMT_EDOMAIN when a cell's sum(W) exceeds 2^40 (covered more than 256 times over; the products could wrap) —
+ * the outputs are then unspecified. */
+int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32_t ny, int32_t nchan, int32_t img_dtype,
+                            uint64_t min_weight, double* area, void* out_img, uint8_t* out_mask, double* out_coverage);
 /* Median binning (auromat_amd.resample.resampleMedian; the reference names method='median' and leaves it unbuilt,
  * auromat/resample.py:353-357): the pixels amt_bin_frame would bin into cell (ix, iy) — same arguments, same membership —
  * and for every cell and channel np.median of their values: the order statistic of rank (n-1)/2, or for an even count n
