@@ -611,7 +611,7 @@ __global__ __launch_bounds__(kBlock) void k_points_in_polygon(const double* __re
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     const bool live = i < n;
     const double tx = live ? px[i] : 0.0, ty = live ? py[i] : 0.0;
-    // y-range of this block's points (NaN coordinates never compare, they stay outside)
+    // y-range of this block's points (a NaN y never compares: it takes no part in the range)
     double lo = live && ty == ty ? ty : __builtin_huge_val(), hi = live && ty == ty ? ty : -__builtin_huge_val();
     for (int o = 32; o > 0; o >>= 1) {
         lo = fmin(lo, __shfl_xor(lo, o));
@@ -653,7 +653,9 @@ __global__ __launch_bounds__(kBlock) void k_points_in_polygon(const double* __re
             if (f0 != f1 && (((y1 - ty) * (x0 - x1) >= (x1 - tx) * (y0 - y1)) == f1)) in = !in;
         }
     }
-    if (live) inside[i] = in ? 1 : 0;
+    // Agg's point_in_path leaves a point with a coordinate that is not finite outside; a NaN y never compares and stays outside
+    // by itself, a NaN x fails every comparison above, which `== f1` turns into a crossing of every edge that ends below ty
+    if (live) inside[i] = (in && isfinite(tx) && isfinite(ty)) ? 1 : 0;
 }
 
 bool uniform_axis_ok(const amt_axis* a) {
