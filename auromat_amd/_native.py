@@ -83,6 +83,12 @@ class MosaicMember(C.Structure):
                [(k, C.c_int32) for k in ('height', 'width', 'win_x0', 'win_y0', 'win_nx', 'win_ny')]
 
 
+class AreaMosaicMember(C.Structure):
+    """amt_area_mosaic_member"""
+    _fields_ = [(k, C.c_void_p) for k in ('lat', 'lon', 'lat_c', 'elev', 'img', 'center_mask')] + \
+               [(k, C.c_int32) for k in ('height', 'width', 'win_x0', 'win_y0', 'win_nx', 'win_ny')]
+
+
 class PipeResult(C.Structure):
     """amt_pipe_result"""
     _fields_ = [('status', C.c_int32), ('fused', C.c_int32), ('lon_wrapped', C.c_int32), ('edge_pixels', C.c_int32),
@@ -218,6 +224,8 @@ _SIGNATURES = {
                                   C.POINTER(Axis), _I, C.c_int32, _P, _P, _P, _P, _P], _I),
     'amt_mosaic_quantile_frames': ([_P, C.POINTER(MosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                                     C.POINTER(Axis), _I, C.c_int32, c_double_p, _I, _P, _P, _P, _P, _P], _I),
+    'amt_area_mosaic_frames': ([_P, C.POINTER(AreaMosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                                C.POINTER(Axis), _I, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
                            _P], _I),
     'amt_nearest_gather': ([_P, _P, _L, _P, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),

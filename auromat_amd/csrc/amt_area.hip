@@ -21,6 +21,17 @@
 // cells), a window of u64 LDS counters (W has 33 bits, so the u32 window of amt_bin_tile.h does not do) would be
 // filled and flushed with one global atomic per LDS atomic, and the large quadrilaterals fall outside any window.
 // The global atomics of a wave go to neighbouring cells of one or two grid columns (iy runs fastest).
+//
+// Area-weighted mosaics (amt_area_mosaic_frames, auromat_amd.resample.resampleMosaic(statistic='area')): the members of a
+// collection on ONE grid in a fixed number of launches whatever the member count, as amt_mosaic.hip does for the mean.  The
+// member table is uploaded, the members' window accumulators and the overflow flag are zeroed by one memset, one launch of
+// k_area_frame<..., WIN = true> bins every member (a workgroup finds its member through a prefix of workgroups per member; a
+// pixel's candidate cells are cut to the member's window BEFORE the choice between the lane and the wave path, and the window
+// planes are column-major with iy fastest like the grid's, so a wave's atomics keep their layout), and k_area_select gives every
+// cell its value by the overlap rule with the finalise arithmetic of k_area_finalize (area_finalize_cell, shared by both).
+#include <algorithm>
+#include <type_traits>
+
 #include "amt_common.h"
 
 namespace {
@@ -47,6 +58,44 @@ struct area_args {
     int lon_wrap;
     unsigned long long* acc;
 };
+
+// Cells [x0, x0 + nx) x [y0, y0 + ny) of the common grid that a member of a mosaic keeps; its accumulator planes hold the window
+// only (cell (x, y) at (x - x0) * ny + (y - y0), nx * ny cells per plane).
+struct area_window {
+    int x0, y0, nx, ny;
+};
+
+// The members of an area-weighted mosaic: one descriptor per member in device memory, and the first workgroup of every
+// member (a prefix over the members' workgroups, n + 1 entries).
+struct area_member {
+    area_args A;            // the member's frame on the common axes; A.acc = its window planes
+    area_window W;
+};
+struct area_mosaic_args {
+    const area_member* __restrict__ members;
+    const int* __restrict__ block_start;
+    int n;
+};
+
+template <bool WIN> struct area_kernel_args { using type = area_args; };
+template <> struct area_kernel_args<true> { using type = area_mosaic_args; };
+
+// The member of global workgroup b: the last i with block_start[i] <= b (a binary search over wave-uniform loads).
+__device__ __forceinline__ int area_member_of(const area_args&, unsigned) { return 0; }
+__device__ __forceinline__ int area_member_of(const area_mosaic_args& M, unsigned b) {
+    int lo = 0, hi = M.n;                   // block_start[lo] <= b < block_start[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)M.block_start[mid] <= b) lo = mid; else hi = mid;
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+__device__ __forceinline__ const area_args& frame_args(const area_args& A, int) { return A; }
+__device__ __forceinline__ const area_args& frame_args(const area_mosaic_args& M, int m) { return M.members[m].A; }
+__device__ __forceinline__ area_window frame_window(const area_args&, int) { return area_window{0, 0, 0, 0}; }
+__device__ __forceinline__ area_window frame_window(const area_mosaic_args& M, int m) { return M.members[m].W; }
+__device__ __forceinline__ unsigned first_block(const area_args&, int) { return 0; }
+__device__ __forceinline__ unsigned first_block(const area_mosaic_args& M, int m) { return (unsigned)M.block_start[m]; }
 
 // Edge i of an axis: the double bin_index compares against.
 __device__ __forceinline__ double axis_edge(const axis_dev& ax, int i) {
@@ -129,13 +178,16 @@ struct area_pixel {
     long long E;
 };
 
-// Adds the pixel's share of candidate cell (jx, jy) of its range to the accumulators.
-__device__ __forceinline__ void add_cell(const area_args& A, const area_pixel& P, int jx, int jy, int64_t plane) {
+// Adds the pixel's share of candidate cell (jx, jy) of its range to the accumulators (WIN: of the member's window Wn, which
+// holds the whole range).
+template <bool WIN>
+__device__ __forceinline__ void add_cell(const area_args& A, const area_window& Wn, const area_pixel& P, int jx, int jy,
+                                         int64_t plane) {
     const int ix = P.ix0 + jx, iy = P.iy0 + jy;
     const unsigned long long W = cell_weight(P.X, P.Y, axis_edge(A.ax, ix), axis_edge(A.ax, ix + 1), axis_edge(A.ay, iy),
                                              axis_edge(A.ay, iy + 1));
     if (W == 0) return;
-    const int64_t cell = (int64_t)ix * A.ay.nbin + iy;
+    const int64_t cell = WIN ? (int64_t)(ix - Wn.x0) * Wn.ny + (iy - Wn.y0) : (int64_t)ix * A.ay.nbin + iy;
     atomicAdd(&A.acc[cell], W);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -145,14 +197,26 @@ __device__ __forceinline__ void add_cell(const area_args& A, const area_pixel& P
 
 __device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }     // false for NaN
 
-template <typename IMG_T>
-__global__ __launch_bounds__(kAreaBlock) void k_area_frame(area_args A) {
-    const int64_t npix = (int64_t)A.height * A.width, plane = (int64_t)A.ax.nbin * A.ay.nbin;
+// WIN = false: the argument is the frame (area_args); the whole grid is kept (A.ax.nbin x A.ay.nbin cells per plane).
+// WIN = true (the binning of amt_area_mosaic_frames): the argument is the member table (area_mosaic_args); the workgroup finds
+// its member by the workgroup prefix, sweeps that member's pixels with the member's other workgroups and keeps only the cells of
+// the member's window.  The weights and the sums are the same integers either way.
+template <typename IMG_T, bool WIN>
+__global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_args<WIN>::type K) {
+    const int member = WIN ? area_member_of(K, blockIdx.x) : 0;
+    // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
+    //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
+    typename std::conditional<WIN, const area_args, const area_args&>::type A = frame_args(K, member);
+    const area_window Wn = frame_window(K, member);
+    const unsigned block0 = first_block(K, member);
+    const unsigned nblocks = WIN ? first_block(K, member + 1) - block0 : gridDim.x;
+    const int64_t npix = (int64_t)A.height * A.width;
+    const int64_t plane = WIN ? (int64_t)Wn.nx * Wn.ny : (int64_t)A.ax.nbin * A.ay.nbin;
     const int lane = threadIdx.x & 63;
     const IMG_T* img = static_cast<const IMG_T*>(A.img);
     // (whole waves run every iteration: the cooperative part below needs all 64 lanes)
-    const int64_t per_sweep = (int64_t)gridDim.x * kAreaBlock;
-    for (int64_t base = (int64_t)blockIdx.x * kAreaBlock + (threadIdx.x & ~63); base < npix; base += per_sweep) {
+    const int64_t per_sweep = (int64_t)nblocks * kAreaBlock;
+    for (int64_t base = (int64_t)(blockIdx.x - block0) * kAreaBlock + (threadIdx.x & ~63); base < npix; base += per_sweep) {
         const int64_t p = base + lane;
         area_pixel P;
         P.nxr = P.nyr = 0;
@@ -191,19 +255,28 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(area_args A) {
                     // edges[g] <= v < edges[g + 1] for the bin g + 1 of bin_index: no cell below that of the minimum or
                     // above that of the maximum meets the quadrilateral
                     const int nbx = A.ax.nbin, nby = A.ay.nbin;
-                    const int ix0 = min(max(bin_index(A.ax, xmin) - 1, 0), nbx - 1);
-                    const int ix1 = min(max(bin_index(A.ax, xmax) - 1, 0), nbx - 1);
-                    const int iy0 = min(max(bin_index(A.ay, ymin) - 1, 0), nby - 1);
-                    const int iy1 = min(max(bin_index(A.ay, ymax) - 1, 0), nby - 1);
-                    P.ix0 = ix0;
-                    P.iy0 = iy0;
-                    P.nxr = ix1 - ix0 + 1;
-                    P.nyr = iy1 - iy0 + 1;
+                    int ix0 = min(max(bin_index(A.ax, xmin) - 1, 0), nbx - 1);
+                    int ix1 = min(max(bin_index(A.ax, xmax) - 1, 0), nbx - 1);
+                    int iy0 = min(max(bin_index(A.ay, ymin) - 1, 0), nby - 1);
+                    int iy1 = min(max(bin_index(A.ay, ymax) - 1, 0), nby - 1);
+                    if (WIN) {
+                        // the range is cut to the window before the path is chosen: what is left decides lane or wave
+                        ix0 = max(ix0, Wn.x0);
+                        ix1 = min(ix1, Wn.x0 + Wn.nx - 1);
+                        iy0 = max(iy0, Wn.y0);
+                        iy1 = min(iy1, Wn.y0 + Wn.ny - 1);
+                    }
+                    if (!WIN || (ix1 >= ix0 && iy1 >= iy0)) {
+                        P.ix0 = ix0;
+                        P.iy0 = iy0;
+                        P.nxr = ix1 - ix0 + 1;
+                        P.nyr = iy1 - iy0 + 1;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (k < A.nch) P.ch[k] = img[p * A.nch + k];
-                    // (a NaN elevation of an admitted pixel contributes 0, as in amt_bin_tile.h)
-                    P.E = (ev == ev) ? (long long)rint(ev * kElevFix) : 0;
+                        for (int k = 0; k < 4; ++k)
+                            if (k < A.nch) P.ch[k] = img[p * A.nch + k];
+                        // (a NaN elevation of an admitted pixel contributes 0, as in amt_bin_tile.h)
+                        P.E = (ev == ev) ? (long long)rint(ev * kElevFix) : 0;
+                    }
                 }
             }
         }
@@ -211,7 +284,7 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(area_args A) {
         const bool wide = ncells > kLaneCells;
         if (!wide)
             for (int jx = 0; jx < P.nxr; ++jx)
-                for (int jy = 0; jy < P.nyr; ++jy) add_cell(A, P, jx, jy, plane);
+                for (int jy = 0; jy < P.nyr; ++jy) add_cell<WIN>(A, Wn, P, jx, jy, plane);
         // the wide quadrilaterals of this wave, one at a time over all 64 lanes
         unsigned long long todo = __ballot(wide);
         while (todo) {
@@ -234,7 +307,7 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(area_args A) {
             const int step_x = 64 / Q.nyr, step_y = 64 - step_x * Q.nyr;
             int jx = lane / Q.nyr, jy = lane - jx * Q.nyr;
             while (jx < Q.nxr) {
-                add_cell(A, Q, jx, jy, plane);
+                add_cell<WIN>(A, Wn, Q, jx, jy, plane);
                 jx += step_x;
                 jy += step_y;
                 if (jy >= Q.nyr) {
@@ -246,13 +319,34 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(area_args A) {
     }
 }
 
+// The finalise arithmetic of one cell, for k_area_finalize and k_area_select alike: w = sum(W), sum(k) the cell's plane 1 + k
+// (k = nch: sum(W * E)), read only where it is needed; output cell i.  A cell is valid when w reaches min_weight.
+template <typename IMG_T, typename SUM>
+__device__ __forceinline__ void area_finalize_cell(unsigned long long w, unsigned long long min_weight, SUM sum, int nch, int64_t i,
+                                                   double* __restrict__ area, IMG_T* __restrict__ out_img,
+                                                   uint8_t* __restrict__ out_mask, double* __restrict__ out_coverage) {
+#pragma clang fp contract(off)
+    const bool valid = w >= min_weight;
+    const double dw = (double)w;
+    for (int k = 0; k < nch; ++k) {
+        const double m = valid ? (double)sum(k) / dw : NAN;
+        if (area) area[i * (nch + 1) + k] = m;
+        if (out_img) out_img[i * nch + k] = valid ? (IMG_T)rint(m) : (IMG_T)0;
+    }
+    if (area) {
+        const double e = (double)(long long)sum(nch) / dw;
+        area[i * (nch + 1) + nch] = valid ? e / kElevFix : NAN;
+    }
+    if (out_mask) out_mask[i] = valid ? 0 : 1;
+    if (out_coverage) out_coverage[i] = dw / kWeightOne;
+}
+
 // Transpose + flipud as k_bin_finalize; a cell is valid when its total weight reaches min_weight.
 template <typename IMG_T>
 __global__ void k_area_finalize(const unsigned long long* __restrict__ acc, int nx, int ny, int nch,
                                 unsigned long long min_weight, double* __restrict__ area, IMG_T* __restrict__ out_img,
                                 uint8_t* __restrict__ out_mask, double* __restrict__ out_coverage,
                                 unsigned int* __restrict__ over) {
-#pragma clang fp contract(off)
     const int64_t n = (int64_t)nx * ny;
     bool too_much = false;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -260,21 +354,96 @@ __global__ void k_area_finalize(const unsigned long long* __restrict__ acc, int 
         const int64_t cell = (int64_t)c * ny + (ny - 1 - r);
         const unsigned long long w = acc[cell];
         too_much = too_much || w > kWeightLimit;
-        const bool valid = w >= min_weight;
-        const double dw = (double)w;
-        for (int k = 0; k < nch; ++k) {
-            const double m = valid ? (double)acc[(int64_t)(1 + k) * n + cell] / dw : NAN;
-            if (area) area[i * (nch + 1) + k] = m;
-            if (out_img) out_img[i * nch + k] = valid ? (IMG_T)rint(m) : (IMG_T)0;
-        }
-        if (area) {
-            const double e = (double)(long long)acc[(int64_t)(1 + nch) * n + cell] / dw;
-            area[i * (nch + 1) + nch] = valid ? e / kElevFix : NAN;
-        }
-        if (out_mask) out_mask[i] = valid ? 0 : 1;
-        if (out_coverage) out_coverage[i] = dw / kWeightOne;
+        area_finalize_cell(w, min_weight, [&](int k) { return acc[(int64_t)(1 + k) * n + cell]; }, nch, i, area, out_img,
+                           out_mask, out_coverage);
     }
     if (too_much) atomicOr(over, 1u);
+}
+
+constexpr int kSelTile = 16;        // k_area_select: one workgroup per 16 x 16 cells of the common grid
+
+struct area_select_args {
+    const area_member* __restrict__ members;
+    const int* __restrict__ list_start;     // CSR per 16 x 16 tile of cells: members whose window meets the tile,
+    const int* __restrict__ list;           // ascending
+    int tiles_y;                            // tiles along the (ascending) latitude bins
+    int nx, ny, nch, rule;
+    unsigned long long min_weight;          // >= 1
+    double* area;
+    void* img;
+    uint8_t* mask;
+    double* coverage;
+    int32_t* source;
+    unsigned int* over;
+};
+
+// One thread per output cell: the cell's tile's members, in ascending order.
+// rule 0: the accumulators of every member added (source: the first member with weight there, where the total is valid);
+// rule 1: of the members whose OWN weight in the cell reaches min_weight, the one with the largest (double)(int64)sum(W * E) /
+// (double)sum(W) — the quotient area_finalize_cell forms — the first on a tie; without such a member the cell is masked and
+// its coverage is the largest single weight.  Then area_finalize_cell.  The flag: a member's weight in a cell, or under rule 0
+// a cell's total, above 2^40 (below it no sum can wrap: the members' weights are checked one by one, so the total of n members
+// stays below n * 2^40 < 2^64 while it is compared).
+template <typename IMG_T>
+__global__ __launch_bounds__(kSelTile * kSelTile) void k_area_select(area_select_args S) {
+#pragma clang fp contract(off)
+    const int tile = (int)blockIdx.x;
+    const int tx = tile / S.tiles_y, ty = tile - tx * S.tiles_y;
+    const int cx = tx * kSelTile + (int)(threadIdx.x % kSelTile), cy = ty * kSelTile + (int)(threadIdx.x / kSelTile);
+    if (cx >= S.nx || cy >= S.ny) return;
+    const int64_t i = (int64_t)(S.ny - 1 - cy) * S.nx + cx;      // output row r = ny - 1 - cy (north to south)
+    const int nch = S.nch;
+    const int b = S.list_start[tile], e = S.list_start[tile + 1];
+    // the cell's sum(W), channel sums and sum(W * E): the total (rule 0) or the elected member's (rule 1; before a member is
+    // elected w is the largest weight seen)
+    unsigned long long w = 0, s0 = 0, s1 = 0, s2 = 0, s3 = 0, se = 0;
+    int src = -1;
+    double best = 0.0;
+    bool too_much = false;
+    for (int k = b; k < e; ++k) {
+        const int m = S.list[k];
+        const area_member& D = S.members[m];
+        const int wx = cx - D.W.x0, wy = cy - D.W.y0;
+        if (wx < 0 || wx >= D.W.nx || wy < 0 || wy >= D.W.ny) continue;
+        const unsigned long long* acc = D.A.acc;
+        const int64_t plane = (int64_t)D.W.nx * D.W.ny, cell = (int64_t)wx * D.W.ny + wy;
+        const unsigned long long c = acc[cell];
+        if (c == 0) continue;
+        too_much = too_much || c > kWeightLimit;
+        if (S.rule == 0) {
+            w += c;
+            if (0 < nch) s0 += acc[1 * plane + cell];
+            if (1 < nch) s1 += acc[2 * plane + cell];
+            if (2 < nch) s2 += acc[3 * plane + cell];
+            if (3 < nch) s3 += acc[4 * plane + cell];
+            se += acc[(int64_t)(1 + nch) * plane + cell];
+            if (src < 0) src = m;
+        } else if (c >= S.min_weight) {
+            const unsigned long long f = acc[(int64_t)(1 + nch) * plane + cell];
+            const double el = (double)(long long)f / (double)c;
+            if (src < 0 || el > best) {
+                src = m;
+                best = el;
+                w = c;
+                if (0 < nch) s0 = acc[1 * plane + cell];
+                if (1 < nch) s1 = acc[2 * plane + cell];
+                if (2 < nch) s2 = acc[3 * plane + cell];
+                if (3 < nch) s3 = acc[4 * plane + cell];
+                se = f;
+            }
+        } else if (src < 0 && c > w) {
+            w = c;
+        }
+    }
+    if (S.rule == 0) {
+        too_much = too_much || w > kWeightLimit;
+        if (w < S.min_weight) src = -1;
+    }
+    area_finalize_cell(w, S.min_weight,
+                       [&](int k) { return k == nch ? se : (k == 0 ? s0 : (k == 1 ? s1 : (k == 2 ? s2 : s3))); }, nch, i, S.area,
+                       static_cast<IMG_T*>(S.img), S.mask, S.coverage);
+    if (S.source) S.source[i] = src;
+    if (too_much) atomicOr(S.over, 1u);
 }
 
 inline dim3 blocks_for(int64_t n) {
@@ -317,9 +486,9 @@ int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const dou
     A.acc = reinterpret_cast<unsigned long long*>(acc);
     const dim3 grid = blocks_for((int64_t)height * width), block(kAreaBlock);
     if (img_dtype == 2)
-        hipLaunchKernelGGL((k_area_frame<uint16_t>), grid, block, 0, ctx->stream, A);
+        hipLaunchKernelGGL((k_area_frame<uint16_t, false>), grid, block, 0, ctx->stream, A);
     else
-        hipLaunchKernelGGL((k_area_frame<uint8_t>), grid, block, 0, ctx->stream, A);
+        hipLaunchKernelGGL((k_area_frame<uint8_t, false>), grid, block, 0, ctx->stream, A);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
@@ -351,6 +520,160 @@ int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32
     AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (flag) {
         ctx->last_error = "amt_area_frame_finalize: a cell's total weight exceeds 2^40 (covered more than 256 times over)";
+        return AMT_EDOMAIN;
+    }
+    return AMT_OK;
+}
+
+int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                           int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                           int32_t rule, uint64_t min_weight, double* area, void* out_img, uint8_t* out_mask,
+                           double* out_coverage, int32_t* out_source) {
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, members && xaxis && yaxis, "NULL argument");
+    AMT_REQUIRE(ctx, n_members >= 1, "no members");
+    AMT_REQUIRE(ctx, rule == 0 || rule == 1, "rule must be 0 (union) or 1 (highest elevation)");
+    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
+    AMT_REQUIRE(ctx, out_img == nullptr || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
+    const int nx = xaxis->nbin, ny = yaxis->nbin;
+    for (int32_t i = 0; i < n_members; ++i) {
+        const amt_area_mosaic_member& m = members[i];
+        AMT_REQUIRE(ctx, m.lat && m.lon && m.lat_c, "member without corners or centres");
+        AMT_REQUIRE(ctx, m.height > 0 && m.width > 0, "empty member");
+        AMT_REQUIRE(ctx, (int64_t)(m.height + 1) * (m.width + 1) < ((int64_t)1 << 31), "members below 2^31 pixels");
+        AMT_REQUIRE(ctx, nchan == 0 || (m.img && (img_dtype == 1 || img_dtype == 2)), "member image missing");
+        AMT_REQUIRE(ctx, rule == 0 || m.elev != nullptr, "rule 1 needs every member's elevation");
+        AMT_REQUIRE(ctx, m.win_nx >= 0 && m.win_ny >= 0, "bad window");
+        AMT_REQUIRE(ctx, m.win_nx == 0 || m.win_ny == 0 ||
+                         (m.win_x0 >= 0 && m.win_y0 >= 0 && m.win_x0 + m.win_nx <= nx && m.win_y0 + m.win_ny <= ny),
+                    "window outside the grid");
+    }
+    if (amt_set_device(ctx)) return AMT_EHIP;
+
+    // host tables: member descriptors | workgroup prefix [n + 1] | CSR of the 16 x 16 cell tiles; then the flag and the
+    // accumulators, zeroed together
+    axis_dev ax, ay;
+    make_axis(xaxis, &ax);
+    make_axis(yaxis, &ay);
+    const int stx = (nx + kSelTile - 1) / kSelTile, sty = (ny + kSelTile - 1) / kSelTile;
+    const int64_t n_sel = (int64_t)stx * sty;
+    std::vector<area_member> dev((size_t)n_members);
+    std::vector<int> block_start((size_t)n_members + 1, 0);
+    std::vector<int> list_start((size_t)n_sel + 1, 0), list;
+    std::vector<size_t> acc_off((size_t)n_members, 0);
+    size_t acc_words = 0;
+    int64_t blocks = 0;
+    for (int32_t i = 0; i < n_members; ++i) {
+        const amt_area_mosaic_member& m = members[i];
+        area_member& d = dev[(size_t)i];
+        const bool empty = m.win_nx == 0 || m.win_ny == 0;
+        d.A.lat = m.lat;
+        d.A.lon = m.lon;
+        d.A.lat_c = m.lat_c;
+        d.A.elev = m.elev;
+        d.A.img = m.img;
+        d.A.mask = m.center_mask;
+        d.A.height = m.height;
+        d.A.width = m.width;
+        d.A.nch = nchan;
+        d.A.min_elev = min_elevation;
+        d.A.use_elev_threshold = (m.elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
+        d.A.ax = ax;
+        d.A.ay = ay;
+        d.A.lon_wrap = lon_wrap ? 1 : 0;
+        d.A.acc = nullptr;
+        d.W = {m.win_x0, m.win_y0, empty ? 0 : m.win_nx, empty ? 0 : m.win_ny};
+        block_start[(size_t)i] = (int)blocks;
+        if (!empty) {
+            blocks += blocks_for((int64_t)m.height * m.width).x;
+            acc_off[(size_t)i] = acc_words;
+            acc_words += (size_t)(nchan + 2) * (size_t)m.win_nx * (size_t)m.win_ny;
+        }
+        AMT_REQUIRE(ctx, blocks < (int64_t)1 << 31, "too many workgroups");
+    }
+    block_start[(size_t)n_members] = (int)blocks;
+    for (int tx = 0; tx < stx; ++tx)
+        for (int ty = 0; ty < sty; ++ty) {
+            const int64_t t = (int64_t)tx * sty + ty;
+            list_start[(size_t)t] = (int)list.size();
+            for (int32_t i = 0; i < n_members; ++i) {
+                const area_window& w = dev[(size_t)i].W;
+                if (w.nx == 0) continue;
+                if (w.x0 < (tx + 1) * kSelTile && w.x0 + w.nx > tx * kSelTile && w.y0 < (ty + 1) * kSelTile &&
+                    w.y0 + w.ny > ty * kSelTile)
+                    list.push_back(i);
+            }
+        }
+    list_start[(size_t)n_sel] = (int)list.size();
+
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_bstart = up(dev.size() * sizeof(area_member));
+    const size_t o_lstart = o_bstart + up(block_start.size() * sizeof(int));
+    const size_t o_list = o_lstart + up(list_start.size() * sizeof(int));
+    const size_t o_flag = o_list + up(std::max<size_t>(list.size(), 1) * sizeof(int));
+    const size_t o_acc = o_flag + 256;
+    const size_t bytes = o_acc + acc_words * sizeof(unsigned long long);
+    char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
+    if (ws == nullptr) {
+        ctx->last_error = "amt_area_mosaic_frames: no device memory for the workspace";
+        return AMT_ENOMEM;
+    }
+    unsigned int* over = reinterpret_cast<unsigned int*>(ws + o_flag);
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + o_acc);
+    for (int32_t i = 0; i < n_members; ++i) dev[(size_t)i].A.acc = acc + acc_off[(size_t)i];
+    std::vector<char> host(o_flag, 0);
+    std::memcpy(host.data(), dev.data(), dev.size() * sizeof(area_member));
+    std::memcpy(host.data() + o_bstart, block_start.data(), block_start.size() * sizeof(int));
+    std::memcpy(host.data() + o_lstart, list_start.data(), list_start.size() * sizeof(int));
+    if (!list.empty()) std::memcpy(host.data() + o_list, list.data(), list.size() * sizeof(int));
+    // (pageable source: the copy has consumed `host` when the call returns)
+    AMT_HIP(ctx, hipMemcpyAsync(ws, host.data(), o_flag, hipMemcpyHostToDevice, ctx->stream));
+    AMT_HIP(ctx, hipMemsetAsync(over, 0, bytes - o_flag, ctx->stream));
+
+    if (blocks > 0) {
+        area_mosaic_args M;
+        M.members = reinterpret_cast<const area_member*>(ws);
+        M.block_start = reinterpret_cast<const int*>(ws + o_bstart);
+        M.n = n_members;
+        const dim3 grid((unsigned)blocks), block(kAreaBlock);
+        if (img_dtype == 2)
+            hipLaunchKernelGGL((k_area_frame<uint16_t, true>), grid, block, 0, ctx->stream, M);
+        else
+            hipLaunchKernelGGL((k_area_frame<uint8_t, true>), grid, block, 0, ctx->stream, M);
+        AMT_LAUNCH_CHECK(ctx);
+    }
+
+    area_select_args S;
+    S.members = reinterpret_cast<const area_member*>(ws);
+    S.list_start = reinterpret_cast<const int*>(ws + o_lstart);
+    S.list = reinterpret_cast<const int*>(ws + o_list);
+    S.tiles_y = sty;
+    S.nx = nx;
+    S.ny = ny;
+    S.nch = nchan;
+    S.rule = rule;
+    S.min_weight = min_weight < 1 ? 1ull : (unsigned long long)min_weight;
+    S.area = area;
+    S.img = out_img;
+    S.mask = out_mask;
+    S.coverage = out_coverage;
+    S.source = out_source;
+    S.over = over;
+    const dim3 sgrid((unsigned)n_sel), sblock(kSelTile * kSelTile);
+    if (img_dtype == 2)
+        hipLaunchKernelGGL(k_area_select<uint16_t>, sgrid, sblock, 0, ctx->stream, S);
+    else
+        hipLaunchKernelGGL(k_area_select<uint8_t>, sgrid, sblock, 0, ctx->stream, S);
+    AMT_LAUNCH_CHECK(ctx);
+    unsigned int flag = 0;
+    AMT_HIP(ctx, hipMemcpyAsync(&flag, over, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag) {
+        ctx->last_error = rule == 0
+            ? "amt_area_mosaic_frames: a cell's total weight exceeds 2^40 (covered more than 256 times over)"
+            : "amt_area_mosaic_frames: a member's weight in a cell exceeds 2^40 (covered more than 256 times over)";
         return AMT_EDOMAIN;
     }
     return AMT_OK;

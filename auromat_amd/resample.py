@@ -24,7 +24,7 @@ from .mapping.mapping import (BaseMapping, MappingCollection, convertMappingToSM
                               wrap_at_180)
 from .coordinates.geodesic import angularDistanceOnParallel
 from .util.histogram import make_axis
-from ._native import Context, MosaicMember, host9, ptr, to_host
+from ._native import AreaMosaicMember, Context, MosaicMember, host9, ptr, to_host
 
 
 def plateCarreeResolution(boundingBox, arcsecPerPx):
@@ -362,14 +362,19 @@ def resampleAreaMLatMLT(mapping, **kw):
     return convertSMMappingToGeo(resampleArea(convertMappingToSM(mapping), **kw))
 
 
-MOSAIC_STATISTICS = ('mean', 'median', 'quantile')
+MOSAIC_STATISTICS = ('mean', 'median', 'quantile', 'area')
 
 
-def mosaic_statistic(statistic, q):
-    """The quantiles of a mosaic call as a list (None for 'mean' and 'median').  ValueError for an unknown statistic, `q` given
-    with 'mean' or 'median', 'quantile' without `q`, and what :func:`quantile_list` refuses — before any member is looked at."""
+def mosaic_statistic(statistic, q, minCoverage=None):
+    """The quantiles of a mosaic call as a list (None for 'mean', 'median' and 'area').  ValueError for an unknown statistic, `q`
+    given with 'mean', 'median' or 'area', 'quantile' without `q`, what :func:`quantile_list` refuses, `minCoverage` given with
+    another statistic than 'area' or outside [0, 1] — before any member is looked at."""
     if statistic not in MOSAIC_STATISTICS:
         raise ValueError('statistic must be one of {}, but is: {!r}'.format(', '.join(MOSAIC_STATISTICS), statistic))
+    if minCoverage is not None:
+        if statistic != 'area':
+            raise ValueError('minCoverage={!r} goes with statistic=\'area\', not with {!r}'.format(minCoverage, statistic))
+        min_coverage_weight(minCoverage)
     if statistic != 'quantile':
         if q is not None:
             raise ValueError('q={!r} goes with statistic=\'quantile\', not with {!r}'.format(q, statistic))
@@ -379,7 +384,7 @@ def mosaic_statistic(statistic, q):
     return quantile_list(q)
 
 
-def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, statistic='mean', q=None):
+def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, statistic='mean', q=None, minCoverage=None):
     """
     Bins every member of a :class:`MappingCollection` onto ONE grid and returns ONE mapping (:class:`MosaicMapping`), where
     :func:`resample` of a collection grids each member on its own box.
@@ -403,17 +408,33 @@ def resampleMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None,
     moves its mean.  With ``'quantile'`` a number `q` gives one mapping, a sequence of 1 to 8 a list with one mapping per `q`
     from ONE device call (:func:`resampleQuantile`'s convention).
 
-    :param str statistic: 'mean' | 'median' | 'quantile'
+    ``'area'`` is the area-weighted mosaic: every member's pixels are the quadrilaterals of their corners and are shared among
+    the cells of the common grid they overlap, with the integer weights of :func:`resampleArea` (``amt_area_mosaic_frames``).
+    The other statistics put a pixel into the one cell that holds its centre, so towards the horizon, where pixels are many
+    cells wide, every member leaves holes and the overlap rule chooses between whichever centres happened to land in a cell.
+    mayOverlap False: the members' weighted sums are added and a cell is valid when together they cover at least `minCoverage`
+    of it.  True: of the members that cover at least `minCoverage` of the cell on their OWN, the one with the highest weighted
+    mean elevation wins it whole (the earlier member on a tie); a sliver of a well-placed member does not take a cell that
+    another member covers.  ``source`` is set exactly where the cell is valid.  In the pole plan the members' corners are
+    rotated like their centres.
+
+    :param str statistic: 'mean' | 'median' | 'quantile' | 'area'
     :param None|number|sequence q: the quantile(s), for statistic='quantile' only
-    :raises ValueError: for an unknown statistic, `q` with 'mean' or 'median', 'quantile' without `q` (all before the
-                        collection is looked at); for an empty collection, members of different altitudes or image dtypes /
-                        channel counts, and a member without elevation when ``mayOverlap`` is True
+    :param None|number minCoverage: for statistic='area' only: a cell is masked unless the pixels cover at least this
+                                    fraction of it, in [0, 1] (None: 0.5)
+    :raises ValueError: for an unknown statistic, `q` with 'mean', 'median' or 'area', 'quantile' without `q`, `minCoverage`
+                        with another statistic than 'area' or outside [0, 1] (all before the collection is looked at); for an
+                        empty collection, members of different altitudes or image dtypes / channel counts, and a member
+                        without elevation when ``mayOverlap`` is True; with 'area', when a cell is covered more than 256 times
+                        over
     :rtype: MosaicMapping, or a list of them
     """
-    qs = mosaic_statistic(statistic, q)
-    res = mosaic_frames(collection, pxPerDeg, arcsecPerPx, containsPole, statistic=statistic, q=qs)
+    qs = mosaic_statistic(statistic, q, minCoverage)
+    res = mosaic_frames(collection, pxPerDeg, arcsecPerPx, containsPole, statistic=statistic, q=qs, minCoverage=minCoverage)
     if statistic == 'mean':
         return _mosaic_mapping(collection, res)
+    if statistic == 'area':
+        return _mosaic_mapping(collection, res, res['area'], res['img'])
     if statistic == 'median':
         return _mosaic_mapping(collection, res, res['median'], res['img'])
     out = [_mosaic_mapping(collection, res, res['quantile'][j], res['img'][j]) for j in range(len(qs))]
@@ -427,7 +448,7 @@ def resampleMosaicMLatMLT(collection, **kw):
     See :func:`resampleMosaic` for parameters; a list result (several quantiles) is mapped element by element.
     """
     from .mapping.mapping import MosaicMapping
-    mosaic_statistic(kw.get('statistic', 'mean'), kw.get('q'))
+    mosaic_statistic(kw.get('statistic', 'mean'), kw.get('q'), kw.get('minCoverage'))
     sm = MappingCollection([convertMappingToSM(m) for m in collection.mappings], collection.identifier,
                            mayOverlap=collection.mayOverlap)
 
@@ -541,17 +562,21 @@ def mosaic_layout(memberBoxes, pxPerDeg=25, arcsecPerPx=None, poleBoxes=None):
     return dict(grid=grid, pole=poleBoxes is not None, discontinuity=disc, lon_wrap=lon_wrap, boxes=boxes, windows=windows)
 
 
-def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, statistic='mean', q=None):
+def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, statistic='mean', q=None, minCoverage=None):
     """The mosaic of a collection's device frames on the common grid (``amt_mosaic_frames``; ``amt_mosaic_median_frames`` /
-    ``amt_mosaic_quantile_frames`` for the other statistics): see :func:`resampleMosaic`.
+    ``amt_mosaic_quantile_frames`` / ``amt_area_mosaic_frames`` for the other statistics): see :func:`resampleMosaic`.
 
     :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mean (ny,nx,C+1), img (ny,nx,C), mask (ny,nx),
                   count (ny,nx), source (ny,nx) int32 [-1: empty], has_elev, plan); with statistic='median' ``median`` in place
                   of ``mean``, with 'quantile' ``quantile`` (nq,ny,nx,C+1) and img (nq,ny,nx,C), as
-                  :func:`resample_frame_median` / :func:`resample_frame_quantile` return them, and ``q``
+                  :func:`resample_frame_median` / :func:`resample_frame_quantile` return them, and ``q``; with 'area' ``area``
+                  (ny,nx,C+1) in place of ``mean`` and ``coverage`` (ny,nx) in place of ``count``, as
+                  :func:`resample_frame_area` returns them
     """
     import torch
-    qs = mosaic_statistic(statistic, q)
+    qs = mosaic_statistic(statistic, q, minCoverage)
+    if statistic == 'area':
+        return _mosaic_frames_area(collection, pxPerDeg, arcsecPerPx, containsPole, 0.5 if minCoverage is None else minCoverage)
     plan = mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole)
     grid, frames, altitude = plan['grid'], plan['frames'], plan['altitude']
     ctx = frames[0].ctx
@@ -591,6 +616,50 @@ def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, 
     out.update(plan=plan)
     if qs:
         out.update(q=qs)
+    return out
+
+
+def _mosaic_frames_area(collection, pxPerDeg, arcsecPerPx, containsPole, minCoverage):
+    """:func:`mosaic_frames` for statistic='area' (``amt_area_mosaic_frames``): the plan, the windows and the rule of the other
+    statistics; every member hands over its corner arrays as well, rotated like its centres in the pole plan."""
+    import torch
+    least = min_coverage_weight(minCoverage)
+    plan = mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole)
+    grid, frames, altitude = plan['grid'], plan['frames'], plan['altitude']
+    ctx = frames[0].ctx
+    fd0 = frames[0]
+    nch = fd0.nchan
+    keep = []                    # device arrays the call reads (the rotated corners and centres of the pole plan)
+    table = (AreaMosaicMember * len(frames))()
+    for i, (fd, (x0, y0, wnx, wny)) in enumerate(zip(frames, plan['windows'])):
+        lat, lon, lat_c = fd.lat, fd.lon, fd.lat_c
+        if plan['pole']:
+            lat, lon = _rotate_pole_dev(ctx, fd.lat, fd.lon, altitude, 90)
+            lat_c, _ = _rotate_pole_dev(ctx, fd.lat_c, fd.lon_c, altitude, 90)
+            keep.append((lat, lon, lat_c))
+        t = table[i]
+        addr = [None if a is None else ptr(a).value for a in (lat, lon, lat_c, fd.elev, fd.img if nch else None,
+                                                              fd.center_mask)]
+        t.lat, t.lon, t.lat_c, t.elev, t.img, t.center_mask = addr
+        t.height, t.width = fd.height, fd.width
+        t.win_x0, t.win_y0, t.win_nx, t.win_ny = x0, y0, wnx, wny
+    xaxis, yaxis = grid.axes(ctx)
+    area, img, mask, coverage = _bin_outputs(ctx, grid, nch, fd0.img_dtype_code)
+    source = ctx.empty((grid.ny, grid.nx), torch.int32)
+    if not nch:
+        img.zero_()
+    rc = ctx._lib.amt_area_mosaic_frames(ctx.handle, table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'),
+                                         C.byref(xaxis), C.byref(yaxis), plan['lon_wrap'], plan['rule'], least, ptr(area),
+                                         ptr(img) if nch else None, ptr(mask), ptr(coverage), ptr(source))
+    if rc == -5:                            # AMT_EDOMAIN
+        raise ValueError('resampleMosaic: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
+                         'fit (is the resolution far too low for this collection?)')
+    ctx.check(rc)
+    out = _result(grid, plan['pole'], plan['discontinuity'], altitude, all(fd.elev is not None for fd in frames),
+                  dict(area=area, img=img, mask=mask, coverage=coverage, source=source), False,
+                  fd0.img_dtype if nch else None)
+    del keep                     # (after the read-back above: the kernels are done with them)
+    out.update(plan=plan)
     return out
 
 

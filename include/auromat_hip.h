@@ -44,7 +44,8 @@ extern "C" {
 /* 9: amt_mosaic_frames, amt_mosaic_member (the members of a collection binned onto one grid, auromat_amd.resample.resampleMosaic) */
 /* 10, additions only (no struct changed, the number stays): quantile binning — amt_quantile_frame, amt_quantile_frame_async,
  *    amt_quantile_rank, amt_run_set_quantile, AMT_QUANTILES_MAX (auromat_amd.resample.resampleQuantile); the median and quantile
- *    mosaics; area-weighted binning — amt_area_frame, amt_area_frame_finalize (auromat_amd.resample.resampleArea) */
+ *    mosaics; area-weighted binning — amt_area_frame, amt_area_frame_finalize (auromat_amd.resample.resampleArea);
+ *    area-weighted mosaics — amt_area_mosaic_frames, amt_area_mosaic_member */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -623,6 +624,44 @@ int amt_mosaic_quantile_frames(amt_ctx* ctx, const amt_mosaic_member* members, i
                                int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
                                int32_t rule, const double* q, int nq, double* quantile, void* out_img, uint8_t* out_mask,
                                double* out_count, int32_t* out_source);
+/* Area-weighted mosaics (addition to ABI v10; auromat_amd.resample.resampleMosaic(statistic='area')): amt_mosaic_frames' member
+ * table, windows and overlap rules with amt_area_frame's weights in place of the centre binning.  Both hold for any pair of axes
+ * (the geodetic grid and the (MLat, SM longitude) grid alike).
+ * Per member: integer accumulators sum(W), sum(W * v_k), sum(W * E) on the member's window [win_x0, win_x0 + win_nx) x [win_y0,
+ * win_y0 + win_ny) of the common grid; W, E, the admission rules, lon_wrap and the candidate cells are amt_area_frame's on the
+ * common axes (lat / lon: the member's CORNER arrays, (height+1) x (width+1); lat_c: the NaN test of the centres).  For every
+ * cell of the window the accumulators equal amt_area_frame's on the whole common grid; cells outside it receive nothing; an
+ * empty window bins nothing.
+ *   rule 0 (union): the accumulators of all members are added per cell and amt_area_frame_finalize's arithmetic is applied to
+ *     the totals: a cell is valid when total sum(W) >= max(1, min_weight); out_coverage: total sum(W) / 2^32, every cell;
+ *     out_source: the lowest member index with sum(W) > 0 in the cell where it is valid, -1 where it is masked;
+ *   rule 1 (highest elevation wins): candidates are the members whose OWN sum(W) in the cell reaches max(1, min_weight) (a sliver
+ *     of a well-placed member does not take a cell that another covers whole); of them the member with the largest float64
+ *     (double)(int64)sum(W * E) / (double)sum(W) wins, the lower index on a tie, and the cell takes its values, image, mask and
+ *     coverage, bit for bit those of amt_area_frame_finalize on that member's accumulators.  Without a candidate the cell is
+ *     masked (NaN, image 0, source -1) and its coverage is the largest single member's sum(W) / 2^32 (0 without any).  Every
+ *     member needs `elev`.
+ * In both rules out_source >= 0 exactly where out_mask == 0.  Outputs in the layout of amt_area_frame_finalize, each optional:
+ * area (ny, nx, nchan+1), out_img (ny, nx, nchan), out_mask, out_coverage (ny, nx), out_source int32 (ny, nx).
+ * AMT_EDOMAIN (outputs unspecified) when a member's own sum(W) in a window cell exceeds 2^40, or under rule 0 a cell's total
+ * does; below that no 64-bit sum can wrap.  A fixed number of launches whatever n_members is (upload, one memset, one binning
+ * launch — none when every window is empty: an all-masked grid, source -1, coverage 0 —, one election launch, the flag's
+ * read-back); the accumulators ((nchan + 2) x 8 bytes per window cell of every member) live in the context's workspace.
+ * Synchronises, as amt_area_frame_finalize does.  Alignment: any. */
+typedef struct amt_area_mosaic_member {
+    const double* lat;                /* corners, (height + 1) x (width + 1) */
+    const double* lon;
+    const double* lat_c;              /* centres, height x width */
+    const double* elev;               /* may be NULL only for rule 0 */
+    const void* img;                  /* may be NULL when nchan == 0 */
+    const uint8_t* center_mask;       /* optional */
+    int32_t height, width;
+    int32_t win_x0, win_y0, win_nx, win_ny;   /* window in cells of the common grid */
+} amt_area_mosaic_member;
+int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, int32_t n_members, int32_t img_dtype,
+                           int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                           int32_t rule, uint64_t min_weight, double* area, void* out_img, uint8_t* out_mask,
+                           double* out_coverage, int32_t* out_source);
 /* Same for float accumulators of amt_hist2d_accumulate: mean[k] = sums[k]/count, NaN where empty,
  * transposed + flipped to (ny, nx, nweights). */
 int amt_hist2d_finalize_mean(amt_ctx* ctx, const double* count, const double* const* sums, int32_t nweights,
