@@ -209,6 +209,8 @@ _SIGNATURES = {
     'amt_area_frame': ([_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                         C.POINTER(Axis), _I, _P], _I),
     'amt_area_frame_finalize': ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P, _P, _P, _P], _I),
+    'amt_area_frame_async': ([_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                              C.POINTER(Axis), _I, _I, C.c_int32, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P], _I),
     'amt_median_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                           C.POINTER(Axis), _I, _P, _P, _P, _P], _I),
     'amt_median_frame_async': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
@@ -261,6 +263,8 @@ _SIGNATURES = {
     'amt_run_reset_hints': ([_P], _I),
     'amt_run_fill_stats': ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _I),
     'amt_run_set_quantile': ([_P, _D], _I),
+    'amt_run_set_min_coverage': ([_P, C.c_uint64], _I),
+    'amt_run_area_overflow': ([_P, C.POINTER(C.c_int32), C.c_int32], _I),
     'amt_seq_payload_size': ([C.POINTER(SeqFrame), C.c_int32, C.POINTER(_L)], _I),
     'amt_seq_pack': ([_P, C.POINTER(SeqFrame), C.c_int32, C.c_int32, _P, _L], _I),
     'amt_seq_unpack': ([_P, _L, C.c_int32, C.c_int32, C.POINTER(SeqFrame), C.c_int32, C.POINTER(C.c_int32)], _I),

@@ -24,6 +24,10 @@ What differs, and why:
   mean (:func:`auromat_amd.resample.resampleMedian` / ``resampleMedianMLatMLT``), through the same two routes; the files
   are written exactly as mean grids are.  ``--statistic quantile --quantile Q`` bins by the quantile Q in [0, 1] of a cell's
   pixels in the same way (:func:`auromat_amd.resample.resampleQuantile` / ``resampleQuantileMLatMLT``).
+* ``--statistic area`` (an addition; needs ``--resample``) shares every pixel — the quadrilateral of its four corners — among
+  the cells it overlaps, weighted with the covered fraction of the cell (:func:`auromat_amd.resample.resampleArea` /
+  ``resampleAreaMLatMLT``), through the same two routes: no holes between the pixel centres on fine grids.  ``--min-coverage F``
+  (default 0.5, in [0, 1]) masks the cells of which the pixels cover less than F.  The files hold the variables a mean grid's do.
 """
 from __future__ import print_function
 
@@ -97,12 +101,17 @@ def getParser():
                                    'runs through the single-pass frame pipeline')
     resampleArgs.add_argument('--grid', help='The grid which will be regular after resampling. Default is MLat/MLT grid. '
                                              'Use geo for geographical grid.', default=Grid.mag, choices=[Grid.geo, Grid.mag])
-    resampleArgs.add_argument('--statistic', choices=['mean', 'median', 'quantile'], default='mean',
+    resampleArgs.add_argument('--statistic', choices=['mean', 'median', 'quantile', 'area'], default='mean',
                               help='How the pixels of a grid cell are combined, default mean; median is robust to stars, city '
-                                   'lights and hot pixels; quantile takes --quantile (both need --resample)')
+                                   'lights and hot pixels; quantile takes --quantile; area weights every pixel with the part of '
+                                   'the cell that its footprint covers and leaves no holes between pixel centres on fine grids '
+                                   '(see --min-coverage); all but mean need --resample')
     resampleArgs.add_argument('--quantile', metavar='Q', type=float,
                               help='the quantile of a cell\'s pixels, in [0, 1], for --statistic quantile (numpy.quantile, '
                                    'method linear): 0.25 a background estimate, 0.9 a peak estimate')
+    resampleArgs.add_argument('--min-coverage', dest='minCoverage', metavar='F', type=float,
+                              help='for --statistic area: a cell is masked unless the pixels cover at least this fraction of it, '
+                                   'in [0, 1], default 0.5 (0: any overlap at all)')
     outputArgs = parser.add_argument_group('output')
     outputArgs.add_argument('--out', help='Output directory, by default the "converted" subdirectory of --data')
     outputArgs.add_argument('--overwrite', help='Overwrites existing files.', action='store_true')
@@ -144,6 +153,13 @@ def parseargs(argv=None):
             parser.error('--quantile must be in the range [0, 1]')
     elif args.quantile is not None:
         parser.error('--quantile is only usable with --statistic quantile')
+    if args.statistic == 'area':
+        if args.minCoverage is None:
+            args.minCoverage = 0.5
+        if not 0.0 <= args.minCoverage <= 1.0:
+            parser.error('--min-coverage must be in the range [0, 1]')
+    elif args.minCoverage is not None:
+        parser.error('--min-coverage is only usable with --statistic area')
     if args.withoutGeo and args.format == Format.netcdf:
         parser.error('--without-geo is only usable with --format cdf')
     if args.format == Format.cdf:
@@ -234,8 +250,8 @@ def extension(args):
 def convert_with_classes(args, frames, export):
     """Frame by frame through the mapping classes: the reference's flow, its resolution rule included."""
     from ..mapping.spacecraft import getMapping
-    from ..resample import (resample, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT, resampleQuantile,
-                            resampleQuantileMLatMLT)
+    from ..resample import (resample, resampleArea, resampleAreaMLatMLT, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT,
+                            resampleQuantile, resampleQuantileMLatMLT)
     for identifier, hdr, img_path in frames:
         path = target_path(args, identifier)
         if path is None:
@@ -252,6 +268,10 @@ def convert_with_classes(args, frames, export):
                 fn = resampleQuantile if args.grid == Grid.geo else resampleQuantileMLatMLT
                 mapping = fn(mapping, args.quantile,
                              **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
+            elif args.statistic == 'area':
+                fn = resampleArea if args.grid == Grid.geo else resampleAreaMLatMLT
+                mapping = fn(mapping, minCoverage=args.minCoverage,
+                             **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
             else:
                 fn = resample if args.grid == Grid.geo else resampleMLatMLT
                 mapping = fn(mapping, arcsecPerPx=args.resolution)
@@ -263,7 +283,8 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
     """The resampled grid of one frame (host arrays of the few hundred KB the pipeline returns) as the mapping that
     ``resample`` / ``resampleMLatMLT`` would have returned: a GenericMapping in geodetic coordinates; a grid that is
     regular in (MLat, SM longitude) goes through SM -> GEO like ``convertSMMappingToGeo`` (reference
-    mapping.py:1549-1559).  The elevation comes from the 'mean' block or, for median and quantile grids, the 'median' / 'quantile' block."""
+    mapping.py:1549-1559).  The elevation comes from the 'mean' block or, for median, quantile and area-weighted grids, the
+    'median' / 'quantile' / 'area' block."""
     from ..coordinates.transform import smToLatLon
     from ..mapping.mapping import GenericMapping
     lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
@@ -271,7 +292,7 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
         lat, lon = smToLatLon(lat, lon, t)
         lat_c, lon_c = smToLatLon(lat_c, lon_c, t)
     img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    block = res['mean'] if 'mean' in res else res['median'] if 'median' in res else res['quantile']
+    block = next(res[k] for k in ('mean', 'median', 'quantile', 'area') if k in res)
     return GenericMapping(lat, lon, lat_c, lon_c, ma.masked_invalid(block[:, :, -1]), altitude, img, cam, t, identifier)
 
 
@@ -332,7 +353,7 @@ def convert_with_pipeline(args, frames, export):
                                min_elevation=args.minElevation if args.minElevation >= 0 else None,
                                pxPerDeg=args.pxPerDeg or 10, magnetic=magnetic, keep_coordinates=False,
                                arcsecPerPx=None if args.pxPerDeg else args.resolution, statistic=args.statistic,
-                               quantile=args.quantile)
+                               quantile=args.quantile, minCoverage=args.minCoverage)
 
         def feed():
             # decoding a 12 Mpx JPEG takes ~100 ms of host time, the GPU 0.2 ms per frame: images are read ahead on a
@@ -376,7 +397,7 @@ def convert_with_pipeline(args, frames, export):
                     continue
                 host = dict(res)
                 host.update(grid_coordinates(res))
-                stat = args.statistic               # the name of the block: 'mean', 'median' or 'quantile'
+                stat = args.statistic               # the name of the block: 'mean', 'median', 'quantile' or 'area'
                 host[stat] = to_host(res[stat])
                 host.update(img=to_host(res['img'], dtype=first.dtype), mask=to_host(res['mask']).astype(bool))
                 print('storing', path)

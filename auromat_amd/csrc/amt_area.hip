@@ -77,8 +77,16 @@ struct area_mosaic_args {
     int n;
 };
 
-template <bool WIN> struct area_kernel_args { using type = area_args; };
-template <> struct area_kernel_args<true> { using type = area_mosaic_args; };
+// The frame of a sequence (amt_area_frame_async): the corners' x may be MLT hours, and only the pixels of the rows
+// [row_begin, row_end) are visited.
+struct area_seq_args : area_args {
+    int lon_from_mlt;
+    int row_begin, row_end;
+};
+
+template <bool WIN, bool SEQ> struct area_kernel_args { using type = area_args; };
+template <> struct area_kernel_args<true, false> { using type = area_mosaic_args; };
+template <> struct area_kernel_args<false, true> { using type = area_seq_args; };
 
 // The member of global workgroup b: the last i with block_start[i] <= b (a binary search over wave-uniform loads).
 __device__ __forceinline__ int area_member_of(const area_args&, unsigned) { return 0; }
@@ -96,6 +104,16 @@ __device__ __forceinline__ area_window frame_window(const area_args&, int) { ret
 __device__ __forceinline__ area_window frame_window(const area_mosaic_args& M, int m) { return M.members[m].W; }
 __device__ __forceinline__ unsigned first_block(const area_args&, int) { return 0; }
 __device__ __forceinline__ unsigned first_block(const area_mosaic_args& M, int m) { return (unsigned)M.block_start[m]; }
+// SEQ: the band of pixels the sweep covers, and a corner's x as it is stored
+__device__ __forceinline__ int64_t first_pixel(const area_seq_args& S) { return (int64_t)S.row_begin * S.width; }
+__device__ __forceinline__ int64_t end_pixel(const area_seq_args& S) { return (int64_t)S.row_end * S.width; }
+// MLT hours -> SM longitude, the expression of amt_median.hip (med_cell) and convertMappingToSM, each operation rounded on its own
+__device__ __forceinline__ double corner_x(const area_seq_args& S, double v) {
+#pragma clang fp contract(off)
+    if (!S.lon_from_mlt) return v;
+    const double d = v - 12.0;
+    return d / (24.0 / 360.0);
+}
 
 // Edge i of an axis: the double bin_index compares against.
 __device__ __forceinline__ double axis_edge(const axis_dev& ax, int i) {
@@ -201,8 +219,11 @@ __device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; } 
 // WIN = true (the binning of amt_area_mosaic_frames): the argument is the member table (area_mosaic_args); the workgroup finds
 // its member by the workgroup prefix, sweeps that member's pixels with the member's other workgroups and keeps only the cells of
 // the member's window.  The weights and the sums are the same integers either way.
-template <typename IMG_T, bool WIN>
-__global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_args<WIN>::type K) {
+// SEQ = true (amt_area_frame_async; not with WIN): the argument is the frame with a row band and the MLT switch (area_seq_args);
+// the sweep covers the pixels of the band only, whole waves from its first pixel on.
+template <typename IMG_T, bool WIN, bool SEQ = false>
+__global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_args<WIN, SEQ>::type K) {
+    static_assert(!(WIN && SEQ), "a mosaic member has no row band");
     const int member = WIN ? area_member_of(K, blockIdx.x) : 0;
     // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
     //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
@@ -210,13 +231,14 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_
     const area_window Wn = frame_window(K, member);
     const unsigned block0 = first_block(K, member);
     const unsigned nblocks = WIN ? first_block(K, member + 1) - block0 : gridDim.x;
-    const int64_t npix = (int64_t)A.height * A.width;
+    int64_t pix0 = 0, npix = (int64_t)A.height * A.width;
+    if constexpr (SEQ) pix0 = first_pixel(K), npix = end_pixel(K);
     const int64_t plane = WIN ? (int64_t)Wn.nx * Wn.ny : (int64_t)A.ax.nbin * A.ay.nbin;
     const int lane = threadIdx.x & 63;
     const IMG_T* img = static_cast<const IMG_T*>(A.img);
     // (whole waves run every iteration: the cooperative part below needs all 64 lanes)
     const int64_t per_sweep = (int64_t)nblocks * kAreaBlock;
-    for (int64_t base = (int64_t)(blockIdx.x - block0) * kAreaBlock + (threadIdx.x & ~63); base < npix; base += per_sweep) {
+    for (int64_t base = pix0 + (int64_t)(blockIdx.x - block0) * kAreaBlock + (threadIdx.x & ~63); base < npix; base += per_sweep) {
         const int64_t p = base + lane;
         area_pixel P;
         P.nxr = P.nyr = 0;
@@ -241,7 +263,9 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_
                 bool fin = true;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const double lo = A.lon[at[i]], la = A.lat[at[i]];
+                    double lo = A.lon[at[i]];
+                    if constexpr (SEQ) lo = corner_x(K, lo);
+                    const double la = A.lat[at[i]];
                     fin = fin && finite(lo) && finite(la);
                     const double x = A.lon_wrap ? wrap180_shifted(lo) : lo;
                     P.X[i] = x;
@@ -453,6 +477,27 @@ inline dim3 blocks_for(int64_t n) {
     return dim3(static_cast<unsigned>(blocks));
 }
 
+// The frame of amt_area_frame and amt_area_frame_async as the kernel takes it.
+void fill_frame(area_args* A, const double* lat, const double* lon, const double* lat_c, const double* elev, const void* img,
+                int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width, double min_elevation,
+                const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, unsigned long long* acc) {
+    A->lat = lat;
+    A->lon = lon;
+    A->lat_c = lat_c;
+    A->elev = elev;
+    A->img = img;
+    A->mask = center_mask;
+    A->height = height;
+    A->width = width;
+    A->nch = nchan;
+    A->min_elev = min_elevation;
+    A->use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
+    make_axis(xaxis, &A->ax);
+    make_axis(yaxis, &A->ay);
+    A->lon_wrap = lon_wrap ? 1 : 0;
+    A->acc = acc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -469,21 +514,8 @@ int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const dou
     AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
     AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
     area_args A;
-    A.lat = lat;
-    A.lon = lon;
-    A.lat_c = lat_c;
-    A.elev = elev;
-    A.img = img;
-    A.mask = center_mask;
-    A.height = height;
-    A.width = width;
-    A.nch = nchan;
-    A.min_elev = min_elevation;
-    A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-    make_axis(xaxis, &A.ax);
-    make_axis(yaxis, &A.ay);
-    A.lon_wrap = lon_wrap ? 1 : 0;
-    A.acc = reinterpret_cast<unsigned long long*>(acc);
+    fill_frame(&A, lat, lon, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap,
+               reinterpret_cast<unsigned long long*>(acc));
     const dim3 grid = blocks_for((int64_t)height * width), block(kAreaBlock);
     if (img_dtype == 2)
         hipLaunchKernelGGL((k_area_frame<uint16_t, false>), grid, block, 0, ctx->stream, A);
@@ -522,6 +554,58 @@ int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32
         ctx->last_error = "amt_area_frame_finalize: a cell's total weight exceeds 2^40 (covered more than 256 times over)";
         return AMT_EDOMAIN;
     }
+    return AMT_OK;
+}
+
+int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, const double* lat_c, const double* elev,
+                         const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
+                         int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                         int lon_from_mlt, int32_t row_begin, int32_t row_end, uint64_t min_weight, double* area, void* out_img,
+                         uint8_t* out_mask, double* out_coverage, uint32_t* over) {
+    AMT_CHECK_CTX(ctx);
+    // (the checks of amt_area_frame and amt_area_frame_finalize)
+    AMT_REQUIRE(ctx, lat && lon && lat_c && xaxis && yaxis, "NULL argument");
+    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, (int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31), "frames below 2^31 pixels");
+    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
+    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, out_img == nullptr || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
+    AMT_REQUIRE(ctx, 0 <= row_begin && row_begin <= row_end && row_end <= height, "0 <= row_begin <= row_end <= height");
+    if (amt_set_device(ctx)) return AMT_EHIP;
+    // the workspace: the accumulator planes, then a word for the flag of a caller that passes none; zeroed together
+    const int nx = xaxis->nbin, ny = yaxis->nbin;
+    const size_t acc_bytes = (size_t)(nchan + 2) * (size_t)nx * (size_t)ny * sizeof(unsigned long long);
+    char* ws = static_cast<char*>(amt_workspace(ctx, acc_bytes + 256));
+    if (ws == nullptr) {
+        ctx->last_error = "amt_area_frame_async: no device memory for the workspace";
+        return AMT_ENOMEM;
+    }
+    AMT_HIP(ctx, hipMemsetAsync(ws, 0, acc_bytes + 256, ctx->stream));
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws);
+    unsigned int* flag = over ? over : reinterpret_cast<unsigned int*>(ws + acc_bytes);
+    area_seq_args S;
+    fill_frame(&S, lat, lon, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap, acc);
+    S.lon_from_mlt = lon_from_mlt ? 1 : 0;
+    S.row_begin = row_begin;
+    S.row_end = row_end;
+    const dim3 block(kAreaBlock);
+    const dim3 grid = blocks_for((int64_t)(row_end - row_begin) * width);
+    if (img_dtype == 2)
+        hipLaunchKernelGGL((k_area_frame<uint16_t, false, true>), grid, block, 0, ctx->stream, S);
+    else
+        hipLaunchKernelGGL((k_area_frame<uint8_t, false, true>), grid, block, 0, ctx->stream, S);
+    AMT_LAUNCH_CHECK(ctx);
+    const unsigned long long least = min_weight < 1 ? 1ull : (unsigned long long)min_weight;
+    const dim3 fgrid = blocks_for((int64_t)nx * ny);
+    if (img_dtype == 2)
+        hipLaunchKernelGGL((k_area_finalize<uint16_t>), fgrid, block, 0, ctx->stream, acc, nx, ny, nchan, least, area,
+                           static_cast<uint16_t*>(out_img), out_mask, out_coverage, flag);
+    else
+        hipLaunchKernelGGL((k_area_finalize<uint8_t>), fgrid, block, 0, ctx->stream, acc, nx, ny, nchan, least, area,
+                           static_cast<uint8_t*>(out_img), out_mask, out_coverage, flag);
+    AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
 

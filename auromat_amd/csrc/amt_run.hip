@@ -32,6 +32,12 @@ struct amt_run {
     long long frames_done;
     bool has_quantile;                      // amt_run_set_quantile: the median pass selects `quantile` instead
     double quantile;
+    // area-weighted sequences (cfg.statistic == 2): the least weight of a valid cell (amt_run_set_min_coverage), and one device
+    // word per result record of the call in progress, zeroed by amt_run_begin on the context's stream: frame k's pass ORs its
+    // overflow flag into word k (amt_run_area_overflow reads them)
+    uint64_t min_weight;
+    uint32_t* over;
+    int over_capacity;
     // the call in progress (amt_run_begin ... amt_run_end)
     bool active, full;
     double* grids;
@@ -114,8 +120,8 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     AMT_REQUIRE(ctx, config->batch >= 1 && config->batch <= AMT_PIPE_MAX_BATCH, "batch out of range");
     AMT_REQUIRE(ctx, config->n_slots >= 2 * config->batch && config->slots != nullptr, "n_slots must be at least 2 * batch");
     AMT_REQUIRE(ctx, config->arcsec_per_px > 0 || (config->lat_px_per_deg > 0 && config->lon_px_per_deg > 0), "px per degree must be positive");
-    AMT_REQUIRE(ctx, config->statistic == 0 || config->statistic == 1, "statistic must be 0 (mean) or 1 (median)");
-    AMT_REQUIRE(ctx, !(config->arcsec_per_px > 0) || ((config->statistic == 1 || !config->two_pass) && config->n_slots >= 3 * config->batch),
+    AMT_REQUIRE(ctx, config->statistic >= 0 && config->statistic <= 2, "statistic must be 0 (mean), 1 (median) or 2 (area-weighted)");
+    AMT_REQUIRE(ctx, !(config->arcsec_per_px > 0) || ((config->statistic != 0 || !config->two_pass) && config->n_slots >= 3 * config->batch),
                 "arcsec_per_px: the box-first plan is a single-pass plan and needs n_slots >= 3 * batch");
     amt_run* run = new (std::nothrow) amt_run();
     if (run == nullptr) return AMT_ENOMEM;
@@ -126,6 +132,10 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     run->frames_done = 0;
     run->has_quantile = false;
     run->quantile = 0.5;
+    run->min_weight = (uint64_t)1 << 31;
+    run->over = nullptr;
+    run->over_capacity = 0;
+    run->max_frames = 0;
     const int ns = config->n_slots;
     run->outs.assign(config->slots, config->slots + ns);
     run->cfg.slots = nullptr;
@@ -156,8 +166,8 @@ int amt_run_create(amt_ctx* ctx, const amt_run_config* config, amt_run** out_run
     }
     for (int i = 0; i < ns; ++i) {
         int rc = amt_pipe_create(ctx, &run->pipes[i]);
-        // (median: the big kernel writes the slot's arrays and bins nothing; its box in the grid's coordinates)
-        if (rc == AMT_OK) rc = amt_pipe_set_plan(run->pipes[i], config->statistic == 1 ? 2 : config->two_pass);
+        // (median, area: the big kernel writes the slot's arrays and bins nothing; its box in the grid's coordinates)
+        if (rc == AMT_OK) rc = amt_pipe_set_plan(run->pipes[i], config->statistic != 0 ? 2 : config->two_pass);
         if (rc != AMT_OK) {
             amt_run_destroy(run);
             return rc;
@@ -185,6 +195,7 @@ int amt_run_destroy(amt_run* run) {
     for (hipEvent_t e : run->img_free)
         if (e != nullptr) (void)hipEventDestroy(e);
     if (run->copy_stream) (void)hipStreamDestroy(run->copy_stream);
+    if (run->over) (void)hipFree(run->over);
     delete run;
     return AMT_OK;
 }
@@ -197,6 +208,30 @@ int amt_run_set_quantile(amt_run* run, double q) {
     AMT_REQUIRE(ctx, q >= 0.0 && q <= 1.0, "the quantile must lie in [0, 1]");
     run->has_quantile = true;
     run->quantile = q;
+    return AMT_OK;
+}
+
+int amt_run_set_min_coverage(amt_run* run, uint64_t min_weight) {
+    if (run == nullptr) return AMT_EINVAL;
+    amt_ctx* ctx = run->ctx;
+    AMT_REQUIRE(ctx, run->cfg.statistic == 2, "the runner was not created with statistic = 2");
+    AMT_REQUIRE(ctx, !run->active && run->frames_done == 0, "to be called before the first push");
+    run->min_weight = min_weight;
+    return AMT_OK;
+}
+
+int amt_run_area_overflow(amt_run* run, int32_t* flags, int32_t n) {
+    if (run == nullptr) return AMT_EINVAL;
+    amt_ctx* ctx = run->ctx;
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, run->cfg.statistic == 2, "the runner was not created with statistic = 2");
+    AMT_REQUIRE(ctx, !run->active, "to be called after amt_run_end");
+    AMT_REQUIRE(ctx, n >= 0 && n <= run->max_frames && (n == 0 || flags != nullptr), "n beyond the records of the last call");
+    if (n == 0) return AMT_OK;
+    if (amt_set_device(ctx)) return AMT_EHIP;
+    static_assert(sizeof(int32_t) == sizeof(uint32_t), "one word per record");
+    AMT_HIP(ctx, hipMemcpyAsync(flags, run->over, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return AMT_OK;
 }
 
@@ -225,12 +260,14 @@ namespace {
 // Median sequences: the exact grid of a frame the big kernel has written the slot's arrays for (status 1 from amt_pipe_wait),
 // laid out as amt_pipe_general_layout and the single-pass plan lay it out (amt_gl::layout_of_box), in (MLat, SM longitude) on a
 // magnetic grid.  What the median pass does not cover keeps status 1: a pole of the grid in view, exact centres, slots without
-// the arrays.
-void median_layout(const amt_run* run, int slot, amt_pipe_result* pr) {
+// the arrays.  Area-weighted sequences (area = true): the same rule on the arrays the area pass reads — the corners and their
+// centres' latitude (the NaN test) in place of the centres.
+void median_layout(const amt_run* run, int slot, amt_pipe_result* pr, bool area = false) {
     const amt_run_config& cfg = run->cfg;
     const amt_georef_out& o = run->outs[slot];
     const double* b = pr->bbox;
-    const bool have = cfg.magnetic ? (o.mlat_c && o.mlt_c) : (o.lat_c && o.lon_c);
+    const bool have = area ? (cfg.magnetic ? (o.mlat && o.mlt && o.mlat_c) : (o.lat && o.lon && o.lat_c))
+                           : (cfg.magnetic ? (o.mlat_c && o.mlt_c) : (o.lat_c && o.lon_c));
     if (pr->status != 1 || b[7] != 0 || !cfg.fast_center || !have || !o.elev || o.row_layout != 0 || !(b[6] > 0)) return;
     amt_grid g;
     int32_t wrapped = 0;
@@ -288,17 +325,20 @@ int run_finish(amt_run* run, int k0, int count) {
             if (int rc = amt_pipe_wait(run->pipes[slot], &pr)) return rc;
             r.retried = 1;
         }
-        bool general = false, median = false;
+        bool general = false, median = false, area = false;
         if (cfg.statistic == 1) {
             median_layout(run, slot, &pr);
             median = pr.status == 0;
+        } else if (cfg.statistic == 2) {
+            median_layout(run, slot, &pr, true);
+            area = pr.status == 0;
         } else if (pr.status == 1) {
             // the two-pass plan, natively, when the frame's coordinate arrays exist and nothing else is needed
             if (int rc = amt_pipe_general_layout(run->pipes[slot], &pr)) return rc;
             general = pr.status == 0;
         }
         r.status = pr.status;
-        r.two_pass = general || median ? 1 : 0;
+        r.two_pass = general || median || area ? 1 : 0;
         std::memcpy(r.bbox, pr.bbox, sizeof(r.bbox));
         r.edge_pixels = pr.edge_pixels;
         if (pr.status != 0) {
@@ -339,6 +379,26 @@ int run_finish(amt_run* run, int k0, int count) {
                                              &pr.grid.xaxis, &pr.grid.yaxis, pr.lon_wrapped, mag ? 1 : 0, f_mean, f_img, f_mask,
                                              f_mean + 4 * cells);
             if (rc) return rc;
+            if (run->img[slot] == run->own_img[slot] && run->own_img[slot] != nullptr) {
+                AMT_HIP(ctx, hipEventRecord(run->img_free[slot], ctx->stream));
+                run->img_busy[slot] = 1;
+            }
+        } else if (area) {
+            // where the median pass goes: on the context's stream behind the frame's big kernel, sharing that stream's
+            // workspace with the other frames' passes.  The rows that can be binned (amt_georef_image_rows is conservative for
+            // exactly the pixels this pass admits: centre on the shell, elevation >= min_elevation) — of a host image only those
+            // were uploaded, the others hold an older frame's bytes.
+            const amt_georef_out& o = run->outs[slot];
+            const bool mag = cfg.magnetic != 0;
+            int32_t r0 = 0, r1 = cfg.height;
+            if (int rc = amt_georef_image_rows(&run->prm[slot], cfg.min_elevation, &r0, &r1)) return rc;
+            r0 = std::min(std::max(r0, 0), cfg.height);
+            r1 = std::min(std::max(r1, r0), cfg.height);
+            if (int rc = amt_area_frame_async(ctx, mag ? o.mlat : o.lat, mag ? o.mlt : o.lon, mag ? o.mlat_c : o.lat_c, o.elev,
+                                              run->img[slot], cfg.img_dtype, 3, nullptr, cfg.height, cfg.width, cfg.min_elevation,
+                                              &pr.grid.xaxis, &pr.grid.yaxis, pr.lon_wrapped, mag ? 1 : 0, r0, r1, run->min_weight,
+                                              f_mean, f_img, f_mask, f_mean + 4 * cells, run->over + k))
+                return rc;
             if (run->img[slot] == run->own_img[slot] && run->own_img[slot] != nullptr) {
                 AMT_HIP(ctx, hipEventRecord(run->img_free[slot], ctx->stream));
                 run->img_busy[slot] = 1;
@@ -545,6 +605,23 @@ int amt_run_begin(amt_run* run, double* grids, int64_t grids_capacity, void* ima
     if (int rc = amt_pipe_finalize_stream(run->pipes[0], &fin)) return rc;
     AMT_HIP(ctx, hipEventRecord(run->entry, ctx->stream));
     AMT_HIP(ctx, hipStreamWaitEvent(static_cast<hipStream_t>(fin), run->entry, 0));
+    if (run->cfg.statistic == 2 && max_frames > 0) {
+        if (max_frames > run->over_capacity) {
+            // (hipFree waits for whatever still uses the old words)
+            if (run->over) (void)hipFree(run->over);
+            run->over = nullptr;
+            run->over_capacity = 0;
+            const int cap = std::max(max_frames, 64);
+            if (hipMalloc(reinterpret_cast<void**>(&run->over), (size_t)cap * sizeof(uint32_t)) != hipSuccess) {
+                (void)hipGetLastError();
+                run->over = nullptr;
+                ctx->last_error = "amt_run_begin: no device memory for the overflow flags";
+                return AMT_ENOMEM;
+            }
+            run->over_capacity = cap;
+        }
+        AMT_HIP(ctx, hipMemsetAsync(run->over, 0, (size_t)max_frames * sizeof(uint32_t), ctx->stream));
+    }
     run->grids = grids, run->grids_capacity = grids_capacity;
     run->images = static_cast<char*>(images), run->images_capacity = images_capacity;
     run->results = results, run->max_frames = max_frames;

@@ -899,6 +899,17 @@ class _SMMapping(GenericMapping):
         return Location(mlat[0], mltToSmLon(mlt)[0])
 
 
+def mlt_to_sm_lon(mlt):
+    """
+    mltToSmLon (reference transform.py:388-401) on a device tensor with the reference's bits: ``(mlt - 12) / (24 / 360)`` as a
+    division.  The divisor is a device tensor on purpose: torch divides a device tensor by a Python number as a multiplication
+    with its reciprocal — here 15.0 —, which differs from the quotient in the last bit for one value in nine, and the kernels
+    (the fused binning, ``lon_from_mlt`` of the median and area passes) divide.  The area weights see that bit.
+    """
+    import torch
+    return torch.div(mlt - 12, torch.full((), 24 / 360, dtype=mlt.dtype, device=mlt.device))
+
+
 def convertMappingToSM(mapping):
     """
     Return a new mapping with the coordinates transformed to solar magnetic latitudes and
@@ -909,8 +920,7 @@ def convertMappingToSM(mapping):
     mlat_c, mlt_c = mapping._mlatmlt_tensors(True)
     new = fd.shallow_copy()
     new.lat, new.lat_c = mlat, mlat_c
-    new.lon = (mlt - 12) / (24 / 360)          # mltToSmLon (transform.py:388-401)
-    new.lon_c = (mlt_c - 12) / (24 / 360)
+    new.lon, new.lon_c = mlt_to_sm_lon(mlt), mlt_to_sm_lon(mlt_c)
     new.mlat = new.mlt = new.mlat_c = new.mlt_c = None
     new.bbox = None
     # masks follow the geodetic masks (astrometry.py:181-182, mapping.py:1540-1546)

@@ -31,9 +31,9 @@ import numpy as np
 
 from .frame import FrameData, PaddedFrameData, has_array
 from .mapping.astrometry import frame_params, pole_in_view, run_frame
-from .mapping.mapping import bounding_box_from_reduction, grid_box_from_reduction
-from .resample import (_px_per_deg, cached_grid, grid_coordinates, quantile_list, resample_frame, resample_frame_median,
-                       resample_frame_quantile)
+from .mapping.mapping import bounding_box_from_reduction, grid_box_from_reduction, mlt_to_sm_lon
+from .resample import (_px_per_deg, area_overflow_error, cached_grid, grid_coordinates, min_coverage_weight, quantile_list,
+                       resample_frame, resample_frame_area, resample_frame_median, resample_frame_quantile)
 from ._native import PIPE_MAX_EDGE_PIXELS, Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
 
 NEG_INF = float('-inf')
@@ -622,14 +622,24 @@ class FramePipeline(object):
             done.append(q._fused_wrap(*o, keep_on_device=keep_on_device))
         return done
 
-    def resample(self, pxPerDeg=10, containsPole=None, magnetic=False, keep_on_device=False, statistic='mean', q=None):
+    def resample(self, pxPerDeg=10, containsPole=None, magnetic=False, keep_on_device=False, statistic='mean', q=None,
+                 minCoverage=None):
         """Stages 2 + 3.  magnetic=True bins on the (MLat, SM longitude) grid (resampleMLatMLT).  statistic='median': the
         median of every cell (resampleMedian / resampleMedianMLatMLT) by the two-pass plan; the result holds 'median'
         in place of 'mean'.  statistic='quantile': the quantile(s) `q` of every cell (resampleQuantile /
         resampleQuantileMLatMLT; a number or up to 8 numbers in [0, 1]) in the same way; the result is that of
-        :func:`auromat_amd.resample.resample_frame_quantile`, 'quantile' and 'img' with a leading axis over `q`."""
-        assert statistic in ('mean', 'median', 'quantile')
+        :func:`auromat_amd.resample.resample_frame_quantile`, 'quantile' and 'img' with a leading axis over `q`.
+        statistic='area': the area-weighted mean (resampleArea / resampleAreaMLatMLT; `minCoverage` in [0, 1], 0.5 when None) by
+        :func:`auromat_amd.resample.resample_frame_area` on the frame's corner arrays — on a magnetic grid the SM copy whose
+        corner longitudes are formed below —, never fused; the result holds 'area' and 'coverage' in place of 'mean' and
+        'count'.  `minCoverage` with another statistic is a ValueError."""
+        assert statistic in ('mean', 'median', 'quantile', 'area')
         assert (q is not None) == (statistic == 'quantile'), "q goes with statistic='quantile'"
+        if minCoverage is not None and statistic != 'area':
+            raise ValueError("minCoverage goes with statistic='area'")
+        if statistic == 'area':
+            minCoverage = 0.5 if minCoverage is None else minCoverage
+            min_coverage_weight(minCoverage)
         if statistic == 'quantile':
             q = quantile_list(q)
         pxPerDeg = _px_per_deg(pxPerDeg)
@@ -675,7 +685,7 @@ class FramePipeline(object):
             assert self.with_mag
             sm = fd.shallow_copy()
             sm.lat, sm.lat_c = fd.mlat, fd.mlat_c
-            sm.lon, sm.lon_c = (fd.mlt - 12) / (24 / 360), (fd.mlt_c - 12) / (24 / 360)
+            sm.lon, sm.lon_c = mlt_to_sm_lon(fd.mlt), mlt_to_sm_lon(fd.mlt_c)
             # corners of centres that pass the elevation threshold, in SM coordinates
             red = self._reduce_bbox(sm.lat, sm.lon)
             if red[6] == 0:
@@ -693,15 +703,19 @@ class FramePipeline(object):
         if statistic == 'quantile':
             return resample_frame_quantile(fd, self.altitude, bb, pxPerDeg, q, bb.containsDiscontinuity, pole,
                                            min_elevation=self.min_elevation, keep_on_device=keep_on_device)
+        if statistic == 'area':
+            return resample_frame_area(fd, self.altitude, bb, pxPerDeg, bb.containsDiscontinuity, pole,
+                                       min_elevation=self.min_elevation, keep_on_device=keep_on_device, minCoverage=minCoverage)
         return resample_frame(fd, self.altitude, bb, pxPerDeg, bb.containsDiscontinuity, pole,
                               min_elevation=self.min_elevation, keep_on_device=keep_on_device, shard=self.shard)
 
     def run(self, wcsHeader, altitude, cameraPosGCRS, photoTime, img=None, fast=True, min_elevation=10.0,
             pxPerDeg=10, containsPole=None, magnetic=False, params=None, keep_on_device=False, fuse=False,
-            arcsecPerPx=None, dirs=None, statistic='mean', q=None):
+            arcsecPerPx=None, dirs=None, statistic='mean', q=None, minCoverage=None):
         """One frame end to end; returns the dict of :func:`auromat_amd.resample.resample_frame` (statistic='median': of
         :func:`auromat_amd.resample.resample_frame_median`, statistic='quantile' with the quantile(s) `q`: of
-        :func:`auromat_amd.resample.resample_frame_quantile`; neither is fused).  `arcsecPerPx` (has
+        :func:`auromat_amd.resample.resample_frame_quantile`, statistic='area' with `minCoverage`: of
+        :func:`auromat_amd.resample.resample_frame_area`; none of them is fused).  `arcsecPerPx` (has
         precedence over pxPerDeg, like the reference's resample()): the box-first plan — a box pass, px/deg from the frame's
         own bounding box, then the single-pass launch (``fuse``) or the two-pass plan; the px/deg pair used is in the
         result as 'pxPerDeg'."""
@@ -736,7 +750,8 @@ class FramePipeline(object):
         self.georef(wcsHeader, altitude, cameraPosGCRS, photoTime, fast, min_elevation, params=params,
                     fuse_pxPerDeg=pxPerDeg if fuse else None, fuse_magnetic=bool(magnetic), coarse_started=coarse_started,
                     dirs=dirs, pole_in_view=-1 if containsPole is None else int(bool(containsPole)))
-        res = self.resample(pxPerDeg, containsPole, magnetic, keep_on_device=keep_on_device, statistic=statistic, q=q)
+        res = self.resample(pxPerDeg, containsPole, magnetic, keep_on_device=keep_on_device, statistic=statistic, q=q,
+                            minCoverage=minCoverage)
         res['pxPerDeg'] = tuple(pxPerDeg)
         return res
 
@@ -854,18 +869,19 @@ class NativeResults(object):
         seq = self._seq
         fd = seq.pipes[0].fd
         ppd = (r.lat_px_per_deg, r.lon_px_per_deg)
-        stat = seq.statistic            # 'mean', 'median' or 'quantile': the name of the block in the result
+        stat = seq.statistic            # 'mean', 'median', 'quantile' or 'area': the name of the block in the result
+        cnt = 'coverage' if stat == 'area' else 'count'     # (the area pass writes the coverage where the others count)
         out, packed, mean, count, img, mask, _ = _frame_block(
             r.grid, ppd, r.bbox, bool(r.lon_wrapped), bool(r.contains_pole), r.altitude, self._grids, r.grid_offset, self._images,
             r.image_offset, fd.img_dtype != np.uint8)
         out.update(magnetic=seq.magnetic, pxPerDeg=ppd)
         if self._keep:
-            out.update(img=img, mask=mask, count=count, packed=packed)
-            out[stat] = mean
+            out.update(img=img, mask=mask, packed=packed)
+            out[stat], out[cnt] = mean, count
             return out
         out.update(grid_coordinates(out))
-        out.update(img=to_host(img, dtype=fd.img_dtype), mask=to_host(mask).astype(bool), count=to_host(count))
-        out[stat] = to_host(mean)
+        out.update(img=to_host(img, dtype=fd.img_dtype), mask=to_host(mask).astype(bool))
+        out[stat], out[cnt] = to_host(mean), to_host(count)
         return out
 
     # ---- what the gather needs, without per-frame objects (auromat_amd.sequence) -----------------------------------
@@ -915,7 +931,7 @@ class SequencePipeline(object):
     def __init__(self, width, height, nchan=3, img_dtype=np.uint16, device=None, altitude=110, fast=True,
                  min_elevation=10.0, pxPerDeg=10, plan='single-pass', bin_stream=True, shared_image=None,
                  magnetic=False, batch=3, own_image_buffers=True, keep_coordinates=True, launch_streams=1,
-                 geodetic_arrays=None, arcsecPerPx=None, padded=None, statistic='mean', quantile=None):
+                 geodetic_arrays=None, arcsecPerPx=None, padded=None, statistic='mean', quantile=None, minCoverage=None):
         import torch
         assert plan in ('single-pass', 'two-pass')
         # statistic='median' (resampleMedian / resampleMedianMLatMLT): every frame through the native runner's median pass —
@@ -923,10 +939,21 @@ class SequencePipeline(object):
         # (amt_run_config.statistic, amt_median_frame_async); the results carry 'median' in place of 'mean'
         # statistic='quantile', quantile=q (resampleQuantile / resampleQuantileMLatMLT): the same pass selecting ONE quantile
         # (amt_run_set_quantile, amt_quantile_frame_async); the results carry 'quantile'
-        assert statistic in ('mean', 'median', 'quantile')
+        # statistic='area', minCoverage=f (resampleArea / resampleAreaMLatMLT; 0.5 when None): the runner's area pass on the
+        # buffer's corner arrays, centre latitudes and elevation (amt_run_config.statistic = 2, amt_area_frame_async,
+        # amt_run_set_min_coverage); the results carry 'area' and 'coverage' in place of 'mean' and 'count'
+        assert statistic in ('mean', 'median', 'quantile', 'area')
+        if statistic == 'area' and quantile is not None:
+            raise ValueError("quantile goes with statistic='quantile', not with 'area'")
         assert (quantile is not None) == (statistic == 'quantile'), "quantile goes with statistic='quantile'"
+        if minCoverage is not None and statistic != 'area':
+            raise ValueError("minCoverage goes with statistic='area'")
         self.statistic = statistic
         self.quantile = None
+        self.minCoverage = None
+        if statistic == 'area':
+            self.minCoverage = 0.5 if minCoverage is None else minCoverage
+            self._min_weight = min_coverage_weight(self.minCoverage)
         if statistic == 'quantile':
             if np.ndim(quantile) != 0:
                 raise ValueError('a sequence pipeline takes one quantile, got {!r}'.format(quantile))
@@ -1209,7 +1236,7 @@ class SequencePipeline(object):
             cfg = RunConfig(width=q.width, height=q.height, img_dtype=1 if q.fd.img_dtype == np.uint8 else 2, fast_center=1 if self.fast else 0,
                             magnetic=1 if self.magnetic else 0, batch=self.batch, use_hints=1 if self.use_hints else 0,
                             n_slots=nb, two_pass=0 if self.single_pass else 1,
-                            statistic=0 if self.statistic == 'mean' else 1, altitude=float(self.altitude),
+                            statistic={'mean': 0, 'area': 2}.get(self.statistic, 1), altitude=float(self.altitude),
                             min_elevation=NEG_INF if self.min_elevation is None else float(self.min_elevation),
                             lat_px_per_deg=float(self.pxPerDeg[0]) if self.pxPerDeg else 0.0,
                             lon_px_per_deg=float(self.pxPerDeg[1]) if self.pxPerDeg else 0.0, slots=slots,
@@ -1219,8 +1246,17 @@ class SequencePipeline(object):
             self._run = handle
             if self.statistic == 'quantile':
                 self.ctx.check(self.ctx._lib.amt_run_set_quantile(handle, self.quantile))
+            if self.statistic == 'area':
+                self.ctx.check(self.ctx._lib.amt_run_set_min_coverage(handle, self._min_weight))
             self._run_hints = self.use_hints
         return self._run
+
+    def _area_overflow(self, n):
+        """The overflow words of the first `n` frames of the runner call that has just ended (amt_run_area_overflow: waits for
+        the stream; the one wait an area sequence adds), as an int32 array."""
+        flags = (C.c_int32 * n)()
+        self.ctx.check(self.ctx._lib.amt_run_area_overflow(self._run, flags, n))
+        return np.frombuffer(flags, dtype=np.int32)
 
     def _hint_native_reset(self):
         self.ctx.check(self.ctx._lib.amt_run_reset_hints(self._run))
@@ -1233,7 +1269,8 @@ class SequencePipeline(object):
                 pass
             self._run = None
 
-    def _process_native(self, frames, keep_on_device):
+    def _process_native(self, frames, keep_on_device, index_base=0):
+        """`index_base`: the index of frames[0] in the process() call (a frame named in an error counts from its start)."""
         import torch
         ctx = self.ctx
         n = len(frames)
@@ -1290,6 +1327,10 @@ class SequencePipeline(object):
                     lib.amt_run_destroy(run)
                     self._run = None
                     raise
+                if self.statistic == 'area' and done.value > 0:
+                    over = np.flatnonzero(self._area_overflow(done.value))
+                    if len(over):
+                        raise area_overflow_error(index_base + done_total + int(over[0]))
                 g.record_stream(caller)
                 im.record_stream(caller)
                 arenas.append((done_total, done.value, g, im))
@@ -1342,10 +1383,11 @@ class SequencePipeline(object):
                     ppd = (table['lat_px_per_deg'][k], table['lon_px_per_deg'][k]) if self.arcsecPerPx else self.pxPerDeg
                     # (median: the frames the runner's median pass does not cover — a pole in view, exact centres — by
                     # resample_frame_median on the frame's arrays, what resampleMedian / resampleMedianMLatMLT run; quantile:
-                    # likewise by resample_frame_quantile, its one quantile without the leading axis)
+                    # likewise by resample_frame_quantile, its one quantile without the leading axis; area: by
+                    # resample_frame_area with the pipeline's minCoverage)
                     res = q.run(f[0], alt, f[1], f[2], fast=self.fast, min_elevation=self.min_elevation, pxPerDeg=ppd,
                                 magnetic=self.magnetic, keep_on_device=keep_on_device, fuse=False,
-                                statistic=self.statistic, q=self.quantile)
+                                statistic=self.statistic, q=self.quantile, minCoverage=self.minCoverage)
                     if self.statistic == 'quantile':
                         res['quantile'], res['img'] = res['quantile'][0], res['img'][0]
                     res['magnetic'] = self.magnetic
@@ -1476,7 +1518,7 @@ class SequencePipeline(object):
         return out
 
     def _process_median(self, frames, keep_on_device, on_batch):
-        """process() with statistic='median' or 'quantile': the native runner, in pieces of up to `median_chunk` frames (an iterator — the
+        """process() with statistic='median', 'quantile' or 'area': the native runner, in pieces of up to `median_chunk` frames (an iterator — the
         convert driver's generator of decoded host images — is consumed piece by piece).  Device-resident and pinned images
         go to the runner as they are; any other image is copied to the device first, on the caller's stream."""
         import torch
@@ -1494,13 +1536,13 @@ class SequencePipeline(object):
                         a = a.view(np.int16)
                     img = torch.from_numpy(a).to(self.ctx.device)
                 assert type(f[0]) is dict and tuple(img.shape) == shape, \
-                    "statistic='median' / 'quantile': frames are (header dict, cameraPosGCRS, photoTime, image[, altitude])"
+                    "statistic='median' / 'quantile' / 'area': frames are (header dict, cameraPosGCRS, photoTime, image[, altitude])"
                 chunk.append((f[0], f[1], f[2], img) + tuple(f[4:]))
                 if len(chunk) == self.median_chunk:
                     break
             if not chunk:
                 break
-            got = list(self._process_native(chunk, keep_on_device))
+            got = list(self._process_native(chunk, keep_on_device, index_base=len(out)))
             if on_batch is not None:
                 on_batch(len(out), got)
             out.extend(got)

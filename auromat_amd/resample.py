@@ -316,6 +316,14 @@ def min_coverage_weight(minCoverage):
     return max(1, int(np.rint(v * 4294967296.0)))
 
 
+def area_overflow_error(frame=None):
+    """The ValueError for ``AMT_EDOMAIN`` / a set overflow flag of the area-weighted binning; `frame`: the index of the frame in a
+    sequence."""
+    where = '' if frame is None else ' (frame {} of the sequence)'.format(frame)
+    return ValueError('resampleArea: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
+                      'fit (is the resolution far too low for this mapping?)' + where)
+
+
 def resampleArea(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, minCoverage=0.5):
     """
     Area-weighted (conservative) resampling: like :func:`resample` with ``method='mean'`` on the same grid, but a pixel is the
@@ -774,6 +782,9 @@ def resample_frame_area(fd, altitude, boundingBox, pxPerDeg, containsDiscontinui
     import torch
     least = min_coverage_weight(minCoverage)
     ctx = fd.ctx
+    # (the accumulators are zeroed by torch on its current stream and added to by the library on the context's: the same one,
+    #  also after a sequence pipeline has left the context on its own stream)
+    Context.current(ctx.device)
     grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
                                                min_elevation, outline, None)
     lat, lon = fd.lat, fd.lon
@@ -791,8 +802,7 @@ def resample_frame_area(fd, altitude, boundingBox, pxPerDeg, containsDiscontinui
     rc = ctx._lib.amt_area_frame_finalize(ctx.handle, ptr(acc), grid.nx, grid.ny, nch, fd.img_dtype_code or 1, least, ptr(area),
                                           ptr(img) if nch else None, ptr(mask), ptr(coverage))
     if rc == -5:                            # AMT_EDOMAIN
-        raise ValueError('resampleArea: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
-                         'fit (is the resolution far too low for this mapping?)')
+        raise area_overflow_error()
     ctx.check(rc)
     if not nch:
         img.zero_()                         # (ny,nx,1) so that the result has an image; no kernel writes it without channels

@@ -45,7 +45,9 @@ extern "C" {
 /* 10, additions only (no struct changed, the number stays): quantile binning — amt_quantile_frame, amt_quantile_frame_async,
  *    amt_quantile_rank, amt_run_set_quantile, AMT_QUANTILES_MAX (auromat_amd.resample.resampleQuantile); the median and quantile
  *    mosaics; area-weighted binning — amt_area_frame, amt_area_frame_finalize (auromat_amd.resample.resampleArea);
- *    area-weighted mosaics — amt_area_mosaic_frames, amt_area_mosaic_member */
+ *    area-weighted mosaics — amt_area_mosaic_frames, amt_area_mosaic_member; area-weighted sequences — amt_area_frame_async,
+ *    amt_run_config.statistic = 2, amt_run_set_min_coverage, amt_run_area_overflow
+ *    (auromat_amd.pipeline.SequencePipeline(statistic='area')) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -517,6 +519,23 @@ int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const dou
  * the outputs are then unspecified. */
 int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32_t ny, int32_t nchan, int32_t img_dtype,
                             uint64_t min_weight, double* area, void* out_img, uint8_t* out_mask, double* out_coverage);
+/* amt_area_frame and amt_area_frame_finalize in ONE call that only enqueues on the context's stream (addition to ABI v10): it
+ * reads nothing back and waits for nothing — except that growing the context's workspace synchronises, as for
+ * amt_median_frame_async.  The accumulators are (nchan + 2) * nx * ny uint64 of the context's workspace, zeroed by every call;
+ * consecutive calls run in stream order and share them.  Same argument checks, weights, admission rules, candidate cells and
+ * finalise arithmetic as the two calls: for the same inputs every output has the same bits.  Outputs in the layout of
+ * amt_area_frame_finalize, each optional.
+ * lon_from_mlt != 0: lon holds the corners' MLT in hours; x = (mlt - 12.0) / (24.0 / 360.0), each operation rounded on its own
+ * (auromat_amd.mapping.mapping.convertMappingToSM), before lon_wrap.
+ * [row_begin, row_end), 0 <= row_begin <= row_end <= height (else AMT_EINVAL): only the pixels of these rows are visited;
+ * whatever the arrays hold for the pixels of other rows plays no role.  An empty band: every cell masked, coverage 0.
+ * over (optional): a device word the finalise kernel ORs 1 into when a cell's sum(W) exceeds 2^40 (the outputs of that frame are
+ * then unspecified, as after AMT_EDOMAIN).  Never cleared here: the caller owns and zeroes it. */
+int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, const double* lat_c, const double* elev,
+                         const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
+                         int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                         int lon_from_mlt, int32_t row_begin, int32_t row_end, uint64_t min_weight, double* area, void* out_img,
+                         uint8_t* out_mask, double* out_coverage, uint32_t* over);
 /* Median binning (auromat_amd.resample.resampleMedian; the reference names method='median' and leaves it unbuilt,
  * auromat/resample.py:353-357): the pixels amt_bin_frame would bin into cell (ix, iy) — same arguments, same membership —
  * and for every cell and channel np.median of their values: the order statistic of rank (n-1)/2, or for an even count n
@@ -935,7 +954,15 @@ int amt_pipe_general_finalize(amt_pipe* pipe, double* mean, void* out_img, uint8
  * frames run in stream order and share the context's workspace.  The arenas hold the same blocks: (ny, nx, 4) medians
  * (elevation last, NaN where empty), count, the image rounded half to even and the mask.  status 1 for what the pass does
  * not cover: a pole of the grid in view, exact centres (fast_center = 0); the caller finishes those.  two_pass is ignored;
- * arcsec_per_px works as for the mean (box pass, then the launch that writes the arrays). */
+ * arcsec_per_px works as for the mean (box pass, then the launch that writes the arrays).
+ * Area-weighted sequences (statistic = 2, addition to ABI v10; auromat_amd.resample.resampleArea / resampleAreaMLatMLT): as
+ * the median sequences, with amt_area_frame_async in the place of the median pass.  The slots need the CORNER arrays too: lat,
+ * lon, lat_c, elev, or mlat, mlt, mlat_c, elev for magnetic grids (the MLT hours go to the pass as they are: lon_from_mlt), in
+ * contiguous rows; the pass visits the rows amt_georef_image_rows names for the frame — every pixel it admits lies inside
+ * them, and of a host image only they are on the device.  The arenas hold (ny, nx, 4) weighted means (elevation last, NaN
+ * where masked), the coverage in the count's place, the rounded image and the mask.  A cell is valid from the weight of
+ * amt_run_set_min_coverage on.  The runner keeps one device word per result record of a call, zeroed by amt_run_begin in stream
+ * order, as the `over` of that frame's pass: amt_run_area_overflow reads them. */
 typedef struct amt_run amt_run;
 typedef struct amt_run_config {
     int32_t width, height;
@@ -946,7 +973,8 @@ typedef struct amt_run_config {
     int32_t use_hints;            /* 0: coarse pre-pass for every frame */
     int32_t n_slots;              /* frame slots, >= 2 * batch */
     int32_t two_pass;             /* 1: the two-pass plan for every frame (needs the slots' lat_c / lon_c / elev arrays) */
-    int32_t statistic;            /* ABI v8: 0 mean, 1 median (see "median sequences" below) */
+    int32_t statistic;            /* ABI v8: 0 mean, 1 median, 2 area-weighted mean (see "median sequences", "area-weighted
+                                   * sequences" above) */
     double altitude;              /* mapping shell [km] of frames that name none */
     double min_elevation;         /* maskedByElevation; -inf disables */
     double lat_px_per_deg, lon_px_per_deg;
@@ -1035,6 +1063,14 @@ int amt_run_reset_hints(amt_run* run);
  * Before the first push of the runner; AMT_EINVAL for another statistic, a call in progress, q outside [0, 1] or NaN.  A runner
  * on which it was never called is a median runner, as before. */
 int amt_run_set_quantile(amt_run* run, double q);
+/* Area-weighted sequences: the least total weight of a valid cell, rint(minimum coverage * 2^32) as for amt_area_frame_finalize
+ * (default 2^31: half a cell).  Before the first push of the runner; AMT_EINVAL for another statistic or a call in progress. */
+int amt_run_set_min_coverage(amt_run* run, uint64_t min_weight);
+/* Area-weighted sequences, after amt_run_end: waits for the context's stream and copies the overflow words of the first n result
+ * records of the last call to the host (flags[k] != 0: a cell of frame k was covered more than 256 times over, its grid is
+ * unspecified).  The only wait an area-weighted sequence adds.  AMT_EINVAL for another statistic, a call in progress or n beyond
+ * the records of the last call. */
+int amt_run_area_overflow(amt_run* run, int32_t* flags, int32_t n);
 
 /* ---- sequences over several GPUs: packing of per-frame grids for the gather ------------------------------------
  * Whole frames are independent (reference mapping/spacecraft.py:326-332 iterates them with a plain `map`,
