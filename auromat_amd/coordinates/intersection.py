@@ -29,15 +29,15 @@ def sphereLineIntersection(sphereRadius, lineOrigin, lineDirection, directed=Tru
     :param lineDirection: unit vector or array of unit vectors
     :param bool directed: first intersection along the directed line (True) or the
                           intersection closest to the origin on the infinite line (False)
-    :rtype: vector or array of vectors; NaN where there is no intersection
+    :rtype: vector or array of vectors, shaped like lineDirection; NaN where there is no intersection
     """
     st = Staged(lineDirection)
-    dirs, single = _dirs(st, lineDirection)
+    dirs, _ = _dirs(st, lineDirection)
+    shape = tuple(lineDirection.shape) if st.on_device else np.shape(lineDirection)
     out = st.out(dirs.shape)
     st.ctx.call('amt_intersect_sphere', float(sphereRadius), host3(lineOrigin), ptr(dirs), dirs.shape[0],
                 1 if directed else 0, ptr(out))
-    res = st.result(out)
-    return res[0] if single else res
+    return st.result(out).reshape(shape)        # (the reference broadcasts over any leading shape, intersection.py:26-48)
 
 
 def ellipsoidLineIntersection(a, b, lineOrigin, lineDirection, directed=True):

@@ -50,6 +50,21 @@ class LongDouble(object):
     def acos(self, x):
         return np.arccos(x)
 
+    def asin(self, x):
+        return np.arcsin(x)
+
+    def sin(self, x):
+        return np.sin(x)
+
+    def cos(self, x):
+        return np.cos(x)
+
+    def tan(self, x):
+        return np.tan(x)
+
+    def floor(self, x):
+        return np.floor(x)
+
     def where(self, c, a, b):
         return np.where(c, a, b)
 
@@ -89,6 +104,21 @@ class MultiPrecision(object):
 
     def acos(self, x):
         return self.nan if self._bad(x) else self.mp.acos(x)
+
+    def asin(self, x):
+        return self.nan if self._bad(x) else self.mp.asin(x)
+
+    def sin(self, x):
+        return self.nan if self._bad(x) else self.mp.sin(x)
+
+    def cos(self, x):
+        return self.nan if self._bad(x) else self.mp.cos(x)
+
+    def tan(self, x):
+        return self.nan if self._bad(x) else self.mp.tan(x)
+
+    def floor(self, x):
+        return self.nan if self._bad(x) else self.mp.floor(x)
 
     def where(self, c, a, b):
         return a if c else b
