@@ -89,6 +89,13 @@ class AreaMosaicMember(C.Structure):
                [(k, C.c_int32) for k in ('height', 'width', 'win_x0', 'win_y0', 'win_nx', 'win_ny')]
 
 
+class Projection(C.Structure):
+    """amt_projection"""
+    _fields_ = [('kind', C.c_int32), ('mode', C.c_int32)] + \
+               [(k, C.c_double) for k in ('lat0', 'lon0', 'a', 'e', 'sin_chi1', 'cos_chi1', 'm1', 'k')] + \
+               [('reserved', C.c_double * 4)]
+
+
 class PipeResult(C.Structure):
     """amt_pipe_result"""
     _fields_ = [('status', C.c_int32), ('fused', C.c_int32), ('lon_wrapped', C.c_int32), ('edge_pixels', C.c_int32),
@@ -168,6 +175,10 @@ _SIGNATURES = {
     'amt_rotate_vectors': ([_P, c_double_p, _P, _L, _P], _I),
     'amt_latlon_to_mlat_mlt': ([_P, c_double_p, _P, _P, _D, _L, _D, _D, _P, _P], _I),
     'amt_sm_to_latlon': ([_P, c_double_p, _P, _P, _L, _D, _D, _P, _P], _I),
+    'amt_projection_stereographic': ([_D, _D, _D, _D, C.POINTER(Projection)], _I),
+    'amt_projection_polar_aeqd': ([_I, _D, _D, C.POINTER(Projection)], _I),
+    'amt_project_forward': ([_P, C.POINTER(Projection), _P, _P, _L, _P, _P], _I),
+    'amt_project_inverse': ([_P, C.POINTER(Projection), _P, _P, _L, _P, _P], _I),
     'amt_rotate_pole': ([_P, c_double_p, _P, _P, _D, _L, _D, _D, _P, _P], _I),
     'amt_rotate_pole_deg': ([_P, c_double_p, _P, _P, _D, _L, _D, _D, _P, _P], _I),
     'amt_cartesian_to_spherical': ([_P, _P, _P, _P, _L, _P, _P, _P], _I),
@@ -208,6 +219,8 @@ _SIGNATURES = {
     'amt_bin_frame_finalize_window': ([_P, _P] + [C.c_int32] * 8 + [_P, _P, _P, _P], _I),
     'amt_area_frame': ([_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                         C.POINTER(Axis), _I, _P], _I),
+    'amt_area_plane_frame': ([_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                              C.POINTER(Axis), _P], _I),
     'amt_area_frame_finalize': ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P, _P, _P, _P], _I),
     'amt_area_frame_async': ([_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                               C.POINTER(Axis), _I, _I, C.c_int32, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P], _I),

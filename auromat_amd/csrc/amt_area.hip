@@ -29,6 +29,10 @@
 // pixel's candidate cells are cut to the member's window BEFORE the choice between the lane and the wave path, and the window
 // planes are column-major with iy fastest like the grid's, so a wave's atomics keep their layout), and k_area_select gives every
 // cell its value by the overlap rule with the finalise arithmetic of k_area_finalize (area_finalize_cell, shared by both).
+//
+// On a map plane (amt_area_plane_frame, auromat_amd.resample.resampleStereographic and its kin): k_area_frame<..., PLANE = true>
+// takes the corners' projected x and y (amt_project.hip) on uniform axes in the plane's unit.  x is no longitude there: no wrap,
+// and no rule on a quadrilateral's x extent; everything else is the frame's, bit for bit.
 #include <algorithm>
 #include <type_traits>
 
@@ -84,9 +88,9 @@ struct area_seq_args : area_args {
     int row_begin, row_end;
 };
 
-template <bool WIN, bool SEQ> struct area_kernel_args { using type = area_args; };
-template <> struct area_kernel_args<true, false> { using type = area_mosaic_args; };
-template <> struct area_kernel_args<false, true> { using type = area_seq_args; };
+template <bool WIN, bool SEQ, bool PLANE = false> struct area_kernel_args { using type = area_args; };
+template <> struct area_kernel_args<true, false, false> { using type = area_mosaic_args; };
+template <> struct area_kernel_args<false, true, false> { using type = area_seq_args; };
 
 // The member of global workgroup b: the last i with block_start[i] <= b (a binary search over wave-uniform loads).
 __device__ __forceinline__ int area_member_of(const area_args&, unsigned) { return 0; }
@@ -221,9 +225,12 @@ __device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; } 
 // the member's window.  The weights and the sums are the same integers either way.
 // SEQ = true (amt_area_frame_async; not with WIN): the argument is the frame with a row band and the MLT switch (area_seq_args);
 // the sweep covers the pixels of the band only, whole waves from its first pixel on.
-template <typename IMG_T, bool WIN, bool SEQ = false>
-__global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_args<WIN, SEQ>::type K) {
+// PLANE = true (amt_area_plane_frame; not with WIN or SEQ): the corner arrays hold the x and y of a map plane.  x is no
+// longitude: no wrap, and no limit on a quadrilateral's x extent.  Everything else is the frame's.
+template <typename IMG_T, bool WIN, bool SEQ = false, bool PLANE = false>
+__global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_args<WIN, SEQ, PLANE>::type K) {
     static_assert(!(WIN && SEQ), "a mosaic member has no row band");
+    static_assert(!(PLANE && (WIN || SEQ)), "the plane form is the plain frame's");
     const int member = WIN ? area_member_of(K, blockIdx.x) : 0;
     // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
     //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
@@ -267,14 +274,14 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_
                     if constexpr (SEQ) lo = corner_x(K, lo);
                     const double la = A.lat[at[i]];
                     fin = fin && finite(lo) && finite(la);
-                    const double x = A.lon_wrap ? wrap180_shifted(lo) : lo;
+                    const double x = (!PLANE && A.lon_wrap) ? wrap180_shifted(lo) : lo;
                     P.X[i] = x;
                     P.Y[i] = la;
                     xmin = fmin(xmin, x); xmax = fmax(xmax, x);
                     ymin = fmin(ymin, la); ymax = fmax(ymax, la);
                 }
-                // (a quadrilateral as wide as half the globe straddles the seam of the longitudes)
-                if (fin && xmax - xmin < 180.0 && xmax > A.ax.e0 && xmin < A.ax.e_last && ymax > A.ay.e0 &&
+                // (a quadrilateral as wide as half the globe straddles the seam of the longitudes; a plane has no seam)
+                if (fin && (PLANE || xmax - xmin < 180.0) && xmax > A.ax.e0 && xmin < A.ax.e_last && ymax > A.ay.e0 &&
                     ymin < A.ay.e_last) {
                     // edges[g] <= v < edges[g + 1] for the bin g + 1 of bin_index: no cell below that of the minimum or
                     // above that of the maximum meets the quadrilateral
@@ -521,6 +528,31 @@ int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const dou
         hipLaunchKernelGGL((k_area_frame<uint16_t, false>), grid, block, 0, ctx->stream, A);
     else
         hipLaunchKernelGGL((k_area_frame<uint8_t, false>), grid, block, 0, ctx->stream, A);
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+int amt_area_plane_frame(amt_ctx* ctx, const double* x, const double* y, const double* lat_c, const double* elev,
+                         const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
+                         int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, uint64_t* acc) {
+    AMT_CHECK_CTX(ctx);
+    // (the checks of amt_area_frame)
+    AMT_REQUIRE(ctx, x && y && lat_c && xaxis && yaxis && acc, "NULL argument");
+    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, (int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31), "frames below 2^31 pixels");
+    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
+    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
+    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    AMT_REQUIRE(ctx, xaxis->uniform && yaxis->uniform, "the axes of a map plane are uniform");
+    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
+    area_args A;
+    fill_frame(&A, y, x, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, 0,
+               reinterpret_cast<unsigned long long*>(acc));
+    const dim3 grid = blocks_for((int64_t)height * width), block(kAreaBlock);
+    if (img_dtype == 2)
+        hipLaunchKernelGGL((k_area_frame<uint16_t, false, false, true>), grid, block, 0, ctx->stream, A);
+    else
+        hipLaunchKernelGGL((k_area_frame<uint8_t, false, false, true>), grid, block, 0, ctx->stream, A);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }

@@ -343,4 +343,78 @@ inline sky_known sky_fill(const sky_known& known, int n, int t, int b, int* fill
     return sky_known{t, b};
 }
 
+// ---- map projections ----------------------------------------------------------------------------------------------------------
+// The constants of amt_project_forward / amt_project_inverse (csrc/amt_project.hip), computed once per projection.  Snyder, Map
+// Projections - A Working Manual, ch. 21 (stereographic, ellipsoid) and 25 (azimuthal equidistant, polar, sphere).
+//
+// The conformal latitude chi of the geodetic latitude phi, as its sine and cosine and without tan / atan: with s = sin phi and
+// w = ((1 - e s) / (1 + e s))^e
+//     sin chi = ((1 + s) w - (1 - s)) / ((1 + s) w + (1 - s)),   cos chi = 2 cos phi sqrt(w) / ((1 + s) w + (1 - s)),
+// 1 - s (s >= 0) or 1 + s (s < 0) taken as cos^2 phi / (1 +- s), which keeps its relative accuracy at the poles.  The kernel
+// evaluates the same expressions.
+inline void conformal_sin_cos(double e, double s, double c, double* sin_chi, double* cos_chi) {
+    const double es = e * s;
+    const double w = std::exp(e * std::log((1.0 - es) / (1.0 + es)));
+    const double plus = s >= 0 ? 1.0 + s : c * c / (1.0 - s);
+    const double minus = s >= 0 ? c * c / (1.0 + s) : 1.0 - s;
+    const double pw = plus * w, den = pw + minus;
+    *sin_chi = (pw - minus) / den;
+    *cos_chi = 2.0 * c * std::sqrt(w) / den;
+}
+
+constexpr double kPolarLimit = 1e-8;        // degrees: a centre closer than this to a pole takes the polar form
+
+// Stereographic projection of the ellipsoid (a, b) centred on (lat0, lon0), scale 1 at the centre.  With
+//     D = 1 + sin chi1 sin chi + cos chi1 cos chi cos dlon
+// the plane coordinates are x = k cos chi sin dlon / D, y = k (cos chi1 sin chi - sin chi1 cos chi cos dlon) / D, where
+// k = 2 a m1 / cos chi1 (21-27, 21-24, 21-25 with k0 = 1).  The polar form (21-33, 21-30, 21-31) is the same expression with
+// sin chi1 = +-1, cos chi1 = 0 and k = 2 a / sqrt((1 + e)^(1 + e) (1 - e)^(1 - e)): cos chi / (1 + sin chi) is Snyder's t.
+inline int projection_stereographic(double lat0, double lon0, double a, double b, amt_projection* p) {
+    if (p == nullptr) return AMT_EINVAL;
+    std::memset(p, 0, sizeof(*p));
+    if (!(std::isfinite(lat0) && std::isfinite(lon0) && std::isfinite(a) && std::isfinite(b))) return AMT_EINVAL;
+    if (!(std::fabs(lat0) <= 90.0) || !(a > 0) || !(b > 0) || b > a) return AMT_EINVAL;
+    const double e = std::sqrt((a - b) * (a + b)) / a;
+    p->kind = AMT_PROJ_STEREOGRAPHIC;
+    p->lat0 = lat0;
+    p->lon0 = lon0;
+    p->a = a;
+    p->e = e;
+    if (90.0 - std::fabs(lat0) < kPolarLimit) {
+        p->mode = lat0 > 0 ? 1 : -1;
+        p->sin_chi1 = p->mode;
+        p->cos_chi1 = 0.0;
+        p->m1 = 0.0;
+        p->k = 2.0 * a / std::sqrt(std::pow(1.0 + e, 1.0 + e) * std::pow(1.0 - e, 1.0 - e));
+        return AMT_OK;
+    }
+    // (beyond 45 degrees through the colatitude, which is exact in degrees: cos lat0 keeps its relative accuracy up to the pole)
+    const double colat = (90.0 - std::fabs(lat0)) * kDeg2Rad;
+    const double s1 = std::fabs(lat0) > 45.0 ? std::copysign(std::cos(colat), lat0) : std::sin(lat0 * kDeg2Rad);
+    const double c1 = std::fabs(lat0) > 45.0 ? std::sin(colat) : std::cos(lat0 * kDeg2Rad);
+    conformal_sin_cos(e, s1, c1, &p->sin_chi1, &p->cos_chi1);
+    p->mode = 0;
+    p->m1 = c1 / std::sqrt(1.0 - (e * s1) * (e * s1));
+    p->k = 2.0 * a * p->m1 / p->cos_chi1;
+    return AMT_OK;
+}
+
+// Polar azimuthal equidistant projection of a sphere: rho = radius (pi/2 -+ phi), x = rho sin dlon, y = -+rho cos dlon.
+inline int projection_polar_aeqd(int north, double lon0, double radius, amt_projection* p) {
+    if (p == nullptr) return AMT_EINVAL;
+    std::memset(p, 0, sizeof(*p));
+    if (!(std::isfinite(lon0) && std::isfinite(radius)) || !(radius > 0)) return AMT_EINVAL;
+    p->kind = AMT_PROJ_POLAR_AEQD;
+    p->mode = north ? 1 : -1;
+    p->lat0 = north ? 90.0 : -90.0;
+    p->lon0 = lon0;
+    p->a = radius;
+    p->e = 0.0;
+    p->sin_chi1 = p->mode;
+    p->cos_chi1 = 0.0;
+    p->m1 = 0.0;
+    p->k = radius;
+    return AMT_OK;
+}
+
 }  // namespace amt_prm

@@ -788,6 +788,31 @@ class MosaicMapping(GenericMapping):
     members = property(lambda self: self._members)
 
 
+class ProjectedMapping(GenericMapping):
+    """
+    Mappings resampled onto an equal-scale map plane (``auromat_amd.resample.resampleStereographic``,
+    ``resampleStereographicMLatMLT``, ``resampleMLatMLTPolar``): a :class:`GenericMapping` whose cells are the squares between
+    ``xEdges`` and ``yEdges`` (km in the plane of ``projection``, an ``auromat_amd.coordinates.projection`` object; row 0 is the
+    row of the largest y) and whose coordinate arrays are the inverse projection of the cell corners and centres, geographic
+    whatever ``planeFrame`` says: ``'geo'`` when the plane is a projection of geographic coordinates, ``'sm'`` of (MLat, SM
+    longitude).  ``coverage`` (h, w): the fraction of every cell that the pixels cover.
+    """
+
+    def __init__(self, lats, lons, latsCenter, lonsCenter, elev, alti, img, cameraPosGCRS, photoTime, identifier, projection,
+                 xEdges, yEdges, coverage, frame='geo', metadata=None):
+        GenericMapping.__init__(self, lats, lons, latsCenter, lonsCenter, elev, alti, img, cameraPosGCRS, photoTime,
+                                identifier, metadata=metadata)
+        assert frame in ('geo', 'sm')
+        self._projection, self._xEdges, self._yEdges, self._coverage, self._planeFrame = projection, xEdges, yEdges, coverage, frame
+
+    projection = property(lambda self: self._projection)
+    xEdges = property(lambda self: self._xEdges)
+    yEdges = property(lambda self: self._yEdges)
+    coverage = property(lambda self: self._coverage)
+    # (not `frame`: that is every mapping's method for its device arrays)
+    planeFrame = property(lambda self: self._planeFrame)
+
+
 class MappingCollection(object):
     def __init__(self, mappings, identifier, mayOverlap=True):
         """

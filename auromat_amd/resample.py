@@ -20,7 +20,7 @@ import numpy.ma as ma
 
 from .coordinates.transform import rotation_matrix
 from .coordinates.geodesic import wgs84A, wgs84B
-from .mapping.mapping import (BaseMapping, MappingCollection, convertMappingToSM, convertSMMappingToGeo,
+from .mapping.mapping import (BaseMapping, BoundingBox, MappingCollection, convertMappingToSM, convertSMMappingToGeo,
                               wrap_at_180)
 from .coordinates.geodesic import angularDistanceOnParallel
 from .util.histogram import make_axis
@@ -808,6 +808,260 @@ def resample_frame_area(fd, altitude, boundingBox, pxPerDeg, containsDiscontinui
         img.zero_()                         # (ny,nx,1) so that the result has an image; no kernel writes it without channels
     return _result(grid, bool(containsPole), bool(containsDiscontinuity), altitude, fd.elev is not None,
                    dict(area=area, img=img, mask=mask, coverage=coverage), keep_on_device, fd.img_dtype if nch else None)
+
+
+# ---- map-projected resampling ------------------------------------------------------------------------------------------------
+# The reference's three map products (auromat/draw.py: drawStereographic, drawStereographicMLatMLT, drawMLatMLTPolar) as arrays:
+# the members' pixels, as the quadrilaterals of their projected corners, area-weighted onto the square cells of a map plane.
+
+def projected_km_per_px(kmPerPx=None, arcsecPerPx=100):
+    """The cell size in km: `kmPerPx`, else `arcsecPerPx` of arc on the equator (the reference's default of 100 arcsec: 3.092 km)."""
+    km = float(kmPerPx) if kmPerPx else wgs84A * (float(arcsecPerPx) / 3600) * (np.pi / 180)
+    if not (km > 0 and np.isfinite(km)):
+        raise ValueError('the resolution must be positive, got kmPerPx={!r}, arcsecPerPx={!r}'.format(kmPerPx, arcsecPerPx))
+    return km
+
+
+def projected_edges(extent, kmPerPx):
+    """The edges of ``ceil(extent / kmPerPx)`` cells of `kmPerPx` km centred on 0 (ascending); ValueError for an empty grid."""
+    n = int(np.ceil(extent / kmPerPx)) if np.isfinite(extent) else 0
+    if n < 1:
+        raise ValueError('empty grid: a map of {!r} km at {!r} km per pixel'.format(extent, kmPerPx))
+    return np.linspace(-n * kmPerPx / 2, n * kmPerPx / 2, n + 1)
+
+
+def stereographic_geometry(boundingBoxes, lat0=None, lon0=None, width=None, height=None, boundingBox=None, sizeFactor=1):
+    """(lat0, lon0, width, height) of a stereographic map as drawStereographic chooses them (reference draw.py:192-203): what is
+    missing comes from `boundingBox`, else from the merged `boundingBoxes` — its centre, and 1.05 * sizeFactor times its size."""
+    if lat0 is None or lon0 is None or width is None or height is None:
+        if boundingBox is None:
+            boundingBox = BoundingBox.mergedBoundingBoxes(boundingBoxes)
+        if lat0 is None:
+            lat0 = boundingBox.center.lat
+        if lon0 is None:
+            lon0 = boundingBox.center.lon
+        if width is None:
+            width = boundingBox.size.width * 1.05 * sizeFactor
+        if height is None:
+            height = boundingBox.size.height * 1.05 * sizeFactor
+    return float(lat0), float(lon0), float(width), float(height)
+
+
+def polar_geometry(latSouth, latNorth, radius):
+    """(north, bounding latitude, half width in km) of a polar map as drawMLatMLTPolar chooses them (reference
+    draw.py:375-385): north when the middle latitude is positive; 5 degrees beyond the far latitude; a square that holds the
+    bounding parallel."""
+    north = (latSouth + latNorth) / 2 > 0
+    bounding = latSouth - 5 if north else latNorth + 5
+    return bool(north), float(bounding), float(radius * (90 - abs(bounding)) * np.pi / 180)
+
+
+def _flat_mappings(mappings):
+    """A mapping, a MappingCollection or a list of either -> (the mappings, the items whose bounding boxes the reference merges)"""
+    items = mappings if isinstance(mappings, (list, tuple)) else [mappings]
+    flat = []
+    for item in items:
+        if isinstance(item, MappingCollection):
+            flat.extend(item.mappings)
+        elif isinstance(item, BaseMapping):
+            flat.append(item)
+        else:
+            raise ValueError('expected mappings or mapping collections, but got: {}'.format(type(item)))
+    if not flat:
+        raise ValueError('no mapping to resample')
+    return flat, items
+
+
+def project_and_bin(frames, projection, xEdges, yEdges, min_elevation=None):
+    """
+    The device part of the projected resampling: for every frame, ``amt_project_forward`` on its corner arrays and
+    ``amt_area_plane_frame`` into ONE accumulator on the plane grid (`xEdges`, `yEdges` ascending, km).
+
+    :param frames: list of FrameData with the same channel count and image type
+    :return: (accumulators: device tensor int64 (C + 2, nx * ny) in the layout of ``amt_area_frame``, list of the projected
+             corner arrays (x, y) per frame: device tensors)
+    """
+    import torch
+    fd0 = frames[0]
+    ctx = fd0.ctx
+    Context.current(ctx.device)
+    nch, code = fd0.nchan, fd0.img_dtype_code
+    for fd in frames:
+        if fd.nchan != nch or fd.img_dtype_code != code:
+            raise ValueError('the mappings differ in their channel count or image type')
+    (xaxis, _), (yaxis, _) = make_axis(ctx, xEdges, uniform=True), make_axis(ctx, yEdges, uniform=True)
+    nx, ny = len(xEdges) - 1, len(yEdges) - 1
+    acc = ctx.zeros((nch + 2, nx * ny), torch.int64)
+    planes = []
+    for fd in frames:
+        x, y = ctx.empty(fd.lat.shape), ctx.empty(fd.lat.shape)
+        ctx.call('amt_project_forward', C.byref(projection.params), ptr(fd.lat), ptr(fd.lon), fd.lat.numel(), ptr(x), ptr(y))
+        ctx.call('amt_area_plane_frame', ptr(x), ptr(y), ptr(fd.lat_c), ptr(fd.elev), ptr(fd.img) if nch else None, code or 1,
+                 nch, ptr(fd.center_mask), fd.height, fd.width, _min_elevation(min_elevation), C.byref(xaxis), C.byref(yaxis),
+                 ptr(acc))
+        planes.append((x, y))
+    return acc, planes
+
+
+class _PlaneGrid(object):
+    """nx, ny of a plane grid, for :func:`_bin_outputs`"""
+
+    def __init__(self, xEdges, yEdges):
+        self.nx, self.ny = len(xEdges) - 1, len(yEdges) - 1
+
+
+def resample_frames_projected(frames, projection, xEdges, yEdges, minCoverage=0.5, min_elevation=None):
+    """
+    Area-weighted binning of device-resident frames on a map plane: :func:`project_and_bin`, ``amt_area_frame_finalize``, and
+    the inverse projection of the cell corners and centres (one ``amt_project_inverse`` call for both).
+
+    :return: dict(area (ny,nx,C+1), img (ny,nx,C), mask (ny,nx) bool, coverage (ny,nx), lat, lon (ny+1,nx+1), lat_c, lon_c
+             (ny,nx) [in the projection's own coordinates], has_elev), row 0 the row of the largest y
+    :raises ValueError: `minCoverage` outside [0, 1]; a cell covered more than 256 times over
+    """
+    least = min_coverage_weight(minCoverage)
+    fd0 = frames[0]
+    ctx, nch, code = fd0.ctx, fd0.nchan, fd0.img_dtype_code
+    xEdges, yEdges = np.asarray(xEdges, dtype=np.float64), np.asarray(yEdges, dtype=np.float64)
+    acc, _ = project_and_bin(frames, projection, xEdges, yEdges, min_elevation)
+    grid = _PlaneGrid(xEdges, yEdges)
+    area, img, mask, coverage = _bin_outputs(ctx, grid, nch, code)
+    rc = ctx._lib.amt_area_frame_finalize(ctx.handle, ptr(acc), grid.nx, grid.ny, nch, code or 1, least, ptr(area),
+                                          ptr(img) if nch else None, ptr(mask), ptr(coverage))
+    if rc == -5:                            # AMT_EDOMAIN
+        raise area_overflow_error()
+    ctx.check(rc)
+    if not nch:
+        img.zero_()
+    # corners (ny + 1, nx + 1) and centres (ny, nx) of the cells, north (largest y) first, through one inverse call
+    xc, yc = (xEdges[:-1] + xEdges[1:]) / 2, (yEdges[:-1] + yEdges[1:]) / 2
+    gx, gy = np.meshgrid(xEdges, yEdges[::-1])
+    cx, cy = np.meshgrid(xc, yc[::-1])
+    px, py = np.concatenate((gx.ravel(), cx.ravel())), np.concatenate((gy.ravel(), cy.ravel()))
+    la, lo = projection.inverse(px, py)
+    nc = gx.size
+    out = dict(has_elev=all(fd.elev is not None for fd in frames), lat=la[:nc].reshape(gx.shape), lon=lo[:nc].reshape(gx.shape),
+               lat_c=la[nc:].reshape(cx.shape), lon_c=lo[nc:].reshape(cx.shape), area=to_host(area),
+               img=to_host(img, dtype=fd0.img_dtype if nch else np.uint8), mask=to_host(mask).astype(bool),
+               coverage=to_host(coverage))
+    return out
+
+
+def _projected_mapping(members, res, projection, xEdges, yEdges, frame):
+    """The ProjectedMapping of a resample_frames_projected result; the magnetic forms go through the arithmetic of
+    convertSMMappingToGeo first, so that the coordinate arrays are geographic like every other result's."""
+    from .mapping.mapping import ProjectedMapping
+    times = sorted(m.photoTime for m in members)
+    photoTime = times[len(times) // 2]
+    first = next(m for m in members if m.photoTime == photoTime)
+    lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
+    if frame == 'sm':
+        from .coordinates.transform import smToLatLon
+        nc = lat.size
+        la, lo = smToLatLon(np.concatenate((lat.ravel(), lat_c.ravel())), np.concatenate((lon.ravel(), lon_c.ravel())), photoTime)
+        lat, lon = la[:nc].reshape(lat.shape), lo[:nc].reshape(lon.shape)
+        lat_c, lon_c = la[nc:].reshape(lat_c.shape), lo[nc:].reshape(lon_c.shape)
+    img, elevation = _masked_image_and_elevation(res['mask'], res['area'], res['img'], res['has_elev'])
+    return ProjectedMapping(lat, lon, lat_c, lon_c, elevation, first.altitude, img, first.cameraPosGCRS, photoTime,
+                            first.identifier, projection, xEdges, yEdges, res['coverage'], frame)
+
+
+def _resample_stereographic(members, boxes, frame, lat0, lon0, width, height, boundingBox, sizeFactor, kmPerPx, arcsecPerPx,
+                            minCoverage):
+    from .coordinates.projection import Stereographic
+    min_coverage_weight(minCoverage)
+    km = projected_km_per_px(kmPerPx, arcsecPerPx)
+    lat0, lon0, width, height = stereographic_geometry((b.boundingBox for b in boxes), lat0, lon0, width, height, boundingBox,
+                                                       sizeFactor)
+    xEdges, yEdges = projected_edges(width, km), projected_edges(height, km)
+    projection = Stereographic(lat0, lon0, wgs84A, wgs84B)
+    res = resample_frames_projected([m.frame() for m in members], projection, xEdges, yEdges, minCoverage)
+    return _projected_mapping(members, res, projection, xEdges, yEdges, frame)
+
+
+def resampleStereographic(mappings, lat0=None, lon0=None, width=None, height=None, boundingBox=None, sizeFactor=1, kmPerPx=None,
+                          arcsecPerPx=100, minCoverage=0.5):
+    """
+    The raster of the reference's ``drawStereographic`` (auromat/draw.py:140-222, Basemap 'stere' with ellps='WGS84'): the
+    mappings on the square cells of a stereographic map plane centred on (`lat0`, `lon0`), `width` x `height` km.
+
+    Every pixel is the quadrilateral of its four projected corners and is shared among the cells it overlaps with the integer
+    weights of :func:`resampleArea` (``amt_project_forward`` + ``amt_area_plane_frame``): exact, independent of the order,
+    the same bits on every run.  All members are binned into ONE accumulator: a cell's value is the weighted mean over
+    everything that overlaps it (the union rule); a collection's ``mayOverlap`` plays no role.  A pixel takes part when its
+    centre is unmasked (mask the mappings by elevation first) and its four corners are finite and lie within 90 degrees of
+    the map's centre; there is no limit on its extent in the plane.
+
+    :param mappings: a mapping, a MappingCollection or a list of either
+    :param lat0, lon0: the centre in degrees; default: the centre of the (merged) bounding box
+    :param width, height: of the map in km; default: 1.05 * sizeFactor times the size of the (merged) bounding box
+    :param BoundingBox boundingBox: the box the defaults are taken from, in place of the mappings' own
+    :param number kmPerPx: the cell size; default: `arcsecPerPx` of arc on the equator (100 arcsec: 3.092 km)
+    :param number minCoverage: a cell is masked unless the pixels cover at least this fraction of it, in [0, 1]
+    :raises ValueError: `minCoverage` outside [0, 1]; an empty grid; a cell covered more than 256 times over
+    :rtype: ProjectedMapping: ``nx = ceil(width / kmPerPx)`` by ``ny`` cells around the centre, row 0 the northernmost;
+            coordinates by the inverse projection, ``projection``, ``xEdges``, ``yEdges`` (km), ``coverage``, ``planeFrame``
+    """
+    members, boxes = _flat_mappings(mappings)
+    return _resample_stereographic(members, boxes, 'geo', lat0, lon0, width, height, boundingBox, sizeFactor, kmPerPx,
+                                   arcsecPerPx, minCoverage)
+
+
+def _to_sm(mappings):
+    """The mappings, collections or list of either with every mapping converted to SM coordinates"""
+    def conv(item):
+        if isinstance(item, MappingCollection):
+            return MappingCollection([convertMappingToSM(m) for m in item.mappings], item.identifier, mayOverlap=item.mayOverlap)
+        if isinstance(item, BaseMapping):
+            return convertMappingToSM(item)
+        raise ValueError('expected mappings or mapping collections, but got: {}'.format(type(item)))
+    return [conv(i) for i in mappings] if isinstance(mappings, (list, tuple)) else conv(mappings)
+
+
+def resampleStereographicMLatMLT(mappings, **kw):
+    """
+    :func:`resampleStereographic` in (MLat, SM longitude): the raster of the reference's ``drawStereographicMLatMLT``
+    (auromat/draw.py:224-240), which converts the mappings with ``convertMappingToSM`` and projects the magnetic coordinates
+    with the same WGS84 stereographic projection.  `lat0`, `lon0` and `boundingBox` are magnetic; the coordinate arrays of the
+    result are geographic (the arithmetic of ``convertSMMappingToGeo``), its ``planeFrame`` is ``'sm'``.
+
+    See :func:`resampleStereographic` for parameters.
+    """
+    min_coverage_weight(kw.get('minCoverage', 0.5))
+    members, boxes = _flat_mappings(_to_sm(mappings))
+    args = dict(lat0=None, lon0=None, width=None, height=None, boundingBox=None, sizeFactor=1, kmPerPx=None, arcsecPerPx=100,
+                minCoverage=0.5)
+    unknown = set(kw) - set(args)
+    if unknown:
+        raise TypeError('unexpected arguments: {}'.format(sorted(unknown)))
+    args.update(kw)
+    return _resample_stereographic(members, boxes, 'sm', **args)
+
+
+def resampleMLatMLTPolar(mappings, boundingBox=None, kmPerPx=None, arcsecPerPx=100, minCoverage=0.5):
+    """
+    The raster of the reference's ``drawMLatMLTPolar`` (auromat/draw.py:242-317, Basemap 'npaeqd' / 'spaeqd' with lon_0 = 180
+    on Basemap's sphere of 6370.997 km): the mappings in (MLat, SM longitude) on a polar azimuthal equidistant map, magnetic
+    midnight (MLT 0, SM longitude 180) at the bottom of a north polar map.
+
+    North when the middle of the magnetic latitude range is positive; the map is the square around the bounding parallel 5
+    degrees beyond the range's far end (``latSouth - 5`` / ``latNorth + 5``), half width ``R (90 - |bounding latitude|) pi / 180``.
+    Binning, admission and the union rule are :func:`resampleStereographic`'s; pixels of the other hemisphere take no part.
+
+    :param BoundingBox boundingBox: magnetic; its latitude range in place of the mappings' own
+    :rtype: ProjectedMapping with ``planeFrame == 'sm'`` and geographic coordinate arrays
+    """
+    from .coordinates.projection import BASEMAP_SPHERE_RADIUS, PolarAzimuthalEquidistant
+    min_coverage_weight(minCoverage)
+    km = projected_km_per_px(kmPerPx, arcsecPerPx)
+    members, boxes = _flat_mappings(_to_sm(mappings))
+    if boundingBox is None:
+        boundingBox = BoundingBox.mergedBoundingBoxes([b.boundingBox for b in boxes])
+    north, _, half = polar_geometry(boundingBox.latSouth, boundingBox.latNorth, BASEMAP_SPHERE_RADIUS)
+    xEdges = yEdges = projected_edges(2 * half, km)
+    projection = PolarAzimuthalEquidistant(north, 180.0, BASEMAP_SPHERE_RADIUS)
+    res = resample_frames_projected([m.frame() for m in members], projection, xEdges, yEdges, minCoverage)
+    return _projected_mapping(members, res, projection, xEdges, yEdges, 'sm')
 
 
 def fixedGrid(pxPerDeg, latMin, latMax, lonMin, lonMax):

@@ -47,7 +47,10 @@ extern "C" {
  *    mosaics; area-weighted binning — amt_area_frame, amt_area_frame_finalize (auromat_amd.resample.resampleArea);
  *    area-weighted mosaics — amt_area_mosaic_frames, amt_area_mosaic_member; area-weighted sequences — amt_area_frame_async,
  *    amt_run_config.statistic = 2, amt_run_set_min_coverage, amt_run_area_overflow
- *    (auromat_amd.pipeline.SequencePipeline(statistic='area')) */
+ *    (auromat_amd.pipeline.SequencePipeline(statistic='area')); map projections — amt_projection,
+ *    amt_projection_stereographic, amt_projection_polar_aeqd, amt_project_forward, amt_project_inverse
+ *    (auromat_amd.coordinates.projection) — and area-weighted binning on a map plane — amt_area_plane_frame
+ *    (auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT, resampleMLatMLTPolar) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -304,6 +307,42 @@ int amt_latlon_to_mlat_mlt(amt_ctx* ctx, const double* m, const double* lat_deg,
  * GEO (m = transpose of mat_geo_to_sm, passed already transposed) -> geodetic deg. */
 int amt_sm_to_latlon(amt_ctx* ctx, const double* m_sm_to_geo, const double* smlat_deg, const double* smlon_deg,
                      int64_t n, double a0, double b0, double* out_lat_deg, double* out_lon_deg);
+
+/* ---- map projections (additions to ABI v10; auromat_amd.coordinates.projection) --------------------------------------
+ * Two projections onto an equal-scale map plane, forward and inverse; angles in degrees, lengths in the unit of a / radius.
+ * Snyder, Map Projections - A Working Manual, ch. 21 and 25 (PROJ's stere and aeqd; the reference draws on Basemap's
+ * 'stere' with ellps='WGS84' and 'npaeqd' / 'spaeqd', auromat/draw.py:319-385).
+ *   stereographic, ellipsoid (a, b), centre (lat0, lon0), scale 1 at the centre: with chi the conformal latitude,
+ *     D = 1 + sin chi1 sin chi + cos chi1 cos chi cos dlon,  x = k cos chi sin dlon / D,
+ *     y = k (cos chi1 sin chi - sin chi1 cos chi cos dlon) / D,  k = 2 a m1 / cos chi1;
+ *     the polar form when 90 - |lat0| < 1e-8 deg: sin chi1 = +-1, cos chi1 = 0, k = 2 a / sqrt((1+e)^(1+e) (1-e)^(1-e)).
+ *   polar azimuthal equidistant, sphere: rho = radius (pi/2 -+ lat), x = rho sin dlon, y = -rho cos dlon (north) /
+ *     +rho cos dlon (south).
+ * Domain of the forward direction: a point more than 90 deg from the centre (stereographic: on the conformal sphere, D < 1;
+ * equidistant: the other hemisphere) gives NaN in both outputs, as does a NaN or infinite input.
+ * Inverse: the centre maps to (lat0, lon0); lon in [-180, 180); a NaN or infinite input gives NaN in both outputs (and the
+ * equidistant form beyond rho = pi radius, where no latitude exists).
+ * amt_projection is filled by the two host functions below (no GPU call; AMT_EINVAL for |lat0| > 90, non-finite arguments,
+ * b > a, a, b or radius <= 0, NULL) and passed to the device calls as a HOST pointer. */
+#define AMT_PROJ_STEREOGRAPHIC 1
+#define AMT_PROJ_POLAR_AEQD 2
+typedef struct amt_projection {
+    int32_t kind;               /* AMT_PROJ_* */
+    int32_t mode;               /* 0: oblique (or equatorial), +1 / -1: the north / south polar form */
+    double lat0, lon0;          /* the centre, degrees */
+    double a, e;                /* semi-major axis or radius; eccentricity (0: sphere) */
+    double sin_chi1, cos_chi1;  /* conformal latitude of the centre (exactly +-1 and 0 in the polar forms) */
+    double m1;                  /* cos lat0 / sqrt(1 - e^2 sin^2 lat0) (0 in the polar forms) */
+    double k;                   /* the length constant above (equidistant: the radius) */
+    double reserved[4];
+} amt_projection;
+int amt_projection_stereographic(double lat0, double lon0, double a, double b, amt_projection* out);
+int amt_projection_polar_aeqd(int north, double lon0, double radius, amt_projection* out);
+/* n >= 0 points, elementwise; enqueue only; alignment: any. */
+int amt_project_forward(amt_ctx* ctx, const amt_projection* p, const double* lat_deg, const double* lon_deg, int64_t n,
+                        double* out_x, double* out_y);
+int amt_project_inverse(amt_ctx* ctx, const amt_projection* p, const double* x, const double* y, int64_t n,
+                        double* out_lat_deg, double* out_lon_deg);
 /* auromat/coordinates/transform.py:301-322 rotatePole: geodetic (rad) at `altitude` rotated by the
  * 3x3 `rot` (host) about the origin, back to geodetic (rad). */
 int amt_rotate_pole(amt_ctx* ctx, const double* rot, const double* lat, const double* lon, double altitude,
@@ -511,6 +550,15 @@ int amt_bin_frame_finalize_window(amt_ctx* ctx, const uint64_t* acc, int32_t acc
 int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const double* lat_c, const double* elev, const void* img,
                    int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                    double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, uint64_t* acc);
+/* amt_area_frame on a map plane (addition to ABI v10): the corner arrays are the projected x and y ((height+1) x (width+1),
+ * e.g. from amt_project_forward), the axes are uniform (else AMT_EINVAL) and in the plane's unit.  x is no longitude: there is
+ * no lon_wrap and NO rule on the quadrilateral's x extent — a pixel takes part when lat_c is finite, the elevation threshold
+ * holds, center_mask == 0 and all eight projected corner values are finite (a corner outside the projection's domain is NaN).
+ * Weights, candidate cells, accumulator layout, the ADDING to acc (the members of a collection can share one accumulator)
+ * and the 2^40 limit are amt_area_frame's; amt_area_frame_finalize finishes it.  Alignment: any. */
+int amt_area_plane_frame(amt_ctx* ctx, const double* x, const double* y, const double* lat_c, const double* elev,
+                         const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
+                         int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, uint64_t* acc);
 /* Weighted means in the layout of amt_bin_frame_finalize.  A cell is valid when sum(W) >= max(1, min_weight) (min_weight =
  * rint(minimum coverage * 2^32)).  area (optional): (ny, nx, nchan+1) float64, sum(W * v) / sum(W), the elevation
  * sum(W * E) / sum(W) / 65536, NaN where invalid; out_img (optional): round-half-even of the value, 0 where invalid; out_mask
