@@ -99,14 +99,14 @@ __global__ void k_bin_finalize(unsigned long long* __restrict__ acc, int acc_nx,
 // stays in the cell above it.  One block; resets the counter for the next frame.
 __global__ void k_apply_bin_events(const bin_event* __restrict__ events, unsigned int* __restrict__ count,
                                    unsigned long long* __restrict__ acc, int acc_nx, int acc_ny, int off_x, int off_y,
-                                   int nx, int ny) {
+                                   int nx, int ny, unsigned int xmask, unsigned int ymask) {
     const unsigned int n = *count;
     const int64_t plane = (int64_t)acc_nx * acc_ny;
     for (unsigned int i = threadIdx.x; i < n; i += blockDim.x) {
         const bin_event ev = events[i];
         int cx = ev.bx - 1, cy = ev.by - 1;
-        if ((ev.flags & 1u) && cx == off_x + nx) cx -= 1;
-        if ((ev.flags & 2u) && cy == off_y + ny) cy -= 1;
+        if ((ev.flags & xmask) && cx == off_x + nx) cx -= 1;
+        if ((ev.flags & ymask) && cy == off_y + ny) cy -= 1;
         if (cx < 0 || cx >= acc_nx || cy < 0 || cy >= acc_ny) continue;
         const int64_t cell = (int64_t)cx * acc_ny + cy;
         atomicAdd(&acc[cell], 1ull);
@@ -140,8 +140,8 @@ __global__ void k_pipe_finish(finish_batch B) {
         for (unsigned int e = 0; e < F.n_events; ++e) {
             const bin_event ev = static_cast<const bin_event*>(F.events)[e];
             int cx = ev.bx - 1, cy = ev.by - 1;
-            if ((ev.flags & 1u) && cx == F.off_x + F.nx) cx -= 1;
-            if ((ev.flags & 2u) && cy == F.off_y + F.ny) cy -= 1;
+            if ((ev.flags & (F.masks & 0xffu)) && cx == F.off_x + F.nx) cx -= 1;
+            if ((ev.flags & (F.masks >> 8)) && cy == F.off_y + F.ny) cy -= 1;
             if (cx == ax && cy == ay) {
                 cnt += 1;
                 s0 += ev.c0, s1 += ev.c1, s2 += ev.c2;
@@ -184,10 +184,11 @@ inline dim3 grid_for(int64_t n) {
 }  // namespace
 
 int amt_bin_apply_events_on(amt_ctx* ctx, hipStream_t stream, const void* events, uint32_t* count, uint64_t* acc,
-                            int32_t acc_nx, int32_t acc_ny, int32_t off_x, int32_t off_y, int32_t nx, int32_t ny) {
+                            int32_t acc_nx, int32_t acc_ny, int32_t off_x, int32_t off_y, int32_t nx, int32_t ny,
+                            uint32_t xmask, uint32_t ymask) {
     AMT_REQUIRE(ctx, events && count && acc, "NULL argument");
     hipLaunchKernelGGL(k_apply_bin_events, dim3(1), dim3(kBlock), 0, stream, static_cast<const bin_event*>(events), count,
-                       reinterpret_cast<unsigned long long*>(acc), acc_nx, acc_ny, off_x, off_y, nx, ny);
+                       reinterpret_cast<unsigned long long*>(acc), acc_nx, acc_ny, off_x, off_y, nx, ny, xmask, ymask);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }

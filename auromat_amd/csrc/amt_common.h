@@ -75,7 +75,11 @@ struct amt_georef_tail {
     hipEvent_t kernel_done;
     double* partials;          // buffer of the per-wave partial boxes, amt_georef_partials_bytes() large
     size_t partials_bytes;
+    // fused binning: first edge index of each axis from which on the kernel also records the pixels that are on-edge under
+    // one decimal coarser / finer rounding than the axis's own (see bin_event); kNoBand: nowhere
+    int band_x = 0x7fffffff, band_y = 0x7fffffff;
 };
+constexpr int kNoBand = 0x7fffffff;
 size_t amt_georef_partials_bytes(const amt_frame_params* p);
 int amt_georef_launch(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, const amt_georef_out* out,
                       const amt_georef_tail* tail);
@@ -100,8 +104,10 @@ int amt_pipe_launch_many_sky(amt_pipe* const* pipes, int32_t n, const amt_frame_
 int amt_georef_launch_many_dirs(amt_ctx* ctx, int n, const amt_frame_params* const* p, const double* const* dirs,
                                 const amt_georef_out* const* out, const amt_georef_tail* const* tail);
 // k_apply_bin_events on `stream` (before the finalise kernel): see bin_event
+// xmask / ymask: the flag bit of a record that says "on the lower edge" under the FINAL grid's rounding (bin_event)
 int amt_bin_apply_events_on(amt_ctx* ctx, hipStream_t stream, const void* events, uint32_t* count, uint64_t* acc,
-                            int32_t acc_nx, int32_t acc_ny, int32_t off_x, int32_t off_y, int32_t nx, int32_t ny);
+                            int32_t acc_nx, int32_t acc_ny, int32_t off_x, int32_t off_y, int32_t nx, int32_t ny,
+                            uint32_t xmask, uint32_t ymask);
 // amt_bin_frame_finalize_window on `stream`; clear != 0 also zeroes every cell of the accumulator grid.
 int amt_bin_finalize_on(amt_ctx* ctx, hipStream_t stream, uint64_t* acc, int32_t acc_nx, int32_t acc_ny, int32_t off_x,
                         int32_t off_y, int32_t nx, int32_t ny, int32_t nchan, int32_t img_dtype, double* mean,
@@ -120,7 +126,7 @@ struct finish_frame {
     unsigned long long* acc;
     int acc_nx, acc_ny, off_x, off_y, nx, ny;
     unsigned int n_events;
-    int pad_;
+    unsigned int masks;        // xmask | ymask << 8 (amt_bin_apply_events_on)
     double* mean;
     void* img;
     uint8_t* mask;
@@ -824,6 +830,7 @@ struct axis_dev {
     int uniform;
     double scale, last_rounded;
     double e0, e_last, step, inv_step;
+    int band, band_pad;     // edges from this index on: on_lower_edge_bits also tries the neighbouring decimals (kNoBand: none)
 };
 
 // Edge i of a uniform axis, bit-identical to np.linspace(e0, e_last, nbin+1)[i]:
@@ -872,7 +879,8 @@ __device__ __forceinline__ int bin_index(const axis_dev& ax, double v) {
 // The five scalars of a uniform axis that the common path of the fused binning needs.
 struct axis_lin {
     double e0, e_last, step, inv_step;
-    double margin;      // fractional positions below this (just above an edge) take the exact path, see bin_fast
+    double margin;      // fractional positions below this (just above an edge) take the exact path, see bin_fast: 1.5 units of
+                        // the rounded decimal in bins, 15 on an axis with a band
     int nbin, pad;
 };
 
@@ -883,7 +891,13 @@ struct axis_lin {
 // binned by the kernel but recorded, and resolved when the final grid is known (k_apply_bin_events).
 struct bin_event {
     int bx, by;                 // 1-based superset bins by plain searchsorted(edges, v, 'right')
-    unsigned int flags;         // 1: on the lower x edge of bx, 2: on the lower y edge of by
+    unsigned int flags;         // 1: on the lower x edge of bx, 2: on the lower y edge of by — under the rounding (`scale`) of
+                                // the axis given.  For edges inside the axis's band (the last cells of a superset, where the
+                                // final grid can end) also 4 / 8: the same under one decimal coarser, 16 / 32: one decimal finer
+                                // — a final grid can round coarser or finer than its superset (the smallest edge difference of
+                                // each one's own linspace decides: below the step or not; of 2605 frames of the benchmark's
+                                // sequence 83 final grids round coarser and 27 finer), and k_apply_bin_events takes the bit of
+                                // the final grid's rounding.  A record without the bit that counts stays in its cell.
     unsigned int c0, c1, c2;    // image channels
     long long el;               // elevation, 31.32 fixed point
 };
@@ -898,16 +912,19 @@ inline axis_lin make_axis_lin(const axis_dev& a) {
     l.nbin = a.nbin;
     l.pad = 0;
     // width of the on-edge zone of the rule above: one unit of the rounded decimal, in bins (<= 1e-5), with slack
-    const double zone = a.scale > 0 && a.step > 0 ? 1.5 / (a.scale * a.step) : 0.0;
+    // (with a band: ten times wider, the zone of one decimal coarser)
+    const double zone = a.scale > 0 && a.step > 0 ? (a.band != kNoBand ? 15.0 : 1.5) / (a.scale * a.step) : 0.0;
     l.margin = zone > 1e-7 ? zone : 1e-7;
     return l;
 }
 
 // Common path of bin_index for a uniform axis.  t = (v - e0) / step locates v to ~1e-12 bins (two roundings of
 // the expression, and the edges np.linspace produces differ from e0 + i step by rounding only), so whenever the
-// fractional part of t keeps away from 0 (by ax.margin: the on-edge zone of the right-most-edge rule, <= 1e-5) and
+// fractional part of t keeps away from 0 (by ax.margin: the on-edge zone of the right-most-edge rule, <= 1.2e-5 bins; ten
+// times that on an axis with a band, whose zone is that of one decimal coarser) and
 // from 1 (by 1e-7) the bin floor(t) is certain and no edge needs evaluating.  Everything else — close to an
-// edge, outside the axis, NaN — sets `slow` and is decided exactly by bin_index (a few dozen pixels per frame).
+// edge, outside the axis, NaN — sets `slow` and is decided exactly by bin_index (a few dozen pixels per frame, a few hundred
+// with a band).
 // Returns the 1-based bin, 0 when `slow` is set.
 __device__ __forceinline__ int bin_fast(double e0, double inv_step, double margin, int nbin, double v, bool& slow) {
     const double t = (v - e0) * inv_step;
@@ -922,10 +939,17 @@ __device__ __forceinline__ int bin_fast(const axis_lin& ax, double v, bool& slow
 }
 
 // v lies in bin b (1-based, by plain searchsorted): does it sit on that bin's lower edge in the sense of the
-// right-most-edge rule?
-__device__ __forceinline__ bool on_lower_edge(const axis_dev& ax, int b, double v) {
+// right-most-edge rule (rint(v scale) / scale == rint(edge scale) / scale)?  Bit 1: yes; for an edge inside the band also 2 / 4:
+// the same under one decimal coarser / finer (scale / 10 and scale * 10 are exact: powers of ten)
+__device__ __forceinline__ unsigned int on_lower_edge_bits(const axis_dev& ax, int b, double v) {
     const double e = linspace_edge(ax, b - 1);
-    return rint(v * ax.scale) / ax.scale == rint(e * ax.scale) / ax.scale;
+    unsigned int r = rint(v * ax.scale) / ax.scale == rint(e * ax.scale) / ax.scale ? 1u : 0u;
+    if (b - 1 >= ax.band) {
+        const double c = ax.scale / 10.0, f = ax.scale * 10.0;
+        if (rint(v * c) / c == rint(e * c) / c) r |= 2u;
+        if (rint(v * f) / f == rint(e * f) / f) r |= 4u;
+    }
+    return r;
 }
 
 constexpr double kFix = 4294967296.0;   // 2^32: elevation sums are kept in signed 31.32 fixed point
@@ -950,6 +974,8 @@ inline void make_axis(const amt_axis* a, axis_dev* out) {
     out->e_last = a->last;
     out->step = a->uniform ? a->step : 0.0;
     out->inv_step = a->nbin / (a->last - a->first);
+    out->band = kNoBand;
+    out->band_pad = 0;
 }
 
 inline bool axis_ok(const amt_axis* a) {

@@ -724,11 +724,17 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         const axis_dev ax = karg_load<axis_dev>(K, offsetof(georef_args, bax));
         bx = bin_index<true>(ax, bxv);
         bx = bx > ax.nbin ? 0 : bx;
-        if (bx > 0 && on_lower_edge(ax, bx, bxv)) edge_flags |= 1u;
+        if (bx > 0) {
+            const unsigned int f = on_lower_edge_bits(ax, bx, bxv);
+            edge_flags |= (f & 1u) | ((f & 2u) << 1) | ((f & 4u) << 2);          // bits 0, 2, 4
+        }
         const axis_dev ay = karg_load<axis_dev>(K, offsetof(georef_args, bay));
         by = bin_index<true>(ay, byv);
         by = by > ay.nbin ? 0 : by;
-        if (by > 0 && on_lower_edge(ay, by, byv)) edge_flags |= 2u;
+        if (by > 0) {
+            const unsigned int f = on_lower_edge_bits(ay, by, byv);
+            edge_flags |= ((f & 1u) << 1) | ((f & 2u) << 2) | ((f & 4u) << 3);   // bits 1, 3, 5
+        }
     };
 
     // ---- one corner row + the centre row above it --------------------------------------------------------------
@@ -1498,6 +1504,7 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
         AMT_REQUIRE(ctx, out->bin_xaxis->nbin < 65535 && out->bin_yaxis->nbin < 65535, "at most 65534 bins per axis");
         make_axis(out->bin_xaxis, &A.bax);
         make_axis(out->bin_yaxis, &A.bay);
+        if (tail != nullptr && out->bin_events != nullptr) A.bax.band = tail->band_x, A.bay.band = tail->band_y;
         A.bxl = make_axis_lin(A.bax);
         A.byl = make_axis_lin(A.bay);
         A.bin_img = out->bin_img;

@@ -36,6 +36,8 @@ struct amt_pipe {
     int lon_wrap;                  // the frame straddles the 180 deg discontinuity: longitudes are binned shifted by 180
     amt_grid super, exact;
     int32_t off_x, off_y;          // window of the exact grid inside the superset
+    int band_x = kNoBand, band_y = kNoBand;     // see amt_georef_tail
+    uint32_t xmask = 1, ymask = 2;              // the flag bits of the exact grid's rounding (bin_event)
     double lat_ppd, lon_ppd, min_elev;
     int pole;
     bool pole_unknown;             // direction arrays without a decision of the caller: see amt_pipe_launch_dirs
@@ -331,9 +333,10 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
         pipe->lon_wrap = 1;
         fuse = ranged && box_hi > box_lo;
     }
+    double lon_margin_used = 0.0;
     if (fuse) {
         const double lat_abs = std::fmax(std::fabs(c[0]), std::fabs(c[1]));
-        const double lon_margin = std::fmin(10.0, kMarginDeg / std::fmax(0.1, std::cos(lat_abs * amt::kDeg2Rad)));
+        const double lon_margin = lon_margin_used = std::fmin(10.0, kMarginDeg / std::fmax(0.1, std::cos(lat_abs * amt::kDeg2Rad)));
         const double lat_lo = std::fmax(-89.0, c[0] - kMarginDeg), lat_hi = std::fmin(89.0, c[1] + kMarginDeg);
         // (a box whose MARGIN reaches past +-180 deg — a footprint that ends just short of the date line — is cut there: when
         // the exact box turns out to straddle after all, amt_pipe_wait sees that the coarse pass judged it differently)
@@ -361,6 +364,10 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
         o.bin_events = pipe->events;
         o.bin_event_count = pipe->event_count;
         o.bin_event_capacity = AMT_PIPE_MAX_EDGE_PIXELS;
+        // the exact grid ends inside the margin, so within twice the margin (and a few cells) of the superset's end: from there on
+        // the kernel records what is on-edge under a neighbouring decimal too (amt_pipe_wait knows which rounding the exact grid has)
+        pipe->band_x = std::max(0, pipe->super.nx - (int)std::ceil(2 * lon_margin_used * lon_px_per_deg) - 4);
+        pipe->band_y = std::max(0, pipe->super.ny - (int)std::ceil(2 * kMarginDeg * lat_px_per_deg) - 4);
         pipe->fused = true;
         pipe->acc_zero = false;
     }
@@ -368,6 +375,8 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
     tail_out->kernel_done = pipe->kernel_done;
     tail_out->partials = pipe->partials;
     tail_out->partials_bytes = pipe->partials_bytes;
+    tail_out->band_x = pipe->fused ? pipe->band_x : kNoBand;
+    tail_out->band_y = pipe->fused ? pipe->band_y : kNoBand;
     return AMT_OK;
 }
 
@@ -590,6 +599,17 @@ int amt_pipe_wait(amt_pipe* pipe, amt_pipe_result* result) {
     amt_grid& g = result->grid;
     if (!amt_gl::layout_of_box(pipe->lat_ppd, pipe->lon_ppd, b, &g, &result->lon_wrapped)) return AMT_OK;
     const amt_grid& s = pipe->super;
+    // The kernel flagged on-edge pixels with the superset's rounding (`scale`, from the smallest edge difference of the axis
+    // it was given).  An exact grid can round one decimal coarser (it has no edge difference below the step, its superset
+    // has) or finer (the other way round): its last edge then owns other pixels than the kernel's first flag bit says.
+    // Inside the band the kernel recorded all three readings (bin_event), and the finalise kernels take the bit of the
+    // exact grid's rounding.  Any other relation of the two scales: the general path.
+    auto reading = [](double exact, double super, uint32_t same, uint32_t coarser, uint32_t finer) -> uint32_t {
+        return exact == super ? same : (exact * 10.0 == super ? coarser : (exact == super * 10.0 ? finer : 0u));
+    };
+    const uint32_t xmask = reading(g.xaxis.scale, s.xaxis.scale, 1u, 4u, 16u);
+    const uint32_t ymask = reading(g.yaxis.scale, s.yaxis.scale, 2u, 8u, 32u);
+    if (!xmask || !ymask) return AMT_OK;
     // window of the exact grid inside the superset (same global nodes => integer offsets)
     const long off_x = std::lround((g.lon_center_first - s.lon_center_first) / s.lon_step);
     const long off_y = std::lround((g.lat_center_last - s.lat_center_last) / std::fabs(s.lat_step));
@@ -597,6 +617,9 @@ int amt_pipe_wait(amt_pipe* pipe, amt_pipe_result* result) {
     const double lon_at = s.lon_center_first + off_x * s.lon_step;
     const double lat_at = s.lat_center_last + off_y * std::fabs(s.lat_step);
     if (std::fabs(lon_at - g.lon_center_first) > 1e-9 || std::fabs(lat_at - g.lat_center_last) > 1e-9) return AMT_OK;
+    // (an exact grid that rounds differently and ends below the band — a poor estimate —: the general path)
+    if ((xmask != 1u && off_x + g.nx < pipe->band_x) || (ymask != 2u && off_y + g.ny < pipe->band_y)) return AMT_OK;
+    pipe->xmask = xmask, pipe->ymask = ymask;
     pipe->exact = g;
     pipe->off_x = (int32_t)off_x;
     pipe->off_y = (int32_t)off_y;
@@ -617,7 +640,7 @@ int amt_pipe_finalize(amt_pipe* pipe, double* mean, void* out_img, uint8_t* out_
     // the next frame on the way
     if (pipe->n_events > 0) {
         if (int rc = amt_bin_apply_events_on(ctx, pipe->fin_stream, pipe->events, pipe->event_count, pipe->acc, s.nx, s.ny,
-                                             pipe->off_x, pipe->off_y, g.nx, g.ny))
+                                             pipe->off_x, pipe->off_y, g.nx, g.ny, pipe->xmask, pipe->ymask))
             return rc;
     }
     if (int rc = amt_bin_finalize_on(ctx, pipe->fin_stream, pipe->acc, s.nx, s.ny, pipe->off_x, pipe->off_y, g.nx, g.ny,
@@ -654,6 +677,7 @@ int amt_pipe_finalize_many(amt_pipe* const* pipes, int32_t n, double* const* mea
         F.off_x = pipe->off_x, F.off_y = pipe->off_y;
         F.nx = pipe->exact.nx, F.ny = pipe->exact.ny;
         F.n_events = (unsigned int)pipe->n_events;
+        F.masks = pipe->xmask | (pipe->ymask << 8);
         F.mean = mean[i], F.img = out_img[i], F.mask = out_mask[i], F.out_count = out_count[i];
     }
     // one launch for all of them, on the finalise stream (see amt_pipe_finalize)

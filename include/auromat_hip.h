@@ -847,7 +847,8 @@ int amt_grid_layout(double lat_px_per_deg, double lon_px_per_deg, double lat_min
  *   amt_pipe_finalize crop + finalise into arrays the caller sized from the grid amt_pipe_wait returned
  * status in amt_pipe_result: 0 = ready to finalise; 1 = this frame needs the general path (exact box outside the
  * superset, an extreme of a pole frame's box within 1e-6 cells of a grid node, a geodetic pole frame whose caller also
- * wants MLat / MLT arrays) — the coordinate
+ * wants MLat / MLT arrays, an exact grid that rounds the right-most edge (amt_axis.scale) differently from its superset
+ * and ends below the last cells of the superset, where the kernel records on-edge pixels under both roundings) — the coordinate
  * arrays and bbox are valid, nothing else;
  * 2 = no pixel above the elevation threshold (mapping.py:858-859 -> ValueError). */
 typedef struct amt_pipe amt_pipe;
