@@ -22,9 +22,8 @@ def sources():
 
 
 def _deps():
-    return sources() + [os.path.join(CSRC, 'amt_common.h'), os.path.join(CSRC, 'amt_grid.h'), os.path.join(CSRC, 'amt_params.h'),
-                        os.path.join(CSRC, 'amt_bin_tile.h'),
-                        os.path.join(os.path.dirname(PKG_DIR), 'include', 'auromat_hip.h')]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h'))
+    return sources() + headers + [os.path.join(os.path.dirname(PKG_DIR), 'include', 'auromat_hip.h')]
 
 
 def sources_hash():

@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "amt_common.h"
+#include "amt_mosaic_plan.h"
 
 namespace {
 
@@ -63,17 +64,11 @@ struct area_args {
     unsigned long long* acc;
 };
 
-// Cells [x0, x0 + nx) x [y0, y0 + ny) of the common grid that a member of a mosaic keeps; its accumulator planes hold the window
-// only (cell (x, y) at (x - x0) * ny + (y - y0), nx * ny cells per plane).
-struct area_window {
-    int x0, y0, nx, ny;
-};
-
 // The members of an area-weighted mosaic: one descriptor per member in device memory, and the first workgroup of every
 // member (a prefix over the members' workgroups, n + 1 entries).
 struct area_member {
     area_args A;            // the member's frame on the common axes; A.acc = its window planes
-    area_window W;
+    cell_window W;          // the cells of the common grid the member keeps (amt_mosaic_plan.h)
 };
 struct area_mosaic_args {
     const area_member* __restrict__ members;
@@ -92,22 +87,8 @@ template <bool WIN, bool SEQ, bool PLANE = false> struct area_kernel_args { usin
 template <> struct area_kernel_args<true, false, false> { using type = area_mosaic_args; };
 template <> struct area_kernel_args<false, true, false> { using type = area_seq_args; };
 
-// The member of global workgroup b: the last i with block_start[i] <= b (a binary search over wave-uniform loads).
-__device__ __forceinline__ int area_member_of(const area_args&, unsigned) { return 0; }
-__device__ __forceinline__ int area_member_of(const area_mosaic_args& M, unsigned b) {
-    int lo = 0, hi = M.n;                   // block_start[lo] <= b < block_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)M.block_start[mid] <= b) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
 __device__ __forceinline__ const area_args& frame_args(const area_args& A, int) { return A; }
 __device__ __forceinline__ const area_args& frame_args(const area_mosaic_args& M, int m) { return M.members[m].A; }
-__device__ __forceinline__ area_window frame_window(const area_args&, int) { return area_window{0, 0, 0, 0}; }
-__device__ __forceinline__ area_window frame_window(const area_mosaic_args& M, int m) { return M.members[m].W; }
-__device__ __forceinline__ unsigned first_block(const area_args&, int) { return 0; }
-__device__ __forceinline__ unsigned first_block(const area_mosaic_args& M, int m) { return (unsigned)M.block_start[m]; }
 // SEQ: the band of pixels the sweep covers, and a corner's x as it is stored
 __device__ __forceinline__ int64_t first_pixel(const area_seq_args& S) { return (int64_t)S.row_begin * S.width; }
 __device__ __forceinline__ int64_t end_pixel(const area_seq_args& S) { return (int64_t)S.row_end * S.width; }
@@ -203,7 +184,7 @@ struct area_pixel {
 // Adds the pixel's share of candidate cell (jx, jy) of its range to the accumulators (WIN: of the member's window Wn, which
 // holds the whole range).
 template <bool WIN>
-__device__ __forceinline__ void add_cell(const area_args& A, const area_window& Wn, const area_pixel& P, int jx, int jy,
+__device__ __forceinline__ void add_cell(const area_args& A, const cell_window& Wn, const area_pixel& P, int jx, int jy,
                                          int64_t plane) {
     const int ix = P.ix0 + jx, iy = P.iy0 + jy;
     const unsigned long long W = cell_weight(P.X, P.Y, axis_edge(A.ax, ix), axis_edge(A.ax, ix + 1), axis_edge(A.ay, iy),
@@ -231,13 +212,18 @@ template <typename IMG_T, bool WIN, bool SEQ = false, bool PLANE = false>
 __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_args<WIN, SEQ, PLANE>::type K) {
     static_assert(!(WIN && SEQ), "a mosaic member has no row band");
     static_assert(!(PLANE && (WIN || SEQ)), "the plane form is the plain frame's");
-    const int member = WIN ? area_member_of(K, blockIdx.x) : 0;
+    int member = 0;
+    if constexpr (WIN) member = member_of(K.block_start, K.n, blockIdx.x);
     // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
     //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
     typename std::conditional<WIN, const area_args, const area_args&>::type A = frame_args(K, member);
-    const area_window Wn = frame_window(K, member);
-    const unsigned block0 = first_block(K, member);
-    const unsigned nblocks = WIN ? first_block(K, member + 1) - block0 : gridDim.x;
+    cell_window Wn{0, 0, 0, 0};
+    unsigned block0 = 0, nblocks = gridDim.x;
+    if constexpr (WIN) {
+        Wn = K.members[member].W;
+        block0 = (unsigned)K.block_start[member];
+        nblocks = (unsigned)K.block_start[member + 1] - block0;
+    }
     int64_t pix0 = 0, npix = (int64_t)A.height * A.width;
     if constexpr (SEQ) pix0 = first_pixel(K), npix = end_pixel(K);
     const int64_t plane = WIN ? (int64_t)Wn.nx * Wn.ny : (int64_t)A.ax.nbin * A.ay.nbin;
@@ -391,8 +377,6 @@ __global__ void k_area_finalize(const unsigned long long* __restrict__ acc, int 
     if (too_much) atomicOr(over, 1u);
 }
 
-constexpr int kSelTile = 16;        // k_area_select: one workgroup per 16 x 16 cells of the common grid
-
 struct area_select_args {
     const area_member* __restrict__ members;
     const int* __restrict__ list_start;     // CSR per 16 x 16 tile of cells: members whose window meets the tile,
@@ -418,28 +402,20 @@ struct area_select_args {
 template <typename IMG_T>
 __global__ __launch_bounds__(kSelTile * kSelTile) void k_area_select(area_select_args S) {
 #pragma clang fp contract(off)
-    const int tile = (int)blockIdx.x;
-    const int tx = tile / S.tiles_y, ty = tile - tx * S.tiles_y;
-    const int cx = tx * kSelTile + (int)(threadIdx.x % kSelTile), cy = ty * kSelTile + (int)(threadIdx.x / kSelTile);
-    if (cx >= S.nx || cy >= S.ny) return;
-    const int64_t i = (int64_t)(S.ny - 1 - cy) * S.nx + cx;      // output row r = ny - 1 - cy (north to south)
+    int cx, cy;
+    const int64_t i = select_cell(S.tiles_y, S.nx, S.ny, cx, cy);
+    if (i < 0) return;
     const int nch = S.nch;
-    const int b = S.list_start[tile], e = S.list_start[tile + 1];
     // the cell's sum(W), channel sums and sum(W * E): the total (rule 0) or the elected member's (rule 1; before a member is
     // elected w is the largest weight seen)
     unsigned long long w = 0, s0 = 0, s1 = 0, s2 = 0, s3 = 0, se = 0;
     int src = -1;
     double best = 0.0;
     bool too_much = false;
-    for (int k = b; k < e; ++k) {
-        const int m = S.list[k];
-        const area_member& D = S.members[m];
-        const int wx = cx - D.W.x0, wy = cy - D.W.y0;
-        if (wx < 0 || wx >= D.W.nx || wy < 0 || wy >= D.W.ny) continue;
-        const unsigned long long* acc = D.A.acc;
-        const int64_t plane = (int64_t)D.W.nx * D.W.ny, cell = (int64_t)wx * D.W.ny + wy;
+    walk_tile_members(S.members, S.list_start, S.list, cx, cy,
+                      [&](int m, const unsigned long long* acc, int64_t plane, int64_t cell) {
         const unsigned long long c = acc[cell];
-        if (c == 0) continue;
+        if (c == 0) return;
         too_much = too_much || c > kWeightLimit;
         if (S.rule == 0) {
             w += c;
@@ -465,7 +441,7 @@ __global__ __launch_bounds__(kSelTile * kSelTile) void k_area_select(area_select
         } else if (src < 0 && c > w) {
             w = c;
         }
-    }
+    });
     if (S.rule == 0) {
         too_much = too_much || w > kWeightLimit;
         if (w < S.min_weight) src = -1;
@@ -505,6 +481,33 @@ void fill_frame(area_args* A, const double* lat, const double* lon, const double
     A->acc = acc;
 }
 
+// The checks of a frame that amt_area_frame, amt_area_plane_frame and amt_area_frame_async share; pointers: the entry point's
+// own pointer arguments are there.  Returns what is wrong, or NULL.
+const char* check_area_frame(bool pointers, const void* img, int32_t img_dtype, int32_t nchan, int32_t height, int32_t width,
+                             const amt_axis* xaxis, const amt_axis* yaxis) {
+    if (!pointers) return "NULL argument";
+    if (!(height > 0 && width > 0)) return "empty frame";
+    if (!((int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31))) return "frames below 2^31 pixels";
+    if (!(nchan >= 0 && nchan <= 4)) return "nchan must be 0..4";
+    if (!(nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)))) return "img must be uint8 (1) or uint16 (2)";
+    if (!(axis_ok(xaxis) && axis_ok(yaxis))) return "bad axis";
+    if (!(xaxis->nbin < 65535 && yaxis->nbin < 65535)) return "at most 65534 bins per axis";
+    return nullptr;
+}
+
+// Reads the overflow word of a finalise or select launch back (waits for the stream): AMT_EDOMAIN when it is set, with
+// "<entry>: <what> exceeds 2^40 ..." as the error.
+int area_overflow_status(amt_ctx* ctx, const unsigned int* over, const char* entry, const char* what) {
+    unsigned int flag = 0;
+    AMT_HIP(ctx, hipMemcpyAsync(&flag, over, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag) {
+        ctx->last_error = std::string(entry) + ": " + what + " exceeds 2^40 (covered more than 256 times over)";
+        return AMT_EDOMAIN;
+    }
+    return AMT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -513,13 +516,9 @@ int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const dou
                    int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                    double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, uint64_t* acc) {
     AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, lat && lon && lat_c && xaxis && yaxis && acc, "NULL argument");
-    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
-    AMT_REQUIRE(ctx, (int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31), "frames below 2^31 pixels");
-    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
-    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
-    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
+    const char* bad = check_area_frame(lat && lon && lat_c && xaxis && yaxis && acc, img, img_dtype, nchan, height, width, xaxis,
+                                       yaxis);
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
     area_args A;
     fill_frame(&A, lat, lon, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap,
                reinterpret_cast<unsigned long long*>(acc));
@@ -536,15 +535,10 @@ int amt_area_plane_frame(amt_ctx* ctx, const double* x, const double* y, const d
                          const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
                          int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, uint64_t* acc) {
     AMT_CHECK_CTX(ctx);
-    // (the checks of amt_area_frame)
-    AMT_REQUIRE(ctx, x && y && lat_c && xaxis && yaxis && acc, "NULL argument");
-    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
-    AMT_REQUIRE(ctx, (int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31), "frames below 2^31 pixels");
-    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
-    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
+    const char* bad = check_area_frame(x && y && lat_c && xaxis && yaxis && acc, img, img_dtype, nchan, height, width, xaxis,
+                                       yaxis);
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, xaxis->uniform && yaxis->uniform, "the axes of a map plane are uniform");
-    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
     area_args A;
     fill_frame(&A, y, x, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, 0,
                reinterpret_cast<unsigned long long*>(acc));
@@ -579,14 +573,7 @@ int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32
         hipLaunchKernelGGL((k_area_finalize<uint8_t>), grid, block, 0, ctx->stream, a, nx, ny, nchan, least, area,
                            static_cast<uint8_t*>(out_img), out_mask, out_coverage, over);
     AMT_LAUNCH_CHECK(ctx);
-    unsigned int flag = 0;
-    AMT_HIP(ctx, hipMemcpyAsync(&flag, over, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
-    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (flag) {
-        ctx->last_error = "amt_area_frame_finalize: a cell's total weight exceeds 2^40 (covered more than 256 times over)";
-        return AMT_EDOMAIN;
-    }
-    return AMT_OK;
+    return area_overflow_status(ctx, over, "amt_area_frame_finalize", "a cell's total weight");
 }
 
 int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, const double* lat_c, const double* elev,
@@ -595,15 +582,9 @@ int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, con
                          int lon_from_mlt, int32_t row_begin, int32_t row_end, uint64_t min_weight, double* area, void* out_img,
                          uint8_t* out_mask, double* out_coverage, uint32_t* over) {
     AMT_CHECK_CTX(ctx);
-    // (the checks of amt_area_frame and amt_area_frame_finalize)
-    AMT_REQUIRE(ctx, lat && lon && lat_c && xaxis && yaxis, "NULL argument");
-    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
-    AMT_REQUIRE(ctx, (int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31), "frames below 2^31 pixels");
-    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
-    AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
+    const char* bad = check_area_frame(lat && lon && lat_c && xaxis && yaxis, img, img_dtype, nchan, height, width, xaxis, yaxis);
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, out_img == nullptr || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
-    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
     AMT_REQUIRE(ctx, 0 <= row_begin && row_begin <= row_end && row_end <= height, "0 <= row_begin <= row_end <= height");
     if (amt_set_device(ctx)) return AMT_EHIP;
     // the workspace: the accumulator planes, then a word for the flag of a caller that passes none; zeroed together
@@ -647,113 +628,61 @@ int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, 
                            double* out_coverage, int32_t* out_source) {
     AMT_CHECK_CTX(ctx);
     AMT_REQUIRE(ctx, members && xaxis && yaxis, "NULL argument");
-    AMT_REQUIRE(ctx, n_members >= 1, "no members");
-    AMT_REQUIRE(ctx, rule == 0 || rule == 1, "rule must be 0 (union) or 1 (highest elevation)");
-    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
     AMT_REQUIRE(ctx, out_img == nullptr || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
-    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
     const int nx = xaxis->nbin, ny = yaxis->nbin;
-    for (int32_t i = 0; i < n_members; ++i) {
-        const amt_area_mosaic_member& m = members[i];
-        AMT_REQUIRE(ctx, m.lat && m.lon && m.lat_c, "member without corners or centres");
-        AMT_REQUIRE(ctx, m.height > 0 && m.width > 0, "empty member");
-        AMT_REQUIRE(ctx, (int64_t)(m.height + 1) * (m.width + 1) < ((int64_t)1 << 31), "members below 2^31 pixels");
-        AMT_REQUIRE(ctx, nchan == 0 || (m.img && (img_dtype == 1 || img_dtype == 2)), "member image missing");
-        AMT_REQUIRE(ctx, rule == 0 || m.elev != nullptr, "rule 1 needs every member's elevation");
-        AMT_REQUIRE(ctx, m.win_nx >= 0 && m.win_ny >= 0, "bad window");
-        AMT_REQUIRE(ctx, m.win_nx == 0 || m.win_ny == 0 ||
-                         (m.win_x0 >= 0 && m.win_y0 >= 0 && m.win_x0 + m.win_nx <= nx && m.win_y0 + m.win_ny <= ny),
-                    "window outside the grid");
-    }
+    const char* bad = mosaic_members_bad(members, n_members, rule, nchan, axis_ok(xaxis) && axis_ok(yaxis), nx, ny,
+                                         [](const amt_area_mosaic_member& m) -> const char* {
+        if (!(m.lat && m.lon && m.lat_c)) return "member without corners or centres";
+        if (!(m.height > 0 && m.width > 0)) return "empty member";
+        if (!((int64_t)(m.height + 1) * (m.width + 1) < ((int64_t)1 << 31))) return "members below 2^31 pixels";
+        return nullptr;
+    });
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
+    AMT_REQUIRE(ctx, nchan == 0 || img_dtype == 1 || img_dtype == 2, "member image missing");
     if (amt_set_device(ctx)) return AMT_EHIP;
 
-    // host tables: member descriptors | workgroup prefix [n + 1] | CSR of the 16 x 16 cell tiles; then the flag and the
-    // accumulators, zeroed together
-    axis_dev ax, ay;
-    make_axis(xaxis, &ax);
-    make_axis(yaxis, &ay);
-    const int stx = (nx + kSelTile - 1) / kSelTile, sty = (ny + kSelTile - 1) / kSelTile;
-    const int64_t n_sel = (int64_t)stx * sty;
-    std::vector<area_member> dev((size_t)n_members);
-    std::vector<int> block_start((size_t)n_members + 1, 0);
-    std::vector<int> list_start((size_t)n_sel + 1, 0), list;
-    std::vector<size_t> acc_off((size_t)n_members, 0);
-    size_t acc_words = 0;
-    int64_t blocks = 0;
-    for (int32_t i = 0; i < n_members; ++i) {
-        const amt_area_mosaic_member& m = members[i];
-        area_member& d = dev[(size_t)i];
-        const bool empty = m.win_nx == 0 || m.win_ny == 0;
-        d.A.lat = m.lat;
-        d.A.lon = m.lon;
-        d.A.lat_c = m.lat_c;
-        d.A.elev = m.elev;
-        d.A.img = m.img;
-        d.A.mask = m.center_mask;
-        d.A.height = m.height;
-        d.A.width = m.width;
-        d.A.nch = nchan;
-        d.A.min_elev = min_elevation;
-        d.A.use_elev_threshold = (m.elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-        d.A.ax = ax;
-        d.A.ay = ay;
-        d.A.lon_wrap = lon_wrap ? 1 : 0;
-        d.A.acc = nullptr;
-        d.W = {m.win_x0, m.win_y0, empty ? 0 : m.win_nx, empty ? 0 : m.win_ny};
-        block_start[(size_t)i] = (int)blocks;
-        if (!empty) {
-            blocks += blocks_for((int64_t)m.height * m.width).x;
-            acc_off[(size_t)i] = acc_words;
-            acc_words += (size_t)(nchan + 2) * (size_t)m.win_nx * (size_t)m.win_ny;
-        }
-        AMT_REQUIRE(ctx, blocks < (int64_t)1 << 31, "too many workgroups");
-    }
-    block_start[(size_t)n_members] = (int)blocks;
-    for (int tx = 0; tx < stx; ++tx)
-        for (int ty = 0; ty < sty; ++ty) {
-            const int64_t t = (int64_t)tx * sty + ty;
-            list_start[(size_t)t] = (int)list.size();
-            for (int32_t i = 0; i < n_members; ++i) {
-                const area_window& w = dev[(size_t)i].W;
-                if (w.nx == 0) continue;
-                if (w.x0 < (tx + 1) * kSelTile && w.x0 + w.nx > tx * kSelTile && w.y0 < (ty + 1) * kSelTile &&
-                    w.y0 + w.ny > ty * kSelTile)
-                    list.push_back(i);
-            }
-        }
-    list_start[(size_t)n_sel] = (int)list.size();
+    mosaic_plan P;
+    const bool fits = plan_members(P, members, n_members, nx, ny, nchan, [](const amt_area_mosaic_member& m) {
+        return blocks_for((int64_t)m.height * m.width).x;
+    });
+    AMT_REQUIRE(ctx, fits, "too many workgroups");
+    plan_select_lists(P);
 
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_bstart = up(dev.size() * sizeof(area_member));
-    const size_t o_lstart = o_bstart + up(block_start.size() * sizeof(int));
-    const size_t o_list = o_lstart + up(list_start.size() * sizeof(int));
-    const size_t o_flag = o_list + up(std::max<size_t>(list.size(), 1) * sizeof(int));
-    const size_t o_acc = o_flag + 256;
-    const size_t bytes = o_acc + acc_words * sizeof(unsigned long long);
-    char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
+    // the workspace: member descriptors | workgroup prefix [n + 1] | CSR of the select tiles (one upload); then the flag and
+    // the accumulators, zeroed together
+    std::vector<area_member> dev((size_t)n_members);
+    workspace_packer K;
+    const size_t o_dev = K.upload(dev.data(), dev.size() * sizeof(area_member));     // (filled below, copied by K.host())
+    const size_t o_bstart = K.upload(P.unit_start.data(), P.unit_start.size() * sizeof(int));
+    const size_t o_lstart = K.upload(P.list_start.data(), P.list_start.size() * sizeof(int));
+    const size_t o_list = K.upload(P.list.data(), P.list.size() * sizeof(int));
+    const size_t o_flag = K.add(256);
+    const size_t o_acc = K.add(P.acc_words * sizeof(unsigned long long));
+    char* ws = static_cast<char*>(amt_workspace(ctx, K.total()));
     if (ws == nullptr) {
         ctx->last_error = "amt_area_mosaic_frames: no device memory for the workspace";
         return AMT_ENOMEM;
     }
     unsigned int* over = reinterpret_cast<unsigned int*>(ws + o_flag);
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + o_acc);
-    for (int32_t i = 0; i < n_members; ++i) dev[(size_t)i].A.acc = acc + acc_off[(size_t)i];
-    std::vector<char> host(o_flag, 0);
-    std::memcpy(host.data(), dev.data(), dev.size() * sizeof(area_member));
-    std::memcpy(host.data() + o_bstart, block_start.data(), block_start.size() * sizeof(int));
-    std::memcpy(host.data() + o_lstart, list_start.data(), list_start.size() * sizeof(int));
-    if (!list.empty()) std::memcpy(host.data() + o_list, list.data(), list.size() * sizeof(int));
-    // (pageable source: the copy has consumed `host` when the call returns)
-    AMT_HIP(ctx, hipMemcpyAsync(ws, host.data(), o_flag, hipMemcpyHostToDevice, ctx->stream));
-    AMT_HIP(ctx, hipMemsetAsync(over, 0, bytes - o_flag, ctx->stream));
 
-    if (blocks > 0) {
+    for (int32_t i = 0; i < n_members; ++i) {
+        const amt_area_mosaic_member& m = members[i];
+        fill_frame(&dev[(size_t)i].A, m.lat, m.lon, m.lat_c, m.elev, m.img, nchan, m.center_mask, m.height, m.width,
+                   min_elevation, xaxis, yaxis, lon_wrap, acc + P.acc_off[(size_t)i]);
+        dev[(size_t)i].W = P.win[(size_t)i];
+    }
+    // (pageable source: the copy has consumed the staging buffer when the call returns)
+    const std::vector<char> host = K.host();
+    AMT_HIP(ctx, hipMemcpyAsync(ws + o_dev, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
+    AMT_HIP(ctx, hipMemsetAsync(over, 0, K.total() - o_flag, ctx->stream));
+
+    if (P.units > 0) {
         area_mosaic_args M;
-        M.members = reinterpret_cast<const area_member*>(ws);
+        M.members = reinterpret_cast<const area_member*>(ws + o_dev);
         M.block_start = reinterpret_cast<const int*>(ws + o_bstart);
         M.n = n_members;
-        const dim3 grid((unsigned)blocks), block(kAreaBlock);
+        const dim3 grid((unsigned)P.units), block(kAreaBlock);
         if (img_dtype == 2)
             hipLaunchKernelGGL((k_area_frame<uint16_t, true>), grid, block, 0, ctx->stream, M);
         else
@@ -762,10 +691,10 @@ int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, 
     }
 
     area_select_args S;
-    S.members = reinterpret_cast<const area_member*>(ws);
+    S.members = reinterpret_cast<const area_member*>(ws + o_dev);
     S.list_start = reinterpret_cast<const int*>(ws + o_lstart);
     S.list = reinterpret_cast<const int*>(ws + o_list);
-    S.tiles_y = sty;
+    S.tiles_y = P.sty;
     S.nx = nx;
     S.ny = ny;
     S.nch = nchan;
@@ -777,22 +706,14 @@ int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, 
     S.coverage = out_coverage;
     S.source = out_source;
     S.over = over;
-    const dim3 sgrid((unsigned)n_sel), sblock(kSelTile * kSelTile);
+    const dim3 sgrid((unsigned)(P.stx * P.sty)), sblock(kSelTile * kSelTile);
     if (img_dtype == 2)
         hipLaunchKernelGGL(k_area_select<uint16_t>, sgrid, sblock, 0, ctx->stream, S);
     else
         hipLaunchKernelGGL(k_area_select<uint8_t>, sgrid, sblock, 0, ctx->stream, S);
     AMT_LAUNCH_CHECK(ctx);
-    unsigned int flag = 0;
-    AMT_HIP(ctx, hipMemcpyAsync(&flag, over, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
-    AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (flag) {
-        ctx->last_error = rule == 0
-            ? "amt_area_mosaic_frames: a cell's total weight exceeds 2^40 (covered more than 256 times over)"
-            : "amt_area_mosaic_frames: a member's weight in a cell exceeds 2^40 (covered more than 256 times over)";
-        return AMT_EDOMAIN;
-    }
-    return AMT_OK;
+    return area_overflow_status(ctx, over, "amt_area_mosaic_frames",
+                                rule == 0 ? "a cell's total weight" : "a member's weight in a cell");
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "amt_common.h"
+#include "amt_mosaic_plan.h"
 
 namespace {
 
@@ -60,18 +61,11 @@ constexpr int kWX = 32, kWY = 32;            // LDS window of kWX x kWY cells ce
 constexpr int kRowIters = 4;                 // a workgroup walks kRowIters x kBH image rows (16) with one window
 static_assert(kWX * kWY == kWCap, "window size");
 
-// Cells [x0, x0 + nx) x [y0, y0 + ny) (0-based, x = longitude bin, y = ascending latitude bin) of the grid that a
-// tile body with WIN keeps: pixels binned elsewhere are dropped, and the accumulator planes hold the window only
-// (cell (x, y) at (x - x0) * ny + (y - y0), nx * ny cells per plane).
-struct bin_window {
-    int x0, y0, nx, ny;
-};
-
 // The members of a mosaic (amt_mosaic.hip): one descriptor per member in device memory, and the first global tile of
 // every member (a prefix over the members' tiles, n + 1 entries).
 struct mosaic_dev {
     bin_args A;             // the member's frame; A.acc = its window planes ((nchan + 2) x W.nx * W.ny cells)
-    bin_window W;
+    cell_window W;          // a tile body with WIN keeps the cells of W only (amt_mosaic_plan.h)
 };
 struct mosaic_args {
     const mosaic_dev* __restrict__ members;
@@ -82,22 +76,8 @@ struct mosaic_args {
 template <bool WIN> struct bin_kernel_args { using type = bin_args; };
 template <> struct bin_kernel_args<true> { using type = mosaic_args; };
 
-// The member of global tile t: the last i with tile_start[i] <= t (a binary search over wave-uniform loads).
-__device__ __forceinline__ int mosaic_member(const bin_args&, unsigned) { return 0; }
-__device__ __forceinline__ int mosaic_member(const mosaic_args& M, unsigned t) {
-    int lo = 0, hi = M.n;                   // tile_start[lo] <= t < tile_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)M.tile_start[mid] <= t) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
-}
 __device__ __forceinline__ const bin_args& frame_args(const bin_args& A, int) { return A; }
 __device__ __forceinline__ const bin_args& frame_args(const mosaic_args& M, int m) { return M.members[m].A; }
-__device__ __forceinline__ bin_window frame_window(const bin_args&, int) { return bin_window{0, 0, 0, 0}; }
-__device__ __forceinline__ bin_window frame_window(const mosaic_args& M, int m) { return M.members[m].W; }
-__device__ __forceinline__ unsigned first_tile(const bin_args&, int) { return 0; }
-__device__ __forceinline__ unsigned first_tile(const mosaic_args& M, int m) { return (unsigned)M.tile_start[m]; }
 
 // k_bin_frame: workgroup blockIdx.x bins one BW x (BH * kRowIters) tile of a frame.
 // WIN = false: the argument is the frame (bin_args); the whole grid is kept (A.ax.nbin x A.ay.nbin cells per plane).
@@ -110,13 +90,16 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
     __shared__ unsigned long long sEl[kWCap];
     __shared__ int sCand[kBinBlock / 64];
 
-    const int member = WIN ? mosaic_member(P, blockIdx.x) : 0;
+    int member = 0;
+    if constexpr (WIN) member = member_of(P.tile_start, P.n, blockIdx.x);
     // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
     //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
     typename std::conditional<WIN, const bin_args, const bin_args&>::type A = frame_args(P, member);
-    const bin_window W = frame_window(P, member);
+    cell_window W{0, 0, 0, 0};
+    if constexpr (WIN) W = P.members[member].W;
     const int tiles_x = (A.width + kBW - 1) / kBW;
-    const unsigned t = WIN ? blockIdx.x - first_tile(P, member) : blockIdx.x;
+    unsigned t = blockIdx.x;                    // the tile's number within the frame
+    if constexpr (WIN) t -= (unsigned)P.tile_start[member];
     const int tile_y = t / tiles_x, tile_x = t - tile_y * tiles_x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx0 = tile_x * kBW;

@@ -32,6 +32,7 @@
 // (count_wave, fill_wave) over the concatenated pixels of a mosaic's members, one launch each whatever the member count; a
 // pixel counts inside its member's window and, under rule 1, where amt_mosaic_frames' election (k_mosaic_select) chose its member.
 #include "amt_common.h"
+#include "amt_mosaic_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -197,7 +198,7 @@ struct med_member {
     const void* img;
     const uint8_t* mask;
     int n, g0;                          // pixels; index of pixel 0 in the concatenated space
-    int x0, y0, wnx, wny;               // window in cells of the common grid
+    cell_window W;                      // window in cells of the common grid (amt_mosaic_plan.h)
 };
 struct member_table {
     const med_member* __restrict__ members;
@@ -210,7 +211,8 @@ struct member_table {
 // What a wave of the count pass knows beside the frame: nothing (a frame alone), or its member of a mosaic.
 struct no_member {};
 struct member_view {
-    int m, x0, y0, wnx, wny;
+    int m;
+    cell_window W;
     const int32_t* source;
     int* first;
 };
@@ -220,23 +222,13 @@ __device__ __forceinline__ int keep_cell(const med_args&, const no_member&, int 
 __device__ __forceinline__ int keep_cell(const med_args& A, const member_view& V, int c) {
     if (c < 0) return -1;
     const int iy = c / A.nx, ix = c - iy * A.nx;
-    if ((unsigned)(ix - V.x0) >= (unsigned)V.wnx || (unsigned)(iy - V.y0) >= (unsigned)V.wny) return -1;
+    if ((unsigned)(ix - V.W.x0) >= (unsigned)V.W.nx || (unsigned)(iy - V.W.y0) >= (unsigned)V.W.ny) return -1;
     if (V.source && V.source[(int64_t)(A.ny - 1 - iy) * A.nx + ix] != V.m) return -1;
     return c;
 }
 __device__ __forceinline__ void note_member(const no_member&, int) {}
 __device__ __forceinline__ void note_member(const member_view& V, int c) {
     if (V.first) atomicMin(&V.first[c], V.m);
-}
-
-// The last m with block_start[m] <= b (members without a window have no workgroups: equal entries), by wave-uniform loads.
-__device__ __forceinline__ int table_member(const member_table& T, unsigned b) {
-    int lo = 0, hi = T.n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((unsigned)T.block_start[mid] <= b) lo = mid; else hi = mid;
-    }
-    return __builtin_amdgcn_readfirstlane(lo);
 }
 
 // The frame of a member as the kernels' argument: the call's common part A0 with the member's arrays.
@@ -295,10 +287,10 @@ __global__ __launch_bounds__(kBlock) void k_med_count(med_args A, int* __restric
 __global__ __launch_bounds__(kBlock) void k_med_count_members(med_args A0, member_table T, int* __restrict__ cell_of,
                                                              unsigned* __restrict__ count) {
     const int lane = threadIdx.x & 63;
-    const int m = table_member(T, blockIdx.x);
+    const int m = member_of(T.block_start, T.n, blockIdx.x);
     const med_member D = T.members[m];
     const med_args A = member_args(A0, D);
-    const member_view V = {m, D.x0, D.y0, D.wnx, D.wny, T.source, T.first};
+    const member_view V = {m, D.W, T.source, T.first};
     const int64_t base = ((int64_t)(blockIdx.x - (unsigned)T.block_start[m]) * kBlock + (threadIdx.x & ~63)) * kPPT;
     if (base >= A.n) return;                                        // (wave-uniform)
     count_wave(A, V, base, D.g0, lane, cell_of, count);
@@ -434,7 +426,7 @@ __global__ __launch_bounds__(kBlock) void k_med_fill_members(med_args A0, member
                                                             uint16_t* __restrict__ keys16,
                                                             unsigned long long* __restrict__ keys64) {
     const int lane = threadIdx.x & 63;
-    const int m = table_member(T, blockIdx.x);
+    const int m = member_of(T.block_start, T.n, blockIdx.x);
     const med_member D = T.members[m];
     const med_args A = member_args(A0, D);
     const int64_t base = ((int64_t)(blockIdx.x - (unsigned)T.block_start[m]) * kBlock + (threadIdx.x & ~63)) * kPPT;
@@ -1182,57 +1174,49 @@ int mosaic_median_front(amt_ctx* ctx, const amt_mosaic_member* members, int32_t 
                         const double* q, int nq, double* median, void* out_img, uint8_t* out_mask, double* out_count,
                         int32_t* out_source, median_pass* M) {
     AMT_REQUIRE(ctx, members && xaxis && yaxis && median, "NULL argument");
-    AMT_REQUIRE(ctx, n_members >= 1, "no members");
-    AMT_REQUIRE(ctx, rule == 0 || rule == 1, "rule must be 0 (union) or 1 (highest elevation)");
-    AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
     AMT_REQUIRE(ctx, nchan == 0 || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
-    AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
     const int nx = xaxis->nbin, ny = yaxis->nbin;
     const int64_t cells = (int64_t)nx * ny;
+    int64_t all_pixels = 0;
+    const char* bad = mosaic_members_bad(members, n_members, rule, nchan, axis_ok(xaxis) && axis_ok(yaxis), nx, ny,
+                                         [&](const amt_mosaic_member& m) -> const char* {
+        if (!m.lon_c) return "member without centres";
+        if (m.height > 0 && m.width > 0) all_pixels += (int64_t)m.height * m.width;
+        return all_pixels < 2147483647LL ? nullptr : "the members' pixels together exceed 32-bit pixel indices";
+    });
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
+    mosaic_plan P;
+    const bool fits = plan_members(P, members, n_members, nx, ny, nchan, [](const amt_mosaic_member& m) {
+        return ((int64_t)m.height * m.width + kBlock * kPPT - 1) / (kBlock * kPPT);
+    });
+    AMT_REQUIRE(ctx, fits, "too many workgroups");          // (fewer than the pixels, which fit)
     std::vector<med_member> table((size_t)n_members);
-    std::vector<int> block_start((size_t)n_members + 1, 0);
-    int64_t total = 0, all_pixels = 0, blocks = 0;
+    int64_t total = 0;
     bool has_elev = true;
     for (int32_t i = 0; i < n_members; ++i) {
         const amt_mosaic_member& m = members[i];
-        AMT_REQUIRE(ctx, m.lat_c && m.lon_c && m.height > 0 && m.width > 0, "member without centres");
-        AMT_REQUIRE(ctx, nchan == 0 || m.img, "member image missing");
-        AMT_REQUIRE(ctx, rule == 0 || m.elev != nullptr, "rule 1 needs every member's elevation");
-        AMT_REQUIRE(ctx, m.win_nx >= 0 && m.win_ny >= 0, "bad window");
-        AMT_REQUIRE(ctx, m.win_nx == 0 || m.win_ny == 0 ||
-                         (m.win_x0 >= 0 && m.win_y0 >= 0 && m.win_x0 + m.win_nx <= nx && m.win_y0 + m.win_ny <= ny),
-                    "window outside the grid");
         has_elev = has_elev && m.elev != nullptr;           // (the elevation plane: of every member, or NaN)
-        const int64_t n = (int64_t)m.height * m.width;
-        all_pixels += n;
-        AMT_REQUIRE(ctx, all_pixels < 2147483647LL, "the members' pixels together exceed 32-bit pixel indices");
-        const bool empty = m.win_nx == 0 || m.win_ny == 0;
         med_member& d = table[(size_t)i];
         d.lat_c = m.lat_c;
         d.lon_c = m.lon_c;
         d.elev = m.elev;
         d.img = m.img;
         d.mask = m.center_mask;
-        d.n = (int)n;
+        d.n = m.height * m.width;
         d.g0 = (int)total;
-        d.x0 = m.win_x0, d.y0 = m.win_y0;
-        d.wnx = empty ? 0 : m.win_nx, d.wny = empty ? 0 : m.win_ny;
-        block_start[(size_t)i] = (int)blocks;
-        if (!empty) {
-            total += n;
-            blocks += (n + kBlock * kPPT - 1) / (kBlock * kPPT);
-        }
+        d.W = P.win[(size_t)i];
+        if (d.W.nx != 0) total += d.n;
     }
-    block_start[(size_t)n_members] = (int)blocks;
+    const int64_t blocks = P.units;
     if (amt_set_device(ctx)) return AMT_EHIP;
 
     const med_layout L = median_layout(total, cells, nchan, has_elev);
-    const size_t o_plane = 0;
-    const size_t o_table = align256(o_plane + (size_t)cells * sizeof(int32_t));
-    const size_t o_bstart = align256(o_table + table.size() * sizeof(med_member));
-    const size_t o_med = align256(o_bstart + block_start.size() * sizeof(int));
-    const size_t bytes = o_med + L.bytes;
+    workspace_packer K;
+    const size_t o_plane = K.add((size_t)cells * sizeof(int32_t));
+    const size_t o_table = K.upload(table.data(), table.size() * sizeof(med_member));
+    const size_t o_bstart = K.upload(P.unit_start.data(), P.unit_start.size() * sizeof(int));
+    const size_t o_med = K.add(L.bytes);
+    const size_t bytes = K.total();
     char* ws = nullptr;
     if (rule == 1) {
         // the windowed binning and the election; with no out_source of its own the elected member of every output cell goes
@@ -1272,10 +1256,8 @@ int mosaic_median_front(amt_ctx* ctx, const amt_mosaic_member* members, int32_t 
     T.source = rule == 1 ? plane : nullptr;
     T.first = rule == 0 && out_source ? plane : nullptr;
 
-    // member table and block prefix: one upload (pageable source: the copy has consumed `host` when the call returns)
-    std::vector<char> host(o_med - o_table, 0);
-    std::memcpy(host.data(), table.data(), table.size() * sizeof(med_member));
-    std::memcpy(host.data() + (o_bstart - o_table), block_start.data(), block_start.size() * sizeof(int));
+    // member table and block prefix: one upload (pageable source: the copy has consumed the staging buffer when the call returns)
+    const std::vector<char> host = K.host();
     AMT_HIP(ctx, hipMemcpyAsync(ws + o_table, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
     if (T.first) AMT_HIP(ctx, hipMemsetAsync(plane, 0x7f, (size_t)cells * sizeof(int32_t), ctx->stream));
     AMT_HIP(ctx, hipMemsetAsync(ws + o_med, 0, L.offset, ctx->stream));

@@ -316,12 +316,12 @@ def min_coverage_weight(minCoverage):
     return max(1, int(np.rint(v * 4294967296.0)))
 
 
-def area_overflow_error(frame=None):
+def area_overflow_error(frame=None, function='resampleArea', what='mapping'):
     """The ValueError for ``AMT_EDOMAIN`` / a set overflow flag of the area-weighted binning; `frame`: the index of the frame in a
-    sequence."""
+    sequence; `function`, `what`: who speaks and of what (the mosaic: 'resampleMosaic', 'collection')."""
     where = '' if frame is None else ' (frame {} of the sequence)'.format(frame)
-    return ValueError('resampleArea: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
-                      'fit (is the resolution far too low for this mapping?)' + where)
+    return ValueError('{}: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
+                      'fit (is the resolution far too low for this {}?)'.format(function, what) + where)
 
 
 def resampleArea(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, minCoverage=0.5):
@@ -581,45 +581,33 @@ def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, 
                   (ny,nx,C+1) in place of ``mean`` and ``coverage`` (ny,nx) in place of ``count``, as
                   :func:`resample_frame_area` returns them
     """
-    import torch
     qs = mosaic_statistic(statistic, q, minCoverage)
-    if statistic == 'area':
-        return _mosaic_frames_area(collection, pxPerDeg, arcsecPerPx, containsPole, 0.5 if minCoverage is None else minCoverage)
+    area = statistic == 'area'
+    least = min_coverage_weight(0.5 if minCoverage is None else minCoverage) if area else None
     plan = mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole)
     grid, frames, altitude = plan['grid'], plan['frames'], plan['altitude']
     ctx = frames[0].ctx
     fd0 = frames[0]
     nch = fd0.nchan
-    keep = []                    # device arrays the call reads (the rotated centres of the pole plan)
-    table = (MosaicMember * len(frames))()
-    for i, (fd, (x0, y0, wnx, wny)) in enumerate(zip(frames, plan['windows'])):
-        lat_c, lon_c = fd.lat_c, fd.lon_c
-        if plan['pole']:
-            lat_c, lon_c = _rotate_pole_dev(ctx, fd.lat_c, fd.lon_c, altitude, 90)
-            keep.append((lat_c, lon_c))
-        t = table[i]
-        addr = [None if a is None else ptr(a).value for a in (lat_c, lon_c, fd.elev, fd.img if nch else None,
-                                                              fd.center_mask)]
-        t.lat_c, t.lon_c, t.elev, t.img, t.center_mask = addr
-        t.height, t.width = fd.height, fd.width
-        t.win_x0, t.win_y0, t.win_nx, t.win_ny = x0, y0, wnx, wny
+    # (with 'area' every member hands over its corner arrays as well)
+    table, keep = _mosaic_members(ctx, plan, AreaMosaicMember if area else MosaicMember, nch, corners=area)
     xaxis, yaxis = grid.axes(ctx)
-    planes, img, mask, count = _bin_outputs(ctx, grid, nch, fd0.img_dtype_code, (len(qs),) if qs else ())
-    source = ctx.empty((grid.ny, grid.nx), torch.int32)
-    if not nch:
-        img.zero_()
+    planes, img, mask, count, source = _mosaic_outputs(ctx, grid, nch, fd0.img_dtype_code, (len(qs),) if qs else ())
     head = [table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'), C.byref(xaxis), C.byref(yaxis), plan['lon_wrap'],
             plan['rule']]
     tail = [ptr(planes), ptr(img) if nch else None, ptr(mask), ptr(count), ptr(source)]
-    if statistic == 'mean':
-        ctx.call('amt_mosaic_frames', *(head + tail))
-    elif statistic == 'median':
-        ctx.call('amt_mosaic_median_frames', *(head + tail))
-    else:
+    if area:
+        rc = ctx._lib.amt_area_mosaic_frames(ctx.handle, *(head + [least] + tail))
+        if rc == -5:                            # AMT_EDOMAIN
+            raise area_overflow_error(function='resampleMosaic', what='collection')
+        ctx.check(rc)
+    elif statistic == 'quantile':
         ctx.call('amt_mosaic_quantile_frames', *(head + [(C.c_double * len(qs))(*qs), len(qs)] + tail))
+    else:
+        ctx.call('amt_mosaic_frames' if statistic == 'mean' else 'amt_mosaic_median_frames', *(head + tail))
     out = _result(grid, plan['pole'], plan['discontinuity'], altitude, all(fd.elev is not None for fd in frames),
-                  {statistic: planes, 'img': img, 'mask': mask, 'count': count, 'source': source}, False,
-                  fd0.img_dtype if nch else None)
+                  {statistic: planes, 'img': img, 'mask': mask, 'coverage' if area else 'count': count, 'source': source},
+                  False, fd0.img_dtype if nch else None)
     del keep                     # (after the read-back above: the kernels are done with them)
     out.update(plan=plan)
     if qs:
@@ -627,48 +615,39 @@ def mosaic_frames(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, 
     return out
 
 
-def _mosaic_frames_area(collection, pxPerDeg, arcsecPerPx, containsPole, minCoverage):
-    """:func:`mosaic_frames` for statistic='area' (``amt_area_mosaic_frames``): the plan, the windows and the rule of the other
-    statistics; every member hands over its corner arrays as well, rotated like its centres in the pole plan."""
-    import torch
-    least = min_coverage_weight(minCoverage)
-    plan = mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole)
-    grid, frames, altitude = plan['grid'], plan['frames'], plan['altitude']
-    ctx = frames[0].ctx
-    fd0 = frames[0]
-    nch = fd0.nchan
-    keep = []                    # device arrays the call reads (the rotated corners and centres of the pole plan)
-    table = (AreaMosaicMember * len(frames))()
-    for i, (fd, (x0, y0, wnx, wny)) in enumerate(zip(frames, plan['windows'])):
-        lat, lon, lat_c = fd.lat, fd.lon, fd.lat_c
+def _mosaic_members(ctx, plan, struct, nch, corners):
+    """The member table of a mosaic call from a :func:`mosaic_plan`: `struct` (``MosaicMember``, or ``AreaMosaicMember`` with
+    `corners`: the corner arrays are handed over as well) per member.  In the pole plan the centres, and the corners, are rotated.
+    Returns the table and `keep`: the device arrays made here that the call reads."""
+    frames, altitude = plan['frames'], plan['altitude']
+    keep = []
+    table = (struct * len(frames))()
+    for i, (fd, window) in enumerate(zip(frames, plan['windows'])):
+        lat_c, lon_c, lat, lon = fd.lat_c, fd.lon_c, fd.lat, fd.lon
         if plan['pole']:
-            lat, lon = _rotate_pole_dev(ctx, fd.lat, fd.lon, altitude, 90)
-            lat_c, _ = _rotate_pole_dev(ctx, fd.lat_c, fd.lon_c, altitude, 90)
-            keep.append((lat, lon, lat_c))
+            lat_c, lon_c = _rotate_pole_dev(ctx, lat_c, lon_c, altitude, 90)
+            if corners:
+                lat, lon = _rotate_pole_dev(ctx, lat, lon, altitude, 90)
+            keep.append((lat_c, lon_c, lat, lon))
         t = table[i]
-        addr = [None if a is None else ptr(a).value for a in (lat, lon, lat_c, fd.elev, fd.img if nch else None,
-                                                              fd.center_mask)]
-        t.lat, t.lon, t.lat_c, t.elev, t.img, t.center_mask = addr
+        first = (lat, lon, lat_c) if corners else (lat_c, lon_c)      # (the structs' leading fields, in their order)
+        addr = [None if a is None else ptr(a).value for a in first + (fd.elev, fd.img if nch else None, fd.center_mask)]
+        if corners:
+            t.lat, t.lon, t.lat_c, t.elev, t.img, t.center_mask = addr
+        else:
+            t.lat_c, t.lon_c, t.elev, t.img, t.center_mask = addr
         t.height, t.width = fd.height, fd.width
-        t.win_x0, t.win_y0, t.win_nx, t.win_ny = x0, y0, wnx, wny
-    xaxis, yaxis = grid.axes(ctx)
-    area, img, mask, coverage = _bin_outputs(ctx, grid, nch, fd0.img_dtype_code)
-    source = ctx.empty((grid.ny, grid.nx), torch.int32)
+        t.win_x0, t.win_y0, t.win_nx, t.win_ny = window
+    return table, keep
+
+
+def _mosaic_outputs(ctx, grid, nch, img_dtype_code, lead=()):
+    """:func:`_bin_outputs` plus ``source`` (ny,nx) int32; without channels the image is zeroed (the call does not write it)."""
+    import torch
+    planes, img, mask, count = _bin_outputs(ctx, grid, nch, img_dtype_code, lead)
     if not nch:
         img.zero_()
-    rc = ctx._lib.amt_area_mosaic_frames(ctx.handle, table, len(frames), fd0.img_dtype_code or 1, nch, float('-inf'),
-                                         C.byref(xaxis), C.byref(yaxis), plan['lon_wrap'], plan['rule'], least, ptr(area),
-                                         ptr(img) if nch else None, ptr(mask), ptr(coverage), ptr(source))
-    if rc == -5:                            # AMT_EDOMAIN
-        raise ValueError('resampleMosaic: a cell of the grid is covered more than 256 times over by the pixels; its sums do not '
-                         'fit (is the resolution far too low for this collection?)')
-    ctx.check(rc)
-    out = _result(grid, plan['pole'], plan['discontinuity'], altitude, all(fd.elev is not None for fd in frames),
-                  dict(area=area, img=img, mask=mask, coverage=coverage, source=source), False,
-                  fd0.img_dtype if nch else None)
-    del keep                     # (after the read-back above: the kernels are done with them)
-    out.update(plan=plan)
-    return out
+    return planes, img, mask, count, ctx.empty((grid.ny, grid.nx), torch.int32)
 
 
 def _bin_outputs(ctx, grid, nch, img_dtype_code, lead=(), count=True):

@@ -18,7 +18,7 @@ import numpy as np
 import _bin_oracle as B
 from _median_cases import Case
 
-# The tile constants of auromat_amd/csrc/amt_bin_tile.h and kSelTile of amt_mosaic.hip, by the sources' names;
+# The tile constants of auromat_amd/csrc/amt_bin_tile.h and kSelTile of amt_mosaic_plan.h, by the sources' names;
 # test_bin_cases_cpu.py reads them from the sources and compares.
 K_PPT = 4
 K_BW = 256

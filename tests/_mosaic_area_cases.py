@@ -13,7 +13,7 @@ import numpy as np
 import _area_cases as K
 import _area_oracle as O
 
-SEL_TILE = 16               # kSelTile of amt_area.hip: the election walks the members per 16 x 16 cells
+SEL_TILE = 16               # kSelTile of amt_mosaic_plan.h: the election walks the members per 16 x 16 cells
 EDOMAIN = -5
 
 GX, GY = K.unit_edges(48, 0.5, 0.0), K.unit_edges(40, 0.5, 0.0)      # x in [0, 24], y in [0, 20]

@@ -19,7 +19,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'auromat_a
 
 def test_case_constants_are_the_sources():
     tile = open(os.path.join(CSRC, 'amt_bin_tile.h')).read()
-    mosaic = open(os.path.join(CSRC, 'amt_mosaic.hip')).read()
+    mosaic = open(os.path.join(CSRC, 'amt_mosaic_plan.h')).read() + open(os.path.join(CSRC, 'amt_mosaic.hip')).read()
     assert re.findall(r'constexpr int kBinBlock = (\d+);', tile) == ['256']
     assert re.findall(r'constexpr int kPPT = (\d+);', tile) == [str(K.K_PPT)]
     assert re.findall(r'constexpr int kBW = 64 \* kPPT, kBH = kBinBlock / 64, kWCap = (\d+);', tile) == [str(K.K_WX * K.K_WY)]

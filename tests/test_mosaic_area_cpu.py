@@ -242,7 +242,8 @@ def test_entry_point_is_declared():
 
 # ---- the collections aim where they claim ----------------------------------------------------------------------------------
 def test_cases_aim_where_they_claim():
-    src = open(os.path.join(ROOT, 'auromat_amd', 'csrc', 'amt_area.hip')).read()
+    src = open(os.path.join(ROOT, 'auromat_amd', 'csrc', 'amt_mosaic_plan.h')).read()
+    assert 'kSelTile' in open(os.path.join(ROOT, 'auromat_amd', 'csrc', 'amt_area.hip')).read()
     assert int(re.search(r'constexpr int kSelTile = (\d+);', src).group(1)) == MK.SEL_TILE
     cases = {c.name: c for c in MK.device_cases()}
     assert len(cases) == len(MK.device_cases())
