@@ -89,6 +89,12 @@ class AreaMosaicMember(C.Structure):
                [(k, C.c_int32) for k in ('height', 'width', 'win_x0', 'win_y0', 'win_nx', 'win_ny')]
 
 
+class ScanLineStrip(C.Structure):
+    """amt_scanline_strip"""
+    _fields_ = [(k, C.c_void_p) for k in ('row', 'col', 'planes', 'img')] + \
+               [('count', C.c_int64), ('frame', C.c_int32), ('reserved', C.c_int32)]
+
+
 class Projection(C.Structure):
     """amt_projection"""
     _fields_ = [('kind', C.c_int32), ('mode', C.c_int32)] + \
@@ -241,6 +247,10 @@ _SIGNATURES = {
                                     C.POINTER(Axis), _I, C.c_int32, c_double_p, _I, _P, _P, _P, _P, _P], _I),
     'amt_area_mosaic_frames': ([_P, C.POINTER(AreaMosaicMember), C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                                 C.POINTER(Axis), _I, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P], _I),
+    'amt_scanline_select': ([_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                             _P], _I),
+    'amt_scanline_pack': ([_P, _P] + [C.c_int32] * 4 + [_P, C.c_int32, _P] + [C.c_int32] * 6 + [_L, _P, _P, _P, _P], _I),
+    'amt_scanline_compose': ([_P, C.POINTER(ScanLineStrip)] + [C.c_int32] * 8 + [_P, _P, _P, _P], _I),
     'amt_nearest_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis), C.POINTER(Axis), _I, _P, _P, _P,
                            _P], _I),
     'amt_nearest_gather': ([_P, _P, _L, _P, C.c_int32, C.c_int32, _P, _P, _P, _P], _I),

@@ -8,6 +8,7 @@
 // stops as soon as the best candidate is closer than anything an unvisited cell can hold.  HBM-bound: two passes
 // over the centre coordinates plus ~9 cells x (pixels per cell) gathered coordinate pairs per grid centre.
 #include "amt_common.h"
+#include "amt_polygon.h"
 
 #include <cmath>
 #include <cstring>
@@ -637,7 +638,7 @@ __global__ __launch_bounds__(kBlock) void k_points_in_polygon(const double* __re
             const double x0 = poly[2 * (int64_t)k], y0 = poly[2 * (int64_t)k + 1];
             const double x1 = poly[2 * (int64_t)k1], y1 = poly[2 * (int64_t)k1 + 1];
             // the edge flips a point only if (y0 >= ty) != (y1 >= ty) for some ty in [lo, hi]
-            if (fmax(y0, y1) >= lo && fmin(y0, y1) <= hi) {
+            if (polygon_edge_meets(y0, y1, lo, hi)) {
                 const int slot = atomicAdd(&sCount, 1);
                 sx0[slot] = x0;
                 sy0[slot] = y0;
@@ -648,9 +649,7 @@ __global__ __launch_bounds__(kBlock) void k_points_in_polygon(const double* __re
         __syncthreads();
         const int cnt = sCount;
         for (int e = 0; e < cnt; ++e) {
-            const double x0 = sx0[e], y0 = sy0[e], x1 = sx1[e], y1 = sy1[e];
-            const bool f0 = y0 >= ty, f1 = y1 >= ty;
-            if (f0 != f1 && (((y1 - ty) * (x0 - x1) >= (x1 - tx) * (y0 - y1)) == f1)) in = !in;
+            if (polygon_edge_flips(sx0[e], sy0[e], sx1[e], sy1[e], tx, ty)) in = !in;
         }
     }
     // Agg's point_in_path leaves a point with a coordinate that is not finite outside; a NaN y never compares and stays outside

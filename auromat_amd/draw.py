@@ -1,7 +1,7 @@
 """
 The one thing needed to look at a resampled mapping: its image as a PNG.  Everything else the reference's auromat/draw.py does
 (graticules, coastlines, labels, figures) is matplotlib's business and not built here; the map products themselves are arrays,
-see auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT and resampleMLatMLTPolar.
+see auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT, resampleMLatMLTPolar and resampleScanLines.
 """
 import numpy as np
 import numpy.ma as ma

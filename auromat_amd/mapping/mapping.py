@@ -788,6 +788,43 @@ class MosaicMapping(GenericMapping):
     members = property(lambda self: self._members)
 
 
+class ScanLineMapping(GenericMapping):
+    """
+    The scan-line map of a sequence (``auromat_amd.resample.resampleScanLines``, the raster of the reference's
+    ``drawScanLinesCo``): a plate carree :class:`GenericMapping` on which every frame of the sequence fills the strip through
+    its centroid, later frames over earlier ones.  ``photoTime`` and ``cameraPosGCRS`` are the first frame's.
+
+    ``frameIndex``: masked int32 (h, w), the index of the frame each cell comes from.  Per frame, in sequence order:
+    ``photoTimes``, ``identifiers``, ``centroids`` (:class:`Location`), ``azimuths`` (degrees, the direction of flight the
+    strip is perpendicular to), ``polygons`` ((m, 2) [lat, lon], the strip's outline) and ``lineBoundingBoxes`` (the
+    :class:`BoundingBox` of the strip's cells).  ``width`` and ``height`` of the strips in metres, ``maxHeight`` the largest
+    diagonal of the line bounding boxes in metres (with centroids and azimuths what the reference places its time axis
+    with), ``pxPerDeg`` the (lat, lon) resolution every frame was resampled with.
+    """
+
+    def __init__(self, lats, lons, latsCenter, lonsCenter, elev, alti, img, cameraPosGCRS, photoTime, identifier, frameIndex,
+                 photoTimes, identifiers, centroids, azimuths, polygons, lineBoundingBoxes, width, height, maxHeight, pxPerDeg,
+                 metadata=None):
+        GenericMapping.__init__(self, lats, lons, latsCenter, lonsCenter, elev, alti, img, cameraPosGCRS, photoTime,
+                                identifier, metadata=metadata)
+        self._frameIndex = frameIndex
+        self._perFrame = dict(photoTimes=list(photoTimes), identifiers=list(identifiers), centroids=list(centroids),
+                              azimuths=list(azimuths), polygons=list(polygons), lineBoundingBoxes=list(lineBoundingBoxes))
+        self._width, self._height, self._maxHeight, self._pxPerDeg = width, height, maxHeight, tuple(pxPerDeg)
+
+    frameIndex = property(lambda self: self._frameIndex)
+    photoTimes = property(lambda self: self._perFrame['photoTimes'])
+    identifiers = property(lambda self: self._perFrame['identifiers'])
+    centroids = property(lambda self: self._perFrame['centroids'])
+    azimuths = property(lambda self: self._perFrame['azimuths'])
+    polygons = property(lambda self: self._perFrame['polygons'])
+    lineBoundingBoxes = property(lambda self: self._perFrame['lineBoundingBoxes'])
+    width = property(lambda self: self._width)
+    height = property(lambda self: self._height)
+    maxHeight = property(lambda self: self._maxHeight)
+    pxPerDeg = property(lambda self: self._pxPerDeg)
+
+
 class ProjectedMapping(GenericMapping):
     """
     Mappings resampled onto an equal-scale map plane (``auromat_amd.resample.resampleStereographic``,

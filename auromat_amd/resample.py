@@ -1043,6 +1043,389 @@ def resampleMLatMLTPolar(mappings, boundingBox=None, kmPerPx=None, arcsecPerPx=1
     return _projected_mapping(members, res, projection, xEdges, yEdges, 'sm')
 
 
+# ---- scan-line maps ----------------------------------------------------------------------------------------------------------
+# The raster of the reference's drawScanLinesCo / drawScanLinesMLatMLTCo (auromat/draw.py:589-879): every frame of a sequence
+# contributes the strip through its centroid, perpendicular to the direction of flight, and all strips lie on one grid.
+
+class _ScanLineRule(object):
+    """The strip rule of the reference (draw.py:635-738), one frame at a time: constants from the first step, then per frame
+    the azimuth from the camera footpoints and the strip's polygon."""
+
+    def __init__(self, firstProps, firstCellDiagonal, lineWidthFactor=1):
+        from .coordinates import geodesic
+        bb = firstProps.boundingBox
+        # constant height of the rotated box: bigger than needed, so that it holds as much as possible
+        self.height = geodesic.distance(bb.topLeft, bb.bottomRight) * 1.5
+        self.firstCellDiagonal, self.lineWidthFactor = float(firstCellDiagonal), lineWidthFactor
+        self.width = self.deltaAzimuth = self.deltaDistance = self.az = None
+
+    def strip(self, cur, nxt):
+        """(polygon (m, 2) [lat, lon], azimuth) of the frame with properties `cur`; `nxt`: the next frame's, None for the
+        last frame (it reuses the previous azimuth)."""
+        from .coordinates import geodesic
+        if nxt is not None:
+            azCamFoot = geodesic.course(cur.cameraFootpoint, nxt.cameraFootpoint)
+        if self.width is None:
+            if nxt is None:
+                raise ValueError('mapping sequence too short, need at least 2 mappings')
+            # wide enough for a cell to fit whatever the strip's orientation: three diagonals of the first cell
+            consecutive = geodesic.distance(cur.centroid, nxt.centroid)
+            self.width = max(self.firstCellDiagonal * 3, consecutive) * self.lineWidthFactor
+            self.deltaDistance = geodesic.distance(cur.cameraFootpoint, cur.centroid)
+            self.deltaAzimuth = azCamFoot - geodesic.course(cur.cameraFootpoint, cur.centroid)
+        if nxt is not None:
+            # the centroids' track from the footpoints' (smooth), assuming the camera does not move against the spacecraft
+            toCentroid = azCamFoot - self.deltaAzimuth
+            a = geodesic.destination(cur.cameraFootpoint, toCentroid, self.deltaDistance)
+            b = geodesic.destination(nxt.cameraFootpoint, toCentroid, self.deltaDistance)
+            self.az = geodesic.course(a, b)
+        az, w2, h2 = self.az, self.width / 2, self.height / 2
+        for pole in (90, -90):
+            if geodesic.distance(cur.centroid, geodesic.Location(pole, 0.0)) <= np.hypot(w2, h2) * 1.01:
+                raise ValueError('scan lines: the strip of frame {!r} reaches a pole'.format(cur.identifier))
+        middleRight = geodesic.destination(cur.centroid, az, w2)
+        middleLeft = geodesic.destination(cur.centroid, az + 180, w2)
+        topLeft = geodesic.destination(middleLeft, az - 90, h2)
+        bottomLeft = geodesic.destination(middleLeft, az + 90, h2)
+        topRight = geodesic.destination(middleRight, az - 90, h2)
+        bottomRight = geodesic.destination(middleRight, az + 90, h2)
+        # (without the last point of each line: no point twice)
+        polygon = np.concatenate((geodesic.line(topLeft, topRight)[:-1], geodesic.line(topRight, bottomRight)[:-1],
+                                  geodesic.line(bottomRight, bottomLeft)[:-1], geodesic.line(bottomLeft, topLeft)[:-1]))
+        return polygon, az
+
+
+def scanline_strips(props, firstCellDiagonal, lineWidthFactor=1):
+    """
+    The strips of a sequence's scan-line map (reference draw.py:635-738), on the host.
+
+    :param props: list of ``MappingProperties`` (boundingBox, centroid, cameraFootpoint, ...) of the unresampled frames
+    :param firstCellDiagonal: metres between corners 0 and 2 of the first unmasked cell of the first resampled frame
+    :param lineWidthFactor: widens the strips, for sequences with frames missing
+    :return: dict(polygons [per frame (m, 2) [lat, lon]], azimuths [per frame, degrees], width, height [metres])
+    :raises ValueError: fewer than two frames; a strip that reaches a pole
+    """
+    props = list(props)
+    if len(props) < 2:
+        raise ValueError('mapping sequence too short, need at least 2 mappings')
+    rule = _ScanLineRule(props[0], firstCellDiagonal, lineWidthFactor)
+    strips = [rule.strip(cur, nxt) for cur, nxt in zip(props, props[1:] + [None])]
+    return dict(polygons=[s[0] for s in strips], azimuths=[s[1] for s in strips], width=rule.width, height=rule.height)
+
+
+def scanline_longitude_frame(firstCentroid):
+    """True when a sequence is resampled in longitudes shifted by 180 degrees (``containsDiscontinuity=True`` for every frame):
+    the first frame's centroid lies nearer the date line than longitude 0."""
+    return bool(abs(firstCentroid.lon) > 90)
+
+
+def scanline_check_fits(boundingBox, shifted, frame, identifier=None):
+    """ValueError when a frame's box does not fit the sequence's longitude frame: it contains +-180 (unshifted), or its
+    shifted west edge lies east of its shifted east edge (shifted).  All frames of a scan-line map share one lattice, and 180
+    degrees is not a whole number of its cells."""
+    if shifted:
+        fits = wrap_at_180(boundingBox.lonWest + 180) <= wrap_at_180(boundingBox.lonEast + 180)
+    else:
+        fits = not boundingBox.containsDiscontinuity
+    if not fits:
+        raise ValueError('scan lines: frame {} ({!r}) does not fit the longitude frame of the sequence ({}): the sequence spans '
+                         'the seam of its longitude frame'.format(frame, identifier,
+                                                                  'shifted by 180 degrees' if shifted else 'unshifted'))
+
+
+def lons_contain_discontinuity(lons):
+    """``BoundingBox.minimumBoundingBox(points).containsDiscontinuity`` for points with the longitudes `lons`, without the
+    quadratic table of the general merge: the box is the complement of the widest gap between neighbouring longitudes (the
+    first widest in ascending order), and it crosses +-180 unless that gap is the one across +-180."""
+    cuts = np.sort(np.asarray(lons, dtype=np.float64).ravel())
+    if cuts.size < 2:
+        return False
+    gaps = np.concatenate((cuts[1:] - cuts[:-1], [cuts[0] + 360.0 - cuts[-1]]))
+    k = int(np.argmax(gaps))
+    return k != cuts.size - 1 and bool(wrap_at_180(cuts[k + 1]) > wrap_at_180(cuts[k]))
+
+
+def scanline_global_axes(pxPerDeg):
+    """(latitude nodes ascending, longitude nodes ascending) of the global lattice every grid of `pxPerDeg` is cut from"""
+    latPxPerDeg, lonPxPerDeg = pxPerDeg
+    return (_global_axis(-90, 90, int(round(latPxPerDeg * 180 + 1))), _global_axis(-180, 180, int(round(lonPxPerDeg * 360 + 1))))
+
+
+def _nearest_node(axis, value):
+    i = int(np.clip(np.searchsorted(axis, value), 1, len(axis) - 1))
+    i = i - 1 if abs(axis[i - 1] - value) <= abs(axis[i] - value) else i
+    step = axis[1] - axis[0]
+    assert abs(axis[i] - value) < 1e-3 * step, 'a cell centre {!r} off the global lattice (nearest node {!r})'.format(value, axis[i])
+    return i
+
+
+def scanline_global_origin(grid, pxPerDeg):
+    """(global row of the grid's row 0, global column of its column 0).  Global rows count the latitude nodes from the north
+    (row = number of nodes - 1 - node), global columns the longitude nodes from the west, in the coordinates the grid is laid
+    out in; a cell's index is that of the node nearest its centre (asserted to be within 1e-3 of a step)."""
+    latAll, lonAll = scanline_global_axes(pxPerDeg)
+    top = _nearest_node(latAll, grid.latCenters[0])
+    assert _nearest_node(latAll, grid.latCenters[-1]) == top - (grid.ny - 1)
+    left = _nearest_node(lonAll, grid.lonCenters[0])
+    assert _nearest_node(lonAll, grid.lonCenters[-1]) == left + (grid.nx - 1)
+    return len(latAll) - 1 - top, left
+
+
+def scanline_union_grid(pxPerDeg, rowMin, rowMax, colMin, colMax):
+    """The :class:`_Grid` of the cells with the global rows rowMin .. rowMax and columns colMin .. colMax
+    (:func:`scanline_global_origin`): laid out by ``fixedGrid`` from the nodes one beyond each end, which it returns as they
+    are; its size is checked, and its centres and corners are then taken from the global axes themselves (``linspace`` between
+    two nodes gives the nodes in between only up to rounding)."""
+    latAll, lonAll = scanline_global_axes(pxPerDeg)
+    n = len(latAll) - 1
+    lo, hi = n - rowMax, n - rowMin                                     # latitude nodes of the bottom and the top row
+    assert 1 <= lo <= hi <= n - 1 and 1 <= colMin <= colMax <= len(lonAll) - 2, 'the union reaches the end of the lattice'
+    grid = _Grid(pxPerDeg, latAll[lo - 1], latAll[hi + 1], lonAll[colMin - 1], lonAll[colMax + 1])
+    assert (grid.ny, grid.nx) == (rowMax - rowMin + 1, colMax - colMin + 1), (grid.ny, grid.nx)
+    latStep, lonStep = latAll[0] - latAll[1], lonAll[1] - lonAll[0]
+    grid.latCenters, grid.lonCenters = latAll[lo:hi + 1][::-1].copy(), lonAll[colMin:colMax + 1].copy()
+    grid._latSpace = latAll[lo:hi + 2][::-1] + latStep / 2
+    grid._lonSpace = lonAll[colMin - 1:colMax + 1] + lonStep / 2
+    grid.lat0, grid.lon0 = float(grid.latCenters[0]), float(grid.lonCenters[0])
+    return grid
+
+
+def scanline_window(latAxis, lonAxis, polygon):
+    """(row0, col0, rows, cols): the cells of a frame that can lie in `polygon` — the corners inside the polygon's box, widened
+    by one cell each way and clipped to the grid; all zero when no corner lies in the box.  `latAxis` (ny + 1), `lonAxis`
+    (nx + 1): the corner axes in the polygon's coordinates."""
+    def span(axis, lo, hi):
+        at = np.flatnonzero((axis >= lo) & (axis <= hi))
+        if at.size == 0:
+            return 0, 0
+        first, last = max(int(at[0]) - 1, 0), min(int(at[-1]) + 1, len(axis) - 1)      # corners
+        return first, last - first                                                     # cells between them
+    row0, rows = span(np.asarray(latAxis), polygon[:, 0].min(), polygon[:, 0].max())
+    col0, cols = span(np.asarray(lonAxis), polygon[:, 1].min(), polygon[:, 1].max())
+    return (row0, col0, rows, cols) if rows and cols else (0, 0, 0, 0)
+
+
+def scanline_prepare(lonAxis, polygon, containsDiscontinuity):
+    """The corner axes and the polygon as ``BaseMapping.maskedByPolygon`` prepares a resampled mapping's arrays for the point
+    test: when the mapping or the polygon's box contains the discontinuity, both are shifted by 180 degrees (the same
+    operations, on the 1-D longitude axis).  `lonAxis`: device tensor in the mapping's own longitudes.  Returns (lonAxis
+    [device], polygon [host copy])."""
+    import torch
+    polygon = np.array(polygon, dtype=np.float64)
+    if containsDiscontinuity or lons_contain_discontinuity(polygon[:, 1]):
+        polygon[:, 1] = wrap_at_180(polygon[:, 1] + 180)
+        lonAxis = torch.remainder(lonAxis + 360.0, 360.0) - 180.0           # wrap_at(lon + 180, 180)
+    return lonAxis, polygon
+
+
+def scanline_select(ctx, latAxis, lonAxis, polygon, mask, window):
+    """``amt_scanline_select``: the keep bytes (rows, cols) [device uint8] of `window` and the stats [host int64 (5)]: the
+    number of cells kept and their smallest / largest row and column in the frame."""
+    import torch
+    ny, nx = int(mask.shape[0]), int(mask.shape[1])
+    row0, col0, rows, cols = window
+    keep = ctx.empty((rows, cols), torch.uint8)
+    stats = ctx.empty((5,), torch.int64)
+    poly = ctx.to_device(np.ascontiguousarray(polygon, dtype=np.float64))
+    ctx.call('amt_scanline_select', ptr(latAxis), ptr(lonAxis), ny, nx, ptr(poly), int(poly.shape[0]), ptr(mask), row0, col0, rows,
+             cols, ptr(keep) if rows * cols else None, ptr(stats))
+    return keep, to_host(stats)               # (the read-back waits for the kernel: `poly` may go)
+
+
+def scanline_pack(ctx, keep, window, planes, img, img_dtype_code, nch, rowOffset, colOffset, count):
+    """``amt_scanline_pack``: the records of the kept cells as device tensors (row, col int32 (count), planes (P, count), img
+    (C, count)); `planes` (ny, nx, P), `img` (ny, nx, C)."""
+    import torch
+    ny, nx, nplane = (int(v) for v in planes.shape)
+    row0, col0, rows, cols = window
+    row, col = ctx.empty((count,), torch.int32), ctx.empty((count,), torch.int32)
+    outPlanes = ctx.empty((nplane, count))
+    outImg = ctx.empty((max(nch, 1), count), torch.uint8 if img_dtype_code != 2 else torch.int16)
+    ctx.call('amt_scanline_pack', ptr(keep), row0, col0, rows, cols, ptr(planes), nplane, ptr(img) if nch else None,
+             img_dtype_code or 1, nch, ny, nx, int(rowOffset), int(colOffset), int(count), ptr(row), ptr(col), ptr(outPlanes),
+             ptr(outImg) if nch else None)
+    return dict(row=row, col=col, planes=outPlanes, img=outImg, count=int(count))
+
+
+def scanline_compose(ctx, strips, frames, nch, nplane, img_dtype_code, rowBase, colBase, NY, NX):
+    """``amt_scanline_compose``: the union raster of `strips` (the dicts of :func:`scanline_pack`) with the ascending frame
+    indices `frames`: device tensors planes (NY, NX, nplane), img (NY, NX, max(C, 1)), mask (NY, NX), frameIndex (NY, NX)."""
+    import torch
+    from ._native import ScanLineStrip
+    table = (ScanLineStrip * len(strips))()
+    for t, s, k in zip(table, strips, frames):
+        some = s['count'] > 0
+        t.row, t.col = (s['row'].data_ptr(), s['col'].data_ptr()) if some else (None, None)
+        t.planes = s['planes'].data_ptr() if some and nplane else None
+        t.img = s['img'].data_ptr() if some and nch else None
+        t.count, t.frame = s['count'], int(k)
+    planes = ctx.empty((NY, NX, nplane))
+    img = ctx.zeros((NY, NX, max(nch, 1)), torch.uint8 if img_dtype_code != 2 else torch.int16)
+    mask = ctx.empty((NY, NX), torch.uint8)
+    frameIndex = ctx.empty((NY, NX), torch.int32)
+    ctx.call('amt_scanline_compose', table, len(strips), img_dtype_code or 1, nch, nplane, int(rowBase), int(colBase), NY, NX,
+             ptr(planes), ptr(img) if nch else None, ptr(mask), ptr(frameIndex))
+    return planes, img, mask, frameIndex
+
+
+def _scanline_frame(mapping, k, props, pxPerDeg, shifted):
+    """Frame `k` of a scan-line sequence resampled on the sequence's lattice (device tensors), with what the strip pass needs:
+    the corner axes (latitude on the device; longitude in the mapping's own longitudes, host and device) and the global origin"""
+    fd = mapping.frame()
+    res = resample_frame(fd, mapping.altitude, props.boundingBox, pxPerDeg, containsDiscontinuity=shifted, containsPole=False,
+                         method='mean', keep_on_device=True)
+    grid, ctx = res['grid'], fd.ctx
+    lonOwn = wrap_at_180(grid._lonSpace + 180) if shifted else grid._lonSpace          # (as grid_coordinates does)
+    res.update(ctx=ctx, frame=k, lat_axis_host=grid._latSpace, lon_own_host=lonOwn,
+               lat_axis=ctx.to_device(np.ascontiguousarray(grid._latSpace)), lon_own=ctx.to_device(np.ascontiguousarray(lonOwn)),
+               origin=scanline_global_origin(grid, pxPerDeg), nchan=fd.nchan, img_dtype_code=fd.img_dtype_code,
+               img_dtype=fd.img_dtype if fd.nchan else None, identifier=mapping.identifier)
+    return res
+
+
+def _scanline_free_columns(res):
+    """(first, last) column of `res` with an unmasked cell; ValueError when every cell is masked"""
+    import torch
+    cols = torch.nonzero((res['mask'] == 0).any(0)).reshape(-1)
+    if cols.numel() == 0:
+        raise ValueError('scan lines: frame {} ({!r}) has no valid cell'.format(res['frame'], res['identifier']))
+    return int(cols[0].item()), int(cols[-1].item())
+
+
+def scanline_first_cell_diagonal(res):
+    """Metres between corners 0 and 2 of the first unmasked cell, row-major, of a resampled frame (what the reference reads
+    from the first polygon of ``generatePolygonsFromMapping``, draw.py:701-704)."""
+    import torch
+    from .coordinates import geodesic
+    free = (res['mask'].reshape(-1) == 0)
+    first = int(torch.argmax(free.to(torch.uint8)).item())
+    if not bool(free[first].item()):
+        raise ValueError('scan lines: frame {} ({!r}) has no valid cell'.format(res['frame'], res['identifier']))
+    r, c = divmod(first, int(res['mask'].shape[1]))
+    lat, lon = res['lat_axis_host'], res['lon_own_host']
+    return geodesic.distance(geodesic.Location(float(lat[r]), float(lon[c])), geodesic.Location(float(lat[r + 1]), float(lon[c + 1])))
+
+
+def _scanline_strip_records(res, polygon):
+    """The strip of a resampled frame: select, check, pack.  Returns (records, stats, line bounding box)."""
+    ctx = res['ctx']
+    cmin, cmax = _scanline_free_columns(res)
+    own = res['lon_own_host'][cmin:cmax + 2]
+    # the resampled mapping's containsDiscontinuity: the longitudes of its unmasked corners span more than 180 degrees
+    lonAxis, poly = scanline_prepare(res['lon_own'], polygon, bool(own.max() - own.min() > 180))
+    window = scanline_window(res['lat_axis_host'], lonAxis.cpu().numpy(), poly)
+    keep, stats = scanline_select(ctx, res['lat_axis'], lonAxis.contiguous(), poly, res['mask'], window)
+    count = int(stats[0])
+    if count == 0:
+        raise ValueError('The given mask would mask all pixels! (scan lines: the strip of frame {} ({!r}) keeps no cell)'
+                         .format(res['frame'], res['identifier']))
+    rowOffset, colOffset = res['origin']
+    records = scanline_pack(ctx, keep, window, res['mean'], res['img'], res['img_dtype_code'], res['nchan'], rowOffset, colOffset,
+                            count)
+    lat, lon = res['lat_axis_host'], res['lon_own_host']
+    box = BoundingBox(float(lat[stats[2] + 1]), float(lon[stats[3]]), float(lat[stats[1]]), float(lon[stats[4] + 1]))
+    return records, stats, box
+
+
+def resampleScanLines(mappings, arcsecPerPx=100, pxPerDeg=None, lineWidthFactor=1):
+    """
+    The scan-line map of a sequence as one raster (the reference's ``drawScanLinesCo``, auromat/draw.py:589-879, without the
+    drawing): every mapping contributes the strip of its resampled cells through its centroid, perpendicular to the direction
+    of flight of the centroids, and the strips of all mappings lie side by side on one plate carree grid — an overview of a
+    whole pass in time and space.  Where strips overlap the later mapping's cells lie on top, as the reference draws them.
+
+    The centroid of each mapping becomes the centre of its strip, so mask the mappings by elevation first.  All mappings are
+    resampled (``method='mean'``) with ONE resolution, the first mapping's ``plateCarreeResolution`` for `arcsecPerPx` unless
+    `pxPerDeg` is given, so that all grids are cut from one global lattice; and in ONE longitude frame: shifted by 180 degrees
+    iff the first mapping's centroid has |lon| > 90 (date-line passes stay whole).  A cell belongs to a strip when it is
+    valid and its four corners lie inside the strip's polygon (the rule of ``maskedByPolygon``; ``amt_scanline_select``);
+    only the strips' cells are kept on the device (``amt_scanline_pack``) until they are put together
+    (``amt_scanline_compose``).
+
+    :param mappings: iterable of unresampled mappings, consumed once; one is held at a time
+    :param number arcsecPerPx: spherical resolution of the resampling
+    :param None|number|tuple pxPerDeg: (latPxPerDeg, lonPxPerDeg) or a number; has precedence over `arcsecPerPx`
+    :param number lineWidthFactor: widens the strips relative to the width derived from the first two mappings; useful when
+                                   mappings in between are missing
+    :raises ValueError: fewer than two mappings; a mapping that does not fit the sequence's longitude frame (the sequence
+                        spans its seam); a strip that keeps no cell or reaches a pole; mappings of different altitudes, image
+                        types or channel counts.  A mapping with a pole in view raises what its ``centroid`` raises.
+    :rtype: ScanLineMapping
+    """
+    from .mapping.mapping import ScanLineMapping
+    short = ValueError('mapping sequence too short, need at least 2 mappings')
+    it = iter(mappings)
+    mapping = next(it, None)
+    if mapping is None:
+        raise short
+    # values like the centroid come from the unresampled mapping (more accurate), as in the reference
+    props = mapping.properties
+    ppd = _px_per_deg(pxPerDeg) if pxPerDeg is not None else plateCarreeResolution(props.boundingBox, arcsecPerPx)
+    shifted = scanline_longitude_frame(props.centroid)
+    scanline_check_fits(props.boundingBox, shifted, 0, props.identifier)
+    altitude, cameraPosGCRS, photoTime, metadata = mapping.altitude, mapping.cameraPosGCRS, mapping.photoTime, mapping.metadata
+    cur = _scanline_frame(mapping, 0, props, ppd, shifted)
+    rule = _ScanLineRule(props, scanline_first_cell_diagonal(cur), lineWidthFactor)
+    per = dict(photoTimes=[], identifiers=[], centroids=[], azimuths=[], polygons=[], lineBoundingBoxes=[])
+    strips, extents = [], []
+
+    def finish(res, curProps, nextProps):
+        polygon, az = rule.strip(curProps, nextProps)
+        records, stats, box = _scanline_strip_records(res, polygon)
+        strips.append(records)
+        r0, c0 = res['origin']
+        extents.append((r0 + stats[1], r0 + stats[2], c0 + stats[3], c0 + stats[4]))
+        for name, value in (('photoTimes', curProps.photoTime), ('identifiers', curProps.identifier), ('centroids', curProps.centroid),
+                            ('azimuths', az), ('polygons', polygon), ('lineBoundingBoxes', box)):
+            per[name].append(value)
+
+    k = 0
+    for mapping in it:
+        k += 1
+        nextProps = mapping.properties
+        fd = mapping.frame()
+        if (mapping.altitude, fd.nchan, fd.img_dtype_code) != (altitude, cur['nchan'], cur['img_dtype_code']):
+            raise ValueError('scan lines: frame {} ({!r}) differs from the first in altitude, image type or channel count'
+                             .format(k, mapping.identifier))
+        scanline_check_fits(nextProps.boundingBox, shifted, k, nextProps.identifier)
+        finish(cur, props, nextProps)
+        cur = _scanline_frame(mapping, k, nextProps, ppd, shifted)
+        props = nextProps
+        del mapping, fd
+    if k == 0:
+        raise short
+    finish(cur, props, None)
+
+    from .coordinates import geodesic
+    ctx, nch, code = cur['ctx'], cur['nchan'], cur['img_dtype_code']
+    ext = np.array(extents, dtype=np.int64)
+    rowMin, rowMax, colMin, colMax = int(ext[:, 0].min()), int(ext[:, 1].max()), int(ext[:, 2].min()), int(ext[:, 3].max())
+    union = scanline_union_grid(ppd, rowMin, rowMax, colMin, colMax)
+    planes, img, mask, frameIndex = scanline_compose(ctx, strips, range(len(strips)), nch, nch + 1, code, rowMin, colMin, union.ny,
+                                                     union.nx)
+    out = _result(union, False, shifted, altitude, cur['has_elev'], dict(mean=planes, img=img, mask=mask), False,
+                  cur['img_dtype'])
+    image, elevation = _masked_image_and_elevation(out['mask'], out['mean'], out['img'], out['has_elev'])
+    index = to_host(frameIndex, dtype=np.int32)
+    maxHeight = max(geodesic.distance(b.topLeft, b.bottomRight) for b in per['lineBoundingBoxes'])
+    return ScanLineMapping(out['lat'], out['lon'], out['lat_c'], out['lon_c'], elevation, altitude, image, cameraPosGCRS,
+                           photoTime, '{}..{}'.format(per['identifiers'][0], per['identifiers'][-1]),
+                           ma.masked_array(index, mask=index < 0), per['photoTimes'], per['identifiers'], per['centroids'],
+                           per['azimuths'], per['polygons'], per['lineBoundingBoxes'], rule.width, rule.height, maxHeight, ppd,
+                           metadata=metadata)
+
+
+def resampleScanLinesMLatMLT(mappings, **kw):
+    """
+    :func:`resampleScanLines` in (MLat, SM longitude), the raster of the reference's ``drawScanLinesMLatMLTCo``
+    (auromat/draw.py:858-879): every mapping goes through ``convertMappingToSM`` first.  The coordinate arrays, centroids,
+    polygons and boxes of the result are magnetic (MLat, SM longitude: 180 degrees is magnetic midnight).
+
+    See :func:`resampleScanLines` for parameters.
+    """
+    return resampleScanLines((convertMappingToSM(m) for m in mappings), **kw)
+
+
 def fixedGrid(pxPerDeg, latMin, latMax, lonMin, lonMax):
     """
     Aligns the given bounding box to a fixed plate carree grid as defined by `pxPerDeg`

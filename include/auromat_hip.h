@@ -50,7 +50,8 @@ extern "C" {
  *    (auromat_amd.pipeline.SequencePipeline(statistic='area')); map projections — amt_projection,
  *    amt_projection_stereographic, amt_projection_polar_aeqd, amt_project_forward, amt_project_inverse
  *    (auromat_amd.coordinates.projection) — and area-weighted binning on a map plane — amt_area_plane_frame
- *    (auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT, resampleMLatMLTPolar) */
+ *    (auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT, resampleMLatMLTPolar); scan-line maps —
+ *    amt_scanline_select, amt_scanline_pack, amt_scanline_compose, amt_scanline_strip (auromat_amd.resample.resampleScanLines) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -729,6 +730,53 @@ int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, 
                            int32_t nchan, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
                            int32_t rule, uint64_t min_weight, double* area, void* out_img, uint8_t* out_mask,
                            double* out_coverage, int32_t* out_source);
+/* Scan-line maps (additions to ABI v10; auromat_amd.resample.resampleScanLines, reference draw.py:589-879 drawScanLinesCo): a
+ * narrow strip of every resampled frame of a sequence, all strips on one raster.
+ *
+ * amt_scanline_select: which cells of ONE plate carree frame of ny x nx cells lie in a polygon.  lat_axis [ny + 1] / lon_axis
+ * [nx + 1]: the latitudes of the corner rows and the longitudes of the corner columns (corner (i, j) of the frame is (lat_axis[i],
+ * lon_axis[j]); the 2-D corner arrays are never read); polygon [n_vertices][2] (lat, lon), closed implicitly; cell_mask [ny][nx],
+ * non-zero = masked.  The window [row0, row0 + rows) x [col0, col0 + cols) must lie in the grid (AMT_EINVAL otherwise); cells
+ * outside it are not kept by definition and have no keep byte.  out_keep [rows][cols]: 1 iff the cell is unmasked and all four
+ * of its corners are inside the polygon, the rule of BaseMapping.maskedByPolygon; a corner is inside exactly when
+ * amt_points_in_polygon says so for px = its latitude, py = its longitude (the same arithmetic, bit for bit; a corner that is not
+ * finite is outside).  out_stats int64[5]: the number of cells kept and the smallest / largest kept row and the smallest / largest
+ * kept column, as rows and columns OF THE FRAME (not of the window); with nothing kept 0, INT64_MAX, INT64_MIN, INT64_MAX,
+ * INT64_MIN.  n_vertices < 3 keeps nothing; an empty window writes only out_stats.  Only enqueues work.  AMT_EINVAL (nothing
+ * written): NULL pointers, ny or nx <= 0, a window outside the grid. */
+int amt_scanline_select(amt_ctx* ctx, const double* lat_axis, const double* lon_axis, int32_t ny, int32_t nx,
+                        const double* polygon, int32_t n_vertices, const uint8_t* cell_mask, int32_t row0, int32_t col0,
+                        int32_t rows, int32_t cols, uint8_t* out_keep, int64_t* out_stats);
+/* amt_scanline_pack: one record per keep byte set in the window, structure of arrays: out_row / out_col int32 [count] (the
+ * cell's row / column in the frame plus row_offset / col_offset), out_planes [nplane][count] from planes [ny][nx][nplane]
+ * (float64; nplane 0..5: the image channels' means and, last, the elevation when present), out_img [nchan][count] from img
+ * [ny][nx][nchan] (nchan 0..4; img_dtype 1 = uint8, 2 = uint16).  `count` is amt_scanline_select's out_stats[0].  The records of
+ * one call are unique; their order is unspecified.  Synchronises: AMT_EINVAL when `count` is not the number of keep bytes set
+ * (no record beyond `count` is written). */
+int amt_scanline_pack(amt_ctx* ctx, const uint8_t* keep, int32_t row0, int32_t col0, int32_t rows, int32_t cols,
+                      const double* planes, int32_t nplane, const void* img, int32_t img_dtype, int32_t nchan, int32_t ny,
+                      int32_t nx, int32_t row_offset, int32_t col_offset, int64_t count, int32_t* out_row, int32_t* out_col,
+                      double* out_planes, void* out_img);
+/* amt_scanline_compose: the strips (record arrays of amt_scanline_pack) on one raster of NY x NX cells whose cell (0, 0) is
+ * (row_base, col_base) of the records' global indices.  `strips` is a HOST array; its frame indices are >= 0 and ascend
+ * strictly (AMT_EINVAL otherwise).  Every output is written whole: planes [NY][NX][nplane] (NaN where empty), img
+ * [NY][NX][nchan] (0), mask [NY][NX] (1 where empty), frame_index int32 [NY][NX] (-1).  A cell that several strips hold goes to
+ * the one with the LARGEST frame index, whole (the reference draws later frames over earlier ones): an integer maximum per cell
+ * first, then every record writes where its strip won, so the result does not depend on the order of anything.  Within one
+ * strip the records must be unique.  Synchronises: AMT_EDOMAIN when a record lies outside the raster (none is dropped
+ * silently; the outputs then hold the records inside it). */
+typedef struct amt_scanline_strip {
+    const int32_t* row;               /* [count] */
+    const int32_t* col;               /* [count] */
+    const double* planes;             /* [nplane][count] */
+    const void* img;                  /* [nchan][count] */
+    int64_t count;                    /* may be 0 (the pointers are then not read) */
+    int32_t frame;                    /* the frame's index in the sequence */
+    int32_t reserved;
+} amt_scanline_strip;
+int amt_scanline_compose(amt_ctx* ctx, const amt_scanline_strip* strips, int32_t n_strips, int32_t img_dtype, int32_t nchan,
+                         int32_t nplane, int32_t row_base, int32_t col_base, int32_t NY, int32_t NX, double* planes, void* img,
+                         uint8_t* mask, int32_t* frame_index);
 /* Same for float accumulators of amt_hist2d_accumulate: mean[k] = sums[k]/count, NaN where empty,
  * transposed + flipped to (ny, nx, nweights). */
 int amt_hist2d_finalize_mean(amt_ctx* ctx, const double* count, const double* const* sums, int32_t nweights,
