@@ -132,6 +132,17 @@ class RunResult(C.Structure):
                 ('retried', C.c_int32), ('reserved2_', C.c_int32), ('uploaded_bytes', C.c_int64)]
 
 
+class LensModel(C.Structure):
+    """amt_lens_model"""
+    _fields_ = [(k, C.c_int32) for k in ('kind', 'width', 'height', 'crop_x', 'crop_y', 'crop_width', 'crop_height', 'reserved')] + \
+               [('k', C.c_double * 3)]
+
+
+class LensDebug(C.Structure):
+    """amt_lens_debug"""
+    _fields_ = [('force_path', C.c_int32), ('reserved', C.c_int32), ('tile_path', C.c_void_p)]
+
+
 ABI_VERSION = 10         # include/auromat_hip.h AMT_ABI_VERSION
 QUANTILES_MAX = 8         # AMT_QUANTILES_MAX: quantiles per call of amt_quantile_frame[_async]
 PIPE_MAX_EDGE_PIXELS = 16384     # AMT_PIPE_MAX_EDGE_PIXELS: a fused frame with more on-edge pixels is not launched again
@@ -171,6 +182,10 @@ _SIGNATURES = {
     'amt_directions_tan': ([_P, C.POINTER(FrameParams), _I, _P], _I),
     'amt_directions_zenithal': ([_P, C.POINTER(ZenithalWcs), _P], _I),
     'amt_directions_tan_points': ([_P, C.POINTER(FrameParams), _P, _P, _L, _I, _P], _I),
+    'amt_lens_coords': ([_P, C.POINTER(LensModel)] + [C.c_int32] * 4 + [_I, _P, _P], _I),
+    'amt_lens_undistort': ([_P, C.POINTER(LensModel)] + [C.c_int32] * 4 + [_I, _P], _I),
+    'amt_lens_remap': ([_P, C.POINTER(LensModel), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(LensDebug)], _I),
+    'amt_remap_coords': ([_P, _P] + [C.c_int32] * 4 + [_P] + [C.c_int32] * 3 + [_P, _P, C.POINTER(LensDebug)], _I),
     'amt_intersect_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersects_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersect_sphere': ([_P, _D, c_double_p, _P, _L, _I, _P], _I),

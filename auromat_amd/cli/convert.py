@@ -28,6 +28,12 @@ What differs, and why:
   the cells it overlaps, weighted with the covered fraction of the cell (:func:`auromat_amd.resample.resampleArea` /
   ``resampleAreaMLatMLT``), through the same two routes: no holes between the pixel centres on fine grids.  ``--min-coverage F``
   (default 0.5, in [0, 1]) masks the cells of which the pixels cover less than F.  The files hold the variables a mean grid's do.
+* ``--lens-model`` / ``--lens-params`` (an addition): the images are RAW-developed frames that have not been corrected for lens
+  distortion, while their ``.wcs`` files were solved on the corrected image, cropped to a multiple of ``--crop-divisible-by`` — the
+  state of the ESA ISS archive, whose ``distortion_correction`` entry (reference mapping/iss.py:233-237) is honoured when it is
+  found in ``metadata.json`` or a frame's ``<id>.json`` and no flag is given.  ``--lens-route resample`` (default) corrects and
+  crops every image on the GPU (:meth:`auromat_amd.util.lensdistortion.LensModifier.remap_device`) and goes on as ever;
+  ``--lens-route raw`` maps the uncorrected pixels themselves (``getMapping(..., lensRoute='raw')``), through the mapping classes.
 """
 from __future__ import print_function
 
@@ -112,6 +118,18 @@ def getParser():
     resampleArgs.add_argument('--min-coverage', dest='minCoverage', metavar='F', type=float,
                               help='for --statistic area: a cell is masked unless the pixels cover at least this fraction of it, '
                                    'in [0, 1], default 0.5 (0: any overlap at all)')
+    lensArgs = parser.add_argument_group('lens distortion', 'For images that are not yet corrected for lens distortion (an addition; '
+                                         'by default the distortion_correction entry of metadata.json or <id>.json, if any).')
+    lensArgs.add_argument('--lens-model', dest='lensModel', choices=['poly3', 'poly5', 'ptlens'],
+                          help='lensfun distortion model of the frames')
+    lensArgs.add_argument('--lens-params', dest='lensParams', metavar='P', type=float, nargs='+',
+                          help='its coefficients: k1 (poly3), k1 k2 (poly5) or a b c (ptlens)')
+    lensArgs.add_argument('--lens-route', dest='lensRoute', choices=['resample', 'raw'], default='resample',
+                          help='resample: correct (Lanczos-4) and crop every image on the GPU first, default; raw: map the '
+                               'uncorrected pixels themselves, nothing interpolated')
+    lensArgs.add_argument('--crop-divisible-by', dest='cropDivisibleBy', metavar='N', type=int,
+                          help='the .wcs files belong to the corrected image cropped to the next smaller width and height '
+                               'divisible by N (16 for the ESA ISS archive); default: not cropped')
     outputArgs = parser.add_argument_group('output')
     outputArgs.add_argument('--out', help='Output directory, by default the "converted" subdirectory of --data')
     outputArgs.add_argument('--overwrite', help='Overwrites existing files.', action='store_true')
@@ -160,6 +178,14 @@ def parseargs(argv=None):
             parser.error('--min-coverage must be in the range [0, 1]')
     elif args.minCoverage is not None:
         parser.error('--min-coverage is only usable with --statistic area')
+    if (args.lensModel is None) != (args.lensParams is None):
+        parser.error('--lens-model and --lens-params go together')
+    if args.lensModel is not None:
+        from ..util.lensdistortion import MODELS
+        if len(args.lensParams) != MODELS[args.lensModel][1]:
+            parser.error('--lens-model %s takes %d parameter(s)' % (args.lensModel, MODELS[args.lensModel][1]))
+    if args.cropDivisibleBy is not None and args.cropDivisibleBy < 1:
+        parser.error('--crop-divisible-by must be positive')
     if args.withoutGeo and args.format == Format.netcdf:
         parser.error('--without-geo is only usable with --format cdf')
     if args.format == Format.cdf:
@@ -226,6 +252,40 @@ def list_frames(data_dir, start=None, end=None):
     return [(b, h, i) for _, b, h, i in frames]
 
 
+def lens_spec(args, hdr, metadata=None):
+    """(model, params) of the lens distortion a frame still carries, or None: the flags, else the ``distortion_correction`` entry
+    ({"model": ..., "params": [...]}, the key of the reference's ISS archive, mapping/iss.py:233-237) of the frame's own
+    ``<id>.json``, else that of ``metadata.json`` (top level, or under ``sequence_metadata``)."""
+    if args.lensModel is not None:
+        return args.lensModel, list(args.lensParams)
+    entry = hdr.get('distortion_correction')
+    if not entry and metadata:
+        entry = metadata.get('distortion_correction') or (metadata.get('sequence_metadata') or {}).get('distortion_correction')
+    if not entry:
+        return None
+    return entry['model'], [float(p) for p in entry['params']]
+
+
+def read_metadata(data_dir):
+    """metadata.json of the data directory as a dict, or None"""
+    import json
+    path = os.path.join(data_dir, 'metadata.json')
+    if not os.path.exists(path):
+        return None
+    with open(path) as fp:
+        return json.load(fp)
+
+
+def lens_of(args, hdr, metadata, width, height):
+    """The LensModifier (crop included) for a raw frame of the given size, or None when the frame carries no distortion."""
+    spec = lens_spec(args, hdr, metadata)
+    if spec is None:
+        return None
+    from ..util.lensdistortion import getLensfunModifierFromParams
+    mod = getLensfunModifierFromParams(spec[0], spec[1], width, height)
+    return mod.cropped(args.cropDivisibleBy) if args.cropDivisibleBy else mod
+
+
 def target_path(args, identifier):
     """-> path to write, or None when the frame is to be skipped; exits like the reference when the file exists."""
     path = os.path.join(args.out, identifier + extension(args))
@@ -252,12 +312,14 @@ def convert_with_classes(args, frames, export):
     from ..mapping.spacecraft import getMapping
     from ..resample import (resample, resampleArea, resampleAreaMLatMLT, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT,
                             resampleQuantile, resampleQuantileMLatMLT)
+    metadata = read_metadata(args.data)
     for identifier, hdr, img_path in frames:
         path = target_path(args, identifier)
         if path is None:
             continue
-        mapping = getMapping(read_image(img_path), hdr, altitude=args.altitude,
-                             fastCenterCalculation=not args.exactCenters, identifier=identifier)
+        img = read_image(img_path)
+        mapping = getMapping(img, hdr, altitude=args.altitude, fastCenterCalculation=not args.exactCenters, identifier=identifier,
+                             lens=lens_of(args, hdr, metadata, img.shape[1], img.shape[0]), lensRoute=args.lensRoute)
         if args.resample:
             if args.minElevation >= 0:
                 mapping = mapping.maskedByElevation(args.minElevation)
@@ -348,7 +410,14 @@ def convert_with_pipeline(args, frames, export):
     if todo:
         first = read_image(todo[0][2], mmap=True)
         magnetic = args.grid == Grid.mag
-        seq = SequencePipeline(first.shape[1], first.shape[0], nchan=first.shape[2], img_dtype=first.dtype,
+        metadata = read_metadata(args.data)
+        # frames that still carry their lens distortion are corrected and cropped on the device and handed to the pipeline as
+        # device-resident images of the corrected size (the lens is not part of the native runner)
+        lenses = [lens_of(args, hdr, metadata, first.shape[1], first.shape[0]) for _, hdr, _, _ in todo]
+        if any(m is not None for m in lenses) and any(m is None or m.corrected_size != lenses[0].corrected_size for m in lenses):
+            raise NotImplementedError('a sequence of which only some frames carry a lens distortion')
+        size = lenses[0].corrected_size if lenses[0] is not None else (first.shape[1], first.shape[0])
+        seq = SequencePipeline(size[0], size[1], nchan=first.shape[2], img_dtype=first.dtype,
                                altitude=args.altitude, fast=not args.exactCenters,
                                min_elevation=args.minElevation if args.minElevation >= 0 else None,
                                pxPerDeg=args.pxPerDeg or 10, magnetic=magnetic, keep_coordinates=False,
@@ -375,7 +444,11 @@ def convert_with_pipeline(args, frames, export):
                     if nxt is not None:
                         pending.append((nxt, pool.submit(read_image, nxt[2])))
                     cam, t = frame_inputs(hdr)
-                    yield hdr, cam, t, fut.result()
+                    img = fut.result()
+                    if lenses[0] is not None:
+                        img = lens_of(args, hdr, metadata, img.shape[1], img.shape[0]).remap_device(img, 'lanczos4')
+                        torch.cuda.current_stream().synchronize()       # (the pipeline reads it on streams of its own)
+                    yield hdr, cam, t, img
 
         metas = [frame_inputs(hdr) for _, hdr, _, _ in todo]
         results = seq.process(feed(), keep_on_device=True)
@@ -437,7 +510,10 @@ def main(argv=None):
     # --resample, with the reference's --resolution (default 100 arcsec per pixel) or with --px-per-deg: the sequence pipeline;
     # without --resample the frames are exported as they are, through the mapping classes (AMT_CONVERT_CLASSES=1 sends
     # resampling runs that way too: the reference's flow frame by frame, for A/B runs)
-    if args.resample and not os.environ.get('AMT_CONVERT_CLASSES'):
+    # (the raw lens route maps through direction arrays, which the sequence pipeline's runner does not take)
+    metadata = read_metadata(args.data)
+    raw_route = args.lensRoute == 'raw' and any(lens_spec(args, hdr, metadata) for _, hdr, _ in frames)
+    if args.resample and not raw_route and not os.environ.get('AMT_CONVERT_CLASSES'):
         convert_with_pipeline(args, frames, export)
     else:
         convert_with_classes(args, frames, export)

@@ -120,7 +120,7 @@ ArrayMapping = ArraySpacecraftMapping
 
 def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, tleFolder=None, spacetrack=None,
                altitude=110, fastCenterCalculation=False, metadata=None, nosanitize=False, identifier=None,
-               cameraPosGCRS=None):
+               cameraPosGCRS=None, lens=None, lensRoute='resample', cropDivisibleBy=None):
     """
     Build a mapping from an image (array, or path of an image file) and a WCS header (dict, or path of a ``.wcs``
     header-only FITS file) — the reference's signature and positional order (spacecraft.py:380-426, 428-485).  Photo
@@ -132,6 +132,15 @@ def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, 
     instead of being ignored: ``noradId`` / ``tleFolder`` / ``spacetrack`` (camera position from two-line elements:
     pass ``cameraPosGCRS`` instead, which is also needed with ``timeshift`` or for a header without POS? cards).
     ``nosanitize`` only affects the reference's file-based mappings and is accepted.
+
+    ``lens`` (a :class:`auromat_amd.util.lensdistortion.LensModifier` for the raw frame's size): the image is a RAW frame that
+    has not been corrected for lens distortion, and the header was solved on the corrected image (cropped to a multiple of
+    ``cropDivisibleBy`` if given) — the state of the ISS archive (reference mapping/iss.py:232-243).  ``lensRoute='resample'``
+    corrects and crops the image on the device (Lanczos-4) and goes on as without a lens; ``'raw'`` keeps the image as it is, at
+    its full size, and maps it through a :class:`DirectionArrayMapping`: every raw pixel corner's place in the corrected frame
+    (``amt_lens_undistort``) goes through the TAN model into a direction — no interpolated image in between.  Raw pixels that the
+    model cannot be inverted for are masked.  The raw route's centres are the mean of their corners' hits (the fast mode).
+    Only plain TAN headers take a lens.
     """
     imageArray, wcsHeader = imagePathOrArray, wcsPathOrHeader
     if isinstance(wcsHeader, str):
@@ -162,6 +171,24 @@ def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, 
         raise ValueError('Spacecraft position is missing in the header; pass cameraPosGCRS '
                          '(TLE propagation is not part of this package)')
     from ..coordinates.wcs import is_plain_tan, zenithal_directions_device
+    if lens is not None:
+        if lensRoute not in ('resample', 'raw'):
+            raise ValueError("lensRoute must be 'resample' or 'raw', not %r" % (lensRoute,))
+        if not is_plain_tan(wcsHeader):
+            raise NotImplementedError('lens= is supported for plain TAN headers only')
+        mod = lens.cropped(cropDivisibleBy) if cropDivisibleBy else lens
+        if (wcsHeader['IMAGEW'], wcsHeader['IMAGEH']) != mod.corrected_size:
+            raise ValueError('the header is for a %d x %d image, the corrected%s frame is %d x %d'
+                             % ((wcsHeader['IMAGEW'], wcsHeader['IMAGEH'], ' and cropped' if mod.crop else '') + mod.corrected_size))
+        if lensRoute == 'raw':
+            from ..coordinates.wcs import tan_pix2world
+            from .astrometry import DirectionArrayMapping
+            xy = mod.undistorted_coordinates_device(corner=True)
+            dirs = tan_pix2world(wcsHeader, xy[..., 0].contiguous(), xy[..., 1].contiguous(), 0, ascartesian=True)
+            m = DirectionArrayMapping(dirs, altitude, np.asarray(imageArray), cam, photoTime, identifier, metadata)
+            m.originalPhotoTime = originalPhotoTime
+            return m
+        imageArray = mod.remap(np.asarray(imageArray), 'lanczos4')
     if not is_plain_tan(wcsHeader):
         # another zenithal projection or SIP terms (the reference hands such headers to astropy.wcs, wcs.py:54-56): the
         # corner directions from the device generator (amt_directions_zenithal; coordinates.wcs.zenithal_pix2world is its
@@ -185,12 +212,24 @@ def getMappingSequence(imagePathsOrArrays, wcsPaths, metadatas=None, timeshift=N
     given order — the reference's signature and positional order (spacecraft.py:308-332).  ``parallel`` (a process
     pool per frame in the reference) is accepted and ignored: frames are independent and
     :mod:`auromat_amd.sequence` / :class:`auromat_amd.pipeline.SequencePipeline` shard and pipeline them on the GPUs.
+    Frames that still carry their lens distortion: :func:`getLensMappingSequence`.
     """
+    return getLensMappingSequence(imagePathsOrArrays, wcsPaths, None, metadatas=metadatas, timeshift=timeshift, noradId=noradId,
+                                  tleFolder=tleFolder, spacetrack=spacetrack, altitude=altitude, parallel=parallel,
+                                  fastCenterCalculation=fastCenterCalculation)
+
+
+def getLensMappingSequence(imagePathsOrArrays, wcsPaths, lens, lensRoute='resample', cropDivisibleBy=None, metadatas=None,
+                           timeshift=None, noradId=None, tleFolder=None, spacetrack=None, altitude=110, parallel=False,
+                           fastCenterCalculation=False):
+    """:func:`getMappingSequence` for raw frames of one size with the ``lens``, ``lensRoute`` and ``cropDivisibleBy`` of
+    :func:`getMapping` (a function of its own: the reference's signature of ``getMappingSequence`` stays as it is)."""
     if not metadatas:
         metadatas = [None] * len(wcsPaths)
     for img, hdr, meta in zip(imagePathsOrArrays, wcsPaths, metadatas):
         yield getMapping(img, hdr, timeshift, noradId, tleFolder, spacetrack, altitude=altitude,
-                         fastCenterCalculation=fastCenterCalculation, metadata=meta)
+                         fastCenterCalculation=fastCenterCalculation, metadata=meta, lens=lens, lensRoute=lensRoute,
+                         cropDivisibleBy=cropDivisibleBy)
 
 
 def getShiftedPhotoTime(header):
@@ -256,12 +295,14 @@ class SpacecraftMappingProvider(BaseMappingProvider):
 
     def __init__(self, imageSequenceFolder, wcsFolder=None, imageFileExtension=None, timeshift=None, noradId=None,
                  tleFolder=None, spacetrack=None, altitude=110, maxTimeOffset=3, sequenceInParallel=False,
-                 fastCenterCalculation=False):
+                 fastCenterCalculation=False, lens=None, lensRoute='resample', cropDivisibleBy=None):
         """
         :param imageSequenceFolder: folder path or a list of image file paths
         :param wcsFolder: folder path or a list of wcs file paths; may be left out when the image folder holds the wcs files too
+        :param lens, lensRoute, cropDivisibleBy: as for :func:`getMapping`
         """
         BaseMappingProvider.__init__(self, maxTimeOffset=maxTimeOffset)
+        self.lens, self.lensRoute, self.cropDivisibleBy = lens, lensRoute, cropDivisibleBy
         lists = isinstance(imageSequenceFolder, list), isinstance(wcsFolder, list)
         if wcsFolder is None:
             if lists[0]:
@@ -334,7 +375,8 @@ class SpacecraftMappingProvider(BaseMappingProvider):
     def _mapping(self, frame):
         identifier, image, solution = frame
         return getMapping(image, solution, self.timeshift, self.noradId, self.tleFolder, self.spacetrack, altitude=self.altitude,
-                          fastCenterCalculation=self.fastCenterCalculation, metadata=_metadata_of(self.metadata, identifier))
+                          fastCenterCalculation=self.fastCenterCalculation, metadata=_metadata_of(self.metadata, identifier),
+                          lens=self.lens, lensRoute=self.lensRoute, cropDivisibleBy=self.cropDivisibleBy)
 
     def get(self, date):
         if not len(self._frames):
@@ -353,9 +395,9 @@ class SpacecraftMappingProvider(BaseMappingProvider):
             raise NotImplementedError('sequences of a date range (the reference does not support them either, spacecraft.py:226-228)')
         frames = self._frames.payloads
         metadatas = [_metadata_of(self.metadata, f[0]) for f in frames] if self.metadata else None
-        return getMappingSequence([f[1] for f in frames], [f[2] for f in frames], metadatas, self.timeshift, self.noradId,
-                                  self.tleFolder, self.spacetrack, altitude=self.altitude, parallel=self._sequenceInParallel,
-                                  fastCenterCalculation=self.fastCenterCalculation)
+        return getLensMappingSequence([f[1] for f in frames], [f[2] for f in frames], self.lens, self.lensRoute, self.cropDivisibleBy,
+                                      metadatas, self.timeshift, self.noradId, self.tleFolder, self.spacetrack, altitude=self.altitude,
+                                      parallel=self._sequenceInParallel, fastCenterCalculation=self.fastCenterCalculation)
 
 
 class SpacecraftMappingPathProvider(BaseMappingProvider):
@@ -363,8 +405,10 @@ class SpacecraftMappingPathProvider(BaseMappingProvider):
     only; look-up by date or identifier is not offered (reference spacecraft.py:250-300)."""
 
     def __init__(self, imagePaths, wcsPaths, metadataPath=None, timeshift=None, noradId=None, tleFolder=None,
-                 spacetrack=None, altitude=110, maxTimeOffset=3, sequenceInParallel=False, fastCenterCalculation=False):
+                 spacetrack=None, altitude=110, maxTimeOffset=3, sequenceInParallel=False, fastCenterCalculation=False, lens=None,
+                 lensRoute='resample', cropDivisibleBy=None):
         BaseMappingProvider.__init__(self, maxTimeOffset=maxTimeOffset)
+        self.lens, self.lensRoute, self.cropDivisibleBy = lens, lensRoute, cropDivisibleBy
         if len(imagePaths) != len(wcsPaths):
             raise ValueError('%d images for %d solutions' % (len(imagePaths), len(wcsPaths)))
         from ..fits import readHeader
@@ -404,6 +448,6 @@ class SpacecraftMappingPathProvider(BaseMappingProvider):
         if dateBegin is not None or dateEnd is not None:
             raise NotImplementedError('sequences of a date range')
         metadatas = [_metadata_of(self.metadata, _stem(p)) for p in self.imagePaths] if self.metadata else None
-        return getMappingSequence(self.imagePaths, self.wcsPaths, metadatas, self.timeshift, self.noradId, self.tleFolder,
-                                  self.spacetrack, altitude=self.altitude, parallel=self.sequenceInParallel,
-                                  fastCenterCalculation=self.fastCenterCalculation)
+        return getLensMappingSequence(self.imagePaths, self.wcsPaths, self.lens, self.lensRoute, self.cropDivisibleBy, metadatas,
+                                      self.timeshift, self.noradId, self.tleFolder, self.spacetrack, altitude=self.altitude,
+                                      parallel=self.sequenceInParallel, fastCenterCalculation=self.fastCenterCalculation)

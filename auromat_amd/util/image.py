@@ -30,4 +30,23 @@ def loadImage(imagePath):
     return rgb
 
 
-__all__ = ['loadImage']
+def cropWindow(height, width, divisible_by=16):
+    """(top, left, cropped height, cropped width) of :func:`croppedImage` for an image of the given size."""
+    keep_h, keep_w = (height // divisible_by) * divisible_by, (width // divisible_by) * divisible_by
+    assert (height - keep_h) % 2 == 0, 'rows to crop cannot be shared between top and bottom'
+    assert (width - keep_w) % 2 == 0, 'columns to crop cannot be shared between left and right'
+    return (height - keep_h) // 2, (width - keep_w) // 2, keep_h, keep_w
+
+
+def croppedImage(im, divisible_by=16):
+    """
+    The image cropped to the next smaller width and height divisible by `divisible_by`, the same amount taken from
+    opposite sides (reference util/image.py:59-72; ``AssertionError`` when an amount to crop is odd, as there).  A view
+    of `im`.  The distortion-corrected image of an ISS frame matches its ``.wcs`` only after this crop
+    (reference mapping/iss.py:242).
+    """
+    top, left, h, w = cropWindow(im.shape[0], im.shape[1], divisible_by)
+    return im[top:top + h, left:left + w]
+
+
+__all__ = ['loadImage', 'croppedImage', 'cropWindow']

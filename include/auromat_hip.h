@@ -272,6 +272,66 @@ int amt_directions_zenithal(amt_ctx* ctx, const amt_zenithal_wcs* w, double* out
 int amt_directions_tan_points(amt_ctx* ctx, const amt_frame_params* p, const double* px, const double* py,
                               int64_t n, int origin, double* out_dirs);
 
+/* ---- lens distortion (auromat.util.lensdistortion, auromat/mapping/iss.py:232-243) ------------------------------------
+ * The step the reference takes through lensfunpy (Modifier.apply_geometry_distortion) and cv2 (lensfunpy.util.remap) before an
+ * image matches its .wcs.  Radial models with the radius in units of half the frame's smaller side (reference draw.py:1104-1148):
+ * with cx = (width-1)/2, cy = (height-1)/2, norm = 2/(min(width,height)-1), u = (x-cx) norm, v = (y-cy) norm, r^2 = u^2+v^2,
+ *   poly3 (k[0]):            g = 1 - k0 + k0 r^2
+ *   poly5 (k[0], k[1]):      g = 1 + k0 r^2 + k1 r^4
+ *   ptlens (k[0],k[1],k[2]): g = a r^3 + b r^2 + c r + 1 - a - b - c
+ * FORWARD: pixel (x, y) of the corrected image is sampled at (cx + u g / norm, cy + v g / norm) of the raw one (a factor of exactly
+ * 1 gives (x, y) itself).  INVERSE: the ru with ru g(ru) = rd, by Newton's method from ru = rd with a fixed cap of steps; NaN where
+ * it does not converge or the slope d(ru g)/dru is not positive on the way (the model folds over); rd = 0 is the centre exactly.
+ * lensfun's rescaling by aspect ratio and crop factor is not part of this (crop factor 1, focal length 1: the reference's
+ * getLensfunModifierFromParams), and agreement with lensfun's own output is not pinned: tests/_lens_oracle.py is the statement.
+ * crop_*: the corrected image is the window [crop_x, crop_x + crop_width) x [crop_y, crop_y + crop_height) of the full corrected
+ * frame (the reference crops to a multiple of 16, util/image.py:59-72) and its pixel coordinates count from the window's corner;
+ * crop_width = crop_height = 0: no crop.  The raw frame is always width x height.  Additions to ABI 10. */
+#define AMT_LENS_NONE 0
+#define AMT_LENS_POLY3 1
+#define AMT_LENS_POLY5 2
+#define AMT_LENS_PTLENS 3
+typedef struct amt_lens_model {
+    int32_t kind, width, height;
+    int32_t crop_x, crop_y, crop_width, crop_height, reserved;
+    double k[3];
+} amt_lens_model;
+/* Forward coordinates of the pixels [x0, x0 + cols) x [y0, y0 + rows) of the (cropped) corrected image: out_xy (rows, cols, 2)
+ * float64 in [x, y] order; corner = 1: the (rows + 1, cols + 1) lattice of pixel corners at x - 0.5, y - 0.5.  out_xy32 (optional):
+ * the same rounded to float32, the array lensfunpy hands out. */
+int amt_lens_coords(amt_ctx* ctx, const amt_lens_model* model, int32_t x0, int32_t y0, int32_t cols, int32_t rows, int corner,
+                    double* out_xy, float* out_xy32);
+/* Inverse: where the pixels (or corners) of that rectangle of the RAW frame lie in the (cropped) corrected frame. */
+int amt_lens_undistort(amt_ctx* ctx, const amt_lens_model* model, int32_t x0, int32_t y0, int32_t cols, int32_t rows, int corner,
+                       double* out_xy);
+/* Sampling (both remap calls): interpolation 0 = linear, taps floor(xs), floor(xs) + 1; 1 = Lanczos-4, taps floor(xs) - 3 ...
+ * floor(xs) + 4 weighted L(i - fx), L(t) = sinc(t) sinc(t/4), exactly 1 at 0 and 0 at other integers, each axis' eight weights
+ * normalised to sum 1 (the role of cv2.INTER_LANCZOS4).  Taps outside the image count 0 (cv2.remap's constant border) without
+ * renormalising; float64 accumulation; uint8 / uint16 results are clip(rint(v)) (half to even), float32 unrounded; a non-finite
+ * source coordinate gives 0.  support (optional, one byte per output pixel): 1 where the source point lies in
+ * [0, width-1] x [0, height-1].  Images are interleaved (height, width, channels), channels 1, 3 or 4, sample_bytes 1 (uint8),
+ * 2 (uint16) or 4 (float32); dst has the type of src.
+ * debug (optional): force_path AMT_LENS_PATH_GATHER makes every tile take its taps from global memory instead of the window staged
+ * in LDS (a tile whose taps do not fit the window always does; both give the same bits); tile_path (optional, one byte per 32 x 32
+ * output tile, row-major) reports what each tile did: 0 no tap inside the image, else AMT_LENS_PATH_STAGED / _GATHER. */
+#define AMT_INTERP_LINEAR 0
+#define AMT_INTERP_LANCZOS4 1
+#define AMT_LENS_PATH_AUTO 0
+#define AMT_LENS_PATH_STAGED 1     /* as AUTO: staged wherever the window holds the tile's taps */
+#define AMT_LENS_PATH_GATHER 2
+#define AMT_LENS_TILE 32
+typedef struct amt_lens_debug {
+    int32_t force_path, reserved;
+    uint8_t* tile_path;
+} amt_lens_debug;
+/* The corrected (and cropped) image of a raw frame in one kernel: coordinates in float64 in registers, never stored. */
+int amt_lens_remap(amt_ctx* ctx, const amt_lens_model* model, const void* src, int32_t sample_bytes, int32_t channels,
+                   int32_t interpolation, void* dst, uint8_t* support, const amt_lens_debug* debug);
+/* lensfunpy.util.remap(im, coords) for a coordinate array made elsewhere: coords (dst_height, dst_width, 2) float32, [x, y]. */
+int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t src_height, int32_t sample_bytes, int32_t channels,
+                     const float* coords, int32_t dst_width, int32_t dst_height, int32_t interpolation, void* dst, uint8_t* support,
+                     const amt_lens_debug* debug);
+
 /* auromat/coordinates/intersection.py:144-163 ellipsoidLineIntersection (and
  * auromat/mapping/mapping.py:1474-1510 inflatedEarthIntersection with a=wgs84A+h, b=wgs84B+h).
  * origin: host double[3]; dirs/out: (n,3) AoS.  Misses / points behind a directed ray are NaN. */
