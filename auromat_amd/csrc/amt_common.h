@@ -81,9 +81,6 @@ struct amt_georef_tail {
 };
 constexpr int kNoBand = 0x7fffffff;
 size_t amt_georef_partials_bytes(const amt_frame_params* p);
-int amt_georef_launch(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, const amt_georef_out* out,
-                      const amt_georef_tail* tail);
-// n <= AMT_MAX_BATCH equally sized frames in ONE launch of the big kernel (falls back to n launches otherwise)
 #define AMT_MAX_BATCH 3
 // sky (optional, n entries): the sky rows of each frame that its arrays already hold as NaN and need not be written again
 // (amt_prm::sky_fill, amt_params.h).  In: rows [0, known_top_end) and [known_bottom_begin, number of rows) of work items hold
@@ -94,15 +91,15 @@ struct amt_sky_state {
     int known_top_end, known_bottom_begin;
     int bands_filled, bands_skipped;
 };
-int amt_georef_launch_many(amt_ctx* ctx, int n, const amt_frame_params* const* p, const amt_georef_out* const* out,
-                           const amt_georef_tail* const* tail, amt_sky_state* sky = nullptr);
+// THE launcher of the big kernel (every georeferencing entry point ends here): n <= AMT_MAX_BATCH frames, equally sized and of
+// one kernel variant in ONE launch (n launches otherwise).  dirs: NULL, or n caller-supplied corner direction arrays (all frames
+// or none, none of them NULL).  tail: NULL (folds on the context's stream, partials from its workspace) or n entries.
+int amt_georef_launch_many(amt_ctx* ctx, int n, const amt_frame_params* const* p, const double* const* dirs,
+                           const amt_georef_out* const* out, const amt_georef_tail* const* tail, amt_sky_state* sky);
 // amt_pipe_launch_many_res (amt_pipe.hip) with the sky state of each frame's arrays, as above; the sequence runner's launch
 int amt_pipe_launch_many_sky(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, const amt_georef_out* const* out,
                              const void* const* img, int32_t img_dtype, double min_elevation, const double* lat_px_per_deg,
                              const double* lon_px_per_deg, int pole_in_view, int magnetic, amt_sky_state* sky);
-// the same with caller-supplied corner directions, one array per frame (all frames or none)
-int amt_georef_launch_many_dirs(amt_ctx* ctx, int n, const amt_frame_params* const* p, const double* const* dirs,
-                                const amt_georef_out* const* out, const amt_georef_tail* const* tail);
 // k_apply_bin_events on `stream` (before the finalise kernel): see bin_event
 // xmask / ymask: the flag bit of a record that says "on the lower edge" under the FINAL grid's rounding (bin_event)
 int amt_bin_apply_events_on(amt_ctx* ctx, hipStream_t stream, const void* events, uint32_t* count, uint64_t* acc,

@@ -1425,6 +1425,20 @@ void elevation_bands(const georef_args& A, const launch_shape& sh, double min_el
     if (t == n) *top_end = n, *bottom_begin = n;          // nothing above the threshold in the frame
 }
 
+// The camera-model constants of a frame: the TAN WCS, the GEO-frame affine camera and shell ray (camera model and shell composed
+// with M = J2000 -> GEO, what k_georef_rows and the band rules work with) and the frame's size
+void camera_model(const amt_frame_params* p, georef_args* A) {
+    double rot_geo[9];
+    A->wcs = make_tan_wcs(p);
+    mat_mul3(p->m_geo, p->rot, rot_geo);
+    tan_wcs wcs_geo = A->wcs;
+    wcs_geo.rot = make_mat3(rot_geo);
+    A->cam = make_affine_cam(wcs_geo);
+    A->sray = make_shell_ray(p->a, p->b, p->cam, p->m_geo);
+    A->width = p->width;
+    A->height = p->height;
+}
+
 // One frame of a launch, validated and with its kernel arguments assembled
 struct prepared_frame {
     georef_args A;
@@ -1449,26 +1463,19 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
     AMT_REQUIRE(ctx, (out->mlat_c == nullptr) == (out->mlt_c == nullptr), "mlat_c and mlt_c must be given together");
     AMT_REQUIRE(ctx, dirs == nullptr || p->fast_center, "caller-supplied directions need fast_center");
     georef_args& A = F->A;
-    A.wcs = make_tan_wcs(p);
+    camera_model(p, &A);
     A.ray = make_ray(p->a, p->b, p->cam, 1);
     A.m_geo = make_mat3(p->m_geo);
     A.m_sm = make_mat3(p->m_sm);
     {
-        // GEO-frame constants of k_georef_rows: camera model and SM rotation composed with M = J2000 -> GEO
-        double rot_geo[9], mt[9], geo_sm[9];
-        mat_mul3(p->m_geo, p->rot, rot_geo);
-        tan_wcs wcs_geo = A.wcs;
-        wcs_geo.rot = make_mat3(rot_geo);
-        A.cam = make_affine_cam(wcs_geo);
-        A.sray = make_shell_ray(p->a, p->b, p->cam, p->m_geo);
+        // the SM rotation composed with M = J2000 -> GEO, like the camera model
+        double mt[9], geo_sm[9];
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) mt[3 * i + j] = p->m_geo[3 * j + i];
         mat_mul3(p->m_sm, mt, geo_sm);               // M_sm M^T: GEO -> SM
         A.m_geo_sm = make_mat3(geo_sm);
     }
     A.bw = make_bowring_fast(p->a0, p->b0);
-    A.width = p->width;
-    A.height = p->height;
     A.dirs_in = dirs;
     A.lat = out->lat;
     A.lon = out->lon;
@@ -1655,44 +1662,21 @@ int launch_prepared(amt_ctx* ctx, int n, prepared_frame* F) {
     return AMT_OK;
 }
 
-int launch_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, const amt_georef_out* out,
-                  const amt_georef_tail* tail = nullptr) {
-    prepared_frame F;
-    if (int rc = prepare_georef(ctx, p, dirs, out, tail, &F)) return rc;
-    return launch_prepared(ctx, 1, &F);
-}
-
-
 }  // namespace
 
 size_t amt_georef_partials_bytes(const amt_frame_params* p) {
     return (size_t)(shape_of(p).n_items + kFoldBlocks) * 8 * sizeof(double);
 }
 
-int amt_georef_launch(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, const amt_georef_out* out,
-                      const amt_georef_tail* tail) {
+int amt_georef_launch_many(amt_ctx* ctx, int n, const amt_frame_params* const* p, const double* const* dirs,
+                           const amt_georef_out* const* out, const amt_georef_tail* const* tail, amt_sky_state* sky) {
     AMT_CHECK_CTX(ctx);
-    return launch_georef(ctx, p, dirs, out, tail);
-}
-
-int amt_georef_launch_many(amt_ctx* ctx, int n, const amt_frame_params* const* p, const amt_georef_out* const* out,
-                           const amt_georef_tail* const* tail, amt_sky_state* sky) {
-    AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, n >= 1 && n <= kMaxBatch && p && out && tail, "bad batch");
-    prepared_frame F[kMaxBatch];
-    for (int i = 0; i < n; ++i)
-        if (int rc = prepare_georef(ctx, p[i], nullptr, out[i], tail[i], &F[i], sky ? sky + i : nullptr)) return rc;
-    return launch_prepared(ctx, n, F);
-}
-
-int amt_georef_launch_many_dirs(amt_ctx* ctx, int n, const amt_frame_params* const* p, const double* const* dirs,
-                                const amt_georef_out* const* out, const amt_georef_tail* const* tail) {
-    AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, n >= 1 && n <= kMaxBatch && p && dirs && out && tail, "bad batch");
+    AMT_REQUIRE(ctx, n >= 1 && n <= kMaxBatch && p && out, "bad batch");
     prepared_frame F[kMaxBatch];
     for (int i = 0; i < n; ++i) {
-        AMT_REQUIRE(ctx, dirs[i] != nullptr, "corner_dirs is NULL");
-        if (int rc = prepare_georef(ctx, p[i], dirs[i], out[i], tail[i], &F[i])) return rc;
+        AMT_REQUIRE(ctx, dirs == nullptr || dirs[i] != nullptr, "corner_dirs is NULL");
+        if (int rc = prepare_georef(ctx, p[i], dirs ? dirs[i] : nullptr, out[i], tail ? tail[i] : nullptr, &F[i], sky ? sky + i : nullptr))
+            return rc;
     }
     return launch_prepared(ctx, n, F);
 }
@@ -1700,8 +1684,7 @@ int amt_georef_launch_many_dirs(amt_ctx* ctx, int n, const amt_frame_params* con
 extern "C" {
 
 int amt_georef_frame(amt_ctx* ctx, const amt_frame_params* p, const amt_georef_out* out) {
-    AMT_CHECK_CTX(ctx);
-    return launch_georef(ctx, p, nullptr, out);
+    return amt_georef_launch_many(ctx, 1, &p, nullptr, &out, nullptr, nullptr);
 }
 
 namespace {
@@ -1770,15 +1753,7 @@ int amt_georef_sky_rows(const amt_frame_params* p, int32_t* rows_per_item, int32
     if (p->width <= 0 || p->height <= 0) return AMT_EINVAL;
     georef_args A;
     std::memset(&A, 0, sizeof(A));
-    A.wcs = make_tan_wcs(p);
-    double rot_geo[9];
-    mat_mul3(p->m_geo, p->rot, rot_geo);
-    tan_wcs wcs_geo = A.wcs;
-    wcs_geo.rot = make_mat3(rot_geo);
-    A.cam = make_affine_cam(wcs_geo);
-    A.sray = make_shell_ray(p->a, p->b, p->cam, p->m_geo);
-    A.width = p->width;
-    A.height = p->height;
+    camera_model(p, &A);
     const launch_shape sh = shape_of(p);
     int t = 0, b = sh.chunks_y;
     sky_bands(A, sh, &t, &b);
@@ -1802,15 +1777,7 @@ int amt_georef_image_rows(const amt_frame_params* p, double min_elevation, int32
     if (p->width <= 0 || p->height <= 0) return AMT_EINVAL;
     georef_args A;
     std::memset(&A, 0, sizeof(A));
-    A.wcs = make_tan_wcs(p);
-    double rot_geo[9];
-    mat_mul3(p->m_geo, p->rot, rot_geo);
-    tan_wcs wcs_geo = A.wcs;
-    wcs_geo.rot = make_mat3(rot_geo);
-    A.cam = make_affine_cam(wcs_geo);
-    A.sray = make_shell_ray(p->a, p->b, p->cam, p->m_geo);
-    A.width = p->width;
-    A.height = p->height;
+    camera_model(p, &A);
     const launch_shape sh = shape_of(p);
     int t = 0, b = sh.chunks_y, te = 0, be = sh.chunks_y;
     sky_bands(A, sh, &t, &b);
@@ -1827,9 +1794,7 @@ int amt_georef_image_rows(const amt_frame_params* p, double min_elevation, int32
 
 int amt_georef_frame_dirs(amt_ctx* ctx, const amt_frame_params* p, const double* corner_dirs,
                           const amt_georef_out* out) {
-    AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, corner_dirs != nullptr, "corner_dirs is NULL");
-    return launch_georef(ctx, p, corner_dirs, out);
+    return amt_georef_launch_many(ctx, 1, &p, &corner_dirs, &out, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -224,47 +224,26 @@ int amt_pipe_coarse(amt_pipe* pipe, const amt_frame_params* p, double min_elevat
 
 namespace {
 
-int pipe_wait_tail(amt_pipe* pipe);
-int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_georef_out* out, const void* img,
-                      int32_t img_dtype, double min_elevation, double lat_px_per_deg, double lon_px_per_deg,
-                      int magnetic, int mode, amt_georef_out* o_out, amt_georef_tail* tail_out);
+// One frame of a launch: camera model, the caller's corner directions in its place (direction launches), where the kernel
+// writes and what it bins (not in a box pass), and the resolution of the frame's grid
+struct launch_frame {
+    const amt_frame_params* p;
+    const double* dirs;
+    const amt_georef_out* out;
+    const void* img;
+    double lat_ppd, lon_ppd;
+};
 
-// Everything amt_pipe_launch does before the big kernel: wait for the coarse box, superset grid, accumulators,
-// kernel outputs (`o`) and the tail description for this frame.
-int pipe_prepare(amt_pipe* pipe, const amt_frame_params* p, const amt_georef_out* out, const void* img,
-                 int32_t img_dtype, double min_elevation, double lat_px_per_deg, double lon_px_per_deg,
-                 int pole_in_view, int magnetic, amt_georef_out* o_out, amt_georef_tail* tail_out,
-                 const double* dirs = nullptr) {
-    amt_ctx* ctx = pipe->ctx;
-    AMT_REQUIRE(ctx, p && out && img, "NULL argument");
-    AMT_REQUIRE(ctx, img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
-    magnetic = magnetic ? 1 : 0;
-    // (direction arrays: there is no camera model to project the pole through — the caller decides, or nobody does)
-    pipe->pole_unknown = dirs != nullptr && pole_in_view < 0;
-    pipe->pole = pole_in_view < 0 ? (dirs == nullptr && amt_prm::pole_in_view(p, min_elevation, magnetic) != 0 ? 1 : 0) : (pole_in_view ? 1 : 0);
-    // frames with a pole of their grid in view take a pole plan (binned in rotated coordinates; a geodetic pole frame of
-    // a caller that wants the MLat / MLT arrays as well runs the kernel variant of the magnetic pole plan with the
-    // rotated pair taken from (lat, lon), see prepare_georef); direction arrays have none: their pole frames are not fused
-    const int mode = dirs ? magnetic : (magnetic ? (pipe->pole ? 3 : 1) : (pipe->pole ? 2 : 0));
-    pipe->pole_plan = mode >= 2;
-    if (!pipe->coarse_pending || pipe->coarse_magnetic != mode) {
-        if (pipe->coarse_pending && !pipe->coarse_hinted) AMT_HIP(ctx, hipEventSynchronize(pipe->coarse_done));
-        if (int rc = pipe_coarse(pipe, p, min_elevation, mode, dirs)) return rc;
-    }
-    if (!pipe->coarse_hinted) AMT_HIP(ctx, hipEventSynchronize(pipe->coarse_done));
-    pipe->coarse_pending = false;
-    pipe->coarse_hinted = false;
-    pipe->lat_ppd = lat_px_per_deg;
-    pipe->lon_ppd = lon_px_per_deg;
-    pipe->min_elev = min_elevation;
-    pipe->img_dtype = img_dtype;
-    pipe->fused = false;
-
-    if (int rc = pipe_wait_tail(pipe)) return rc;
-    if (int rc = ensure_partials(pipe, amt_georef_partials_bytes(p))) return rc;
-    return pipe_prepare_rest(pipe, p, out, img, img_dtype, min_elevation, lat_px_per_deg, lon_px_per_deg, magnetic, mode, o_out,
-                             tail_out);
-}
+// What the frames of a launch share.  A box pass (amt_pipe_launch_box) is a camera launch whose frames have neither outputs nor
+// image nor resolution: the kernel writes nothing but each frame's bounding box.
+enum class launch_kind { camera, directions, box };
+struct launch_common {
+    launch_kind kind;
+    int32_t img_dtype;
+    double min_elevation;
+    int pole_in_view, magnetic;
+    amt_sky_state* sky;             // optional, one per frame (amt_common.h)
+};
 
 // the folds / finalise of the previous frame on this driver still use the partials and the accumulators
 int pipe_wait_tail(amt_pipe* pipe) {
@@ -289,23 +268,57 @@ int pipe_wait_tail(amt_pipe* pipe) {
     return AMT_OK;
 }
 
-int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_georef_out* out, const void* img,
-                      int32_t img_dtype, double min_elevation, double lat_px_per_deg, double lon_px_per_deg,
-                      int magnetic, int mode, amt_georef_out* o_out, amt_georef_tail* tail_out) {
+// Everything a launch does for one frame before the big kernel: wait for the coarse box, superset grid, accumulators,
+// kernel outputs (`o`) and the tail description for this frame.  Box pass: no estimate, no grid — the driver keeps nothing
+// of an earlier frame's plan, the kernel gets no output but the box.
+int pipe_prepare(amt_pipe* pipe, const launch_frame& f, const launch_common& L, amt_georef_out* o_out, amt_georef_tail* tail_out) {
     amt_ctx* ctx = pipe->ctx;
+    const amt_frame_params* p = f.p;
+    const bool box_only = L.kind == launch_kind::box;
+    const double* dirs = f.dirs;
+    const void* img = f.img;
+    const double min_elevation = L.min_elevation, lat_px_per_deg = f.lat_ppd, lon_px_per_deg = f.lon_ppd;
+    const int magnetic = L.magnetic ? 1 : 0, pole_in_view = L.pole_in_view;
+    // (direction arrays: there is no camera model to project the pole through — the caller decides, or nobody does)
+    pipe->pole_unknown = dirs != nullptr && pole_in_view < 0;
+    pipe->pole = pole_in_view < 0 ? (dirs == nullptr && amt_prm::pole_in_view(p, min_elevation, magnetic) != 0 ? 1 : 0) : (pole_in_view ? 1 : 0);
+    // frames with a pole of their grid in view take a pole plan (binned in rotated coordinates; a geodetic pole frame of
+    // a caller that wants the MLat / MLT arrays as well runs the kernel variant of the magnetic pole plan with the
+    // rotated pair taken from (lat, lon), see prepare_georef); direction arrays have none: their pole frames are not fused
+    const int mode = dirs ? magnetic : (magnetic ? (pipe->pole ? 3 : 1) : (pipe->pole ? 2 : 0));
+    pipe->pole_plan = !box_only && mode >= 2;
+    // (box pass: an estimate that is still pending belongs to another plan of this frame: dropped)
+    if (box_only || !pipe->coarse_pending || pipe->coarse_magnetic != mode) {
+        if (pipe->coarse_pending && !pipe->coarse_hinted) AMT_HIP(ctx, hipEventSynchronize(pipe->coarse_done));
+        if (!box_only)
+            if (int rc = pipe_coarse(pipe, p, min_elevation, mode, dirs)) return rc;
+    }
+    if (!box_only && !pipe->coarse_hinted) AMT_HIP(ctx, hipEventSynchronize(pipe->coarse_done));
+    pipe->coarse_pending = false;
+    pipe->coarse_hinted = false;
+    pipe->lat_ppd = lat_px_per_deg;
+    pipe->lon_ppd = lon_px_per_deg;
+    pipe->min_elev = min_elevation;
+    if (!box_only) pipe->img_dtype = L.img_dtype;
+    pipe->fused = false;
+
+    if (int rc = pipe_wait_tail(pipe)) return rc;
+    if (int rc = ensure_partials(pipe, amt_georef_partials_bytes(p))) return rc;
+
     amt_georef_out& o = *o_out;
-    o = *out;
+    if (box_only) std::memset(&o, 0, sizeof(o));
+    else o = *f.out;
     o.bbox = pipe->host_small_dev + 8;          // the last fold writes straight into pinned host memory
     o.bbox_min_elevation = min_elevation;
     o.bin_acc = nullptr;
     o.bin_xaxis = o.bin_yaxis = nullptr;
     o.bin_img = nullptr;
     o.bin_img_dtype = o.bin_lon_wrap = o.bin_magnetic = o.bin_pole = 0;
-    if (pipe->box_in_grid) o.bin_magnetic = magnetic;       // (without bin_acc: the box in the grid's coordinates)
+    if (pipe->box_in_grid || box_only) o.bin_magnetic = magnetic;       // (without bin_acc: the box in the grid's coordinates)
     o.bin_events = nullptr;
     o.bin_event_count = nullptr;
     o.bin_event_capacity = 0;
-    {
+    if (!box_only) {
         // start with the side of the frame where the coarse pass found the hits (see amt_georef_out.item_order)
         const long long packed = (long long)pipe->host_small[7];
         long long sy = ((packed % (1 << 20)) + (1 << 20)) % (1 << 20);
@@ -315,13 +328,15 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
         o.item_order = (ax | ay) == 0 ? 0 : ((ay >= ax && sy > 0) ? 2 : 1);
     }
 
-    pipe->g_lat_c = out->lat_c, pipe->g_lon_c = out->lon_c, pipe->g_elev = out->elev, pipe->g_img = img;
-    pipe->g_row_layout = out->row_layout;
-    pipe->g_width = p->width, pipe->g_height = p->height, pipe->g_fast = p->fast_center, pipe->g_mode = mode;
+    // (a box pass: no arrays, so no general path either)
+    pipe->g_lat_c = o.lat_c, pipe->g_lon_c = o.lon_c, pipe->g_elev = o.elev, pipe->g_img = img;
+    pipe->g_row_layout = o.row_layout;
+    pipe->g_width = p->width, pipe->g_height = p->height, pipe->g_fast = p->fast_center;
+    pipe->g_mode = dirs ? -1 : mode;      // (amt_pipe_general_layout: the pole of a direction-array frame is the caller's business)
     pipe->general_ready = false;
     // coarse [lat_min, lat_max, lon_min, lon_max, lon_min_positive, lon_max_nonpositive, n, hint]
     const double* c = pipe->host_small;
-    bool fuse = !pipe->two_pass && c[6] > 0 && (!pipe->pole || pipe->pole_plan);
+    bool fuse = !box_only && !pipe->two_pass && c[6] > 0 && (!pipe->pole || pipe->pole_plan);
     if (pipe->pole_unknown && !(c[0] > -kPoleGuardDeg && c[1] < kPoleGuardDeg)) fuse = false;
     pipe->lon_wrap = 0;
     amt_gl::box_range r;
@@ -356,7 +371,7 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
         o.bin_xaxis = &pipe->super.xaxis;
         o.bin_yaxis = &pipe->super.yaxis;
         o.bin_img = img;
-        o.bin_img_dtype = img_dtype;
+        o.bin_img_dtype = L.img_dtype;
         o.bin_acc = pipe->acc;
         o.bin_magnetic = magnetic;
         o.bin_pole = pipe->pole_plan ? 1 : 0;
@@ -380,13 +395,55 @@ int pipe_prepare_rest(amt_pipe* pipe, const amt_frame_params* p, const amt_geore
     return AMT_OK;
 }
 
-int pipe_after_launch(amt_pipe* pipe) {
-    amt_ctx* ctx = pipe->ctx;
-    AMT_HIP(ctx, hipEventRecord(pipe->bbox_done, pipe->tail_stream));
-    AMT_HIP(ctx, hipEventRecord(pipe->tail_done, pipe->tail_stream));
-    pipe->tail_pending = true;
-    pipe->launched = true;
+// THE launch: frame i of `f` on driver i of `pipes`, all of them in one launch of the big kernel (amt_georef_launch_many).
+// f == NULL: the caller's arrays were not all there.  The whole batch is checked before any driver's state changes.
+int launch_frames(amt_pipe* const* pipes, int32_t n, const launch_frame* f, const launch_common& L) {
+    if (pipes == nullptr || n < 1 || pipes[0] == nullptr) return AMT_EINVAL;
+    amt_ctx* ctx = pipes[0]->ctx;
+    AMT_REQUIRE(ctx, n <= AMT_MAX_BATCH, "at most AMT_PIPE_MAX_BATCH frames per launch");
+    AMT_REQUIRE(ctx, f != nullptr, "NULL argument");
+    const bool box_only = L.kind == launch_kind::box, with_dirs = L.kind == launch_kind::directions;
+    for (int i = 0; i < n; ++i) {
+        AMT_REQUIRE(ctx, pipes[i] != nullptr && pipes[i]->ctx == ctx, "drivers of one launch must share the context");
+        for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipes[i], "a driver can hold one frame of a launch");
+        AMT_REQUIRE(ctx, f[i].p && (box_only || (f[i].out && f[i].img)) && (!with_dirs || f[i].dirs), "NULL argument");
+        AMT_REQUIRE(ctx, !with_dirs || f[i].p->fast_center, "caller-supplied directions need fast_center");
+    }
+    AMT_REQUIRE(ctx, box_only || L.img_dtype == 1 || L.img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
+    amt_georef_out o[AMT_MAX_BATCH];
+    amt_georef_tail tails[AMT_MAX_BATCH];
+    const amt_frame_params* pp[AMT_MAX_BATCH];
+    const double* dp[AMT_MAX_BATCH];
+    const amt_georef_out* op[AMT_MAX_BATCH];
+    const amt_georef_tail* tp[AMT_MAX_BATCH];
+    for (int i = 0; i < n; ++i) {
+        if (int rc = pipe_prepare(pipes[i], f[i], L, &o[i], &tails[i])) return rc;
+        pp[i] = f[i].p, dp[i] = f[i].dirs, op[i] = &o[i], tp[i] = &tails[i];
+    }
+    if (int rc = amt_georef_launch_many(ctx, n, pp, with_dirs ? dp : nullptr, op, tp, L.sky)) return rc;
+    for (int i = 0; i < n; ++i) {
+        amt_pipe* pipe = pipes[i];
+        AMT_HIP(ctx, hipEventRecord(pipe->bbox_done, pipe->tail_stream));
+        AMT_HIP(ctx, hipEventRecord(pipe->tail_done, pipe->tail_stream));
+        pipe->tail_pending = true;
+        pipe->launched = true;
+    }
     return AMT_OK;
+}
+
+// The arrays of an exported launch function as frames: dirs for direction launches, out / img / lat / lon for all but box passes;
+// res_stride 1: a resolution per frame, 0: one for all
+int launch_arrays(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, const double* const* dirs,
+                  const amt_georef_out* const* out, const void* const* img, const double* lat, const double* lon, int res_stride,
+                  const launch_common& L) {
+    launch_frame f[AMT_MAX_BATCH];
+    const bool box_only = L.kind == launch_kind::box, with_dirs = L.kind == launch_kind::directions;
+    const bool all = p && (box_only || (out && img && lat && lon)) && (!with_dirs || dirs);
+    for (int i = 0; all && n <= AMT_MAX_BATCH && i < n; ++i) {      // (n out of range: launch_frames says so, nothing is read)
+        if (box_only) f[i] = {p[i], nullptr, nullptr, nullptr, 0.0, 0.0};
+        else f[i] = {p[i], with_dirs ? dirs[i] : nullptr, out[i], img[i], lat[i * res_stride], lon[i * res_stride]};
+    }
+    return launch_frames(pipes, n, all ? f : nullptr, L);
 }
 
 }  // namespace
@@ -395,27 +452,8 @@ int pipe_after_launch(amt_pipe* pipe) {
 int amt_pipe_launch_many_sky(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, const amt_georef_out* const* out,
                              const void* const* img, int32_t img_dtype, double min_elevation, const double* lat_px_per_deg,
                              const double* lon_px_per_deg, int pole_in_view, int magnetic, amt_sky_state* sky) {
-    if (pipes == nullptr || n < 1 || pipes[0] == nullptr) return AMT_EINVAL;
-    amt_ctx* ctx = pipes[0]->ctx;
-    AMT_REQUIRE(ctx, n <= AMT_MAX_BATCH, "at most AMT_PIPE_MAX_BATCH frames per launch");
-    AMT_REQUIRE(ctx, p && out && img && lat_px_per_deg && lon_px_per_deg, "NULL argument");
-    amt_georef_out o[AMT_MAX_BATCH];
-    amt_georef_tail tails[AMT_MAX_BATCH];
-    const amt_georef_out* op[AMT_MAX_BATCH];
-    const amt_georef_tail* tp[AMT_MAX_BATCH];
-    for (int i = 0; i < n; ++i) {
-        AMT_REQUIRE(ctx, pipes[i] != nullptr && pipes[i]->ctx == ctx, "drivers of one launch must share the context");
-        for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipes[i], "a driver can hold one frame of a launch");
-        if (int rc = pipe_prepare(pipes[i], p[i], out[i], img[i], img_dtype, min_elevation, lat_px_per_deg[i],
-                                  lon_px_per_deg[i], pole_in_view, magnetic, &o[i], &tails[i]))
-            return rc;
-        op[i] = &o[i];
-        tp[i] = &tails[i];
-    }
-    if (int rc = amt_georef_launch_many(ctx, n, p, op, tp, sky)) return rc;
-    for (int i = 0; i < n; ++i)
-        if (int rc = pipe_after_launch(pipes[i])) return rc;
-    return AMT_OK;
+    return launch_arrays(pipes, n, p, nullptr, out, img, lat_px_per_deg, lon_px_per_deg, 1,
+                         {launch_kind::camera, img_dtype, min_elevation, pole_in_view, magnetic, sky});
 }
 
 extern "C" {
@@ -441,9 +479,8 @@ int amt_pipe_launch_many(amt_pipe* const* pipes, int32_t n, const amt_frame_para
                          const amt_georef_out* const* out, const void* const* img, int32_t img_dtype,
                          double min_elevation, double lat_px_per_deg, double lon_px_per_deg, int pole_in_view,
                          int magnetic) {
-    double la[AMT_MAX_BATCH], lo[AMT_MAX_BATCH];
-    for (int i = 0; i < AMT_MAX_BATCH; ++i) la[i] = lat_px_per_deg, lo[i] = lon_px_per_deg;
-    return amt_pipe_launch_many_res(pipes, n, p, out, img, img_dtype, min_elevation, la, lo, pole_in_view, magnetic);
+    return launch_arrays(pipes, n, p, nullptr, out, img, &lat_px_per_deg, &lon_px_per_deg, 0,
+                         {launch_kind::camera, img_dtype, min_elevation, pole_in_view, magnetic, nullptr});
 }
 
 int amt_pipe_launch_many_res(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p,
@@ -455,112 +492,37 @@ int amt_pipe_launch_many_res(amt_pipe* const* pipes, int32_t n, const amt_frame_
                                     magnetic, nullptr);
 }
 
-int amt_pipe_launch_dirs(amt_pipe* pipe, const amt_frame_params* p, const double* corner_dirs, const amt_georef_out* out,
-                         const void* img, int32_t img_dtype, double min_elevation, double lat_px_per_deg,
-                         double lon_px_per_deg, int pole_in_view, int magnetic) {
-    if (pipe == nullptr) return AMT_EINVAL;
-    amt_ctx* ctx = pipe->ctx;
-    AMT_REQUIRE(ctx, p && corner_dirs && out && img, "NULL argument");
-    AMT_REQUIRE(ctx, p->fast_center, "caller-supplied directions need fast_center");
-    amt_georef_out o;
-    amt_georef_tail tail;
-    if (int rc = pipe_prepare(pipe, p, out, img, img_dtype, min_elevation, lat_px_per_deg, lon_px_per_deg, pole_in_view, magnetic,
-                              &o, &tail, corner_dirs))
-        return rc;
-    pipe->g_mode = -1;                    // (amt_pipe_general_layout: the pole of a direction-array frame is the caller's business)
-    if (int rc = amt_georef_launch(ctx, p, corner_dirs, &o, &tail)) return rc;
-    return pipe_after_launch(pipe);
-}
-
 int amt_pipe_launch_dirs_many(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, const double* const* corner_dirs,
                               const amt_georef_out* const* out, const void* const* img, int32_t img_dtype, double min_elevation,
                               double lat_px_per_deg, double lon_px_per_deg, int pole_in_view, int magnetic) {
-    if (pipes == nullptr || n < 1 || pipes[0] == nullptr) return AMT_EINVAL;
-    amt_ctx* ctx = pipes[0]->ctx;
-    AMT_REQUIRE(ctx, n <= AMT_MAX_BATCH, "at most AMT_PIPE_MAX_BATCH frames per launch");
-    AMT_REQUIRE(ctx, p && corner_dirs && out && img, "NULL argument");
-    amt_georef_out o[AMT_MAX_BATCH];
-    amt_georef_tail tails[AMT_MAX_BATCH];
-    const amt_georef_out* op[AMT_MAX_BATCH];
-    const amt_georef_tail* tp[AMT_MAX_BATCH];
-    for (int i = 0; i < n; ++i) {
-        AMT_REQUIRE(ctx, pipes[i] != nullptr && pipes[i]->ctx == ctx, "drivers of one launch must share the context");
-        for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipes[i], "a driver can hold one frame of a launch");
-        AMT_REQUIRE(ctx, p[i] && corner_dirs[i] && out[i] && img[i], "NULL argument");
-        AMT_REQUIRE(ctx, p[i]->fast_center, "caller-supplied directions need fast_center");
-        if (int rc = pipe_prepare(pipes[i], p[i], out[i], img[i], img_dtype, min_elevation, lat_px_per_deg, lon_px_per_deg,
-                                  pole_in_view, magnetic, &o[i], &tails[i], corner_dirs[i]))
-            return rc;
-        pipes[i]->g_mode = -1;
-        op[i] = &o[i];
-        tp[i] = &tails[i];
-    }
-    if (int rc = amt_georef_launch_many_dirs(ctx, n, p, corner_dirs, op, tp)) return rc;
-    for (int i = 0; i < n; ++i)
-        if (int rc = pipe_after_launch(pipes[i])) return rc;
-    return AMT_OK;
+    return launch_arrays(pipes, n, p, corner_dirs, out, img, &lat_px_per_deg, &lon_px_per_deg, 0,
+                         {launch_kind::directions, img_dtype, min_elevation, pole_in_view, magnetic, nullptr});
 }
 
 int amt_pipe_launch_box_many(amt_pipe* const* pipes, int32_t n, const amt_frame_params* const* p, double min_elevation,
                              int magnetic) {
-    if (pipes == nullptr || n < 1 || pipes[0] == nullptr) return AMT_EINVAL;
-    amt_ctx* ctx = pipes[0]->ctx;
-    AMT_REQUIRE(ctx, n <= AMT_MAX_BATCH, "at most AMT_PIPE_MAX_BATCH frames per launch");
-    AMT_REQUIRE(ctx, p != nullptr, "NULL argument");
-    magnetic = magnetic ? 1 : 0;
-    amt_georef_out o[AMT_MAX_BATCH];
-    amt_georef_tail tails[AMT_MAX_BATCH];
-    const amt_georef_out* op[AMT_MAX_BATCH];
-    const amt_georef_tail* tp[AMT_MAX_BATCH];
-    for (int i = 0; i < n; ++i) {
-        amt_pipe* pipe = pipes[i];
-        AMT_REQUIRE(ctx, pipe != nullptr && pipe->ctx == ctx && p[i] != nullptr, "drivers of one launch must share the context");
-        for (int k = 0; k < i; ++k) AMT_REQUIRE(ctx, pipes[k] != pipe, "a driver can hold one frame of a launch");
-        // (an estimate that is still pending belongs to another plan of this frame: dropped)
-        if (pipe->coarse_pending && !pipe->coarse_hinted) AMT_HIP(ctx, hipEventSynchronize(pipe->coarse_done));
-        pipe->coarse_pending = pipe->coarse_hinted = false;
-        pipe->pole = amt_prm::pole_in_view(p[i], min_elevation, magnetic) != 0 ? 1 : 0;
-        pipe->pole_unknown = false;
-        pipe->pole_plan = false;
-        pipe->lat_ppd = pipe->lon_ppd = 0;
-        pipe->min_elev = min_elevation;
-        pipe->fused = false;
-        pipe->general_ready = false;
-        pipe->lon_wrap = 0;
-        pipe->g_lat_c = pipe->g_lon_c = pipe->g_elev = nullptr;
-        pipe->g_img = nullptr;
-        if (int rc = pipe_wait_tail(pipe)) return rc;
-        if (int rc = ensure_partials(pipe, amt_georef_partials_bytes(p[i]))) return rc;
-        std::memset(&o[i], 0, sizeof(o[i]));
-        o[i].bbox = pipe->host_small_dev + 8;
-        o[i].bbox_min_elevation = min_elevation;
-        o[i].bin_magnetic = magnetic;          // without bin_acc: the box in (MLat, SM longitude)
-        tails[i].stream = pipe->tail_stream;
-        tails[i].kernel_done = pipe->kernel_done;
-        tails[i].partials = pipe->partials;
-        tails[i].partials_bytes = pipe->partials_bytes;
-        op[i] = &o[i];
-        tp[i] = &tails[i];
-    }
-    if (int rc = amt_georef_launch_many(ctx, n, p, op, tp)) return rc;
-    for (int i = 0; i < n; ++i)
-        if (int rc = pipe_after_launch(pipes[i])) return rc;
-    return AMT_OK;
+    return launch_arrays(pipes, n, p, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                         {launch_kind::box, 0, min_elevation, -1, magnetic, nullptr});
 }
 
-int amt_pipe_launch_box(amt_pipe* pipe, const amt_frame_params* p, double min_elevation, int magnetic) {
-    if (pipe == nullptr) return AMT_EINVAL;
-    return amt_pipe_launch_box_many(&pipe, 1, &p, min_elevation, magnetic);
-}
-
+// one frame: the same with arrays of one (a NULL driver is the first thing launch_frames looks for)
 int amt_pipe_launch(amt_pipe* pipe, const amt_frame_params* p, const amt_georef_out* out, const void* img,
                     int32_t img_dtype, double min_elevation, double lat_px_per_deg, double lon_px_per_deg,
                     int pole_in_view, int magnetic) {
-    if (pipe == nullptr) return AMT_EINVAL;
     return amt_pipe_launch_many(&pipe, 1, &p, &out, &img, img_dtype, min_elevation, lat_px_per_deg, lon_px_per_deg,
                                 pole_in_view, magnetic);
 }
 
+int amt_pipe_launch_dirs(amt_pipe* pipe, const amt_frame_params* p, const double* corner_dirs, const amt_georef_out* out,
+                         const void* img, int32_t img_dtype, double min_elevation, double lat_px_per_deg,
+                         double lon_px_per_deg, int pole_in_view, int magnetic) {
+    return amt_pipe_launch_dirs_many(&pipe, 1, &p, &corner_dirs, &out, &img, img_dtype, min_elevation, lat_px_per_deg,
+                                     lon_px_per_deg, pole_in_view, magnetic);
+}
+
+int amt_pipe_launch_box(amt_pipe* pipe, const amt_frame_params* p, double min_elevation, int magnetic) {
+    return amt_pipe_launch_box_many(&pipe, 1, &p, min_elevation, magnetic);
+}
 
 int amt_pipe_wait(amt_pipe* pipe, amt_pipe_result* result) {
     if (pipe == nullptr) return AMT_EINVAL;

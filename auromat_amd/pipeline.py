@@ -384,11 +384,9 @@ class FramePipeline(object):
         Context.current(self.ctx.device)      # enqueue on whatever stream torch has current now
         out = self._out
         min_elev = NEG_INF if min_elevation is None else float(min_elevation)
-        self.params, self.altitude, self.min_elevation = p, altitude, min_elevation
         if dirs is not None:
             assert dirs.is_cuda and dirs.is_contiguous() and tuple(dirs.shape) == (self.height + 1, self.width + 1, 3), \
                 'one direction per pixel corner, (h + 1, w + 1, 3) float64 on the device'
-        self._dirs = dirs
         self._written()
         if fuse_pxPerDeg is not None and fd.nchan == 3 and (self.with_mag or not fuse_magnetic):
             # coarse pre-pass (unless already enqueued), superset grid, fused kernel, bbox copy: all in the driver
@@ -402,11 +400,9 @@ class FramePipeline(object):
             else:
                 self._pcall('amt_pipe_launch', C.byref(p), C.byref(out), fd.img.data_ptr(),
                             fd.img_dtype_code, min_elev, float(fuse_pxPerDeg[0]), float(fuse_pxPerDeg[1]), -1, mag)
-            self._fused = dict(pxPerDeg=tuple(fuse_pxPerDeg), magnetic=bool(mag), result=None, pole_in_view=int(pole_in_view))
-            fd.corner_mask = fd.center_mask = None
-            self._coords_valid = has_array(fd, 'lat') and self.with_geo
-            self._kept_valid = has_array(fd, 'elev')
+            self._launched(p, altitude, min_elevation, dirs, tuple(fuse_pxPerDeg), mag, pole_in_view)
             return fd
+        self.params, self.altitude, self.min_elevation, self._dirs = p, altitude, min_elevation, dirs
         self._alloc_coords(full=True)
         self._coords_valid = self._kept_valid = True
         self._fused = None
@@ -428,7 +424,7 @@ class FramePipeline(object):
     def georef_many(pipes, params, altitudes, min_elevation, fuse_pxPerDeg, fuse_magnetic=False, dirs=None, pole_in_view=-1):
         """
         The single-pass launch of :meth:`georef` for up to AMT_PIPE_MAX_BATCH pipelines at once (one frame each, coarse
-        pre-pass already started): ONE launch of the big kernel covers all frames (amt_pipe_launch_many).  `dirs`: one
+        pre-pass already started): ONE launch of the big kernel covers all frames (amt_pipe_launch_many_res).  `dirs`: one
         (h + 1, w + 1, 3) direction tensor per frame instead of the camera model (amt_pipe_launch_dirs_many).
         """
         n = len(pipes)
@@ -456,19 +452,19 @@ class FramePipeline(object):
             dd = (C.c_void_p * n)(*[d.data_ptr() for d in dirs])
             ctx.check(ctx._lib.amt_pipe_launch_dirs_many(handles, n, pp, dd, oo, ii, pipes[0].fd.img_dtype_code, min_elev,
                                                          float(ppd[0][0]), float(ppd[0][1]), int(pole_in_view), mag))
-        elif per_frame:
+        else:
             la, lo = (C.c_double * n)(*[float(v[0]) for v in ppd]), (C.c_double * n)(*[float(v[1]) for v in ppd])
             ctx.check(ctx._lib.amt_pipe_launch_many_res(handles, n, pp, oo, ii, pipes[0].fd.img_dtype_code, min_elev, la, lo, -1, mag))
-        else:
-            ctx.check(ctx._lib.amt_pipe_launch_many(handles, n, pp, oo, ii, pipes[0].fd.img_dtype_code, min_elev,
-                                                    float(ppd[0][0]), float(ppd[0][1]), -1, mag))
         for i, (q, p, altitude, v) in enumerate(zip(pipes, params, altitudes, ppd)):
-            q.params, q.altitude, q.min_elevation = p, altitude, min_elevation
-            q._dirs = None if dirs is None else dirs[i]
-            q._fused = dict(pxPerDeg=v, magnetic=bool(mag), result=None, pole_in_view=int(pole_in_view))
-            q.fd.corner_mask = q.fd.center_mask = None
-            q._coords_valid = has_array(q.fd, 'lat') and q.with_geo
-            q._kept_valid = has_array(q.fd, 'elev')
+            q._launched(p, altitude, min_elevation, None if dirs is None else dirs[i], v, mag, pole_in_view)
+
+    def _launched(self, p, altitude, min_elevation, dirs, pxPerDeg, mag, pole_in_view):
+        """What a single-pass launch leaves on the pipeline: the frame it holds, the launch in flight and which arrays it wrote."""
+        self.params, self.altitude, self.min_elevation, self._dirs = p, altitude, min_elevation, dirs
+        self._fused = dict(pxPerDeg=pxPerDeg, magnetic=bool(mag), result=None, pole_in_view=int(pole_in_view))
+        self.fd.corner_mask = self.fd.center_mask = None
+        self._coords_valid = has_array(self.fd, 'lat') and self.with_geo
+        self._kept_valid = has_array(self.fd, 'elev')
 
     def bounding_box(self):
         """Waits for the fused reduction of the last georef() -> BoundingBox; ValueError if nothing is valid."""

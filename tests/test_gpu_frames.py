@@ -901,6 +901,86 @@ def test_direction_arrays_three_frames_per_launch_equal_single_launches(padded):
     ctx.synchronize()
 
 
+def _same_result(got, want, where):
+    """every entry of two results of FramePipeline.run / resample: arrays bit for bit (NaN == NaN), plain values equal (the grid
+    description is an object of the pipeline's: its numbers are in the arrays)"""
+    assert sorted(got) == sorted(want), where
+    arrays = 0
+    for k, v in want.items():
+        if isinstance(v, np.ndarray):
+            assert got[k].shape == v.shape and got[k].dtype == v.dtype, (where, k)
+            assert np.array_equal(got[k], v, equal_nan=True), (where, k)
+            arrays += 1
+        elif v is None or isinstance(v, (bool, int, float, str, tuple)):
+            assert got[k] == v, (where, k)
+    assert arrays >= 1, where
+
+
+def test_one_driver_through_every_launch_kind():
+    """Driver state carried from one kind of launch into the next: ONE FramePipeline (one amt_pipe) takes a camera frame fused,
+    a direction-array frame, a box pass (amt_pipe_launch_box), a camera frame again, a two-pass frame, a camera frame and a
+    direction-array frame, and after every step gives what a fresh pipeline gives for that step alone: every array of the
+    result bit for bit, the eight box numbers, last_plan (a box pass has none: it leaves last_plan alone).  Then three
+    pipelines whose last launches were a box pass, a direction-array frame and a camera frame share one launch
+    (FramePipeline.georef_many), against three fresh ones."""
+    import torch
+    from auromat_amd.mapping.astrometry import frame_params, pixelDirection
+    from auromat_amd.pipeline import FramePipeline
+    from auromat_amd.synthetic import frame_header, frame_image
+    w, h = 640, 420
+    hdr, cam, t = frame_header(w, h, 'iss030')
+    img = frame_image(w, h, seed=11)
+    p = frame_params(hdr, 110, cam, t, True, magnetic=False)
+    used = FramePipeline(w, h)
+    dirs = torch.from_numpy(np.ascontiguousarray(pixelDirection(hdr, corner=True))).to(used.ctx.device)
+
+    def camera(pipe, fuse=True):
+        res = pipe.run(hdr, 110, cam, t, img=img, fast=True, min_elevation=10, pxPerDeg=10, fuse=fuse)
+        assert pipe.last_plan == ('single-pass' if fuse else 'two-pass'), pipe.last_plan
+        return res, pipe.last_plan
+
+    def two_pass(pipe):
+        return camera(pipe, fuse=False)
+
+    def directions(pipe):
+        res = pipe.run(None, 110, cam, t, img=img, fast=True, min_elevation=10, pxPerDeg=10, fuse=True, params=p, dirs=dirs)
+        assert pipe.last_plan == 'single-pass', pipe.last_plan
+        return res, pipe.last_plan
+
+    def box(pipe):
+        return {'box': np.array(pipe.box_first(p, 10))}, None
+
+    fresh = {}
+    for i, step in enumerate((camera, directions, box, camera, two_pass, camera, directions)):
+        if step not in fresh:
+            fresh[step] = step(FramePipeline(w, h))
+        got, plan = step(used)
+        where = (i, step.__name__)
+        assert plan == fresh[step][1], where
+        _same_result(got, fresh[step][0], where)
+    assert fresh[box][0]['box'].shape == (8,)
+
+    # three drivers with three different pasts in one launch
+    frames = [(frame_header(w, h, name), frame_image(w, h, seed=30 + i)) for i, name in enumerate(('iss030', 'iss029', 'iss030'))]
+    ps = [frame_params(hd, 110, c, tt, True, magnetic=False) for (hd, c, tt), _ in frames]
+
+    def together(pipes):
+        for q, q_p, (_, q_img) in zip(pipes, ps, frames):
+            q.set_image(q_img)
+            q.start_coarse(q_p, 10, False)
+        FramePipeline.georef_many(pipes, ps, 110, 10, (10, 10))
+        return [(q.resample((10, 10)), q.last_plan) for q in pipes]
+
+    pasts = [FramePipeline(w, h) for _ in range(3)]
+    for q, step in zip(pasts, (box, directions, camera)):
+        step(q)
+    want = together([FramePipeline(w, h) for _ in range(3)])
+    for i, ((a, plan_a), (b, plan_b)) in enumerate(zip(together(pasts), want)):
+        assert plan_a == plan_b, i
+        _same_result(a, b, ('one launch', i))
+    assert [plan for _, plan in want] == ['single-pass'] * 3
+
+
 @pytest.mark.parametrize('proj', ['TAN', 'SIN', 'ARC', 'STG', 'ZEA'])
 def test_device_generator_for_zenithal_headers_equals_the_numpy_restatement(proj):
     """amt_directions_zenithal (what getMapping runs for a header that is not plain TAN — the reference hands those to
