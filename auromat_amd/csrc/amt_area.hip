@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "amt_common.h"
+#include "amt_frame_src.h"
 #include "amt_mosaic_plan.h"
 
 namespace {
@@ -44,23 +45,18 @@ namespace {
 using namespace amt;
 
 constexpr int kAreaBlock = 256;
+static_assert(kAreaBlock == kBlock, "grid_for counts workgroups of kBlock threads");
 constexpr int kLaneCells = 16;                   // a pixel with more candidate cells is walked by the whole wave
 constexpr double kWeightOne = 4294967296.0;      // 2^32: the weight of a cell that a pixel covers whole
 constexpr double kElevFix = 65536.0;             // 2^16: E = rint(elev * 2^16)
 constexpr unsigned long long kWeightLimit = 1ull << 40;   // a cell covered more than 256 times over: AMT_EDOMAIN
 
 struct area_args {
+    frame_src S;             // (of the centres, the latitude decides whether a pixel counts; lon_c is not read)
     const double* lat;       // corners, (height + 1) x (width + 1)
     const double* lon;
-    const double* lat_c;     // centres, height x width (the NaN test only)
-    const double* elev;
     const void* img;
-    const uint8_t* mask;
-    int height, width, nch;
-    double min_elev;
-    int use_elev_threshold;
-    axis_dev ax, ay;
-    int lon_wrap;
+    int nch;
     unsigned long long* acc;
 };
 
@@ -76,10 +72,8 @@ struct area_mosaic_args {
     int n;
 };
 
-// The frame of a sequence (amt_area_frame_async): the corners' x may be MLT hours, and only the pixels of the rows
-// [row_begin, row_end) are visited.
+// The frame of a sequence (amt_area_frame_async): only the pixels of the rows [row_begin, row_end) are visited.
 struct area_seq_args : area_args {
-    int lon_from_mlt;
     int row_begin, row_end;
 };
 
@@ -89,16 +83,9 @@ template <> struct area_kernel_args<false, true, false> { using type = area_seq_
 
 __device__ __forceinline__ const area_args& frame_args(const area_args& A, int) { return A; }
 __device__ __forceinline__ const area_args& frame_args(const area_mosaic_args& M, int m) { return M.members[m].A; }
-// SEQ: the band of pixels the sweep covers, and a corner's x as it is stored
-__device__ __forceinline__ int64_t first_pixel(const area_seq_args& S) { return (int64_t)S.row_begin * S.width; }
-__device__ __forceinline__ int64_t end_pixel(const area_seq_args& S) { return (int64_t)S.row_end * S.width; }
-// MLT hours -> SM longitude, the expression of amt_median.hip (med_cell) and convertMappingToSM, each operation rounded on its own
-__device__ __forceinline__ double corner_x(const area_seq_args& S, double v) {
-#pragma clang fp contract(off)
-    if (!S.lon_from_mlt) return v;
-    const double d = v - 12.0;
-    return d / (24.0 / 360.0);
-}
+// SEQ: the band of pixels the sweep covers
+__device__ __forceinline__ int64_t first_pixel(const area_seq_args& K) { return (int64_t)K.row_begin * K.S.width; }
+__device__ __forceinline__ int64_t end_pixel(const area_seq_args& K) { return (int64_t)K.row_end * K.S.width; }
 
 // Edge i of an axis: the double bin_index compares against.
 __device__ __forceinline__ double axis_edge(const axis_dev& ax, int i) {
@@ -187,10 +174,10 @@ template <bool WIN>
 __device__ __forceinline__ void add_cell(const area_args& A, const cell_window& Wn, const area_pixel& P, int jx, int jy,
                                          int64_t plane) {
     const int ix = P.ix0 + jx, iy = P.iy0 + jy;
-    const unsigned long long W = cell_weight(P.X, P.Y, axis_edge(A.ax, ix), axis_edge(A.ax, ix + 1), axis_edge(A.ay, iy),
-                                             axis_edge(A.ay, iy + 1));
+    const unsigned long long W = cell_weight(P.X, P.Y, axis_edge(A.S.ax, ix), axis_edge(A.S.ax, ix + 1), axis_edge(A.S.ay, iy),
+                                             axis_edge(A.S.ay, iy + 1));
     if (W == 0) return;
-    const int64_t cell = WIN ? (int64_t)(ix - Wn.x0) * Wn.ny + (iy - Wn.y0) : (int64_t)ix * A.ay.nbin + iy;
+    const int64_t cell = WIN ? (int64_t)(ix - Wn.x0) * Wn.ny + (iy - Wn.y0) : (int64_t)ix * A.S.ay.nbin + iy;
     atomicAdd(&A.acc[cell], W);
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -198,9 +185,7 @@ __device__ __forceinline__ void add_cell(const area_args& A, const cell_window& 
     atomicAdd(&A.acc[(int64_t)(1 + A.nch) * plane + cell], (unsigned long long)((long long)W * P.E));
 }
 
-__device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }     // false for NaN
-
-// WIN = false: the argument is the frame (area_args); the whole grid is kept (A.ax.nbin x A.ay.nbin cells per plane).
+// WIN = false: the argument is the frame (area_args); the whole grid is kept (ax.nbin x ay.nbin cells per plane).
 // WIN = true (the binning of amt_area_mosaic_frames): the argument is the member table (area_mosaic_args); the workgroup finds
 // its member by the workgroup prefix, sweeps that member's pixels with the member's other workgroups and keeps only the cells of
 // the member's window.  The weights and the sums are the same integers either way.
@@ -217,6 +202,7 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_
     // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
     //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
     typename std::conditional<WIN, const area_args, const area_args&>::type A = frame_args(K, member);
+    const frame_src& S = A.S;
     cell_window Wn{0, 0, 0, 0};
     unsigned block0 = 0, nblocks = gridDim.x;
     if constexpr (WIN) {
@@ -224,9 +210,9 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_
         block0 = (unsigned)K.block_start[member];
         nblocks = (unsigned)K.block_start[member + 1] - block0;
     }
-    int64_t pix0 = 0, npix = (int64_t)A.height * A.width;
+    int64_t pix0 = 0, npix = (int64_t)S.height * S.width;
     if constexpr (SEQ) pix0 = first_pixel(K), npix = end_pixel(K);
-    const int64_t plane = WIN ? (int64_t)Wn.nx * Wn.ny : (int64_t)A.ax.nbin * A.ay.nbin;
+    const int64_t plane = WIN ? (int64_t)Wn.nx * Wn.ny : (int64_t)S.ax.nbin * S.ay.nbin;
     const int lane = threadIdx.x & 63;
     const IMG_T* img = static_cast<const IMG_T*>(A.img);
     // (whole waves run every iteration: the cooperative part below needs all 64 lanes)
@@ -243,39 +229,34 @@ __global__ __launch_bounds__(kAreaBlock) void k_area_frame(typename area_kernel_
             P.ch[i] = 0;
         }
         if (p < npix) {
-            const int r = (int)(p / A.width), c = (int)(p - (int64_t)r * A.width);
-            const double ev = A.elev ? A.elev[p] : 0.0;
-            bool ok = finite(A.lat_c[p]);
-            if (A.use_elev_threshold) ok = ok && (ev >= A.min_elev);
-            if (A.mask) ok = ok && A.mask[p] == 0;
-            if (ok) {
+            const int r = (int)(p / S.width), c = (int)(p - (int64_t)r * S.width);
+            const double ev = S.elev ? S.elev[p] : 0.0;
+            if (src_keeps(S, S.lat_c[p], ev, S.mask ? S.mask[p] : 0u)) {
                 // corners (r, c), (r, c + 1), (r + 1, c + 1), (r + 1, c)
-                const int64_t q = (int64_t)r * (A.width + 1) + c;
-                const int64_t at[4] = {q, q + 1, q + A.width + 2, q + A.width + 1};
+                const int64_t q = (int64_t)r * (S.width + 1) + c;
+                const int64_t at[4] = {q, q + 1, q + S.width + 2, q + S.width + 1};
                 double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
                 bool fin = true;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    double lo = A.lon[at[i]];
-                    if constexpr (SEQ) lo = corner_x(K, lo);
-                    const double la = A.lat[at[i]];
+                    const double lo = A.lon[at[i]], la = A.lat[at[i]];
                     fin = fin && finite(lo) && finite(la);
-                    const double x = (!PLANE && A.lon_wrap) ? wrap180_shifted(lo) : lo;
+                    const double x = PLANE ? lo : src_x(S, lo);        // (a plane's x is no longitude)
                     P.X[i] = x;
                     P.Y[i] = la;
                     xmin = fmin(xmin, x); xmax = fmax(xmax, x);
                     ymin = fmin(ymin, la); ymax = fmax(ymax, la);
                 }
                 // (a quadrilateral as wide as half the globe straddles the seam of the longitudes; a plane has no seam)
-                if (fin && (PLANE || xmax - xmin < 180.0) && xmax > A.ax.e0 && xmin < A.ax.e_last && ymax > A.ay.e0 &&
-                    ymin < A.ay.e_last) {
+                if (fin && (PLANE || xmax - xmin < 180.0) && xmax > S.ax.e0 && xmin < S.ax.e_last && ymax > S.ay.e0 &&
+                    ymin < S.ay.e_last) {
                     // edges[g] <= v < edges[g + 1] for the bin g + 1 of bin_index: no cell below that of the minimum or
                     // above that of the maximum meets the quadrilateral
-                    const int nbx = A.ax.nbin, nby = A.ay.nbin;
-                    int ix0 = min(max(bin_index(A.ax, xmin) - 1, 0), nbx - 1);
-                    int ix1 = min(max(bin_index(A.ax, xmax) - 1, 0), nbx - 1);
-                    int iy0 = min(max(bin_index(A.ay, ymin) - 1, 0), nby - 1);
-                    int iy1 = min(max(bin_index(A.ay, ymax) - 1, 0), nby - 1);
+                    const int nbx = S.ax.nbin, nby = S.ay.nbin;
+                    int ix0 = min(max(bin_index(S.ax, xmin) - 1, 0), nbx - 1);
+                    int ix1 = min(max(bin_index(S.ax, xmax) - 1, 0), nbx - 1);
+                    int iy0 = min(max(bin_index(S.ay, ymin) - 1, 0), nby - 1);
+                    int iy1 = min(max(bin_index(S.ay, ymax) - 1, 0), nby - 1);
                     if (WIN) {
                         // the range is cut to the window before the path is chosen: what is left decides lane or wave
                         ix0 = max(ix0, Wn.x0);
@@ -453,45 +434,26 @@ __global__ __launch_bounds__(kSelTile * kSelTile) void k_area_select(area_select
     if (too_much) atomicOr(S.over, 1u);
 }
 
-inline dim3 blocks_for(int64_t n) {
-    int64_t blocks = (n + kAreaBlock - 1) / kAreaBlock;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
-// The frame of amt_area_frame and amt_area_frame_async as the kernel takes it.
-void fill_frame(area_args* A, const double* lat, const double* lon, const double* lat_c, const double* elev, const void* img,
-                int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width, double min_elevation,
-                const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, unsigned long long* acc) {
-    A->lat = lat;
-    A->lon = lon;
-    A->lat_c = lat_c;
-    A->elev = elev;
-    A->img = img;
-    A->mask = center_mask;
-    A->height = height;
-    A->width = width;
-    A->nch = nchan;
-    A->min_elev = min_elevation;
-    A->use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-    make_axis(xaxis, &A->ax);
-    make_axis(yaxis, &A->ay);
-    A->lon_wrap = lon_wrap ? 1 : 0;
-    A->acc = acc;
-}
-
-// The checks of a frame that amt_area_frame, amt_area_plane_frame and amt_area_frame_async share; pointers: the entry point's
-// own pointer arguments are there.  Returns what is wrong, or NULL.
-const char* check_area_frame(bool pointers, const void* img, int32_t img_dtype, int32_t nchan, int32_t height, int32_t width,
-                             const amt_axis* xaxis, const amt_axis* yaxis) {
-    if (!pointers) return "NULL argument";
-    if (!(height > 0 && width > 0)) return "empty frame";
+// The frame of amt_area_frame, amt_area_plane_frame, amt_area_frame_async and of a mosaic's member as the kernel takes it, with
+// the checks they share beside make_frame_src's.  The centres' longitudes are not among an entry point's arguments and are not
+// read (the corners' are): S.lon_c stands on lat_c.  Returns what is wrong, or NULL.
+const char* make_area_frame(area_args* A, const double* lat, const double* lon, const double* lat_c, const double* elev,
+                            const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
+                            int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
+                            int lon_from_mlt, unsigned long long* acc) {
+    if (!(lat && lon)) return "NULL argument";
+    if (const char* bad = make_frame_src(&A->S, lat_c, lat_c, elev, center_mask, height, width, min_elevation, xaxis, yaxis,
+                                         lon_wrap, lon_from_mlt))
+        return bad;
     if (!((int64_t)(height + 1) * (width + 1) < ((int64_t)1 << 31))) return "frames below 2^31 pixels";
     if (!(nchan >= 0 && nchan <= 4)) return "nchan must be 0..4";
     if (!(nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)))) return "img must be uint8 (1) or uint16 (2)";
-    if (!(axis_ok(xaxis) && axis_ok(yaxis))) return "bad axis";
     if (!(xaxis->nbin < 65535 && yaxis->nbin < 65535)) return "at most 65534 bins per axis";
+    A->lat = lat;
+    A->lon = lon;
+    A->img = img;
+    A->nch = nchan;
+    A->acc = acc;
     return nullptr;
 }
 
@@ -516,13 +478,12 @@ int amt_area_frame(amt_ctx* ctx, const double* lat, const double* lon, const dou
                    int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                    double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, uint64_t* acc) {
     AMT_CHECK_CTX(ctx);
-    const char* bad = check_area_frame(lat && lon && lat_c && xaxis && yaxis && acc, img, img_dtype, nchan, height, width, xaxis,
-                                       yaxis);
-    AMT_REQUIRE(ctx, bad == nullptr, bad);
+    AMT_REQUIRE(ctx, acc != nullptr, "NULL argument");
     area_args A;
-    fill_frame(&A, lat, lon, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap,
-               reinterpret_cast<unsigned long long*>(acc));
-    const dim3 grid = blocks_for((int64_t)height * width), block(kAreaBlock);
+    const char* bad = make_area_frame(&A, lat, lon, lat_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation,
+                                      xaxis, yaxis, lon_wrap, 0, reinterpret_cast<unsigned long long*>(acc));
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
+    const dim3 grid = grid_for((int64_t)height * width), block(kAreaBlock);
     if (img_dtype == 2)
         hipLaunchKernelGGL((k_area_frame<uint16_t, false>), grid, block, 0, ctx->stream, A);
     else
@@ -535,14 +496,13 @@ int amt_area_plane_frame(amt_ctx* ctx, const double* x, const double* y, const d
                          const void* img, int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height,
                          int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, uint64_t* acc) {
     AMT_CHECK_CTX(ctx);
-    const char* bad = check_area_frame(x && y && lat_c && xaxis && yaxis && acc, img, img_dtype, nchan, height, width, xaxis,
-                                       yaxis);
+    AMT_REQUIRE(ctx, acc != nullptr, "NULL argument");
+    area_args A;
+    const char* bad = make_area_frame(&A, y, x, lat_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation,
+                                      xaxis, yaxis, 0, 0, reinterpret_cast<unsigned long long*>(acc));
     AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, xaxis->uniform && yaxis->uniform, "the axes of a map plane are uniform");
-    area_args A;
-    fill_frame(&A, y, x, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, 0,
-               reinterpret_cast<unsigned long long*>(acc));
-    const dim3 grid = blocks_for((int64_t)height * width), block(kAreaBlock);
+    const dim3 grid = grid_for((int64_t)height * width), block(kAreaBlock);
     if (img_dtype == 2)
         hipLaunchKernelGGL((k_area_frame<uint16_t, false, false, true>), grid, block, 0, ctx->stream, A);
     else
@@ -564,7 +524,7 @@ int amt_area_frame_finalize(amt_ctx* ctx, const uint64_t* acc, int32_t nx, int32
     }
     AMT_HIP(ctx, hipMemsetAsync(over, 0, sizeof(unsigned int), ctx->stream));
     const unsigned long long least = min_weight < 1 ? 1ull : (unsigned long long)min_weight;
-    const dim3 grid = blocks_for((int64_t)nx * ny), block(kAreaBlock);
+    const dim3 grid = grid_for((int64_t)nx * ny), block(kAreaBlock);
     const unsigned long long* a = reinterpret_cast<const unsigned long long*>(acc);
     if (img_dtype == 2)
         hipLaunchKernelGGL((k_area_finalize<uint16_t>), grid, block, 0, ctx->stream, a, nx, ny, nchan, least, area,
@@ -582,7 +542,9 @@ int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, con
                          int lon_from_mlt, int32_t row_begin, int32_t row_end, uint64_t min_weight, double* area, void* out_img,
                          uint8_t* out_mask, double* out_coverage, uint32_t* over) {
     AMT_CHECK_CTX(ctx);
-    const char* bad = check_area_frame(lat && lon && lat_c && xaxis && yaxis, img, img_dtype, nchan, height, width, xaxis, yaxis);
+    area_seq_args S;
+    const char* bad = make_area_frame(&S, lat, lon, lat_c, elev, img, img_dtype, nchan, center_mask, height, width, min_elevation,
+                                      xaxis, yaxis, lon_wrap, lon_from_mlt, nullptr);
     AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, out_img == nullptr || img_dtype == 1 || img_dtype == 2, "img must be uint8 (1) or uint16 (2)");
     AMT_REQUIRE(ctx, 0 <= row_begin && row_begin <= row_end && row_end <= height, "0 <= row_begin <= row_end <= height");
@@ -598,20 +560,18 @@ int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, con
     AMT_HIP(ctx, hipMemsetAsync(ws, 0, acc_bytes + 256, ctx->stream));
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws);
     unsigned int* flag = over ? over : reinterpret_cast<unsigned int*>(ws + acc_bytes);
-    area_seq_args S;
-    fill_frame(&S, lat, lon, lat_c, elev, img, nchan, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap, acc);
-    S.lon_from_mlt = lon_from_mlt ? 1 : 0;
+    S.acc = acc;
     S.row_begin = row_begin;
     S.row_end = row_end;
     const dim3 block(kAreaBlock);
-    const dim3 grid = blocks_for((int64_t)(row_end - row_begin) * width);
+    const dim3 grid = grid_for((int64_t)(row_end - row_begin) * width);
     if (img_dtype == 2)
         hipLaunchKernelGGL((k_area_frame<uint16_t, false, true>), grid, block, 0, ctx->stream, S);
     else
         hipLaunchKernelGGL((k_area_frame<uint8_t, false, true>), grid, block, 0, ctx->stream, S);
     AMT_LAUNCH_CHECK(ctx);
     const unsigned long long least = min_weight < 1 ? 1ull : (unsigned long long)min_weight;
-    const dim3 fgrid = blocks_for((int64_t)nx * ny);
+    const dim3 fgrid = grid_for((int64_t)nx * ny);
     if (img_dtype == 2)
         hipLaunchKernelGGL((k_area_finalize<uint16_t>), fgrid, block, 0, ctx->stream, acc, nx, ny, nchan, least, area,
                            static_cast<uint16_t*>(out_img), out_mask, out_coverage, flag);
@@ -643,7 +603,7 @@ int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, 
 
     mosaic_plan P;
     const bool fits = plan_members(P, members, n_members, nx, ny, nchan, [](const amt_area_mosaic_member& m) {
-        return blocks_for((int64_t)m.height * m.width).x;
+        return grid_for((int64_t)m.height * m.width).x;
     });
     AMT_REQUIRE(ctx, fits, "too many workgroups");
     plan_select_lists(P);
@@ -668,8 +628,9 @@ int amt_area_mosaic_frames(amt_ctx* ctx, const amt_area_mosaic_member* members, 
 
     for (int32_t i = 0; i < n_members; ++i) {
         const amt_area_mosaic_member& m = members[i];
-        fill_frame(&dev[(size_t)i].A, m.lat, m.lon, m.lat_c, m.elev, m.img, nchan, m.center_mask, m.height, m.width,
-                   min_elevation, xaxis, yaxis, lon_wrap, acc + P.acc_off[(size_t)i]);
+        bad = make_area_frame(&dev[(size_t)i].A, m.lat, m.lon, m.lat_c, m.elev, m.img, img_dtype, nchan, m.center_mask, m.height,
+                              m.width, min_elevation, xaxis, yaxis, lon_wrap, 0, acc + P.acc_off[(size_t)i]);
+        AMT_REQUIRE(ctx, bad == nullptr, bad);          // (mosaic_members_bad has looked at every member)
         dev[(size_t)i].W = P.win[(size_t)i];
     }
     // (pageable source: the copy has consumed the staging buffer when the call returns)

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "amt_common.h"
+#include "amt_frame_src.h"
 #include "amt_mosaic_plan.h"
 
 namespace {
@@ -20,16 +21,8 @@ using namespace amt;
 constexpr int kBinBlock = 256;
 
 struct bin_args {
-    const double* lat_c;
-    const double* lon_c;
-    const double* elev;
+    frame_src S;
     const void* img;
-    const uint8_t* mask;
-    int height, width;
-    double min_elev;
-    int use_elev_threshold;
-    axis_dev ax, ay;
-    int lon_wrap;
     unsigned long long* acc;
 };
 
@@ -80,7 +73,7 @@ __device__ __forceinline__ const bin_args& frame_args(const bin_args& A, int) { 
 __device__ __forceinline__ const bin_args& frame_args(const mosaic_args& M, int m) { return M.members[m].A; }
 
 // k_bin_frame: workgroup blockIdx.x bins one BW x (BH * kRowIters) tile of a frame.
-// WIN = false: the argument is the frame (bin_args); the whole grid is kept (A.ax.nbin x A.ay.nbin cells per plane).
+// WIN = false: the argument is the frame (bin_args); the whole grid is kept (ax.nbin x ay.nbin cells per plane).
 // WIN = true (the mosaic binning of amt_mosaic_frames, "k_mosaic_bin"): the argument is the member table (mosaic_args); the
 // workgroup finds its member by the tile prefix and keeps only the cells of the member's window W.
 template <typename IMG_T, int NCH, bool VEC, bool WIN>
@@ -95,15 +88,16 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
     // (the frame: the kernel argument itself; a member: its descriptor copied into registers once, so that the global
     //  atomics below, which may alias the table for all the compiler knows, do not make every use reload it)
     typename std::conditional<WIN, const bin_args, const bin_args&>::type A = frame_args(P, member);
+    const frame_src& S = A.S;
     cell_window W{0, 0, 0, 0};
     if constexpr (WIN) W = P.members[member].W;
-    const int tiles_x = (A.width + kBW - 1) / kBW;
+    const int tiles_x = (S.width + kBW - 1) / kBW;
     unsigned t = blockIdx.x;                    // the tile's number within the frame
     if constexpr (WIN) t -= (unsigned)P.tile_start[member];
     const int tile_y = t / tiles_x, tile_x = t - tile_y * tiles_x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int gx0 = tile_x * kBW;
-    const int64_t ncell = WIN ? (int64_t)W.nx * W.ny : (int64_t)A.ax.nbin * A.ay.nbin;
+    const int64_t ncell = WIN ? (int64_t)W.nx * W.ny : (int64_t)S.ax.nbin * S.ay.nbin;
     const IMG_T* img = static_cast<const IMG_T*>(A.img);
 
     for (int i = threadIdx.x; i < kWCap; i += kBinBlock) {
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
 
     for (int it = 0; it < kRowIters; ++it) {
         const int gy = (tile_y * kRowIters + it) * kBH + wave;
-        const int n_row = (gy < A.height) ? min(kBW, A.width - gx0) : 0;   // pixels of this tile row inside the image
+        const int n_row = (gy < S.height) ? min(kBW, S.width - gx0) : 0;   // pixels of this tile row inside the image
 
         // ---- all loads first (one memory latency per row group), then arithmetic ---------------------
         double la[kPPT], lo[kPPT], ev[kPPT];
@@ -132,8 +126,8 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
             for (int c = 0; c < NCH; ++c) ch[j][c] = 0;
         }
         if (n_row > 0) {
-            const int64_t g0 = (int64_t)gy * A.width + gx0;
-            load_run<VEC>(A.lat_c + g0, lane, n_row, la);
+            const int64_t g0 = (int64_t)gy * S.width + gx0;
+            load_run<VEC>(S.lat_c + g0, lane, n_row, la);
         }
         // a pixel without a latitude is not binned (resample.py:315-321): where a wave's whole tile row has none — the sky
         // above the limb, 30-40 % of an ISS frame — its longitudes, elevations and image bytes (22 of the 30 B per pixel)
@@ -142,12 +136,12 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
 #pragma unroll
         for (int j = 0; j < kPPT; ++j) any_lat = any_lat || la[j] == la[j];
         if (n_row > 0 && __any(any_lat)) {
-            const int64_t g0 = (int64_t)gy * A.width + gx0;
-            load_run<VEC>(A.lon_c + g0, lane, n_row, lo);
-            if (A.elev) load_run<VEC>(A.elev + g0, lane, n_row, ev);
-            if (A.mask) {
+            const int64_t g0 = (int64_t)gy * S.width + gx0;
+            load_run<VEC>(S.lon_c + g0, lane, n_row, lo);
+            if (S.elev) load_run<VEC>(S.elev + g0, lane, n_row, ev);
+            if (S.mask) {
 #pragma unroll
-                for (int j = 0; j < kPPT; ++j) mk[j] = tile_col(lane, j) < n_row ? A.mask[g0 + tile_col(lane, j)] : 1;
+                for (int j = 0; j < kPPT; ++j) mk[j] = tile_col(lane, j) < n_row ? S.mask[g0 + tile_col(lane, j)] : 1;
             }
             if (NCH > 0) {
                 constexpr int kPairBytes = 2 * NCH * (int)sizeof(IMG_T);
@@ -182,15 +176,11 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
         int first = 0;                                  // first valid cell of this thread, packed (x << 16 | y) + 1
 #pragma unroll
         for (int j = kPPT - 1; j >= 0; --j) {
-            bool ok = la[j] == la[j];                                          // resample.py:315-321
-            if (A.use_elev_threshold) ok = ok && (ev[j] >= A.min_elev);        // mapping.py:856
-            ok = ok && mk[j] == 0;
             cellx[j] = 0;
             celly[j] = 0;
-            if (ok) {
-                const double xv = A.lon_wrap ? wrap180_shifted(lo[j]) : lo[j];
-                const int bx = bin_index(A.ax, xv), by = bin_index(A.ay, la[j]);
-                if (bx >= 1 && bx <= A.ax.nbin && by >= 1 && by <= A.ay.nbin &&
+            if (src_keeps(S, la[j], ev[j], mk[j])) {
+                int bx, by;
+                if (src_cell(S, la[j], src_x(S, lo[j]), bx, by) &&
                     (!WIN || ((unsigned)(bx - 1 - W.x0) < (unsigned)W.nx && (unsigned)(by - 1 - W.y0) < (unsigned)W.ny))) {
                     cellx[j] = bx;
                     celly[j] = by;
@@ -247,7 +237,7 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
             } else {
                 // outside the LDS window (very fine grids or strongly stretched tiles): global atomics
                 const int64_t cell = WIN ? (int64_t)(run_x - 1 - W.x0) * W.ny + (run_y - 1 - W.y0)
-                                         : (int64_t)(run_x - 1) * A.ay.nbin + (run_y - 1);
+                                         : (int64_t)(run_x - 1) * S.ay.nbin + (run_y - 1);
                 atomicAdd(&A.acc[cell], (unsigned long long)rcnt);
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) atomicAdd(&A.acc[(int64_t)(1 + c) * ncell + cell], (unsigned long long)rch[c]);
@@ -281,7 +271,7 @@ __global__ __launch_bounds__(kBinBlock) void k_bin_frame(typename bin_kernel_arg
         if (cnt == 0) continue;
         const int dx = i / kWY, dy = i - dx * kWY;
         const int64_t cell = WIN ? (int64_t)(ax0 + dx - 1 - W.x0) * W.ny + (ay0 + dy - 1 - W.y0)
-                                 : (int64_t)(ax0 + dx - 1) * A.ay.nbin + (ay0 + dy - 1);
+                                 : (int64_t)(ax0 + dx - 1) * S.ay.nbin + (ay0 + dy - 1);
         atomicAdd(&A.acc[cell], (unsigned long long)cnt);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) atomicAdd(&A.acc[(int64_t)(1 + c) * ncell + cell], (unsigned long long)sCh[c][i]);

@@ -12,8 +12,6 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
-
 // ------------------------------------------------------------------------------------------
 // generic float64 histogram (operator-level API)
 // ------------------------------------------------------------------------------------------
@@ -33,8 +31,7 @@ struct hist_args {
 
 __global__ __launch_bounds__(kBlock) void k_hist2d(hist_args A) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * blockDim.x) {
-        double xv = A.x[i];
-        if (A.lon_wrap) xv = wrap180_shifted(xv);
+        const double xv = src_x(0, A.lon_wrap, A.x[i]);
         const int ix = bin_index(A.ax, xv);
         const int iy = bin_index(A.ay, A.y[i]);
         if (ix < 1 || ix > A.ax.nbin || iy < 1 || iy > A.ay.nbin) continue;
@@ -174,13 +171,6 @@ __global__ void k_pipe_finish(finish_batch B) {
     if (blockIdx.x == 0 && threadIdx.x == 0 && F.count != nullptr) *F.count = 0;
 }
 
-inline dim3 grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
 }  // namespace
 
 int amt_bin_apply_events_on(amt_ctx* ctx, hipStream_t stream, const void* events, uint32_t* count, uint64_t* acc,
@@ -284,25 +274,14 @@ int amt_bin_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const 
                   int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
                   double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, uint64_t* acc) {
     AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && acc, "NULL argument");
-    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, acc != nullptr, "NULL argument");
+    bin_args A;
+    const char* bad = make_frame_src(&A.S, lat_c, lon_c, elev, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap, 0);
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
     AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
     AMT_REQUIRE(ctx, xaxis->nbin < 65535 && yaxis->nbin < 65535, "at most 65534 bins per axis");
-    bin_args A;
-    A.lat_c = lat_c;
-    A.lon_c = lon_c;
-    A.elev = elev;
     A.img = img;
-    A.mask = center_mask;
-    A.height = height;
-    A.width = width;
-    A.min_elev = min_elevation;
-    A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-    make_axis(xaxis, &A.ax);
-    make_axis(yaxis, &A.ay);
-    A.lon_wrap = lon_wrap ? 1 : 0;
     A.acc = reinterpret_cast<unsigned long long*>(acc);
     const int tiles_x = (width + kBW - 1) / kBW, tiles_y = (height + kBH * kRowIters - 1) / (kBH * kRowIters);
     const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(kBlock);

@@ -211,8 +211,25 @@ static inline int amt_set_device(amt_ctx* ctx) {
 // ------------------------------------------------------------------------------------------
 namespace amt {
 
+// ---- launch helpers of the one-thread-per-element kernels ----
+constexpr int kBlock = 256;
+
+// workgroups of kBlock threads for n elements of a grid-stride loop: at most 256 CUs x 16 resident blocks of light kernels
+inline dim3 grid_for(int64_t n) {
+    int64_t blocks = (n + kBlock - 1) / kBlock;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (blocks < 1) blocks = 1;
+    return dim3(static_cast<unsigned>(blocks));
+}
+
+#define AMT_GRID_STRIDE(i, n) \
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
+
+__device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }     // false for NaN
+
 constexpr double kRad2Deg = 57.29577951308232;     // 180/pi, also the TAN projection constant
 constexpr double kDeg2Rad = 0.017453292519943295;  // pi/180
+constexpr double kMltPerDeg = (24.0 / 360.0);      // hours of magnetic local time per degree of SM longitude
 
 struct vec3 {
     double x, y, z;
@@ -423,7 +440,7 @@ __host__ inline pole_consts make_pole_consts(double a0, double b0, double altitu
 __device__ __forceinline__ void sm_to_mlat_mlt(const vec3& s, double& mlat, double& mlt) {
     const double sxy = sqrt(s.x * s.x + s.y * s.y);
     mlat = atan2(s.z, sxy) * kRad2Deg;
-    mlt = (atan2(s.y, s.x) * kRad2Deg) * (24.0 / 360.0) + 12.0;
+    mlt = (atan2(s.y, s.x) * kRad2Deg) * kMltPerDeg + 12.0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -7,19 +7,6 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    const int64_t cap = 256 * 16;  // 256 CUs x 16 resident 256-thread blocks of light kernels
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
-#define AMT_GRID_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
 __global__ void k_directions_tan(tan_wcs w, int width, int height, int corner, double* __restrict__ out) {
     const int cols = width + corner;
     const int64_t n = (int64_t)(height + corner) * cols;

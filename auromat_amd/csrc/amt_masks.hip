@@ -6,18 +6,7 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
 constexpr double kInf = __builtin_huge_val();
-
-inline dim3 grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
-#define AMT_GRID_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
 __global__ void k_center_mask_by_elevation(const double* __restrict__ elev, int64_t n, double min_elev,
                                            uint8_t* __restrict__ center_mask, unsigned long long* n_valid) {

@@ -2,9 +2,9 @@
 // resample(method='mean') bins into a cell (reference auromat/resample.py:353-357 names the statistic and leaves it
 // unbuilt).  Exact and independent of scatter order: every result is an order statistic of the cell's keys.
 //
-//   k_med_count    cell of every pixel by the membership rule of k_bin_frame (histogram2d's edges), counts per cell;
+//   k_med_count    cell of every pixel by the membership rule of k_bin_frame (amt_frame_src.h), counts per cell;
 //                  a lane takes 4 consecutive pixels and a run of lanes with one cell issues one atomic
-//   k_med_scan_*   exclusive scan of the counts (block sums, one workgroup over the sums, block rescan)
+//   k_cell_scan_*  exclusive scan of the counts (amt_cell_scan.h: block sums, one workgroup over the sums, block rescan)
 //   k_med_fill     scatter of the KEYS into contiguous per-cell segments, one plane per channel: u16 channel values,
 //                  elevation as an order-preserving u64 of its float64 bits; positions reserved per run of lanes
 //   k_med_small    one wave per cell: outputs of every cell (count, mask, empty cells) and, for cells of <= 64 pixels,
@@ -32,6 +32,8 @@
 // (count_wave, fill_wave) over the concatenated pixels of a mosaic's members, one launch each whatever the member count; a
 // pixel counts inside its member's window and, under rule 1, where amt_mosaic_frames' election (k_mosaic_select) chose its member.
 #include "amt_common.h"
+#include "amt_cell_scan.h"
+#include "amt_frame_src.h"
 #include "amt_mosaic_plan.h"
 
 #include <algorithm>
@@ -41,12 +43,10 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
 constexpr int kPPT = 4;                 // consecutive pixels per lane in the count and fill passes
 constexpr int kSmallMax = 64;           // cells up to one wave's lanes are sorted in registers
 constexpr int kLargeMin = 16384;        // cells above this many keys are spread over several workgroups
 constexpr int kChunk = 4096;            // keys per workgroup of the large tier
-constexpr int kScanItems = 8;           // cells per thread of the scan
 constexpr int kQuantilesMax = AMT_QUANTILES_MAX;
 
 // The rank rule: which two order statistics of a cell's n >= 1 sorted keys a result is made of (k2 is k or k + 1), and the
@@ -87,41 +87,18 @@ __host__ __device__ inline rank_pair rank_rule(int64_t n, double q, bool median)
     return r;
 }
 
-inline dim3 grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
 struct med_args {
-    const double* lat_c;
-    const double* lon_c;
-    const double* elev;
+    frame_src S;
     const void* img;
-    const uint8_t* mask;
-    int64_t n;
-    double min_elev;
-    int use_elev_threshold;
-    int lon_wrap;
-    int lon_from_mlt;                   // lon_c holds MLT hours: SM longitude as convertMappingToSM computes it
-    axis_dev ax, ay;
     int nx, ny, nch, img_dtype;
 };
 
-// Flat cell (iy * nx + ix) of pixel i or -1: the membership of k_bin_frame (amt_binning.hip) — finite latitude,
-// elevation >= the threshold, centre mask 0, and inside the edges by histogram2d's rules (bin_index).
-__device__ __forceinline__ int pixel_cell(const med_args& A, int64_t i) {
-    const double la = A.lat_c[i];
-    if (!(la == la)) return -1;
-    if (A.use_elev_threshold && !(A.elev[i] >= A.min_elev)) return -1;
-    if (A.mask && A.mask[i]) return -1;
-    double lo = A.lon_c[i];
-    if (A.lon_from_mlt) lo = (lo - 12.0) / (24.0 / 360.0);     // mltToSmLon (mapping/mapping.py convertMappingToSM)
-    const double xv = A.lon_wrap ? wrap180_shifted(lo) : lo;
-    const int bx = bin_index(A.ax, xv), by = bin_index(A.ay, la);
-    if (bx < 1 || bx > A.ax.nbin || by < 1 || by > A.ay.nbin) return -1;
-    return (by - 1) * A.nx + (bx - 1);
+__device__ __forceinline__ int64_t pixels_of(const med_args& A) { return (int64_t)A.S.height * A.S.width; }
+
+// Flat cell (iy * nx + ix) of pixel i or -1: the membership of k_bin_frame (pixel_cell, amt_frame_src.h).
+__device__ __forceinline__ int flat_cell(const med_args& A, int64_t i) {
+    int bx, by;
+    return pixel_cell(A.S, i, bx, by) ? (by - 1) * A.nx + (bx - 1) : -1;
 }
 
 // order-preserving integer key of a float64 (NaN with the sign bit clear sorts above +inf)
@@ -159,45 +136,14 @@ __device__ __forceinline__ void summarise(lane_cells& L) {
     }
 }
 
-// Runs of consecutive lanes with the same cell: for every lane the first lane of its run, and the number of
-// pixels of the run before this lane (excl) and in all of it (total).  Called by the whole wave.
-struct lane_run {
-    int head;
-    unsigned excl, total;
-};
-
-__device__ __forceinline__ lane_run run_of(int cell, unsigned cnt, int lane) {
-    unsigned incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    const int prev = __shfl_up(cell, 1);
-    const bool is_head = lane == 0 || prev != cell;
-    const unsigned long long heads = __ballot(is_head);
-    const unsigned long long upto = heads & (~0ull >> (63 - lane));
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    lane_run r;
-    r.head = 63 - __clzll(upto);
-    const int last = above ? lane + __ffsll((long long)above) - 1 : 63;
-    const unsigned before_run = __shfl(incl, r.head) - __shfl(cnt, r.head);
-    r.excl = incl - cnt - before_run;
-    r.total = __shfl(incl, last) - before_run;
-    return r;
-}
-
 // ---- the member table of a mosaic (amt_mosaic_median_frames, amt_mosaic_quantile_frames) ----
 // The pixel index space of the count and fill passes is the concatenation of the members that have a window: member m's
 // pixel i is g0 + i.  Work is handed out in whole workgroups of kBlock * kPPT pixels of ONE member (block_start: the first
 // workgroup of every member, n + 1 entries), so a wave only ever sees one member and the run rule below carries over.
 struct med_member {
-    const double* lat_c;
-    const double* lon_c;
-    const double* elev;
+    frame_src S;                        // the member's frame on the common axes
     const void* img;
-    const uint8_t* mask;
-    int n, g0;                          // pixels; index of pixel 0 in the concatenated space
+    int g0;                             // index of pixel 0 in the concatenated space
     cell_window W;                      // window in cells of the common grid (amt_mosaic_plan.h)
 };
 struct member_table {
@@ -234,13 +180,8 @@ __device__ __forceinline__ void note_member(const member_view& V, int c) {
 // The frame of a member as the kernels' argument: the call's common part A0 with the member's arrays.
 __device__ __forceinline__ med_args member_args(const med_args& A0, const med_member& D) {
     med_args A = A0;
-    A.lat_c = D.lat_c;
-    A.lon_c = D.lon_c;
-    A.elev = D.elev;
+    A.S = D.S;
     A.img = D.img;
-    A.mask = D.mask;
-    A.n = D.n;
-    A.use_elev_threshold = A0.use_elev_threshold && D.elev != nullptr;
     return A;
 }
 
@@ -249,13 +190,13 @@ __device__ __forceinline__ med_args member_args(const med_args& A0, const med_me
 template <typename VIEW>
 __device__ __forceinline__ void count_wave(const med_args& A, const VIEW& V, int64_t base, int64_t g0, int lane, int* cell_of,
                                            unsigned* count) {
-    const int64_t i0 = base + (int64_t)lane * kPPT;
+    const int64_t i0 = base + (int64_t)lane * kPPT, n = pixels_of(A);
     lane_cells L;
 #pragma unroll
     for (int j = 0; j < kPPT; ++j) {
         const int64_t i = i0 + j;
-        L.c[j] = i < A.n ? keep_cell(A, V, pixel_cell(A, i)) : -1;
-        if (i < A.n) cell_of[g0 + i] = L.c[j];
+        L.c[j] = i < n ? keep_cell(A, V, flat_cell(A, i)) : -1;
+        if (i < n) cell_of[g0 + i] = L.c[j];
     }
     summarise(L);
     if (L.mixed) {
@@ -276,9 +217,9 @@ __device__ __forceinline__ void count_wave(const med_args& A, const VIEW& V, int
 __global__ __launch_bounds__(kBlock) void k_med_count(med_args A, int* __restrict__ cell_of,
                                                      unsigned* __restrict__ count) {
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT;
+    const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT, n = pixels_of(A);
     // whole waves stay in the loop together (the shuffles need every lane)
-    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride)
+    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < n; base += stride)
         count_wave(A, no_member{}, base, 0, lane, cell_of, count);
 }
 
@@ -292,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void k_med_count_members(med_args A0, membe
     const med_args A = member_args(A0, D);
     const member_view V = {m, D.W, T.source, T.first};
     const int64_t base = ((int64_t)(blockIdx.x - (unsigned)T.block_start[m]) * kBlock + (threadIdx.x & ~63)) * kPPT;
-    if (base >= A.n) return;                                        // (wave-uniform)
+    if (base >= pixels_of(A)) return;                               // (wave-uniform)
     count_wave(A, V, base, D.g0, lane, cell_of, count);
 }
 
@@ -306,78 +247,6 @@ __global__ __launch_bounds__(kBlock) void k_med_source(const unsigned* __restric
     }
 }
 
-// ---- exclusive scan of the counts: offset[0..cells], offset[cells] = number of binned pixels ----
-constexpr int kScanTile = kBlock * kScanItems;
-
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned* sWave, unsigned& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) sWave[wave] = incl;
-    __syncthreads();
-    unsigned before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        before += w < wave ? sWave[w] : 0u;
-        total += sWave[w];
-    }
-    __syncthreads();
-    return before + incl - v;
-}
-
-__global__ __launch_bounds__(kBlock) void k_med_scan_sums(const unsigned* __restrict__ count, int64_t cells,
-                                                         unsigned* __restrict__ bsum) {
-    __shared__ unsigned sWave[kBlock / 64];
-    const int64_t b0 = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-    unsigned s = 0;
-#pragma unroll
-    for (int q = 0; q < kScanItems; ++q) s += b0 + q < cells ? count[b0 + q] : 0u;
-    unsigned total;
-    (void)block_excl_scan(s, sWave, total);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup: exclusive scan of the nb block sums in place, bsum[nb] = the grand total
-__global__ __launch_bounds__(kBlock) void k_med_scan_blocks(unsigned* __restrict__ bsum, int nb) {
-    __shared__ unsigned sWave[kBlock / 64];
-    unsigned carry = 0;
-    for (int base = 0; base < nb; base += kBlock) {
-        const int i = base + threadIdx.x;
-        const unsigned v = i < nb ? bsum[i] : 0u;
-        unsigned total;
-        const unsigned e = block_excl_scan(v, sWave, total);
-        if (i < nb) bsum[i] = carry + e;
-        carry += total;
-    }
-    if (threadIdx.x == 0) bsum[nb] = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void k_med_scan_apply(const unsigned* __restrict__ count, int64_t cells,
-                                                          const unsigned* __restrict__ bsum, int nb,
-                                                          unsigned* __restrict__ offset) {
-    __shared__ unsigned sWave[kBlock / 64];
-    const int64_t b0 = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-    unsigned v[kScanItems], s = 0;
-#pragma unroll
-    for (int q = 0; q < kScanItems; ++q) {
-        v[q] = b0 + q < cells ? count[b0 + q] : 0u;
-        s += v[q];
-    }
-    unsigned total;
-    unsigned run = bsum[blockIdx.x] + block_excl_scan(s, sWave, total);
-#pragma unroll
-    for (int q = 0; q < kScanItems; ++q) {
-        if (b0 + q < cells) offset[b0 + q] = run;
-        run += v[q];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) offset[cells] = bsum[nb];
-}
-
 // ---- scatter of the keys ----
 // One wave's kPPT * 64 pixels of frame A from pixel `base` on (pixel 0 is g0 in cell_of; the key planes are `stride` keys
 // apart): the body of the fill pass, shared like count_wave.  Called by the whole wave.
@@ -386,10 +255,10 @@ __device__ __forceinline__ void fill_wave(const med_args& A, int64_t base, int64
                                           const int* cell_of, const unsigned* offset, unsigned* cursor, uint16_t* keys16,
                                           unsigned long long* keys64) {
     const IMG_T* img = static_cast<const IMG_T*>(A.img);
-    const int64_t i0 = base + (int64_t)lane * kPPT;
+    const int64_t i0 = base + (int64_t)lane * kPPT, n = pixels_of(A);
     lane_cells L;
 #pragma unroll
-    for (int j = 0; j < kPPT; ++j) L.c[j] = i0 + j < A.n ? cell_of[g0 + i0 + j] : -1;
+    for (int j = 0; j < kPPT; ++j) L.c[j] = i0 + j < n ? cell_of[g0 + i0 + j] : -1;
     summarise(L);
     const lane_run r = run_of(L.cell, L.cnt, lane);
     unsigned first = 0;
@@ -404,7 +273,7 @@ __device__ __forceinline__ void fill_wave(const med_args& A, int64_t base, int64
         else pos = first++;
         const int64_t i = i0 + j;
         for (int ch = 0; ch < A.nch; ++ch) keys16[(int64_t)ch * stride + pos] = (uint16_t)img[i * A.nch + ch];
-        if (keys64) keys64[pos] = elev_key(A.elev[i]);
+        if (keys64) keys64[pos] = elev_key(A.S.elev[i]);
     }
 }
 
@@ -413,9 +282,9 @@ __global__ __launch_bounds__(kBlock) void k_med_fill(med_args A, const int* __re
                                                     const unsigned* __restrict__ offset, unsigned* __restrict__ cursor,
                                                     uint16_t* __restrict__ keys16, unsigned long long* __restrict__ keys64) {
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT;
-    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < A.n; base += stride)
-        fill_wave<IMG_T>(A, base, 0, A.n, lane, cell_of, offset, cursor, keys16, keys64);
+    const int64_t stride = (int64_t)gridDim.x * kBlock * kPPT, n = pixels_of(A);
+    for (int64_t base = (blockIdx.x * (int64_t)kBlock + (threadIdx.x & ~63)) * kPPT; base < n; base += stride)
+        fill_wave<IMG_T>(A, base, 0, n, lane, cell_of, offset, cursor, keys16, keys64);
 }
 
 // The fill pass over a member table (the workgroups of k_med_count_members); total: the pixels of the concatenated space.
@@ -430,7 +299,7 @@ __global__ __launch_bounds__(kBlock) void k_med_fill_members(med_args A0, member
     const med_member D = T.members[m];
     const med_args A = member_args(A0, D);
     const int64_t base = ((int64_t)(blockIdx.x - (unsigned)T.block_start[m]) * kBlock + (threadIdx.x & ~63)) * kPPT;
-    if (base >= A.n) return;                                        // (wave-uniform)
+    if (base >= pixels_of(A)) return;                               // (wave-uniform)
     fill_wave<IMG_T>(A, base, D.g0, total, lane, cell_of, offset, cursor, keys16, keys64);
 }
 
@@ -1032,7 +901,7 @@ struct med_layout {
 
 med_layout median_layout(int64_t n, int64_t cells, int nchan, bool has_elev) {
     med_layout L;
-    L.nb = (int)((cells + kScanTile - 1) / kScanTile);
+    L.nb = cell_scan_blocks(cells);
     L.large_cap = n / (kLargeMin + 1) + 1;
     const int nplane = nchan + (has_elev ? 1 : 0);
     size_t at = 0;
@@ -1080,12 +949,6 @@ med_buffers median_bind(char* ws, const med_layout& L, int64_t n, int64_t cells,
     return B;
 }
 
-void median_scan(amt_ctx* ctx, const med_buffers& B, int64_t cells, int nb) {
-    hipLaunchKernelGGL(k_med_scan_sums, dim3(nb), dim3(kBlock), 0, ctx->stream, B.count, cells, B.bsum);
-    hipLaunchKernelGGL(k_med_scan_blocks, dim3(1), dim3(kBlock), 0, ctx->stream, B.bsum, nb);
-    hipLaunchKernelGGL(k_med_scan_apply, dim3(nb), dim3(kBlock), 0, ctx->stream, B.count, cells, B.bsum, nb, B.offset);
-}
-
 // the output arguments and the small tier (k_med_small), after the fill pass
 int median_small(amt_ctx* ctx, const med_buffers& B, const med_args& A, bool has_elev, const double* q, int nq, double* median,
                  void* out_img, uint8_t* out_mask, double* out_count, median_pass* M) {
@@ -1117,31 +980,21 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
                  const double* q, int nq, double* median, void* out_img, uint8_t* out_mask, double* out_count,
                  median_pass* M) {
     // (nq == 0: the median; the callers have checked the quantiles)
-    AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && median, "NULL argument");
-    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, median != nullptr, "NULL argument");
+    med_args A;
+    const char* bad = make_frame_src(&A.S, lat_c, lon_c, elev, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap,
+                                     lon_from_mlt);
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, (int64_t)height * width < 2147483647LL, "frame too large for 32-bit pixel indices");
     AMT_REQUIRE(ctx, nchan >= 0 && nchan <= 4, "nchan must be 0..4");
     AMT_REQUIRE(ctx, nchan == 0 || (img && (img_dtype == 1 || img_dtype == 2)), "img must be uint8 (1) or uint16 (2)");
-    AMT_REQUIRE(ctx, axis_ok(xaxis) && axis_ok(yaxis), "bad axis");
     AMT_REQUIRE(ctx, (int64_t)xaxis->nbin * yaxis->nbin < 2147483647LL, "grid too large");
-    med_args A;
-    A.lat_c = lat_c;
-    A.lon_c = lon_c;
-    A.elev = elev;
     A.img = img;
-    A.mask = center_mask;
-    A.n = (int64_t)height * width;
-    A.min_elev = min_elevation;
-    A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-    A.lon_wrap = lon_wrap ? 1 : 0;
-    A.lon_from_mlt = lon_from_mlt ? 1 : 0;
-    make_axis(xaxis, &A.ax);
-    make_axis(yaxis, &A.ay);
     A.nx = xaxis->nbin;
     A.ny = yaxis->nbin;
     A.nch = nchan;
     A.img_dtype = img_dtype;
-    const int64_t n = A.n, cells = (int64_t)A.nx * A.ny;
+    const int64_t n = (int64_t)height * width, cells = (int64_t)A.nx * A.ny;
     const med_layout L = median_layout(n, cells, nchan, elev != nullptr);
     char* ws = static_cast<char*>(amt_workspace(ctx, L.bytes));
     if (ws == nullptr) {
@@ -1153,7 +1006,7 @@ int median_front(amt_ctx* ctx, const double* lat_c, const double* lon_c, const d
     // count, cursor and the tier counters are adjacent: one clear
     AMT_HIP(ctx, hipMemsetAsync(ws, 0, L.offset, ctx->stream));
     hipLaunchKernelGGL(k_med_count, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, B.cell_of, B.count);
-    median_scan(ctx, B, cells, L.nb);
+    cell_scan(ctx, B.count, cells, B.bsum, B.offset);
     if (nchan == 0 || img_dtype == 1)
         hipLaunchKernelGGL(k_med_fill<uint8_t>, grid_for((n + kPPT - 1) / kPPT), dim3(kBlock), 0, ctx->stream, A, B.cell_of,
                            B.offset, B.cursor, B.keys16, B.keys64);
@@ -1197,15 +1050,13 @@ int mosaic_median_front(amt_ctx* ctx, const amt_mosaic_member* members, int32_t 
         const amt_mosaic_member& m = members[i];
         has_elev = has_elev && m.elev != nullptr;           // (the elevation plane: of every member, or NaN)
         med_member& d = table[(size_t)i];
-        d.lat_c = m.lat_c;
-        d.lon_c = m.lon_c;
-        d.elev = m.elev;
+        bad = make_frame_src(&d.S, m.lat_c, m.lon_c, m.elev, m.center_mask, m.height, m.width, min_elevation, xaxis, yaxis, lon_wrap,
+                             0);
+        AMT_REQUIRE(ctx, bad == nullptr, bad);              // (mosaic_members_bad has looked at every member)
         d.img = m.img;
-        d.mask = m.center_mask;
-        d.n = m.height * m.width;
         d.g0 = (int)total;
         d.W = P.win[(size_t)i];
-        if (d.W.nx != 0) total += d.n;
+        if (d.W.nx != 0) total += (int64_t)m.height * m.width;
     }
     const int64_t blocks = P.units;
     if (amt_set_device(ctx)) return AMT_EHIP;
@@ -1234,17 +1085,7 @@ int mosaic_median_front(amt_ctx* ctx, const amt_mosaic_member* members, int32_t 
     int32_t* plane = reinterpret_cast<int32_t*>(ws + o_plane);
     const med_buffers B = median_bind(ws + o_med, L, total, cells, nchan, has_elev, M);
 
-    med_args A;                         // the call's common part; the kernels put a member's arrays in
-    A.lat_c = A.lon_c = A.elev = nullptr;
-    A.img = nullptr;
-    A.mask = nullptr;
-    A.n = 0;
-    A.min_elev = min_elevation;
-    A.use_elev_threshold = !(std::isinf(min_elevation) && min_elevation < 0);
-    A.lon_wrap = lon_wrap ? 1 : 0;
-    A.lon_from_mlt = 0;
-    make_axis(xaxis, &A.ax);
-    make_axis(yaxis, &A.ay);
+    med_args A = {};                    // the call's common part; the kernels put a member's frame in (member_args)
     A.nx = nx;
     A.ny = ny;
     A.nch = nchan;
@@ -1269,7 +1110,7 @@ int mosaic_median_front(amt_ctx* ctx, const amt_mosaic_member* members, int32_t 
         else
             hipLaunchKernelGGL(k_med_source, grid_for(cells), dim3(kBlock), 0, ctx->stream, B.count, plane, nx, ny, out_source);
     }
-    median_scan(ctx, B, cells, L.nb);
+    cell_scan(ctx, B.count, cells, B.bsum, B.offset);
     if (blocks > 0) {
         if (nchan == 0 || img_dtype == 1)
             hipLaunchKernelGGL(k_med_fill_members<uint8_t>, dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, A, T, total,

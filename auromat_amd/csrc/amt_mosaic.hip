@@ -109,27 +109,16 @@ int amt_mosaic_run(amt_ctx* ctx, const amt_mosaic_member* members, int32_t n_mem
     if (tail != nullptr) *tail = ws + o_tail;
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + o_acc);
 
-    axis_dev ax, ay;
-    make_axis(xaxis, &ax);
-    make_axis(yaxis, &ay);
     bool vec = true;
     auto aligned16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3) == 0; };
     for (int32_t i = 0; i < n_members; ++i) {
         const amt_mosaic_member& m = members[i];
         mosaic_dev& d = dev[(size_t)i];
-        d.A.lat_c = m.lat_c;
-        d.A.lon_c = m.lon_c;
-        d.A.elev = m.elev;
+        bad = make_frame_src(&d.A.S, m.lat_c, m.lon_c, m.elev, m.center_mask, m.height, m.width, min_elevation, xaxis, yaxis,
+                             lon_wrap, 0);
+        AMT_REQUIRE(ctx, bad == nullptr, bad);          // (mosaic_members_bad has looked at every member)
         d.A.img = m.img;
-        d.A.mask = m.center_mask;
-        d.A.height = m.height;
-        d.A.width = m.width;
-        d.A.min_elev = min_elevation;
-        d.A.use_elev_threshold = (m.elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-        d.A.ax = ax;
-        d.A.ay = ay;
-        d.A.lon_wrap = lon_wrap ? 1 : 0;
         d.A.acc = acc + P.acc_off[(size_t)i];
         d.W = P.win[(size_t)i];
         // (as amt_bin_frame: even width, 16-byte aligned coordinates and a 4-byte aligned image, of every member with a window)

@@ -8,6 +8,8 @@
 // stops as soon as the best candidate is closer than anything an unvisited cell can hold.  HBM-bound: two passes
 // over the centre coordinates plus ~9 cells x (pixels per cell) gathered coordinate pairs per grid centre.
 #include "amt_common.h"
+#include "amt_cell_scan.h"
+#include "amt_frame_src.h"
 #include "amt_polygon.h"
 
 #include <cmath>
@@ -17,46 +19,21 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
-constexpr int kScanThreads = 1024;
-
-inline dim3 grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
-#define AMT_GRID_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
 struct nn_args {
-    const double* lat_c;
-    const double* lon_c;
-    const double* elev;
-    const uint8_t* mask;
-    int64_t n;
-    double min_elev;
-    int use_elev_threshold;
-    int lon_wrap;
-    axis_dev ax, ay;
+    frame_src S;
     int nx, ny;
 };
 
+// A source: a pixel the mean would bin were the grid large enough (src_pixel), with a finite longitude besides — the search
+// measures distances along both axes.
 __device__ __forceinline__ bool source_xy(const nn_args& A, int64_t i, double& x, double& y) {
-    y = A.lat_c[i];
-    x = A.lon_c[i];
-    if (!(y == y) || !(x == x)) return false;
-    if (A.mask && A.mask[i]) return false;
-    if (A.use_elev_threshold && !(A.elev[i] >= A.min_elev)) return false;
-    if (A.lon_wrap) x = wrap180_shifted(x);
-    return true;
+    return src_pixel(A.S, i, y, x) && finite(x);
 }
 
-// cell of a source pixel; pixels beyond the outermost edges go to the border cells (they can still be the
-// nearest neighbour of a border centre, and a border cell is never farther from any centre than their own)
+// cell of a source pixel: NOT the mean's rule (src_cell).  Pixels beyond the outermost edges go to the border cells (they can
+// still be the nearest neighbour of a border centre, and a border cell is never farther from any centre than their own)
 __device__ __forceinline__ int source_cell(const nn_args& A, double x, double y) {
-    int ix = bin_index<true>(A.ax, x) - 1, iy = bin_index<true>(A.ay, y) - 1;
+    int ix = bin_index<true>(A.S.ax, x) - 1, iy = bin_index<true>(A.S.ay, y) - 1;
     ix = ix < 0 ? 0 : (ix >= A.nx ? A.nx - 1 : ix);
     iy = iy < 0 ? 0 : (iy >= A.ny ? A.ny - 1 : iy);
     return iy * A.nx + ix;
@@ -64,65 +41,20 @@ __device__ __forceinline__ int source_cell(const nn_args& A, double x, double y)
 
 // Neighbouring pixels mostly fall into the same grid cell: lanes of a wave that hold a run of equal cells let the
 // first lane of the run issue ONE atomic for all of them (6-10 atomics per wave instead of 64).
-struct lane_run {
-    int head;       // lane that starts this lane's run
-    int length;     // pixels in the run (meaningful on the head lane)
-};
-
-__device__ __forceinline__ lane_run run_of(int c, int lane) {
-    const int prev = __shfl_up(c, 1);
-    const bool is_head = lane == 0 || prev != c;
-    const unsigned long long heads = __ballot(is_head);
-    const unsigned long long upto = heads & (~0ull >> (63 - lane));      // heads at or below this lane
-    lane_run r;
-    r.head = 63 - __clzll(upto);
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    r.length = above ? __ffsll((long long)above) : 64 - lane;
-    return r;
-}
-
 __global__ __launch_bounds__(kBlock) void k_nn_count(nn_args A, int* __restrict__ cell_of,
                                                     unsigned* __restrict__ count) {
     const int lane = threadIdx.x & 63;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = (int64_t)A.S.height * A.S.width;
     // whole waves stay in the loop together (the shuffles need every lane)
-    for (int64_t base = blockIdx.x * (int64_t)blockDim.x + (threadIdx.x & ~63); base < A.n; base += stride) {
+    for (int64_t base = blockIdx.x * (int64_t)blockDim.x + (threadIdx.x & ~63); base < n; base += stride) {
         const int64_t i = base + lane;
         double x, y;
         int c = -1;
-        if (i < A.n && source_xy(A, i, x, y)) c = source_cell(A, x, y);
-        if (i < A.n) cell_of[i] = c;
-        const lane_run r = run_of(c, lane);
-        if (r.head == lane && c >= 0) atomicAdd(&count[c], (unsigned)r.length);
+        if (i < n && source_xy(A, i, x, y)) c = source_cell(A, x, y);
+        if (i < n) cell_of[i] = c;
+        const lane_run r = run_of(c, c >= 0, lane);
+        if (r.head == lane && c >= 0) atomicAdd(&count[c], r.total);
     }
-}
-
-// exclusive prefix sum of count[0..n) into offset[0..n], one workgroup (n is the number of grid cells)
-__global__ __launch_bounds__(kScanThreads) void k_nn_scan(const unsigned* __restrict__ count, int64_t n,
-                                                         unsigned* __restrict__ offset) {
-    __shared__ unsigned sWave[kScanThreads / 64];
-    __shared__ unsigned sCarry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) sCarry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n; base += kScanThreads) {
-        const int64_t i = base + threadIdx.x;
-        const unsigned v = i < n ? count[i] : 0u;
-        unsigned incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) sWave[wave] = incl;
-        __syncthreads();
-        unsigned before = sCarry;
-        for (int w = 0; w < wave; ++w) before += sWave[w];
-        if (i < n) offset[i] = before + incl - v;
-        __syncthreads();
-        if (threadIdx.x == kScanThreads - 1) sCarry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) offset[n] = sCarry;
 }
 
 __global__ __launch_bounds__(kBlock) void k_nn_fill(const int* __restrict__ cell_of, int64_t n,
@@ -133,11 +65,11 @@ __global__ __launch_bounds__(kBlock) void k_nn_fill(const int* __restrict__ cell
     for (int64_t base = blockIdx.x * (int64_t)blockDim.x + (threadIdx.x & ~63); base < n; base += stride) {
         const int64_t i = base + lane;
         const int c = i < n ? cell_of[i] : -1;
-        const lane_run r = run_of(c, lane);
+        const lane_run r = run_of(c, c >= 0, lane);
         unsigned first = 0;
-        if (r.head == lane && c >= 0) first = offset[c] + atomicAdd(&cursor[c], (unsigned)r.length);
+        if (r.head == lane && c >= 0) first = offset[c] + atomicAdd(&cursor[c], r.total);
         first = __shfl(first, r.head);
-        if (c >= 0) order[first + (unsigned)(lane - r.head)] = (int)i;
+        if (c >= 0) order[first + r.excl] = (int)i;
     }
 }
 
@@ -172,8 +104,7 @@ __global__ __launch_bounds__(kBlock) void k_nn_search(nn_args A, const unsigned*
             const int c = iy * A.nx;
             for (unsigned k = offset[c + ix0] + lane, e = offset[c + ix1 + 1]; k < e; k += 64) {
                 const int i = order[k];
-                double y = A.lat_c[i], x = A.lon_c[i];
-                if (A.lon_wrap) x = wrap180_shifted(x);
+                const double y = A.S.lat_c[i], x = src_x(A.S, A.S.lon_c[i]);
                 const double dy = y - ty, dx = x - tx;
                 const double d = dy * dy + dx * dx;
                 if (d < best || (d == best && i < best_i)) {
@@ -670,27 +601,19 @@ int amt_nearest_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, co
                       const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, const double* target_lat,
                       const double* target_lon, const uint8_t* target_mask, int64_t* out_index) {
     AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, lat_c && lon_c && xaxis && yaxis && target_lat && target_lon && out_index, "NULL argument");
-    AMT_REQUIRE(ctx, height > 0 && width > 0, "empty frame");
+    AMT_REQUIRE(ctx, target_lat && target_lon && out_index, "NULL argument");
+    nn_args A;
+    const char* bad = make_frame_src(&A.S, lat_c, lon_c, elev, center_mask, height, width, min_elevation, xaxis, yaxis, lon_wrap, 0);
+    AMT_REQUIRE(ctx, bad == nullptr, bad);
     AMT_REQUIRE(ctx, (int64_t)height * width < 2147483647LL, "frame too large for 32-bit pixel indices");
     AMT_REQUIRE(ctx, uniform_axis_ok(xaxis) && uniform_axis_ok(yaxis), "axes must be uniform (amt_grid_layout)");
     AMT_REQUIRE(ctx, (int64_t)xaxis->nbin * yaxis->nbin < 2147483647LL, "grid too large");
-    nn_args A;
-    A.lat_c = lat_c;
-    A.lon_c = lon_c;
-    A.elev = elev;
-    A.mask = center_mask;
-    A.n = (int64_t)height * width;
-    A.min_elev = min_elevation;
-    A.use_elev_threshold = (elev != nullptr) && !(std::isinf(min_elevation) && min_elevation < 0);
-    A.lon_wrap = lon_wrap ? 1 : 0;
-    make_axis(xaxis, &A.ax);
-    make_axis(yaxis, &A.ay);
     A.nx = xaxis->nbin;
     A.ny = yaxis->nbin;
-    const int64_t cells = (int64_t)A.nx * A.ny;
-    // workspace: count[cells], cursor[cells], offset[cells + 1] (u32), cell_of[n], order[n] (i32)
-    const size_t bytes = (size_t)(3 * cells + 1) * sizeof(unsigned) + (size_t)2 * A.n * sizeof(int) + 64;
+    const int64_t n = (int64_t)height * width, cells = (int64_t)A.nx * A.ny;
+    // workspace: count[cells], cursor[cells], offset[cells + 1], the scan's block sums (u32), cell_of[n], order[n] (i32)
+    const size_t words = (size_t)(3 * cells + 1) + (size_t)cell_scan_blocks(cells) + 1;
+    const size_t bytes = words * sizeof(unsigned) + (size_t)2 * n * sizeof(int) + 64;
     char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
     if (ws == nullptr) {
         ctx->last_error = "amt_nearest_frame: workspace allocation failed";
@@ -699,15 +622,16 @@ int amt_nearest_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, co
     unsigned* count = reinterpret_cast<unsigned*>(ws);
     unsigned* cursor = count + cells;
     unsigned* offset = cursor + cells;
-    int* cell_of = reinterpret_cast<int*>(offset + cells + 1);
-    int* order = cell_of + A.n;
+    unsigned* bsum = offset + cells + 1;
+    int* cell_of = reinterpret_cast<int*>(count + words);
+    int* order = cell_of + n;
     if (hipMemsetAsync(count, 0, (size_t)2 * cells * sizeof(unsigned), ctx->stream) != hipSuccess) {
         ctx->last_error = "amt_nearest_frame: memset failed";
         return AMT_EHIP;
     }
-    hipLaunchKernelGGL(k_nn_count, grid_for(A.n), dim3(kBlock), 0, ctx->stream, A, cell_of, count);
-    hipLaunchKernelGGL(k_nn_scan, dim3(1), dim3(kScanThreads), 0, ctx->stream, count, cells, offset);
-    hipLaunchKernelGGL(k_nn_fill, grid_for(A.n), dim3(kBlock), 0, ctx->stream, cell_of, A.n, offset, cursor, order);
+    hipLaunchKernelGGL(k_nn_count, grid_for(n), dim3(kBlock), 0, ctx->stream, A, cell_of, count);
+    cell_scan(ctx, count, cells, bsum, offset);
+    hipLaunchKernelGGL(k_nn_fill, grid_for(n), dim3(kBlock), 0, ctx->stream, cell_of, n, offset, cursor, order);
     // cell sizes as the centres see them, with a margin for the rounding of edges and centres
     const double safe_step = std::fmin(xaxis->step, yaxis->step) * (1.0 - 1e-9);
     hipLaunchKernelGGL(k_nn_search, grid_for(cells * 64), dim3(kBlock), 0, ctx->stream, A, offset, order, target_lat,

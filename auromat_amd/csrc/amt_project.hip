@@ -18,24 +18,10 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
-
-inline dim3 grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    return dim3(static_cast<unsigned>(blocks));
-}
-
-#define AMT_GRID_STRIDE(i, n) \
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
-
 struct proj_dev {
     double lon0, e, sin_chi1, cos_chi1, k;
     int north;
 };
-
-__device__ __forceinline__ bool finite(double v) { return fabs(v) < INFINITY; }     // false for NaN
 
 // a longitude into [-180, 180) (the two corrections: l + 180 may round up to a multiple of 360 from just below it)
 __device__ __forceinline__ double wrap_lon(double l) {

@@ -23,8 +23,7 @@ namespace {
 
 using namespace amt;
 
-constexpr int kBlock = 256;
-constexpr int kSide = 16;              // corners per tile side: kSide * kSide == kBlock, one corner per thread
+constexpr int kSide = 16;             // corners per tile side: kSide * kSide == kBlock, one corner per thread
 constexpr int kTile = kSide - 1;       // cells per tile side
 constexpr long long kNoMin = 0x7fffffffffffffffLL, kNoMax = -kNoMin - 1;
 

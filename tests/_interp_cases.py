@@ -762,12 +762,21 @@ def nearest_lon_wrap():
     return case
 
 
+K_SCAN_TILE = 2048      # kScanTile = kBlock * kScanItems of amt_cell_scan.h: cells per workgroup of the scan
 SCAN_GRIDS = ((5, 7), (32, 32), (25, 41), (60, 97))
+SCAN_TILE_GRIDS = ((32, 64), (3, 683), (33, 62))       # one tile of the scan, a tile and a cell, a tile less two cells
+
+
+def scan_chunk(ny, nx):
+    """The chunk of cells whose last one most sources of a scan case go to: the scan's tile for the grids at its boundaries,
+    half a tile (1024 cells) for SCAN_GRIDS"""
+    return K_SCAN_TILE if (ny, nx) in SCAN_TILE_GRIDS else 1024
 
 
 def nearest_scan(ny, nx):
-    """Grids of fewer than 64 cells, exactly 1024, 1025 and several thousand (no multiple of 1024); most sources sit in the
-    last chunk of the scan (the top rows of the histogram)."""
+    """Grids of fewer than 64 cells, exactly 1024, 1025 and several thousand (no multiple of 1024), and of one tile of the scan
+    (2048 cells), one cell more and two fewer; most sources sit in the last chunk of the scan (the top rows of the histogram;
+    (60, 97) = 5820 cells spans three tiles)."""
     args = box((8, 8), ny, nx)
     g = grid_of(*args)
     assert (g.ny, g.nx) == (ny, nx)
@@ -775,7 +784,8 @@ def nearest_scan(ny, nx):
     shape = (10, 13)
     n = shape[0] * shape[1]
     _, _, ey, ex = grid_units(g)
-    flat = rng.randint(1024 * ((ny * nx - 1) // 1024), ny * nx, n)               # cells of the last chunk
+    chunk = scan_chunk(ny, nx)
+    flat = rng.randint(chunk * ((ny * nx - 1) // chunk), ny * nx, n)             # cells of the last chunk
     lat = (ey[flat // nx] + rng.randint(0, 8, n)) / float(U)
     lon = (ex[flat % nx] + rng.randint(0, 8, n)) / float(U)
     la2, lo2 = _scatter(g, n, rng)
@@ -783,8 +793,8 @@ def nearest_scan(ny, nx):
     lat[few], lon[few] = la2[few], lo2[few]
     case = NearestCase('scan-%dx%d' % (ny, nx), args, lat.reshape(shape), lon.reshape(shape))
     cells = case.flat_cells()
-    last_chunk = (ny * nx - 1) // 1024
-    assert (cells // 1024 == last_chunk).mean() > 0.5
+    last_chunk = (ny * nx - 1) // chunk
+    assert (cells // chunk == last_chunk).mean() > 0.5
     return case
 
 
@@ -792,7 +802,7 @@ def all_nearest_cases():
     cases = [nearest_runs(), nearest_runs(small=True), nearest_crowded()]
     cases += [nearest_ring(ppd, r, axis) for ppd in RING_GRIDS for r in RINGS for axis in 'xy']
     cases += nearest_ties() + nearest_far() + nearest_validity() + [nearest_lon_wrap()]
-    cases += [nearest_scan(*s) for s in SCAN_GRIDS]
+    cases += [nearest_scan(*s) for s in SCAN_GRIDS + SCAN_TILE_GRIDS]
     assert len({c.name for c in cases}) == len(cases)
     for c in cases:
         assert c.height <= 70 and c.width <= 70 and c.grid.nx * c.grid.ny <= 6000, c.name

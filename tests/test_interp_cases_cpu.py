@@ -14,14 +14,19 @@ import pytest
 import _interp_cases as K
 import _interp_oracle as O
 
-SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'auromat_amd', 'csrc', 'amt_nearest.hip')
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'auromat_amd', 'csrc')
+SOURCE = os.path.join(CSRC, 'amt_nearest.hip')
 
 
 def test_constants_are_the_sources():
     text = open(SOURCE).read()
-    for name, value in (('kGsPre', K.K_GS_PRE), ('kGsChan', K.K_GS_CHAN), ('kBlock', K.K_BLOCK), ('kScanThreads', 1024)):
-        m = re.search(r'constexpr int %s = (\d+);' % name, text)
+    common, scan = open(os.path.join(CSRC, 'amt_common.h')).read(), open(os.path.join(CSRC, 'amt_cell_scan.h')).read()
+    for name, value, where in (('kGsPre', K.K_GS_PRE, text), ('kGsChan', K.K_GS_CHAN, text), ('kBlock', K.K_BLOCK, common),
+                               ('kScanItems', K.K_SCAN_TILE // K.K_BLOCK, scan)):
+        m = re.search(r'constexpr int %s = (\d+);' % name, where)
         assert m and int(m.group(1)) == value, name
+    # the scan of the cell counts: the shared one, over tiles of kBlock * kScanItems cells
+    assert 'constexpr int kScanTile = kBlock * kScanItems;' in scan and 'cell_scan(ctx, count, cells, bsum, offset);' in text
     assert 'k += 64' in text and 'nchan <= 63' in text
 
 
@@ -277,7 +282,14 @@ def test_nearest_cases_hold_their_patterns():
     assert (x - ex[-1]).max() > 30 * 8 and (ey[0] - y).max() > 30 * 8
     assert not cases['no-valid-source'].valid.any()
     sizes = sorted(c.grid.nx * c.grid.ny for c in cases.values() if c.name.startswith('scan-'))
-    assert sizes[0] < 64 and sizes[1] == 1024 and sizes[2] == 1025 and sizes[3] > 3000 and sizes[3] % 1024 != 0
+    assert sizes[0] < 64 and sizes[1] == 1024 and sizes[2] == 1025 and sizes[6] > 3000 and sizes[6] % 1024 != 0
+    # the boundaries of the scan's tile: a tile less two cells, exactly one tile, a tile and a cell; and more than two tiles
+    assert sizes[3:6] == [K.K_SCAN_TILE - 2, K.K_SCAN_TILE, K.K_SCAN_TILE + 1] and sizes[6] > 2 * K.K_SCAN_TILE and len(sizes) == 7
+    for ny, nx in K.SCAN_TILE_GRIDS:
+        c = cases['scan-%dx%d' % (ny, nx)]
+        assert K.scan_chunk(ny, nx) == K.K_SCAN_TILE and (c.height, c.width) == (10, 13)
+        assert (c.expected() >= 0).all()                                             # every grid centre gets a nearest source
+    assert all(K.scan_chunk(*s) == 1024 for s in K.SCAN_GRIDS)
     wrap = cases['lon-wrap']
     assert wrap.lon_wrap == 1 and (wrap.lon == 180).any() and (wrap.lon == -180).any()
     assert cases['minus-inf'].min_elevation == -np.inf and cases['minus-inf'].elev is not None

@@ -94,11 +94,14 @@ import _median_cases as K
 def test_case_constants_are_the_sources():
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'auromat_amd', 'csrc', 'amt_median.hip')).read()
-    for name, value in (('kSmallMax', K.K_SMALL_MAX), ('kLargeMin', K.K_LARGE_MIN), ('kChunk', K.K_CHUNK),
-                        ('kBlock', K.K_BLOCK)):
-        found = re.findall(r'constexpr int %s = (\d+);' % name, src)
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'auromat_amd', 'csrc')
+    src = open(os.path.join(csrc, 'amt_median.hip')).read()
+    common = open(os.path.join(csrc, 'amt_common.h')).read()      # kBlock: the one block size of the element-wise kernels
+    for name, value, where in (('kSmallMax', K.K_SMALL_MAX, src), ('kLargeMin', K.K_LARGE_MIN, src), ('kChunk', K.K_CHUNK, src),
+                               ('kBlock', K.K_BLOCK, common)):
+        found = re.findall(r'constexpr int %s = (\d+);' % name, where)
         assert found == [str(value)], (name, found)
+    assert 'constexpr int kBlock' not in src
     assert K.COUNTS == (0, 1, 2, 3, 63, 64, 65, 66, 255, 256, 257, 4095, 4096, 4097, 16383, 16384, 16385, 16386, 20480, 20481,
                         65537)
     assert K.BIG == 300001

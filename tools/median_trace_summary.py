@@ -9,7 +9,7 @@ db = sqlite3.connect(sys.argv[1])
 rows = db.execute("select name, duration, scratch_size from kernels order by start").fetchall()
 calls, cur = [], None
 for name, dur, scratch in rows:
-    m = re.search(r'(k_med_[a-z_]+)', name)
+    m = re.search(r'(k_med_[a-z_]+|k_cell_scan_[a-z]+)', name)
     if not m:
         continue
     k = m.group(1)

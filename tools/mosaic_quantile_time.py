@@ -32,8 +32,8 @@ ap.add_argument('--summarise', nargs=2)
 a = ap.parse_args()
 Q3 = (0.25, 0.5, 0.75)
 STATS = (('median', None), ('quantile', Q3))
-FRONT = ('k_bin_frame', 'k_mosaic_select', 'k_med_count_members', 'k_med_source', 'k_med_scan_sums', 'k_med_scan_blocks',
-         'k_med_scan_apply', 'k_med_fill_members', 'k_med_small')
+FRONT = ('k_bin_frame', 'k_mosaic_select', 'k_med_count_members', 'k_med_source', 'k_cell_scan_sums', 'k_cell_scan_blocks',
+         'k_cell_scan_apply', 'k_med_fill_members', 'k_med_small')
 
 
 def summarise(trace_dir, labels_file):
@@ -44,7 +44,7 @@ def summarise(trace_dir, labels_file):
     with open(paths[0]) as fp:
         for r in csv.DictReader(fp):
             r = {k.lower(): v for k, v in r.items()}
-            m = re.search(r'(k_med_[a-z_]+|k_mosaic_select|k_bin_frame)', r['kernel_name'])
+            m = re.search(r'(k_med_[a-z_]+|k_cell_scan_[a-z]+|k_mosaic_select|k_bin_frame)', r['kernel_name'])
             if m:
                 rows.append((int(r['start_timestamp']), int(r['end_timestamp']), m.group(1),
                              int(r.get('scratch_size', r.get('private_segment_size', 0)) or 0)))

@@ -24,12 +24,12 @@ with open(paths[0]) as fp:
 rows.sort()
 calls = []
 for start, end, name, scratch in rows:
-    m = re.search(r'(k_med_[a-z_]+)', name)
+    m = re.search(r'(k_med_[a-z_]+|k_cell_scan_[a-z]+)', name)
     if not m:
         continue
     if m.group(1) == 'k_med_count':
         calls.append([0.0, 0.0])
-    front = m.group(1) in ('k_med_count', 'k_med_scan_sums', 'k_med_scan_blocks', 'k_med_scan_apply', 'k_med_fill')
+    front = m.group(1) in ('k_med_count', 'k_cell_scan_sums', 'k_cell_scan_blocks', 'k_cell_scan_apply', 'k_med_fill')
     calls[-1][0 if front else 1] += (end - start) / 1e3
 labels = meta['labels']
 assert len(calls) == len(labels), (len(calls), len(labels))
