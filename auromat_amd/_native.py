@@ -186,6 +186,9 @@ _SIGNATURES = {
     'amt_lens_undistort': ([_P, C.POINTER(LensModel)] + [C.c_int32] * 4 + [_I, _P], _I),
     'amt_lens_remap': ([_P, C.POINTER(LensModel), _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(LensDebug)], _I),
     'amt_remap_coords': ([_P, _P] + [C.c_int32] * 4 + [_P] + [C.c_int32] * 3 + [_P, _P, C.POINTER(LensDebug)], _I),
+    'amt_world_to_pixel': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, _P, _L, _P, _P, _P], _I),
+    'amt_grid_to_pixel': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P,
+                           _P], _I),
     'amt_intersect_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersects_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersect_sphere': ([_P, _D, c_double_p, _P, _L, _I, _P], _I),

@@ -259,3 +259,34 @@ def tan_pix2world(header, px, py, origin, ascartesian=False):
     ra, dec = _to_radec(st, out, shape)
     st.on_device = keep
     return st.result(ra), st.result(dec)
+
+
+def world2pix(header, ra, dec, origin=0, device=None):
+    """
+    Pixel coordinates of sky positions: what the reference asks ``astropy.wcs.WCS(header).wcs_world2pix`` /
+    ``all_world2pix`` for (fits.py:193-216, 288-296, draw.py:1379: catalogue stars, constellation lines), for every header
+    :func:`zenithal_params` accepts — TAN, SIN, ARC, STG, ZEA, with SIP terms or without, plain TAN included
+    (``amt_world_to_pixel``).  SIP is inverted by Newton's method on the forward polynomial; AP / BP cards are not read.
+
+    :param ra, dec: degrees, arrays (or device tensors) of one shape
+    :param origin: 0 or 1, the coordinate of the first pixel's centre, as in astropy
+    :rtype: tuple (x, y), NaN where the position is outside the projection's domain or the SIP inverse does not converge
+    """
+    assert origin in [0, 1]
+    from .inverse import W2P_J2000, sky_params, world_to_pixel
+    zen = zenithal_params(header, header.get('IMAGEW', 1), header.get('IMAGEH', 1), corner=False)
+    if device is not None:
+        from .._native import Context
+        ra, dec = Context.current(device).to_device(ra), Context.current(device).to_device(dec)
+    xy, _, _ = world_to_pixel(sky_params(zen.width, zen.height), zen, W2P_J2000, dec, ra, elevation=False)
+    return xy[..., 0] + origin, xy[..., 1] + origin
+
+
+def tan_world2pix(header, ra, dec, origin):
+    """The counterpart of :func:`tan_pix2world` (TAN headers with LATPOLE = 0 only): ``(x, y)`` of ``(ra, dec)`` in degrees,
+    NaN for positions 90 degrees or more from the reference point."""
+    assert origin in [0, 1]
+    from .inverse import W2P_J2000, sky_params, world_to_pixel
+    p = fill_wcs_params(sky_params(), dict(header, IMAGEW=header.get('IMAGEW', 1), IMAGEH=header.get('IMAGEH', 1)))
+    xy, _, _ = world_to_pixel(p, None, W2P_J2000, dec, ra, elevation=False)
+    return xy[..., 0] + origin, xy[..., 1] + origin

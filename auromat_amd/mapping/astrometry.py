@@ -148,6 +148,10 @@ class BaseAstrometryMapping(BaseMapping):
         return frame_params(self._wcsHeader, self.altitude, self.cameraPosGCRS, self.photoTime,
                             self.fastCenterCalculation)
 
+    def _inverse_model(self, altitude=None):
+        alt = self.altitude if altitude is None else float(altitude)
+        return frame_params(self._wcsHeader, alt, self.cameraPosGCRS, self.photoTime, self.fastCenterCalculation), None
+
     def frame(self):
         if self._frame is None:
             ctx = Context.current()
@@ -312,9 +316,12 @@ class DirectionArrayMapping(BaseAstrometryMapping):
     what miracle.py:139-160 does).
     """
 
-    def __init__(self, cornerDirections, alti, img, cameraPosGCRS, photoTime, identifier, metadata=None):
+    def __init__(self, cornerDirections, alti, img, cameraPosGCRS, photoTime, identifier, metadata=None, cameraHeader=None,
+                 noInverse=None):
         """`cornerDirections`: (h + 1, w + 1, 3) array, or a float64 device tensor of that shape (e.g. from
-        ``coordinates.wcs.zenithal_directions_device``), which is used where it lies."""
+        ``coordinates.wcs.zenithal_directions_device``), which is used where it lies.  `cameraHeader`: the zenithal (+ SIP)
+        WCS header the directions were made from, if any; it is what ``latLonToPixel`` & co. invert.  `noInverse`: why they
+        cannot (a sentence), for directions that went through something else as well."""
         img = np.asarray(img)
         on_device = hasattr(cornerDirections, 'is_cuda') and cornerDirections.is_cuda
         d = cornerDirections.contiguous() if on_device else np.ascontiguousarray(cornerDirections, dtype=np.float64)
@@ -326,6 +333,18 @@ class DirectionArrayMapping(BaseAstrometryMapping):
         self._dirs = None if on_device else d
         self._dirs_dev = d if on_device else None
         self._img_array = img
+        self._cameraHeader = cameraHeader
+        self._noInverse = noInverse
+
+    def _inverse_model(self, altitude=None):
+        if self._cameraHeader is None:
+            raise NotImplementedError(self._noInverse or 'this mapping was built from a bare array of line-of-sight directions: '
+                                      'there is no camera model in closed form to invert')
+        from ..coordinates.wcs import zenithal_params
+        p = self._params()
+        if altitude is not None:
+            p.a, p.b = wgs84A + float(altitude), wgs84B + float(altitude)
+        return p, zenithal_params(self._cameraHeader, p.width, p.height, corner=False)
 
     def _params(self):
         p = FrameParams()

@@ -504,6 +504,45 @@ class BaseMapping(object):
         lat, lon = polygonCentroid(outline)
         return Location(lat, lon)
 
+    # -- world -> pixel ----------------------------------------------------------------------------
+    def _inverse_model(self, altitude=None):
+        """``(amt_frame_params, amt_zenithal_wcs or None)`` for ``amt_world_to_pixel``.  Only mappings that know their camera
+        model in closed form have one (:class:`auromat_amd.mapping.astrometry.BaseAstrometryMapping`)."""
+        raise NotImplementedError('%s has no closed-form camera model to invert: its pixels come from per-pixel tables '
+                                  '(all-sky calibration arrays, gridded files), not from a WCS header' % type(self).__name__)
+
+    def _to_pixel(self, frame, c0, c1, altitude, returnFlags):
+        from ..coordinates.inverse import NOT_SEEN, world_to_pixel
+        params, zen = self._inverse_model(altitude)
+        xy, _, flags = world_to_pixel(params, zen, frame, np.asarray(c0, dtype=np.float64), np.asarray(c1, dtype=np.float64),
+                                      elevation=False)
+        mask = (flags & NOT_SEEN) != 0
+        x, y = ma.masked_array(xy[..., 0], mask=mask), ma.masked_array(xy[..., 1], mask=mask)
+        return (x, y, flags) if returnFlags else (x, y)
+
+    def latLonToPixel(self, lat, lon, altitude=None, returnFlags=False):
+        """
+        Where in this frame is the point of geodetic latitude / longitude (degrees, arrays of one shape) at `altitude` km
+        (None: the mapping's own; 0 for cities and coastlines)?  ``(x, y)`` masked arrays of 0-based pixel coordinates, a pixel's
+        centre at (column, row); masked where the point does not exist, is hidden behind the shell's limb, lies outside the
+        projection's domain or the SIP inverse did not converge.  Points outside the frame keep their coordinates (a drawn
+        line needs its off-frame end).  ``returnFlags``: also the flag array (``auromat_amd.coordinates.inverse``).
+        """
+        from ..coordinates.inverse import W2P_GEODETIC
+        return self._to_pixel(W2P_GEODETIC, lat, lon, altitude, returnFlags)
+
+    def mLatMltToPixel(self, mlat, mlt, altitude=None, returnFlags=False):
+        """:meth:`latLonToPixel` for geomagnetic latitude (degrees) and magnetic local time (hours)."""
+        from ..coordinates.inverse import W2P_SM
+        from ..coordinates.transform import mltToSmLon
+        return self._to_pixel(W2P_SM, mlat, mltToSmLon(np.asarray(mlt, dtype=np.float64)), altitude, returnFlags)
+
+    def raDecToPixel(self, ra, dec, returnFlags=False):
+        """:meth:`latLonToPixel` for a direction, right ascension / declination in degrees (stars): masked as well where the
+        direction's ray hits the mapping shell, so that stars are seen exactly in sky pixels."""
+        from ..coordinates.inverse import W2P_J2000
+        return self._to_pixel(W2P_J2000, dec, ra, None, returnFlags)
+
     # -- masking -----------------------------------------------------------------------------------
     def maskedByElevation(self, minElevation=10):
         """

@@ -185,7 +185,10 @@ def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, 
             from .astrometry import DirectionArrayMapping
             xy = mod.undistorted_coordinates_device(corner=True)
             dirs = tan_pix2world(wcsHeader, xy[..., 0].contiguous(), xy[..., 1].contiguous(), 0, ascartesian=True)
-            m = DirectionArrayMapping(dirs, altitude, np.asarray(imageArray), cam, photoTime, identifier, metadata)
+            m = DirectionArrayMapping(dirs, altitude, np.asarray(imageArray), cam, photoTime, identifier, metadata,
+                                      noInverse='this mapping is a raw frame with its lens distortion: world -> pixel would need '
+                                                "the lens model applied after the camera model, which is not built "
+                                                "(lensRoute='resample' gives an invertible mapping)")
             m.originalPhotoTime = originalPhotoTime
             return m
         imageArray = mod.remap(np.asarray(imageArray), 'lanczos4')
@@ -197,7 +200,7 @@ def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, 
         from .astrometry import DirectionArrayMapping
         img = np.asarray(imageArray)
         dirs = zenithal_directions_device(wcsHeader, img.shape[1], img.shape[0], corner=True)
-        m = DirectionArrayMapping(dirs, altitude, img, cam, photoTime, identifier, metadata)
+        m = DirectionArrayMapping(dirs, altitude, img, cam, photoTime, identifier, metadata, cameraHeader=wcsHeader)
         m.originalPhotoTime = originalPhotoTime
         return m
     return ArraySpacecraftMapping(wcsHeader, altitude, imageArray, cam, photoTime, identifier, metadata,

@@ -2066,3 +2066,172 @@ def ResampleProvider(provider, **kw):
     wrapped = copy.copy(provider)
     wrapped.__class__ = ResamplingProvider
     return wrapped
+
+
+# ---- gather resampling: every grid cell centre projected into the image ---------------------------------------------------------
+GATHER_INTERPOLATIONS = ('nearest', 'linear', 'lanczos4')
+_GATHER_PIPES = {}
+
+
+def _check_gather_interpolation(interpolation):
+    if interpolation not in GATHER_INTERPOLATIONS:
+        raise ValueError('interpolation must be one of %s, not %r' % (', '.join(GATHER_INTERPOLATIONS), interpolation))
+
+
+def _gather_box(ctx, params, min_elevation, magnetic):
+    """The 8-number bounding-box reduction of a camera frame whose arrays do not exist (the box pass of the frame kernel:
+    no per-pixel array is written), in (lat, lon) or (MLat, SM longitude); [7]: a pole of those coordinates is in view."""
+    from .pipeline import FramePipeline
+    key = (str(ctx.device), params.width, params.height)
+    pipe = _GATHER_PIPES.get(key)
+    if pipe is None:
+        if len(_GATHER_PIPES) >= 4:
+            _GATHER_PIPES.clear()
+        pipe = _GATHER_PIPES[key] = FramePipeline(params.width, params.height, alloc_image=False, alloc_coords=False)
+    return pipe.box_first(params, min_elevation, magnetic)
+
+
+def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magnetic=False):
+    """
+    What :func:`resampleGather` samples where: dict(grid, contains_pole, contains_discontinuity, altitude, params, zenithal,
+    min_elevation, center_mask).  The grid is the one :func:`resample` chooses for the same arguments (same bounding box,
+    :func:`fixedGrid`, longitude frame).  A camera mapping whose arrays nobody has asked for yet gets its box from the box pass
+    of the frame kernel and keeps a remembered ``maskedByElevation`` as a threshold (`min_elevation`); any other mapping is
+    asked for its bounding box, and its centre mask (a device tensor) goes into the plan.
+    """
+    if not isinstance(mapping, BaseMapping):
+        raise NotImplementedError('resampleGather takes one mapping; gather mosaics of collections or lists are not built '
+                                  '(resampleMosaic bins a collection onto one grid)')
+    params, zen = mapping._inverse_model()
+    ctx = Context.current()
+    plan = dict(altitude=mapping.altitude, params=params, zenithal=zen, min_elevation=None, center_mask=None)
+    if zen is None and getattr(mapping, '_frame', True) is None:
+        from .mapping.mapping import bounding_box_from_reduction
+        lazy = getattr(mapping, '_lazy_elev', None)
+        red = _gather_box(ctx, params, lazy, magnetic)
+        pole = bool(red[7]) if containsPole is None else bool(containsPole)
+        if not pole:
+            bb = bounding_box_from_reduction(red)
+            ppd = plateCarreeResolution(bb, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+            lonMin, lonMax = bb.lonWest, bb.lonEast
+            if bb.containsDiscontinuity:
+                lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
+            plan.update(grid=cached_grid(ppd, bb.latSouth, bb.latNorth, lonMin, lonMax), contains_pole=False,
+                        contains_discontinuity=bool(bb.containsDiscontinuity), min_elevation=lazy)
+            return plan
+    # arrays exist (or a pole is in view, whose rotated grid is laid out from them): the two-pass plan's grid
+    src = convertMappingToSM(mapping) if magnetic else mapping
+    pole, ppd = _pole_and_resolution(src, pxPerDeg, arcsecPerPx, containsPole)
+    fd = src.frame()
+    grid, _, _, _ = _frame_grid(fd, src.altitude, src.boundingBox, ppd, src.containsDiscontinuity, pole, None,
+                                src.outline if pole else None, None)
+    plan.update(grid=grid, contains_pole=bool(pole), contains_discontinuity=bool(src.containsDiscontinuity) and not pole,
+                center_mask=fd.center_mask_tensor())
+    return plan
+
+
+def gather_frame(plan, image, interpolation='linear', magnetic=False):
+    """
+    The device side of :func:`resampleGather` on a :func:`gather_plan`: cell centres through ``amt_grid_to_pixel`` (with a pole
+    in view the centres of the rotated grid are rotated back and go through ``amt_world_to_pixel``), the image through
+    ``amt_remap_coords`` or, for 'nearest', a gather of pixel (rint x, rint y).  Returns a :func:`resample_frame`-like dict:
+    lat, lon, lat_c, lon_c, img, mask, elevation (exact line-of-sight elevation of every cell centre), flags, support.
+    """
+    import torch
+    from .coordinates.inverse import W2P_GEODETIC, W2P_SM, grid_to_pixel, world_to_pixel
+    from .util.lensdistortion import INTERPOLATIONS, _image_to_device
+    _check_gather_interpolation(interpolation)
+    ctx = Context.current()
+    grid, params, zen = plan['grid'], plan['params'], plan['zenithal']
+    frame = W2P_SM if magnetic else W2P_GEODETIC
+    coords = grid_coordinates(plan)
+    need64 = interpolation == 'nearest' or plan['center_mask'] is not None
+    if plan['contains_pole']:
+        xy, elev, flags = world_to_pixel(params, zen, frame, ctx.to_device(np.ascontiguousarray(coords['lat_c'])),
+                                         ctx.to_device(np.ascontiguousarray(coords['lon_c'])))
+        xy32 = xy.to(torch.float32)
+    else:
+        xy32, xy, elev, flags = grid_to_pixel(ctx, params, zen, frame, ctx.to_device(np.ascontiguousarray(coords['lat_c'][:, 0])),
+                                              ctx.to_device(np.ascontiguousarray(coords['lon_c'][0, :])), xy64=need64)
+    src, np_dtype, _ = _image_to_device(ctx, image)
+    h, w, nch = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    if (w, h) != (params.width, params.height):
+        raise ValueError('the image is %d x %d, the camera model is for %d x %d' % (w, h, params.width, params.height))
+    mask = flags != 0
+    support = None
+    if need64:
+        # the nearest pixel (half to even, like rint), kept inside the frame for the cells that are masked anyway
+        near = torch.nan_to_num(torch.round(xy), nan=0.0, posinf=0.0, neginf=0.0)
+        ix = near[..., 0].clamp_(0, w - 1).to(torch.int64)
+        iy = near[..., 1].clamp_(0, h - 1).to(torch.int64)
+        if plan['center_mask'] is not None:
+            mask |= plan['center_mask'].reshape(h, w)[iy, ix] != 0
+    if interpolation == 'nearest':
+        dst = src[iy, ix]
+    else:
+        dst = torch.empty((grid.ny, grid.nx, nch), dtype=src.dtype, device=src.device)
+        support = torch.empty((grid.ny, grid.nx), dtype=torch.uint8, device=src.device)
+        ctx.call('amt_remap_coords', ptr(src), w, h, src.element_size(), nch, ptr(xy32), grid.nx, grid.ny,
+                 INTERPOLATIONS[interpolation], ptr(dst), ptr(support), None)
+        mask |= support == 0
+    if plan['min_elevation'] is not None:
+        mask |= ~(elev >= float(plan['min_elevation']))
+    out = dict(coords, grid=grid, img=to_host(dst.contiguous(), dtype=np_dtype), mask=to_host(mask.to(torch.uint8)).astype(bool),
+               elevation=to_host(elev), flags=to_host(flags), support=None if support is None else to_host(support),
+               contains_pole=plan['contains_pole'], contains_discontinuity=plan['contains_discontinuity'])
+    return out
+
+
+def _gather_image(mapping):
+    img = getattr(mapping, '_img_array', None)
+    return mapping.img_unmasked if img is None else img
+
+
+def _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic):
+    _check_gather_interpolation(interpolation)
+    plan = gather_plan(mapping, pxPerDeg, arcsecPerPx, containsPole, magnetic)
+    res = gather_frame(plan, _gather_image(mapping), interpolation, magnetic)
+    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
+    elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
+    if not magnetic:
+        return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
+    from .coordinates.transform import smToLatLon
+    from .mapping.mapping import GenericMapping
+    nc = res['lat'].size
+    la, lo = smToLatLon(np.concatenate((res['lat'].ravel(), res['lat_c'].ravel())),
+                        np.concatenate((res['lon'].ravel(), res['lon_c'].ravel())), mapping.photoTime)
+    return GenericMapping(la[:nc].reshape(res['lat'].shape), lo[:nc].reshape(res['lon'].shape),
+                          la[nc:].reshape(res['lat_c'].shape), lo[nc:].reshape(res['lon_c'].shape), elevation,
+                          mapping.altitude, img, mapping.cameraPosGCRS, mapping.photoTime, mapping.identifier)
+
+
+def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear'):
+    """
+    Resampling by gathering: every cell centre of the grid that :func:`resample` would choose for the same arguments is
+    projected into the image through the inverse of the camera model (``amt_grid_to_pixel``) and the image is sampled there
+    (``amt_remap_coords``: 'linear' or 'lanczos4'; 'nearest': the pixel at (rint x, rint y)).  The result has no holes at any
+    resolution, also finer than the pixel footprint, where binning pixel centres leaves cells empty, and it needs no
+    triangulation: unlike ``resample(method='linear')`` (scipy's griddata) it interpolates in the pixel plane, not in the
+    lat / lon plane.  For cells much coarser than a pixel it samples one point per cell without averaging (aliasing); mean and
+    area binning serve that case.
+
+    A cell is masked where its centre is not seen in the frame (any flag of ``amt_world_to_pixel``: invalid, hidden, outside
+    the projection's domain or the frame), where the sampled point has no support (it lies outside [0, width - 1] x
+    [0, height - 1]; not for 'nearest'), where the mapping's centre mask is set at the nearest pixel, and where the elevation of
+    the cell's line of sight is below the mapping's elevation threshold — a ``maskedByElevation`` that a camera mapping only
+    remembers is applied as that threshold, without computing the frame's arrays.  ``.elevation`` of the result is the exact
+    line-of-sight elevation of each cell centre.
+
+    For mappings with a zenithal (+ SIP) WCS camera model; ``NotImplementedError`` for collections and lists, for mappings
+    made from a bare direction array or a raw frame with a lens, and for MIRACLE / THEMIS.
+
+    :param interpolation: 'nearest', 'linear' or 'lanczos4'
+    :rtype: GenericMapping (what ``mapping.createResampled`` returns)
+    """
+    return _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation, False)
+
+
+def resampleGatherMLatMLT(mapping, **kw):
+    """:func:`resampleGather` on the (MLat, SM longitude) grid of :func:`resampleMLatMLT`; see there for the parameters."""
+    return _resample_gather(mapping, kw.pop('pxPerDeg', 25), kw.pop('arcsecPerPx', None), kw.pop('containsPole', None),
+                            kw.pop('interpolation', 'linear'), True, **kw)

@@ -332,6 +332,73 @@ int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t s
                      const float* coords, int32_t dst_width, int32_t dst_height, int32_t interpolation, void* dst, uint8_t* support,
                      const amt_lens_debug* debug);
 
+/* ---- inverse georeferencing: world -> pixel (additions to ABI 10) -------------------------------------------------------------
+ * The way back from a place to the pixel that sees it: what the reference asks astropy's wcs_world2pix for (fits.py:193-216,
+ * draw.py:1379: catalogue stars, constellation lines) and approximates with a resampled look-up table for parallels and
+ * meridians (draw.py:1482-1609).  For every camera model of this library the inverse exists in closed form; this is its
+ * statement (tests/_inverse_oracle.py holds it in mpmath and NumPy).
+ * Inputs: a frame's amt_frame_params (cam, shell a, b, WGS84 a0, b0, m_geo, m_sm, width, height, and cd, crpix, rot of a plain
+ * TAN header) and, for other zenithal headers, an amt_zenithal_wcs whose cd, crpix, rot, start_x, start_y, projection and SIP
+ * terms then take the place of the camera-model cards of the params (its width, height and corner are not read).  A point is
+ * (c0, c1) = (latitude-like, longitude-like) degrees in one of three frames:
+ *   AMT_W2P_GEODETIC  WGS84 geodetic latitude and longitude of a point ON THE SHELL: with N = a0 / sqrt(1 - e^2 sin^2 lat),
+ *                     G(h) = ((N+h) cos lat cos lon, (N+h) cos lat sin lon, (N (1-e^2) + h) sin lat) in GEO, P(h) = m_geo^T G(h)
+ *                     in J2000, and h the larger root of the quadratic that puts P(h) on the shell (a, b) - the ellipsoid
+ *                     whose axes are J2000's, as the forward intersects it (amt_intersect_ellipsoid on J2000 rays); h varies
+ *                     with latitude and, through the few arc minutes between the two polar axes, by metres with longitude: do
+ *                     not substitute the mapping altitude.  This inverts the exact geodetic latitude; the forward kernels
+ *                     take one Bowring step (ecef_to_geodetic); tests/test_inverse_cpu.py records what that costs in pixels.
+ *   AMT_W2P_SM        (MLat, SM longitude; MLT through mltToSmLon): the unit vector of the two angles goes to J2000 with m_sm^T
+ *                     and is scaled onto the shell, u / sqrt(sum (u_i / rad_i)^2), rad = (a, a, b), as amt_pole_in_view does.
+ *   AMT_W2P_J2000     (declination, right ascension): a direction without a position (stars).
+ * 1. line of sight d = (P - cam) / |P - cam|; J2000: the direction itself.
+ * 2. visibility, with q = P / rad, c = cam / rad: a shell point is visible iff c.c < 1 (camera inside the shell: the forward
+ *    takes the far root, every shell point is seen) or q.c > 1 (camera on the outer side of the tangent plane at P) - the
+ *    forward's root choice (near root outside, far root inside).  A J2000 direction is hidden iff its ray hits the shell by the
+ *    forward's rule (discriminant >= 0 and ray parameter >= 0): stars are visible exactly in sky pixels.
+ * 3. native direction (l, m, n) = rot^T d, rho = sqrt(l^2 + m^2).
+ * 4. projection plane, degrees, k = 180/pi: x = R m / rho, y = -R l / rho with TAN R = k rho / n (domain n > 0), SIN R = k rho
+ *    (n >= 0), ARC R = k atan2(rho, n), STG R = 2 k rho / (1 + n) (n > -1), ZEA R = k sqrt(2 (1 - n)) evaluated as
+ *    k rho sqrt(2 / (1 + n)) (n > -1; exact as rho -> 0).  rho = 0 with n > 0 gives x = y = 0 exactly; rho = 0 with n <= 0 (the
+ *    antipode of the boresight has no position angle) is outside every domain.
+ * 5. pixel offsets (U, V) = CD^-1 (x, y).
+ * 6. SIP: u + A(u, v) = U, v + B(u, v) = V by Newton's method from (U, V), at most 20 steps; it stops after a step of at most
+ *    2^-40 max(1, |u|, |v|) pixels.  Not converged: the cap is reached, an iterate is not finite, or the Jacobian's determinant
+ *    is not positive at an iterate (the polynomial folds over).  This inverts the forward polynomial amt_directions_zenithal
+ *    evaluates; a header's AP / BP tables are not read.  Without SIP (u, v) = (U, V).
+ * 7. 0-based pixel coordinates, a pixel's centre at (column, row): X = u + CRPIX1 - 1 - start_x, Y = v + CRPIX2 - 1 - start_y.
+ * 8. elevation of the line of sight at P as the forward's exact centres define it (astrometry.py:200-212),
+ *    90 deg - angle(-d, P / |P|); NaN for J2000 and invalid input, a number (negative) for hidden points.
+ * Flags (one byte per point):
+ *   AMT_W2P_INVALID        non-finite input or |c0| > 90
+ *   AMT_W2P_HIDDEN         not visible by step 2
+ *   AMT_W2P_UNPROJECTABLE  outside the projection's domain (or P = cam)
+ *   AMT_W2P_NOT_CONVERGED  step 6 did not converge
+ *   AMT_W2P_OUTSIDE        xy is a number and not in [-0.5, width - 0.5] x [-0.5, height - 0.5]
+ * xy is NaN exactly where INVALID, UNPROJECTABLE or NOT_CONVERGED is set; it stays a number for points that are only hidden or
+ * outside the frame (a drawn line needs its off-frame end).  c1 is taken modulo 360 into [-180, 180): 180, -180 and 540 give the
+ * same bits; c0 = +-90 is a valid point.
+ * amt_world_to_pixel: n points, c0 / c1 / out_elev (optional) / out_flags of n elements, out_xy (n, 2) float64 [x, y].
+ * amt_grid_to_pixel: the outer product of two axes, point (i, j) = (lat_centres[i], lon_centres[j]) - the cell centres of a
+ * plate carree grid, which are never materialised; outputs (ny, nx[, 2]); out_xy32 is the float32 array amt_remap_coords takes,
+ * the float64 value rounded once; out_xy32 and out_xy are each optional, but one of them is required.  The two entry points share their device
+ * functions and give identical bits for identical points.  AMT_EINVAL (nothing written): NULL required pointers, n < 0, an
+ * empty axis or frame, an unknown `frame`, a projection index out of range, a SIP order >= AMT_SIP_MAX, a singular CD matrix.
+ * n = 0 is AMT_OK.  Both only enqueue work on the context's stream. */
+#define AMT_W2P_GEODETIC 0
+#define AMT_W2P_SM 1
+#define AMT_W2P_J2000 2
+#define AMT_W2P_INVALID 1
+#define AMT_W2P_HIDDEN 2
+#define AMT_W2P_UNPROJECTABLE 4
+#define AMT_W2P_NOT_CONVERGED 8
+#define AMT_W2P_OUTSIDE 16
+int amt_world_to_pixel(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
+                       const double* c0, const double* c1, int64_t n, double* out_xy, double* out_elev, uint8_t* out_flags);
+int amt_grid_to_pixel(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
+                      const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx, float* out_xy32, double* out_xy,
+                      double* out_elev, uint8_t* out_flags);
+
 /* auromat/coordinates/intersection.py:144-163 ellipsoidLineIntersection (and
  * auromat/mapping/mapping.py:1474-1510 inflatedEarthIntersection with a=wgs84A+h, b=wgs84B+h).
  * origin: host double[3]; dirs/out: (n,3) AoS.  Misses / points behind a directed ray are NaN. */
