@@ -39,7 +39,9 @@ struct amt_ctx {
     hipStream_t aux_pre, aux_tail, aux_fin;     // coarse pre-pass | folds behind a big kernel | crop/finalise
     // optional per-kernel timing (amt_timing_*): event pairs recorded around the dominant kernels
     int last_second, last_bin, last_frames;     // amt_georef_last_variant
-    int timing;                       // 0 = off, n = bracket every n-th launch of each kind
+    int roles_off;                    // amt_georef_set_roles(ctx, 0): every band that casts rays is generic
+    long long last_role_items[3];     // amt_georef_last_roles: work items of the latest launch per role (generic, inner, low)
+    int timing;                      // 0 = off, n = bracket every n-th launch of each kind
     size_t tlaunch[2];                // launches seen per kind since timing was enabled
     int tframes[2];                   // frames covered by the timed launches
     std::vector<hipEvent_t> tev[2];   // [kernel kind] start0, stop0, start1, stop1, ...
@@ -86,10 +88,12 @@ size_t amt_georef_partials_bytes(const amt_frame_params* p);
 // (amt_prm::sky_fill, amt_params.h).  In: rows [0, known_top_end) and [known_bottom_begin, number of rows) of work items hold
 // NaN in every output array of the frame (amt_prm::sky_known_empty(): none).  Out: the same two for the arrays as
 // the launch leaves them — the frame's own sky rows, amt_georef_sky_rows — and how many sky rows of work items it wrote and
-// left alone.  Without it every sky row is written.
+// left alone.  Without it every sky row is written.  Out as well: the frame's work items that cast rays, per role (generic, inner,
+// low: amt_prm::band_roles).
 struct amt_sky_state {
     int known_top_end, known_bottom_begin;
     int bands_filled, bands_skipped;
+    long long role_items[3];
 };
 // THE launcher of the big kernel (every georeferencing entry point ends here): n <= AMT_MAX_BATCH frames, equally sized and of
 // one kernel variant in ONE launch (n launches otherwise).  dirs: NULL, or n caller-supplied corner direction arrays (all frames

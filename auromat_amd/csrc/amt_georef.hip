@@ -125,6 +125,10 @@ struct georef_args {
     // the part of those rows that is still to be written: [fill_top_begin, sky_top_end) and [sky_bottom_begin, fill_bottom_end);
     // the rest already holds NaN (amt_prm::sky_fill; 0 and the number of rows: everything is written)
     int fill_top_begin, fill_bottom_end;
+    // roles of the rows of work items that cast rays (amt_prm::band_roles): [inner_begin, inner_end) take the inner loop of the
+    // row step, [sky_top_end, low_top_end) and [low_bottom_begin, sky_bottom_begin) the low one, the rest the generic one
+    // (amt_prm::band_roles_none(): all of them)
+    int inner_begin, inner_end, low_top_end, low_bottom_begin;
     int bin_pole;                       // amt_georef_out.bin_pole: bin (and box) in the coordinates rotated by 90 deg about x
     int row_layout;                     // amt_georef_out.row_layout: 0 = contiguous rows, 1 = strip-padded rows
     pole_consts pole;
@@ -196,6 +200,13 @@ __device__ __forceinline__ void block_reduce8(double (&v)[8], double* __restrict
         out[k] = r;
     }
 }
+
+// roles of a work item's row step (amt_prm::band_roles); role_tag carries one into the step as a compile-time value
+constexpr int kRoleGeneric = 0, kRoleInner = 1, kRoleLow = 2;
+template <int ROLE>
+struct role_tag {
+    static constexpr int value = ROLE;
+};
 
 constexpr int kDppWaveShl1 = 0x130;   // lane i <- lane i+1
 constexpr int kDppWaveShr1 = 0x138;   // lane i <- lane i-1
@@ -325,8 +336,16 @@ constexpr int kBinW = 8, kBinCells = kBinW * kBinW;
 #ifndef AMT_ROWS_MIN_WAVES_MAGONLY
 #define AMT_ROWS_MIN_WAVES_MAGONLY 4
 #endif
+// Two variants reached one wave more than their class asks for and keep it with the three loops of the roles: the plain
+// camera-model kernel (lat / lon arrays or the box pass, no binning) 6, the fused MLat / MLT kernel with exact centres 4.
+#ifndef AMT_ROWS_MIN_WAVES_PLAIN
+#define AMT_ROWS_MIN_WAVES_PLAIN 6
+#endif
+#ifndef AMT_ROWS_MIN_WAVES_MAG_EXACT
+#define AMT_ROWS_MIN_WAVES_MAG_EXACT 4
+#endif
 template <bool FAST, bool DIRS_IN, int SECOND, int BIN>
-__global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGONLY : (SECOND >= 2 ? AMT_ROWS_MIN_WAVES_POLE : (SECOND == 1 && BIN ? AMT_ROWS_MIN_WAVES_MAG : (BIN ? AMT_ROWS_MIN_WAVES_BIN : AMT_ROWS_MIN_WAVES)))) void k_georef_rows(georef_batch B, int rows_per_chunk, int strips_x,
+__global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0) ? AMT_ROWS_MIN_WAVES_PLAIN : (!FAST && SECOND == 1 && BIN != 0) ? AMT_ROWS_MIN_WAVES_MAG_EXACT : SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGONLY : (SECOND >= 2 ? AMT_ROWS_MIN_WAVES_POLE : (SECOND == 1 && BIN ? AMT_ROWS_MIN_WAVES_MAG : (BIN ? AMT_ROWS_MIN_WAVES_BIN : AMT_ROWS_MIN_WAVES)))) void k_georef_rows(georef_batch B, int rows_per_chunk, int strips_x,
                                                            int n_items, int n_frames) {
     constexpr bool MAG = SECOND != 0, kPole = SECOND == 2, kMagPole = SECOND == 3, kMagOnly = SECOND == 4;
     static_assert(!(kPole || kMagPole) || (BIN != 0 && !DIRS_IN), "the pole plans exist for fused binning with the camera model only");
@@ -521,8 +540,10 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
     // the box-first plan (amt_pipe_launch_box: no output, no binning) needs a centre's elevation only — the box is reduced
     // over the corners — and skips a quarter of the arithmetic (wave-uniform)
     const bool centre_coords = BIN != 0 || A.lat_c != nullptr || A.lon_c != nullptr || (MAG && A.mlat_c != nullptr);
-    int n_valid = 0;
-    auto box_add = [&](double la_v, double lo_v) {
+    int n_valid = 0;                                        // valid pixels of the item (wave-uniform)
+    // inner items: the lanes whose corner is kept by the box — the corner of an own pixel or of the left neighbour's
+    const bool box_lane = px_ok || (lane >= 1 && col_ok);
+    auto box_add =[&](double la_v, double lo_v) {
         __hip_atomic_fetch_min(&sBox[wave][0][lane], la_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_max(&sBox[wave][1][lane], la_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_min(&sBox[wave][2][lane], lo_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -753,7 +774,15 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         vec3 rv;
         double rxy, rla, rlo;
     };
-    auto step = [&](const int r, const bool even, const vec3& dj, const row_state& prev, row_state& cur) {
+    // The step exists in three roles, chosen once per work item from its band (amt_prm::band_roles, wave-uniform):
+    //   generic  the code as described above;
+    //   inner    every corner ray and every centre of the item hits and every pixel passes the threshold: `hit` is "the column
+    //            exists", `live` and `valid` are "the pixel exists", the box takes every owned corner — all of them fixed for the
+    //            item, so the comparisons, the keep flags and the per-row count of valid pixels are not in the loop;
+    //   low      no pixel of the item reaches the threshold: no image pixel is read, no run kept, nothing enters the box.
+    // The guards left out are identities in those items: every value stored and every accumulator keeps its bits.
+    auto step = [&](auto role, const int r, const bool even, const vec3& dj, const row_state& prev, row_state& cur) __attribute__((always_inline)) {
+        constexpr int ROLE = decltype(role)::value;
         const int gy = y0 + r;
         unsigned int ch0 = 0, ch1 = 0, ch2 = 0;          // image pixel (gy-1, gx)
         // ---- corner (gy, gx) ------------------------------------------------------------------
@@ -763,7 +792,7 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         const vec3 u = corner_ray(gy, dj);
         const double uu = fx::dot3(u.x, u.y, u.z, u.x, u.y, u.z);
         const double t = shell_t(ry, u, uu);
-        const bool hit = col_ok && t >= 0.0;
+        const bool hit = ROLE == kRoleInner ? col_ok : (col_ok && t >= 0.0);
         // unit direction (what the centre's elevation averages, reference astrometry.py:154-160); caller-supplied
         // directions are used as they are, like the reference does
         vec3 d;
@@ -777,7 +806,7 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         corner_vals c;
         // with bin_magnetic the bounding box is reduced over (MLat, SM longitude) as well
         const bool magbox = MAG && (kMagOnly || (BIN && !kPole && A.bin_magnetic));
-        if (__builtin_amdgcn_ballot_w64(hit) != 0) {     // wave-uniform
+        if (ROLE == kRoleInner || __builtin_amdgcn_ballot_w64(hit) != 0) {     // wave-uniform
             c.p = shell_point(ry, u, nan_unless(hit, t));         // already in GEO; NaN for a miss
             c.la = c.lo = c.bn = c.bd = NAN;
             if (!kMagOnly) {
@@ -823,7 +852,7 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
             if (pole_bin) c.bla = c.sml, c.blo = c.ssl;
             if (kMagBox && !magbox && !pole_bin && !kMagPole) c.bla = c.la, c.blo = c.lo;
         }
-        if (BIN) take_pixel(r, even, ch0, ch1, ch2);
+        if (BIN && ROLE != kRoleLow) take_pixel(r, even, ch0, ch1, ch2);
         // the last corner row of a chunk is the first of the next one (which owns it) unless it is
         // the image's last; lane 63's column likewise belongs to the next strip unless it is the last
         const bool owner = st_corner && (r < rows || gy == frame_h);
@@ -869,13 +898,14 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
                 dscale = 1.0;
                 const double tc = shell_t(ry, uc, uuc);
                 pc = shell_point(ry, uc, nan_unless(tc >= 0.0, tc));
-                if (want_bbox) {
+                if (ROLE == kRoleGeneric && want_bbox) {
                     // after sanitisation a centre also needs its 4 corners (reference mapping.py:1093-1101)
                     const int h = (prev.p.x == prev.p.x) && (c.p.x == c.p.x);
                     corners_ok = h && from_next_lane(h);
                 }
             }
-            const bool live = px_ok && pc.x == pc.x;          // this lane's pixel exists and its centre hit the shell
+            // this lane's pixel exists and its centre hit the shell
+            const bool live = ROLE == kRoleInner ? px_ok : (px_ok && pc.x == pc.x);
             double lac, loc, el, ml = NAN, mt = NAN, slc = NAN, rlac = NAN, rloc = NAN;
             if (__builtin_amdgcn_ballot_w64(live) != 0) {      // wave-uniform
                 double inv_r, cn = NAN, cd = NAN;
@@ -927,7 +957,7 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
                     at(A.mlt_c, off_pixel) = mt;
                 }
             }
-            const bool valid = px_ok && (el >= min_elev) && corners_ok;
+            const bool valid = ROLE == kRoleInner ? px_ok : (ROLE == kRoleLow ? false : (px_ok && (el >= min_elev) && corners_ok));
             int bin_x = 0, bin_y = 0;            // 1-based bin indices of this pixel, 0 = not binned
             long long el_fix = 0;
             if (BIN && valid) {
@@ -980,13 +1010,20 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
                     }
                 }
             }
-            if (BIN) bin_account(bin_x, bin_y, ch0, ch1, ch2, el_fix);
-            if (want_bbox) {
+            if (BIN && ROLE != kRoleLow) bin_account(bin_x, bin_y, ch0, ch1, ch2, el_fix);
+            if (ROLE == kRoleInner) {
+                // every centre is valid and every corner exists: the corner row gy-1 goes into the box as it is (the item's
+                // count of valid pixels is set before the loop)
+                flag_cur = box_lane ? 1 : 0;
+                if (want_bbox && box_lane) {
+                    if (kMagBox) box_add(prev.bla, prev.blo); else box_add(prev.la, prev.lo);
+                }
+            } else if (ROLE == kRoleGeneric && want_bbox) {
                 // corner row gy-1 is final now: it keeps a corner when a centre above (prev.flag) or below
                 // (this row: own pixel or the left neighbour's) is valid
                 const int vi = valid ? 1 : 0;
                 flag_cur = vi | from_prev_lane(vi);
-                n_valid += vi;
+                n_valid += __builtin_popcountll(__builtin_amdgcn_ballot_w64(valid));      // (wave-uniform: a scalar count)
                 if (kMagBox) {
                     if ((prev.flag | flag_cur) && prev.bla == prev.bla) box_add(prev.bla, prev.blo);
                 } else {
@@ -1019,7 +1056,7 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         cur.flag = flag_cur;
     };
 
-    auto advance = [&](const int r, const bool even, const row_state& prev, row_state& cur) {
+    auto advance = [&](auto role, const int r, const bool even, const row_state& prev, row_state& cur) __attribute__((always_inline)) {
         vec3 dj = {dj0, dj1, dj2};
         if (DIRS_IN) {
             // the direction of this corner was loaded one row ahead; fetch the next row's now, so that its
@@ -1030,15 +1067,32 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
                 dj0 = q[0], dj1 = q[1], dj2 = q[2];
             }
         }
-        step(r, even, dj, prev, cur);
+        step(role, r, even, dj, prev, cur);
         off_corner += pitch_corner;
         off_pixel += pitch_pixel;
         img_off += img_row;
     };
-    if (BIN && px_ok && rows > 0) load_pixel(img_off + img_row, rawB0, rawB1, shiftB);       // pixel row y0: step 1
-    for (int r = 0; r <= rows; r += 2) {
-        advance(r, true, S0, S1);
-        if (r + 1 <= rows) advance(r + 1, false, S1, S0); else S0 = S1;      // the last row's state ends up in S0
+    // (the three lambdas of the loop are inlined by force: left to its cost model the compiler keeps `march` as a function of its
+    // own, and the constants pinned in SGPRs then reach it through memory)
+    auto march = [&](auto role) __attribute__((always_inline)) {
+        constexpr int ROLE = decltype(role)::value;
+        if (BIN && ROLE != kRoleLow && px_ok && rows > 0) load_pixel(img_off + img_row, rawB0, rawB1, shiftB);       // pixel row y0: step 1
+        if (ROLE == kRoleInner) n_valid = __builtin_popcountll(__builtin_amdgcn_ballot_w64(px_ok)) * rows;
+        for (int r = 0; r <= rows; r += 2) {
+            advance(role, r, true, S0, S1);
+            if (r + 1 <= rows) advance(role, r + 1, false, S1, S0); else S0 = S1;      // the last row's state ends up in S0
+        }
+    };
+    // the item's role: one branch per item, not per row (caller-supplied directions and the pole plans have none)
+    if constexpr (DIRS_IN || kPole || kMagPole) {
+        march(role_tag<kRoleGeneric>{});
+    } else {
+        if (chunk >= A.inner_begin && chunk < A.inner_end)              // wave-uniform
+            march(role_tag<kRoleInner>{});
+        else if (BIN != 0 && (chunk < A.low_top_end || chunk >= A.low_bottom_begin))      // (the host names low bands with fused binning only)
+            march(role_tag<kRoleLow>{});
+        else
+            march(role_tag<kRoleGeneric>{});
     }
     if (BIN && bin_anchor) {
         if (run_key) bin_flush(run_key, run_cnt, run_c0, run_c1, run_c2, run_el);
@@ -1068,11 +1122,11 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
         } else {
             if (S0.flag && S0.la == S0.la) box_add(S0.la, S0.lo);
         }
-        double v[7];
+        // (the count of valid pixels is wave-uniform already: it takes no part in the reduction)
+        double v[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k)
             v[k] = __hip_atomic_load(&sBox[wave][k][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        v[6] = (double)n_valid;
         for (int o = 32; o > 0; o >>= 1) {
             v[0] = fmin(v[0], __shfl_xor(v[0], o));
             v[1] = fmax(v[1], __shfl_xor(v[1], o));
@@ -1080,11 +1134,10 @@ __global__ __launch_bounds__(kRowsThreads, SECOND == 4 ? AMT_ROWS_MIN_WAVES_MAGO
             v[3] = fmax(v[3], __shfl_xor(v[3], o));
             v[4] = fmin(v[4], __shfl_xor(v[4], o));
             v[5] = fmax(v[5], __shfl_xor(v[5], o));
-            v[6] += __shfl_xor(v[6], o);
         }
         if (lane < 8) A.bbox_partials[(int64_t)item * 8 + lane] = lane == 0 ? v[0] : lane == 1 ? v[1] : lane == 2 ? v[2]
                                                                   : lane == 3 ? v[3] : lane == 4 ? v[4]
-                                                                  : lane == 5 ? v[5] : lane == 6 ? v[6] : 0.0;
+                                                                  : lane == 5 ? v[5] : lane == 6 ? (double)n_valid : 0.0;
     }
 }
 
@@ -1280,7 +1333,7 @@ launch_shape shape_of(const amt_frame_params* p) {
 // The machinery: bands of rows_per_chunk rows (n of them) of a W x H frame in which a convex region {quadratic >= 0, linear >= 0}
 // of the image plane has no point; eval(x, y, &linear) -> quadratic.  [0, *top_end) and [*bottom_begin, n) are free of it.
 template <class Eval>
-void conic_bands(double W, double H, int n, int rows_per_chunk, Eval eval, int* top_end, int* bottom_begin) {
+void conic_bands(double W, double H, int n, int rows_per_chunk, Eval eval, int* top_end, int* bottom_begin, double margin_px = 1.0) {
     *top_end = 0, *bottom_begin = n;
     // quadratic through (t0, f0), (t1, f1), (t2, f2) with t1 the midpoint: coefficients of f(t0 + s), s in [0, L]
     struct quad {
@@ -1303,7 +1356,8 @@ void conic_bands(double W, double H, int n, int rows_per_chunk, Eval eval, int* 
         q.b = (f2 - f0) / L - q.a * L;
         return q;
     };
-    const double x0 = -1.0, xL = W + 2.0, y0 = -1.0, yL = H + 2.0;        // one pixel beyond the corners on every side
+    // one pixel (margin_px) beyond the corners on every side
+    const double x0 = -margin_px, xL = W + 2.0 * margin_px, y0 = -margin_px, yL = H + 2.0 * margin_px;
     // disc along three columns (as quadratics in y) and nb as a plane
     double nb00, nb10, nb01, tmp;
     quad col[3];
@@ -1343,8 +1397,8 @@ void conic_bands(double W, double H, int n, int rows_per_chunk, Eval eval, int* 
         return segment_free(col[k], nb00 + (k == 2 ? nbx * xL : 0.0), nby, s0, s1);
     };
     auto band_free = [&](int c) {
-        // corner rows c R ... min((c + 1) R, H), a pixel more on both sides; s counts from y0 = -1
-        const double s0 = (double)c * rows_per_chunk, s1 = std::min((double)(c + 1) * rows_per_chunk, H) + 2.0;
+        // corner rows c R ... min((c + 1) R, H), a pixel (margin_px) more on both sides; s counts from y0 = -margin_px
+        const double s0 = (double)c * rows_per_chunk, s1 = std::min((double)(c + 1) * rows_per_chunk, H) + 2.0 * margin_px;
         return line_free(s0) && line_free(s1) && side_free(0, s0, s1) && side_free(2, s0, s1);
     };
     int t = 0;
@@ -1397,7 +1451,11 @@ void sky_bands(const georef_args& A, const launch_shape& sh, int* top_end, int* 
 // asin(a_max / |C| * cos e0) about the nadir — in the image of the affine camera model a conic section again, bounded per band
 // of rows exactly like the limb.  Conservative by construction (|P| bounded from above, a band a pixel wider than its rows and one
 // more band on either side); outside [*top_end, *bottom_begin) no pixel is binned.
-void elevation_bands(const georef_args& A, const launch_shape& sh, double min_elev_deg, int* top_end, int* bottom_begin) {
+// tight (the roles of the bands, thresholds from 5 deg on): bands widened by three pixels instead of one and no band added — what a
+// fast centre's elevation differs by from that of a ray through its pixel is of second order in the pixel's size, a few per cent
+// of the change over one pixel where the elevation is 5 deg or more (towards the limb it grows without bound: there the extra
+// band stays).
+void elevation_bands(const georef_args& A, const launch_shape& sh, double min_elev_deg, int* top_end, int* bottom_begin, bool tight = false) {
     const int n = sh.chunks_y;
     *top_end = 0, *bottom_begin = n;
     const shell_ray& e = A.sray;
@@ -1419,10 +1477,63 @@ void elevation_bands(const georef_args& A, const launch_shape& sh, double min_el
         return uo * uo - cos2 * oo * uu;                  // >= 0: inside the cone (or its mirror image, which `lin` excludes)
     };
     int t = 0, b = n;
-    conic_bands((double)A.width, (double)A.height, n, sh.rows_per_chunk, eval, &t, &b);
+    tight = tight && min_elev_deg >= 5.0;
+    conic_bands((double)A.width, (double)A.height, n, sh.rows_per_chunk, eval, &t, &b, tight ? 3.0 : 1.0);
     // one more band on either side: a fast centre is the mean of four corner hits, not a ray of its own
-    *top_end = std::max(0, t - 1), *bottom_begin = std::min(n, b + 1);
+    const int extra = tight ? 0 : 1;
+    *top_end = std::max(0, t - extra), *bottom_begin = std::min(n, b + extra);
     if (t == n) *top_end = n, *bottom_begin = n;          // nothing above the threshold in the frame
+}
+
+// Which rows of work items lie wholly where every ray hits the shell at an elevation >= min_elev?  The law of sines above, read the
+// other way: |P| >= the shell's SMALLER semi-axis, so every ray within the cone of half-angle asin(r_min / |C| * cos e0) about
+// the nadir hits (the sphere of radius r_min lies inside the shell) at an elevation >= e0.  A cone narrower than 90 deg cuts the
+// image plane of the affine camera model in a convex region, so a rectangle lies inside it when its four corners do: per band,
+// four evaluations.  The margins: e0 is the threshold (0 where it is lower or there is none) plus 0.05 deg, and the rectangle is
+// the band's corner rows and the frame's corner columns widened by two pixels on every side (exact centre rays lie between the
+// corners; a fast centre is the mean of four corner hits, which moves its elevation by less than a thousandth of a pixel's
+// worth where the cone ends two pixels away).  What the test rejects stays generic; the bands it admits are one range.
+void inner_bands(const georef_args& A, const launch_shape& sh, double min_elev_deg, int* begin, int* end) {
+    *begin = *end = 0;
+    const shell_ray& e = A.sray;
+    if (!(e.root_sign < 0) || min_elev_deg != min_elev_deg) return;       // camera inside the shell, no order: undecided
+    const double e0 = std::max(min_elev_deg, 0.0) + 0.05;
+    if (!(e0 < 89.0)) return;
+    const double oo = e.ox * e.ox + e.oy * e.oy + e.oz * e.oz;
+    const double r_min = 1.0 / std::sqrt(std::max(e.qa, e.qa + e.qd));                // min(a, b) of the shell
+    const double k = r_min / std::sqrt(oo) * std::cos(e0 * kDeg2Rad);                 // sin of the cone's half-angle
+    if (!(k > 0.0 && k < 1.0)) return;
+    const double cos2 = 1.0 - k * k;
+    auto inside = [&](double x, double y) {
+        const affine_cam& c = A.cam;
+        const double px = x + c.cx, py = y + c.cy;
+        const double ux = c.u0[0] + px * c.ux[0] + py * c.uy[0], uy = c.u0[1] + px * c.ux[1] + py * c.uy[1],
+                     uz = c.u0[2] + px * c.ux[2] + py * c.uy[2];
+        const double uu = ux * ux + uy * uy + uz * uz;
+        const double uo = ux * e.ox + uy * e.oy + uz * e.oz;
+        // towards the Earth and inside the cone, by a part in 1e9 of the terms compared
+        return uo < 0 && uo * uo - cos2 * oo * uu > 1e-9 * (oo * uu);
+    };
+    const double margin = 2.0, xa = -margin, xb = (double)A.width + margin;
+    auto band_inside = [&](int c) {
+        const double ya = (double)c * sh.rows_per_chunk - margin;
+        const double yb = std::min((double)(c + 1) * sh.rows_per_chunk, (double)A.height) + margin;
+        return inside(xa, ya) && inside(xb, ya) && inside(xa, yb) && inside(xb, yb);
+    };
+    int b = 0;
+    while (b < sh.chunks_y && !band_inside(b)) ++b;
+    int t = b;
+    while (t < sh.chunks_y && band_inside(t)) ++t;
+    if (b < t) *begin = b, *end = t;
+}
+
+// The roles of a camera frame's bands (amt_prm::band_roles) for the threshold min_elev (-inf: none).  with_low: the launch bins
+// (what the low loop leaves out is the image and the runs of the fused binning; without them a low band is a generic one)
+amt_prm::band_role_ranges frame_roles(const georef_args& A, const launch_shape& sh, double min_elev_deg, bool with_low) {
+    int can_top = 0, can_bottom = sh.chunks_y, in_begin = 0, in_end = 0;
+    if (with_low) elevation_bands(A, sh, min_elev_deg, &can_top, &can_bottom, true);
+    inner_bands(A, sh, min_elev_deg, &in_begin, &in_end);
+    return amt_prm::band_roles(sh.chunks_y, A.sky_top_end, A.sky_bottom_begin, can_top, can_bottom, in_begin, in_end);
 }
 
 // The camera-model constants of a frame: the TAN WCS, the GEO-frame affine camera and shell ray (camera model and shell composed
@@ -1450,6 +1561,7 @@ struct prepared_frame {
     double* fold;       // scratch of the first fold stage (behind the partials)
     int second;         // k_georef_rows' SECOND
     int bin;
+    int role_bands[3];  // bands that cast rays, per role: generic, inner, low (amt_prm::band_role_counts)
 };
 
 // sky (optional): what the frame's arrays already hold as NaN on entry, the frame's own sky rows and what was written of
@@ -1595,6 +1707,14 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
         if (bin ? A.bin_magnetic : (A.bin_magnetic || !out->bbox)) F->second = 4;
     }
     F->bin = bin;
+    // roles of the bands that cast rays: the camera model without a pole plan (the kernel's other variants have one loop)
+    amt_prm::band_role_ranges roles = amt_prm::band_roles_none(sh.chunks_y);
+    if (!ctx->roles_off && dirs == nullptr && F->second != 2 && F->second != 3) roles = frame_roles(A, sh, out->bbox_min_elevation, bin != 0);
+    A.inner_begin = roles.inner_begin, A.inner_end = roles.inner_end;
+    A.low_top_end = roles.low_top_end, A.low_bottom_begin = roles.low_bottom_begin;
+    amt_prm::band_role_counts(roles, A.sky_top_end, A.sky_bottom_begin, F->role_bands);
+    if (sky != nullptr)
+        for (int k = 0; k < 3; ++k) sky->role_items[k] = (int64_t)F->role_bands[k] * sh.strips_x;
     return AMT_OK;
 }
 
@@ -1628,6 +1748,10 @@ int launch_prepared(amt_ctx* ctx, int n, prepared_frame* F) {
         if (F[i].tail != nullptr && F[i].out->bbox) ev.stop = F[i].tail->kernel_done;
     georef_batch B;
     ctx->last_second = F[0].second, ctx->last_bin = bin, ctx->last_frames = n;
+    for (int k = 0; k < 3; ++k) {
+        ctx->last_role_items[k] = 0;
+        for (int i = 0; i < n; ++i) ctx->last_role_items[k] += (int64_t)F[i].role_bands[k] * strips_x;
+    }
     for (int i = 0; i < kMaxBatch; ++i) B.f[i] = F[i < n ? i : 0].A;
     B.math = fx::make_math_table();
     if (dirs) {
@@ -1789,6 +1913,24 @@ int amt_georef_image_rows(const amt_frame_params* p, double min_elevation, int32
     }
     *row_begin = std::max(0, t * sh.rows_per_chunk);
     *row_end = std::min(p->height, b * sh.rows_per_chunk);
+    return AMT_OK;
+}
+
+int amt_georef_band_roles(const amt_frame_params* p, double min_elevation, int32_t* rows_per_item, int32_t* ranges8) {
+    if (p == nullptr || rows_per_item == nullptr || ranges8 == nullptr) return AMT_EINVAL;
+    if (p->width <= 0 || p->height <= 0) return AMT_EINVAL;
+    georef_args A;
+    std::memset(&A, 0, sizeof(A));
+    camera_model(p, &A);
+    const launch_shape sh = shape_of(p);
+    A.sky_top_end = 0, A.sky_bottom_begin = sh.chunks_y;
+    sky_bands(A, sh, &A.sky_top_end, &A.sky_bottom_begin);
+    const amt_prm::band_role_ranges r = frame_roles(A, sh, min_elevation, true);
+    *rows_per_item = sh.rows_per_chunk;
+    ranges8[0] = sh.chunks_y, ranges8[1] = sh.strips_x;
+    ranges8[2] = A.sky_top_end, ranges8[3] = A.sky_bottom_begin;
+    ranges8[4] = r.low_top_end, ranges8[5] = r.low_bottom_begin;
+    ranges8[6] = r.inner_begin, ranges8[7] = r.inner_end;
     return AMT_OK;
 }
 

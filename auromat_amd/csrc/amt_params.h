@@ -343,6 +343,47 @@ inline sky_known sky_fill(const sky_known& known, int n, int t, int b, int* fill
     return sky_known{t, b};
 }
 
+// ---- roles of the Earth bands ---------------------------------------------------------------------------------------------------
+// The bands between the two sky ranges, [t, b), cast rays.  Most of them need none of the row step's guards, and some need none
+// of its binning: a band is
+//   inner    when every corner ray and every pixel centre of it hits the shell and every pixel of it lies at or above the
+//            elevation threshold — no miss, nothing masked: the kernel's inner loop has no hit test, no threshold test and no
+//            keep flags;
+//   low      when none of its pixels can reach the threshold — nothing is binned and no corner enters the box: the kernel's low
+//            loop reads no image and keeps no runs and no box;
+//   generic  otherwise (the limb, the threshold line, and every band of a frame the rule does not decide).
+// As ranges of bands: inner [inner_begin, inner_end), low [t, low_top_end) and [low_bottom_begin, b).  Both kinds of region are
+// convex in the image of a TAN camera (cones about the nadir), so the inner bands are one range and the low ones lie at the two
+// ends of the Earth bands.
+struct band_role_ranges {
+    int inner_begin, inner_end;
+    int low_top_end, low_bottom_begin;
+};
+// no roles: every Earth band of a frame of n bands is generic
+inline band_role_ranges band_roles_none(int n) { return band_role_ranges{0, 0, 0, n}; }
+
+// The one rule, on what the geometry gives for a frame of n bands with Earth bands [t, b): [can_top, can_bottom), outside of
+// which no pixel reaches the threshold (elevation_bands(); (0, n) when there is no threshold or no bound), and [in_begin,
+// in_end), the bands that are wholly inside the cone of the threshold with a margin (inner_bands(); empty when undecided).
+// Whatever the inputs, the ranges it returns are ordered and disjoint and lie inside [t, b): t <= low_top_end <= inner_begin
+// <= inner_end <= low_bottom_begin <= b (inner_begin = inner_end = 0 when there is no inner band).
+inline band_role_ranges band_roles(int n, int t, int b, int can_top, int can_bottom, int in_begin, int in_end) {
+    band_role_ranges r = band_roles_none(n);
+    t = std::min(std::max(t, 0), n), b = std::min(std::max(b, t), n);
+    r.low_top_end = std::min(std::max(can_top, t), b);
+    r.low_bottom_begin = std::min(std::max(can_bottom, r.low_top_end), b);
+    const int i0 = std::max(in_begin, r.low_top_end), i1 = std::min(in_end, r.low_bottom_begin);
+    if (i0 < i1) r.inner_begin = i0, r.inner_end = i1;
+    return r;
+}
+// bands per role among the Earth bands [t, b): counts[0] generic, [1] inner, [2] low
+inline void band_role_counts(const band_role_ranges& r, int t, int b, int* counts) {
+    t = std::max(t, 0), b = std::max(b, t);
+    counts[1] = r.inner_end - r.inner_begin;
+    counts[2] = std::max(0, std::min(r.low_top_end, b) - t) + std::max(0, b - std::max(r.low_bottom_begin, t));
+    counts[0] = (b - t) - counts[1] - counts[2];
+}
+
 // ---- map projections ----------------------------------------------------------------------------------------------------------
 // The constants of amt_project_forward / amt_project_inverse (csrc/amt_project.hip), computed once per projection.  Snyder, Map
 // Projections - A Working Manual, ch. 21 (stereographic, ellipsoid) and 25 (azimuthal equidistant, polar, sphere).

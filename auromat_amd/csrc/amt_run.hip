@@ -89,6 +89,7 @@ struct amt_run {
     hipStream_t copy_stream = nullptr;      // host images: the uploads' stream, created with the first of them
     hipStream_t launch_stream = nullptr;    // the stream of the latest launch (slot::known)
     int64_t bands_filled = 0, bands_skipped = 0;    // amt_run_fill_stats: since the last amt_run_begin
+    int64_t role_items[3] = {0, 0, 0};              // amt_run_role_stats: likewise (generic, inner, low)
 
     slot& slot_of(int k) { return slots[k % cfg.n_slots]; }
 };
@@ -264,6 +265,14 @@ int amt_run_fill_stats(amt_run* run, int64_t* bands_filled, int64_t* bands_skipp
     return AMT_OK;
 }
 
+int amt_run_role_stats(amt_run* run, int64_t* generic, int64_t* inner, int64_t* low) {
+    if (run == nullptr) return AMT_EINVAL;
+    if (generic) *generic = run->role_items[0];
+    if (inner) *inner = run->role_items[1];
+    if (low) *low = run->role_items[2];
+    return AMT_OK;
+}
+
 int amt_run_reset_hints(amt_run* run) {
     if (run == nullptr) return AMT_EINVAL;
     forget_hints(run);
@@ -333,7 +342,7 @@ int launch_slots(amt_run* run, const int* slots, int m, bool nothing_known = fal
         pp[j] = s.pipe, prm[j] = &s.prm, oo[j] = &s.out, ii[j] = s.img;
         la[j] = s.ppd_lat, lo[j] = s.ppd_lon;
         const amt_prm::sky_known known = nothing_known ? amt_prm::sky_known_empty() : s.known;
-        sky[j] = {known.top_end, known.bottom_begin, 0, 0};
+        sky[j] = {known.top_end, known.bottom_begin, 0, 0, {0, 0, 0}};
         if (s.img == nullptr) {
             ctx->last_error = "amt_run: a frame has no image";
             return AMT_EINVAL;
@@ -349,6 +358,7 @@ int launch_slots(amt_run* run, const int* slots, int m, bool nothing_known = fal
     for (int j = 0; j < m; ++j) {
         run->slots[slots[j]].known = {sky[j].known_top_end, sky[j].known_bottom_begin};
         run->bands_filled += sky[j].bands_filled, run->bands_skipped += sky[j].bands_skipped;
+        for (int k = 0; k < 3; ++k) run->role_items[k] += sky[j].role_items[k];
     }
     return AMT_OK;
 }
@@ -737,6 +747,7 @@ int amt_run_begin(amt_run* run, double* grids, int64_t grids_capacity, void* ima
     forget_sky(run);                                // whatever the caller did with the slots' arrays since the last call
     run->launch_stream = ctx->stream;
     run->bands_filled = run->bands_skipped = 0;
+    run->role_items[0] = run->role_items[1] = run->role_items[2] = 0;
     run->active = true;
     return AMT_OK;
 }

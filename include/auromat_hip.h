@@ -127,6 +127,23 @@ int amt_timing_read(amt_ctx* ctx, int kernel, double* total_ms, int* launches);
  * MLat / MLT-only mode (see amt_georef_out); *bin = 0 no fused binning, 1 uint8, 2 uint16 image; *frames = frames in that
  * launch.  -1 in all three before the first launch. */
 int amt_georef_last_variant(amt_ctx* ctx, int32_t* second, int32_t* bin, int32_t* frames);
+/* Roles of the frame kernel's work items (additions to ABI 10; csrc/amt_params.h amt_prm::band_roles).  For a
+ * frame of the TAN camera model the host sorts the rows of work items that cast rays into inner (every ray hits the shell and every
+ * pixel lies at or above bbox_min_elevation: the row step runs without its hit, threshold and keep tests), low (no pixel can
+ * reach the threshold: no image read, no binning, no box; launches with fused binning only) and generic rows; results do not
+ * depend on it, bit for bit.  Frames of caller-supplied directions and the pole plans have generic rows only.
+ * amt_georef_set_roles(ctx, 0): every launch through this context — amt_georef_frame, the frame drivers, the sequence runner —
+ * takes generic rows only (tests compare the two); != 0, the default: the rule decides.
+ * amt_georef_last_roles: work items of the context's latest launch per role, summed over its frames (each pointer optional; -1
+ * before the first launch).
+ * amt_georef_band_roles (no context, no GPU call): the rule itself for frame p and the threshold min_elevation (-inf: none) —
+ * *rows_per_item pixel rows per row of work items, and ranges8 = { rows of work items, work items per row, the rows that cast
+ * rays [sky_top_end, sky_bottom_begin) as amt_georef_sky_rows gives them, low_top_end, low_bottom_begin, inner_begin,
+ * inner_end }: rows [sky_top_end, low_top_end) and [low_bottom_begin, sky_bottom_begin) are low, [inner_begin, inner_end) inner. */
+int amt_georef_set_roles(amt_ctx* ctx, int enable);
+int amt_georef_last_roles(amt_ctx* ctx, int64_t* generic, int64_t* inner, int64_t* low);
+struct amt_frame_params;
+int amt_georef_band_roles(const struct amt_frame_params* p, double min_elevation, int32_t* rows_per_item, int32_t* ranges8);
 
 /* ---- per-frame parameter block --------------------------------------------------------
  * Host scalars the reference derives once per frame:
@@ -1280,6 +1297,9 @@ int amt_run_end(amt_run* run, int32_t* frames_done);
  * amt_run_fill_stats: sky rows of work items (per frame launched; a frame launched twice counts twice) that the launches since
  * the last amt_run_begin wrote / left alone.  Either pointer may be NULL. */
 int amt_run_fill_stats(amt_run* run, int64_t* bands_filled, int64_t* bands_skipped);
+/* Work items that cast rays, per role (amt_georef_last_roles), of the launches since the last amt_run_begin (a frame launched
+ * twice counts twice; addition to ABI 10).  Each pointer may be NULL. */
+int amt_run_role_stats(amt_run* run, int64_t* generic, int64_t* inner, int64_t* low);
 /* Forget the box hints (the next frame gets a coarse pre-pass). */
 int amt_run_reset_hints(amt_run* run);
 /* Quantile sequences: the median pass of a runner created with statistic = 1 becomes a one-quantile pass — the frames it covers
