@@ -15,33 +15,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _band_role_cases import band_roles, cases, role_of_bands
+from _band_role_cases import (GEO, MAG, NINE, _ctx, assert_same, band_roles, cases, image, last_roles, launch_frame, role_of_bands,
+                              set_roles)
 
 pytestmark = pytest.mark.gpu
 
 MIN_ELEV = 10.0
-EVENT_ROOM = 256
-GEO = ('lat', 'lon', 'lat_c', 'lon_c', 'elev')
-MAG = ('elev', 'mlat', 'mlt', 'mlat_c', 'mlt_c')
-NINE = GEO + MAG[1:]
-CORNERS = ('lat', 'lon', 'mlat', 'mlt')
-OUTPUTS = {0: GEO, 1: NINE, 4: MAG}
-EVENT_DTYPE = np.dtype([('w%d' % i, np.uint32) for i in range(8)])      # 32-byte records, compared as sorted words
-
-
-def _ctx():
-    from auromat_amd._native import Context
-    return Context.current()
-
-
-def set_roles(ctx, on):
-    ctx.call('amt_georef_set_roles', 1 if on else 0)
-
-
-def last_roles(ctx):
-    g, i, l = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
-    ctx.call('amt_georef_last_roles', C.byref(g), C.byref(i), C.byref(l))
-    return g.value, i.value, l.value
+_GRIDS = {}
 
 
 def params(case, fast, altitude=110.0):
@@ -50,69 +30,9 @@ def params(case, fast, altitude=110.0):
     return frame_params(hdr, altitude, cam, t, fast)
 
 
-_IMAGES, _GRIDS = {}, {}
-
-
-def image(w, h, dtype):
-    if (w, h, dtype) not in _IMAGES:
-        from auromat_amd.synthetic import frame_image
-        a = np.ascontiguousarray(frame_image(w, h, seed=7, dtype=dtype))
-        import torch
-        _IMAGES[(w, h, dtype)] = torch.from_numpy(a.view(np.int16) if dtype == np.uint16 else a).cuda()
-    return _IMAGES[(w, h, dtype)]
-
-
 def launch(case, fast, second, bin_dtype, padded, roles, edges=None):
-    """amt_georef_frame of one variant -> dict(arrays as uint64 bits with the pad columns removed, bbox bits, acc, records,
-    count, variant, items per role)"""
-    import torch
-    from auromat_amd._native import GeorefOut
-    from auromat_amd.util.histogram import make_axis
-    ctx = _ctx()
-    _, w, h = case[:3]
-    out, bufs = GeorefOut(), {}
-    pitch = int(ctx._lib.amt_padded_pitch(w))
-    out.row_layout = 1 if padded else 0
-    for k in OUTPUTS[second]:
-        rows, cols = (h + 1, w + 1) if k in CORNERS else (h, w)
-        bufs[k] = torch.full((rows, pitch if padded else cols), -777.25, dtype=torch.float64, device=ctx.device)
-        setattr(out, k, bufs[k].data_ptr())
-    bbox = torch.full((8,), -1.0, dtype=torch.float64, device=ctx.device)
-    out.bbox, out.bbox_min_elevation = bbox.data_ptr(), MIN_ELEV
-    out.bin_magnetic = 1 if second == 4 else 0
-    acc = ev = counter = keep = None
-    if bin_dtype is not None:
-        xa, kx = make_axis(ctx, edges[0], uniform=True)
-        ya, ky = make_axis(ctx, edges[1], uniform=True)
-        assert xa.uniform == 1 and ya.uniform == 1
-        keep = (xa, ya, kx, ky)
-        acc = torch.zeros(5 * xa.nbin * ya.nbin, dtype=torch.int64, device=ctx.device)
-        ev = torch.zeros(32 * EVENT_ROOM, dtype=torch.uint8, device=ctx.device)
-        counter = torch.zeros(1, dtype=torch.int32, device=ctx.device)
-        out.bin_acc, out.bin_img = acc.data_ptr(), image(w, h, bin_dtype).data_ptr()
-        out.bin_img_dtype = 1 if bin_dtype == np.uint8 else 2
-        out.bin_xaxis, out.bin_yaxis = C.addressof(xa), C.addressof(ya)
-        out.bin_events, out.bin_event_count, out.bin_event_capacity = ev.data_ptr(), counter.data_ptr(), EVENT_ROOM
-    p = params(case, fast)
-    set_roles(ctx, roles)
-    try:
-        ctx.call('amt_georef_frame', C.byref(p), C.byref(out))
-        torch.cuda.synchronize()
-    finally:
-        set_roles(ctx, True)
-    res = dict(variant=ctx.last_variant(), roles=last_roles(ctx), bbox=bbox.cpu().numpy().view(np.uint64), arrays={})
-    for k, v in bufs.items():
-        x = np.arange(w + 1 if k in CORNERS else w)
-        if padded:
-            x = 64 * (x // 63) + x % 63
-        res['arrays'][k] = np.ascontiguousarray(v.cpu().numpy()[:, x]).view(np.uint64)
-    if acc is not None:
-        res['acc'] = acc.cpu().numpy()
-        res['count'] = int(counter.cpu().numpy().view(np.uint32)[0])
-        assert res['count'] <= EVENT_ROOM
-        res['records'] = np.sort(ev.cpu().numpy()[:32 * res['count']].view(EVENT_DTYPE), order=list(EVENT_DTYPE.names))
-    del keep
-    return res
+    """_band_role_cases.launch_frame on a case of this module at MIN_ELEV"""
+    return launch_frame(case[1], case[2], params(case, fast), second, bin_dtype, padded, roles, edges, MIN_ELEV)
 
 
 def grid_edges(case, fast, second):
@@ -142,17 +62,6 @@ def expected_items(case, fast, binning):
     inner, low = kinds.count('i'), kinds.count('l') if binning else 0
     earth = r['n'] - kinds.count('s')
     return tuple(int(v) * r['strips'] for v in (earth - inner - low, inner, low))
-
-
-def assert_same(tag, on, off):
-    assert on['variant'] == off['variant'], tag
-    for k in off['arrays']:
-        same = on['arrays'][k] == off['arrays'][k]
-        assert same.all(), (tag, k, 'first rows that differ', np.unique(np.argwhere(~same)[:, 0])[:8])
-    assert np.array_equal(on['bbox'], off['bbox']), (tag, on['bbox'].view(np.float64), off['bbox'].view(np.float64))
-    if 'acc' in off:
-        assert np.array_equal(on['acc'], off['acc']), (tag, 'accumulators')
-        assert on['count'] == off['count'] and np.array_equal(on['records'], off['records']), (tag, 'on-edge records')
 
 
 VARIANTS = [(fast, second, b) for fast in (True, False) for second in (0, 1, 4) for b in (None, np.uint8, np.uint16)]
