@@ -214,7 +214,9 @@ _SIGNATURES = {
     'amt_georef_coarse_bbox': ([_P, C.POINTER(FrameParams), C.c_int32, _D, _I, _P], _I),
     'amt_georef_set_roles': ([_P, _I], _I),
     'amt_georef_last_roles': ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _I),
+    'amt_georef_last_core': ([_P, C.POINTER(C.c_int64)], _I),
     'amt_georef_band_roles': ([C.POINTER(FrameParams), _D, C.POINTER(C.c_int32), C.POINTER(C.c_int32)], _I),
+    'amt_georef_core_bands': ([C.POINTER(FrameParams), _D, C.POINTER(C.c_int32)], _I),
     'amt_delaunay_create': ([_P, C.c_int64, C.POINTER(C.c_void_p)], _I),
     'amt_delaunay_destroy': ([_P], _I),
     'amt_delaunay_sizes': ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _I),
@@ -307,6 +309,7 @@ _SIGNATURES = {
     'amt_run_reset_hints': ([_P], _I),
     'amt_run_fill_stats': ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _I),
     'amt_run_role_stats': ([_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)], _I),
+    'amt_run_core_stats': ([_P, C.POINTER(C.c_int64)], _I),
     'amt_run_set_quantile': ([_P, _D], _I),
     'amt_run_set_min_coverage': ([_P, C.c_uint64], _I),
     'amt_run_area_overflow': ([_P, C.POINTER(C.c_int32), C.c_int32], _I),

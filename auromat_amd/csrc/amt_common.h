@@ -41,6 +41,8 @@ struct amt_ctx {
     int last_second, last_bin, last_frames;     // amt_georef_last_variant
     int roles_off;                    // amt_georef_set_roles(ctx, 0): every band that casts rays is generic
     long long last_role_items[3];     // amt_georef_last_roles: work items of the latest launch per role (generic, inner, low)
+    int core_off;                     // amt_georef_set_roles(ctx, 2): the roles stop at inner, no item takes the core loop
+    long long last_core_items;        // amt_georef_last_core: the inner items of the latest launch that took the core loop
     int timing;                      // 0 = off, n = bracket every n-th launch of each kind
     size_t tlaunch[2];                // launches seen per kind since timing was enabled
     int tframes[2];                   // frames covered by the timed launches
@@ -94,6 +96,7 @@ struct amt_sky_state {
     int known_top_end, known_bottom_begin;
     int bands_filled, bands_skipped;
     long long role_items[3];
+    long long core_items;
 };
 // THE launcher of the big kernel (every georeferencing entry point ends here): n <= AMT_MAX_BATCH frames, equally sized and of
 // one kernel variant in ONE launch (n launches otherwise).  dirs: NULL, or n caller-supplied corner direction arrays (all frames

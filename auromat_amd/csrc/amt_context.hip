@@ -25,6 +25,8 @@ int amt_ctx_create(int device_id, void* stream, int own_stream, amt_ctx** out_ct
     ctx->copier = nullptr;
     ctx->last_second = ctx->last_bin = ctx->last_frames = -1;
     ctx->roles_off = 0;
+    ctx->core_off = 0;
+    ctx->last_core_items = -1;
     ctx->last_role_items[0] = ctx->last_role_items[1] = ctx->last_role_items[2] = -1;
     ctx->aux_pre = ctx->aux_tail = ctx->aux_fin = nullptr;
     ctx->tlaunch[0] = ctx->tlaunch[1] = 0;
@@ -264,6 +266,7 @@ int amt_georef_last_variant(amt_ctx* ctx, int32_t* second, int32_t* bin, int32_t
 int amt_georef_set_roles(amt_ctx* ctx, int enable) {
     AMT_CHECK_CTX(ctx);
     ctx->roles_off = enable ? 0 : 1;
+    ctx->core_off = enable == 2 ? 1 : 0;
     return AMT_OK;
 }
 
@@ -272,6 +275,13 @@ int amt_georef_last_roles(amt_ctx* ctx, int64_t* generic, int64_t* inner, int64_
     if (generic) *generic = ctx->last_role_items[0];
     if (inner) *inner = ctx->last_role_items[1];
     if (low) *low = ctx->last_role_items[2];
+    return AMT_OK;
+}
+
+int amt_georef_last_core(amt_ctx* ctx, int64_t* core) {
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, core, "NULL argument");
+    *core = ctx->last_core_items;
     return AMT_OK;
 }
 

@@ -129,6 +129,9 @@ struct georef_args {
     // row step, [sky_top_end, low_top_end) and [low_bottom_begin, sky_bottom_begin) the low one, the rest the generic one
     // (amt_prm::band_roles_none(): all of them)
     int inner_begin, inner_end, low_top_end, low_bottom_begin;
+    // the inner bands [core_begin, core_end) whose middle strips (all but the first and the last) take the core loop: nothing of
+    // such an item can be an extreme of the box or leave the small-angle path (amt_prm::core_bands; 0, 0: none)
+    int core_begin, core_end;
     int bin_pole;                       // amt_georef_out.bin_pole: bin (and box) in the coordinates rotated by 90 deg about x
     int row_layout;                     // amt_georef_out.row_layout: 0 = contiguous rows, 1 = strip-padded rows
     pole_consts pole;
@@ -202,7 +205,7 @@ __device__ __forceinline__ void block_reduce8(double (&v)[8], double* __restrict
 }
 
 // roles of a work item's row step (amt_prm::band_roles); role_tag carries one into the step as a compile-time value
-constexpr int kRoleGeneric = 0, kRoleInner = 1, kRoleLow = 2;
+constexpr int kRoleGeneric = 0, kRoleInner = 1, kRoleLow = 2, kRoleCore = 3;
 template <int ROLE>
 struct role_tag {
     static constexpr int value = ROLE;
@@ -418,6 +421,13 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
     const bool col_ok = gx <= A.width;                 // this lane's corner column exists
     const bool px_ok = lane < 63 && gx < A.width;      // this lane's pixel column exists (and is owned)
     const bool want_bbox = A.bbox_partials != nullptr;
+    // core items (see the roles of the step below): the middle strips of the host's core bands.  The host rule bounds latitude and
+    // longitude only, so the variants whose box is always reduced over other coordinates have no core loop, and the host names no
+    // core band where a SECOND = 1 launch reduces it over (MLat, SM longitude) (bin_magnetic)
+    constexpr bool kHasCore = !DIRS_IN && (SECOND == 0 || SECOND == 1);
+    // (a middle strip: corner columns to either side of its 64 exist — the frame's last corner column is kept by the strip in
+    // front of the last one when that has no pixel of its own)
+    const bool core_item = kHasCore && chunk >= A.core_begin && chunk < A.core_end && strip > 0 && (strip + 1) * 63 < A.width;   // wave-uniform
 
     if (!DIRS_IN && (chunk < A.sky_top_end || chunk >= A.sky_bottom_begin)) {      // wave-uniform
         // No ray of this item reaches the shell (the host has bounded the conic section that the limb is in the image,
@@ -553,7 +563,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
         else
             __hip_atomic_fetch_max(&sBox[wave][5][lane], lo_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    if (want_bbox) {
+    if (want_bbox && !core_item) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) sBox[wave][k][lane] = (k & 1) ? -kInf : kInf;
     }
@@ -774,12 +784,14 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
         vec3 rv;
         double rxy, rla, rlo;
     };
-    // The step exists in three roles, chosen once per work item from its band (amt_prm::band_roles, wave-uniform):
+    // The step exists in four roles, chosen once per work item from its band (amt_prm::band_roles, wave-uniform):
     //   generic  the code as described above;
     //   inner    every corner ray and every centre of the item hits and every pixel passes the threshold: `hit` is "the column
     //            exists", `live` and `valid` are "the pixel exists", the box takes every owned corner — all of them fixed for the
     //            item, so the comparisons, the keep flags and the per-row count of valid pixels are not in the loop;
-    //   low      no pixel of the item reaches the threshold: no image pixel is read, no run kept, nothing enters the box.
+    //   low      no pixel of the item reaches the threshold: no image pixel is read, no run kept, nothing enters the box;
+    //   core     an inner item none of whose corners can be an extreme of the box and none of whose small-angle steps can fail
+    //            (amt_prm::core_frame_ok): no box, no keep flags, no test for the full arctangents after the item's first row.
     // The guards left out are identities in those items: every value stored and every accumulator keeps its bits.
     auto step = [&](auto role, const int r, const bool even, const vec3& dj, const row_state& prev, row_state& cur) __attribute__((always_inline)) {
         constexpr int ROLE = decltype(role)::value;
@@ -792,7 +804,8 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
         const vec3 u = corner_ray(gy, dj);
         const double uu = fx::dot3(u.x, u.y, u.z, u.x, u.y, u.z);
         const double t = shell_t(ry, u, uu);
-        const bool hit = ROLE == kRoleInner ? col_ok : (col_ok && t >= 0.0);
+        constexpr bool kAllHit = ROLE == kRoleInner || ROLE == kRoleCore;
+        const bool hit = kAllHit ? col_ok : (col_ok && t >= 0.0);
         // unit direction (what the centre's elevation averages, reference astrometry.py:154-160); caller-supplied
         // directions are used as they are, like the reference does
         vec3 d;
@@ -806,7 +819,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
         corner_vals c;
         // with bin_magnetic the bounding box is reduced over (MLat, SM longitude) as well
         const bool magbox = MAG && (kMagOnly || (BIN && !kPole && A.bin_magnetic));
-        if (ROLE == kRoleInner || __builtin_amdgcn_ballot_w64(hit) != 0) {     // wave-uniform
+        if (kAllHit || __builtin_amdgcn_ballot_w64(hit) != 0) {     // wave-uniform
             c.p = shell_point(ry, u, nan_unless(hit, t));         // already in GEO; NaN for a miss
             c.la = c.lo = c.bn = c.bd = NAN;
             if (!kMagOnly) {
@@ -815,10 +828,14 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
                 double dla, dlo;
                 bool ok;
                 fx::small_angles(prev.bd, prev.bn, c.bd, c.bn, prev.p.x, prev.p.y, c.p.x, c.p.y, small_table().c, dla, dlo, ok);
-                ok = ok && fabs(prev.lo) < 178.0;
                 c.la = prev.la + dla;
                 c.lo = prev.lo + dlo;
-                if (hit && !ok) full_angles(c.bn, c.bd, c.p.x, c.p.y, c.la, c.lo);
+                if (ROLE == kRoleCore) {
+                    if (r == 0 && hit) full_angles(c.bn, c.bd, c.p.x, c.p.y, c.la, c.lo);     // (wave-uniform but for the column test)
+                } else {
+                    ok = ok && fabs(prev.lo) < 178.0;
+                    if (hit && !ok) full_angles(c.bn, c.bd, c.p.x, c.p.y, c.la, c.lo);
+                }
             }
             c.sv = {NAN, NAN, NAN}, c.sxy = c.sml = c.ssl = NAN;
             c.rv = {NAN, NAN, NAN}, c.rxy = c.rla = c.rlo = NAN;
@@ -905,7 +922,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
                 }
             }
             // this lane's pixel exists and its centre hit the shell
-            const bool live = ROLE == kRoleInner ? px_ok : (px_ok && pc.x == pc.x);
+            const bool live = kAllHit ? px_ok : (px_ok && pc.x == pc.x);
             double lac, loc, el, ml = NAN, mt = NAN, slc = NAN, rlac = NAN, rloc = NAN;
             if (__builtin_amdgcn_ballot_w64(live) != 0) {      // wave-uniform
                 double inv_r, cn = NAN, cd = NAN;
@@ -920,10 +937,12 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
                     double dla, dlo;
                     bool ok;
                     fx::small_angles(c.bd, c.bn, cd, cn, c.p.x, c.p.y, pc.x, pc.y, small_table().c, dla, dlo, ok);
-                    ok = ok && fabs(c.lo) < 178.0;
                     lac = c.la + dla;
                     loc = c.lo + dlo;
-                    if (live && !ok) full_angles(cn, cd, pc.x, pc.y, lac, loc);
+                    if (ROLE != kRoleCore) {         // (core: a centre lies within a pixel of its corner, far from +-178 deg)
+                        ok = ok && fabs(c.lo) < 178.0;
+                        if (live && !ok) full_angles(cn, cd, pc.x, pc.y, lac, loc);
+                    }
                 }
                 // reference astrometry.py:200-212, utils.py:33-46: 90 - angle(-d, P/|P|) = asin(-d.P/|P|)
                 // (dot products do not depend on the frame; 1/|P| is a by-product of the Bowring step)
@@ -957,7 +976,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
                     at(A.mlt_c, off_pixel) = mt;
                 }
             }
-            const bool valid = ROLE == kRoleInner ? px_ok : (ROLE == kRoleLow ? false : (px_ok && (el >= min_elev) && corners_ok));
+            const bool valid = kAllHit ? px_ok : (ROLE == kRoleLow ? false : (px_ok && (el >= min_elev) && corners_ok));
             int bin_x = 0, bin_y = 0;            // 1-based bin indices of this pixel, 0 = not binned
             long long el_fix = 0;
             if (BIN && valid) {
@@ -1018,6 +1037,9 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
                 if (want_bbox && box_lane) {
                     if (kMagBox) box_add(prev.bla, prev.blo); else box_add(prev.la, prev.lo);
                 }
+            } else if (ROLE == kRoleCore) {
+                // nothing: no corner of the item can be an extreme of the box (amt_prm::core_bands); its partial is the empty box
+                // with the count of valid pixels, which is set before the loop
             } else if (ROLE == kRoleGeneric && want_bbox) {
                 // corner row gy-1 is final now: it keeps a corner when a centre above (prev.flag) or below
                 // (this row: own pixel or the left neighbour's) is valid
@@ -1037,7 +1059,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
         cur.lo = c.lo;
         cur.bn = c.bn;
         cur.bd = c.bd;
-        if (kMagBox) {
+        if (kMagBox && ROLE != kRoleCore) {
             cur.bla = c.bla;
             cur.blo = c.blo;
         }
@@ -1053,7 +1075,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
             cur.rla = c.rla;
             cur.rlo = c.rlo;
         }
-        cur.flag = flag_cur;
+        if (ROLE != kRoleCore) cur.flag = flag_cur;      // (core: nothing reads the keep flags)
     };
 
     auto advance = [&](auto role, const int r, const bool even, const row_state& prev, row_state& cur) __attribute__((always_inline)) {
@@ -1077,7 +1099,7 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
     auto march = [&](auto role) __attribute__((always_inline)) {
         constexpr int ROLE = decltype(role)::value;
         if (BIN && ROLE != kRoleLow && px_ok && rows > 0) load_pixel(img_off + img_row, rawB0, rawB1, shiftB);       // pixel row y0: step 1
-        if (ROLE == kRoleInner) n_valid = __builtin_popcountll(__builtin_amdgcn_ballot_w64(px_ok)) * rows;
+        if (ROLE == kRoleInner || ROLE == kRoleCore) n_valid = __builtin_popcountll(__builtin_amdgcn_ballot_w64(px_ok)) * rows;
         for (int r = 0; r <= rows; r += 2) {
             advance(role, r, true, S0, S1);
             if (r + 1 <= rows) advance(role, r + 1, false, S1, S0); else S0 = S1;      // the last row's state ends up in S0
@@ -1087,7 +1109,15 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
     if constexpr (DIRS_IN || kPole || kMagPole) {
         march(role_tag<kRoleGeneric>{});
     } else {
-        if (chunk >= A.inner_begin && chunk < A.inner_end)              // wave-uniform
+        bool marched = false;
+        if constexpr (kHasCore) {
+            if (core_item) {                                            // wave-uniform, like the three below
+                march(role_tag<kRoleCore>{});
+                marched = true;
+            }
+        }
+        if (marched) {
+        } else if (chunk >= A.inner_begin && chunk < A.inner_end)
             march(role_tag<kRoleInner>{});
         else if (BIN != 0 && (chunk < A.low_top_end || chunk >= A.low_bottom_begin))      // (the host names low bands with fused binning only)
             march(role_tag<kRoleLow>{});
@@ -1115,7 +1145,10 @@ __global__ __launch_bounds__(kRowsThreads, (!DIRS_IN && SECOND == 0 && BIN == 0)
             atomicAdd(&acc[4 * ncell + cell], sEl[wave][i]);
         }
     }
-    if (want_bbox) {
+    if (want_bbox && core_item) {
+        // nothing entered the box: the empty one and the item's count, without the reduction
+        if (lane < 8) A.bbox_partials[(int64_t)item * 8 + lane] = lane == 6 ? (double)n_valid : lane == 7 ? 0.0 : ((lane & 1) ? -kInf : kInf);
+    } else if (want_bbox) {
         // the chunk's last corner row only has centres above it inside this chunk
         if (kMagBox) {
             if (S0.flag && S0.bla == S0.bla) box_add(S0.bla, S0.blo);
@@ -1536,6 +1569,42 @@ amt_prm::band_role_ranges frame_roles(const georef_args& A, const launch_shape& 
     return amt_prm::band_roles(sh.chunks_y, A.sky_top_end, A.sky_bottom_begin, can_top, can_bottom, in_begin, in_end);
 }
 
+// The core bands of a camera frame with the inner bands [in_begin, in_end) (amt_prm::core_frame_ok / core_bands): the cone of
+// inner_bands() about the sub-satellite point, and the smallest and the largest angle a pixel step spans.  The ray of pixel
+// (x, y) is u0 + x ux + y uy, a point of the TAN plane (in degrees): a step along the unit vector t of the plane moves it by
+// |ux tx + uy ty| — between the two singular values of (ux, uy) —, which the ray at the angle theta off the plane's normal, D / cos
+// theta long (D: the plane's distance), turns by that times between cos^2 theta / D (towards the normal) and cos theta / D.
+void core_range(const georef_args& A, const launch_shape& sh, double min_elev_deg, int in_begin, int in_end, int* begin, int* end) {
+    *begin = *end = 0;
+    const shell_ray& e = A.sray;
+    if (in_end - in_begin < 3 || !(e.root_sign < 0) || min_elev_deg != min_elev_deg || std::isinf(min_elev_deg)) return;
+    const affine_cam& c = A.cam;
+    const double xx = c.ux[0] * c.ux[0] + c.ux[1] * c.ux[1] + c.ux[2] * c.ux[2], yy = c.uy[0] * c.uy[0] + c.uy[1] * c.uy[1] + c.uy[2] * c.uy[2];
+    const double xy = c.ux[0] * c.uy[0] + c.ux[1] * c.uy[1] + c.ux[2] * c.uy[2];
+    const double mean = 0.5 * (xx + yy), dev = std::sqrt(0.25 * (xx - yy) * (xx - yy) + xy * xy);
+    if (!(mean - dev > 0)) return;
+    const double n[3] = {c.ux[1] * c.uy[2] - c.ux[2] * c.uy[1], c.ux[2] * c.uy[0] - c.ux[0] * c.uy[2], c.ux[0] * c.uy[1] - c.ux[1] * c.uy[0]};
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    double dist = 0, cos_min = 1.0;           // distance of the plane from the origin, smallest cos theta among the frame's corners
+    for (int k = 0; k < 4; ++k) {
+        const double px = ((k & 1) ? (double)A.width : 0.0) + c.cx, py = ((k & 2) ? (double)A.height : 0.0) + c.cy;
+        const double u[3] = {c.u0[0] + px * c.ux[0] + py * c.uy[0], c.u0[1] + px * c.ux[1] + py * c.uy[1], c.u0[2] + px * c.ux[2] + py * c.uy[2]};
+        const double un = std::fabs(u[0] * n[0] + u[1] * n[1] + u[2] * n[2]) / nn, uu = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        dist = un;
+        cos_min = std::min(cos_min, un / uu);
+    }
+    if (!(dist > 0) || !(cos_min > 0.2)) return;
+    amt_prm::core_frame f;
+    f.cam_r = std::sqrt(e.ox * e.ox + e.oy * e.oy + e.oz * e.oz);
+    f.r_min = 1.0 / std::sqrt(std::max(e.qa, e.qa + e.qd));
+    f.e0_deg = std::max(min_elev_deg, 0.0) + 0.05;             // as inner_bands() takes it
+    f.lat_s_deg = std::asin(e.oz / f.cam_r) * kRad2Deg;
+    f.lon_s_deg = std::atan2(e.oy, e.ox) * kRad2Deg;
+    f.s_hi = std::sqrt(mean + dev) / dist;
+    f.s_lo = std::sqrt(mean - dev) / dist * cos_min * cos_min;
+    amt_prm::core_bands(in_begin, in_end, amt_prm::core_frame_ok(f), begin, end);
+}
+
 // The camera-model constants of a frame: the TAN WCS, the GEO-frame affine camera and shell ray (camera model and shell composed
 // with M = J2000 -> GEO, what k_georef_rows and the band rules work with) and the frame's size
 void camera_model(const amt_frame_params* p, georef_args* A) {
@@ -1562,6 +1631,7 @@ struct prepared_frame {
     int second;         // k_georef_rows' SECOND
     int bin;
     int role_bands[3];  // bands that cast rays, per role: generic, inner, low (amt_prm::band_role_counts)
+    long long core_items;   // work items that take the core loop (counted among the inner ones above)
 };
 
 // sky (optional): what the frame's arrays already hold as NaN on entry, the frame's own sky rows and what was written of
@@ -1712,9 +1782,17 @@ int prepare_georef(amt_ctx* ctx, const amt_frame_params* p, const double* dirs, 
     if (!ctx->roles_off && dirs == nullptr && F->second != 2 && F->second != 3) roles = frame_roles(A, sh, out->bbox_min_elevation, bin != 0);
     A.inner_begin = roles.inner_begin, A.inner_end = roles.inner_end;
     A.low_top_end = roles.low_top_end, A.low_bottom_begin = roles.low_bottom_begin;
+    // core bands: the variants with a core loop (k_georef_rows' kHasCore) whose box is reduced over (lat, lon)
+    A.core_begin = A.core_end = 0;
+    if (!ctx->roles_off && !ctx->core_off && dirs == nullptr && (F->second == 0 || F->second == 1) && !A.bin_magnetic)
+        core_range(A, sh, out->bbox_min_elevation, roles.inner_begin, roles.inner_end, &A.core_begin, &A.core_end);
     amt_prm::band_role_counts(roles, A.sky_top_end, A.sky_bottom_begin, F->role_bands);
-    if (sky != nullptr)
+    // (core items count as inner ones in the three counts; their own count goes beside them)
+    F->core_items = (int64_t)(A.core_end - A.core_begin) * std::max((p->width - 1) / 63 - 1, 0);      // strips s >= 1 with 63 (s + 1) < width
+    if (sky != nullptr) {
         for (int k = 0; k < 3; ++k) sky->role_items[k] = (int64_t)F->role_bands[k] * sh.strips_x;
+        sky->core_items = F->core_items;
+    }
     return AMT_OK;
 }
 
@@ -1752,6 +1830,8 @@ int launch_prepared(amt_ctx* ctx, int n, prepared_frame* F) {
         ctx->last_role_items[k] = 0;
         for (int i = 0; i < n; ++i) ctx->last_role_items[k] += (int64_t)F[i].role_bands[k] * strips_x;
     }
+    ctx->last_core_items = 0;
+    for (int i = 0; i < n; ++i) ctx->last_core_items += F[i].core_items;
     for (int i = 0; i < kMaxBatch; ++i) B.f[i] = F[i < n ? i : 0].A;
     B.math = fx::make_math_table();
     if (dirs) {
@@ -1931,6 +2011,22 @@ int amt_georef_band_roles(const amt_frame_params* p, double min_elevation, int32
     ranges8[2] = A.sky_top_end, ranges8[3] = A.sky_bottom_begin;
     ranges8[4] = r.low_top_end, ranges8[5] = r.low_bottom_begin;
     ranges8[6] = r.inner_begin, ranges8[7] = r.inner_end;
+    return AMT_OK;
+}
+
+int amt_georef_core_bands(const amt_frame_params* p, double min_elevation, int32_t* core2) {
+    if (p == nullptr || core2 == nullptr) return AMT_EINVAL;
+    if (p->width <= 0 || p->height <= 0) return AMT_EINVAL;
+    georef_args A;
+    std::memset(&A, 0, sizeof(A));
+    camera_model(p, &A);
+    const launch_shape sh = shape_of(p);
+    A.sky_top_end = 0, A.sky_bottom_begin = sh.chunks_y;
+    sky_bands(A, sh, &A.sky_top_end, &A.sky_bottom_begin);
+    const amt_prm::band_role_ranges r = frame_roles(A, sh, min_elevation, true);
+    int begin = 0, end = 0;
+    core_range(A, sh, min_elevation, r.inner_begin, r.inner_end, &begin, &end);
+    core2[0] = begin, core2[1] = end;
     return AMT_OK;
 }
 

@@ -384,6 +384,89 @@ inline void band_role_counts(const band_role_ranges& r, int t, int b, int* count
     counts[0] = (b - t) - counts[1] - counts[2];
 }
 
+// ---- core bands -------------------------------------------------------------------------------------------------------------------
+// An inner band whose two neighbours are inner as well is a CORE band when the frame passes core_frame_ok().  The middle strips of a
+// core band (all but the first and the last) are core items: the kernel's core loop leaves out the bounding box, the keep flags
+// and the test that sends a corner or a centre to the full arctangents from the second row of an item on.  What has to hold
+// for every corner of such an item, its eight neighbours on the pixel lattice included (they lie in inner bands and inside the frame):
+//   (a) none of them is an extreme of the box: each has a strictly larger and a strictly smaller neighbour in latitude and in
+//       longitude, and the longitudes have one sign (the box keeps the smallest positive and the largest non-positive one);
+//   (b) every small-angle step passes: steps far below the 1.7 deg limit, longitudes inside +-178 deg.
+// The rule is decided for the whole frame from the cone about the nadir that inner_bands() proves the inner bands to lie in:
+// nadir angles up to eta_k = asin(k), k = r_min / |C| cos e0, whose rays hit within the ground angle g_k = 90 deg - e0 - eta_k
+// of the sub-satellite point (law of sines on the sphere of radius r_min, which gives the largest angle).  With the
+// sub-satellite point at geocentric latitude lat_s and longitude lon_s:
+//   latitude    |lat| <= |lat_s| + g_k + 0.5 deg (geodetic against geocentric latitude: 0.2 deg; the shell's flattening) must stay
+//               below kCoreMaxLat;
+//   longitude   |lon - lon_s| <= dl, sin dl = sin g_k / cos(lat bound) (a cap on the sphere); that range, widened by 1 deg and by
+//               one step, must hold neither 0 nor +-180 deg and lie inside +-178 deg;
+//   steps       the ground moves by at most gamma'(eta_k) s_hi per pixel (s_lo, s_hi: the smallest and the largest angle a pixel
+//               step spans anywhere in the frame, rad), a longitude by 1 / cos(lat bound) of that: below 0.01 rad, a third of the
+//               limit of fx::small_angles;
+//   (a)         f(x + h) - f(x) = grad f . h + h' H h / 2 on the lattice: among the eight neighbours one has grad f . h >=
+//               |grad f| / sqrt 2, its opposite the negative of that, and |h|^2 <= 2, so |grad f| > sqrt 2 |H| is enough.  Along the
+//               chain pixel -> ray (TAN plane) -> ground (nadir angle eta -> ground angle gamma(eta), sin(eta + gamma) = R sin eta,
+//               R = |C| / r_min) -> angle, per unit of |grad f| on the ground: the gradient is at least s_lo sin gamma / sin eta, the
+//               second derivative at most s_hi^2 (2 tan(lat bound) gamma'^2 + 2 gamma'' + 2 gamma') (the curvature of parallels and
+//               meridians; the ground map; the TAN plane).  gamma', gamma'' and sin gamma / sin eta grow with eta, so the cone is cut into
+//               kCoreRings rings, each with the gradient of its inner and the second derivative of its outer edge, and
+//               the rule asks for a factor kCoreFactor (4, where sqrt 2 would do) in every ring.
+constexpr double kCoreMaxLat = 75.0;       // degrees
+constexpr double kCoreFactor = 4.0;
+constexpr int kCoreRings = 8;
+
+struct core_frame {
+    double cam_r, r_min;        // |C| and the shell's smaller semi-axis (same unit)
+    double e0_deg;              // the elevation the inner cone ends at (inner_bands: threshold + margin)
+    double lat_s_deg, lon_s_deg;
+    double s_lo, s_hi;          // rad per pixel step
+};
+
+inline bool core_frame_ok(const core_frame& f) {
+    if (!(f.cam_r > f.r_min) || !(f.r_min > 0) || !(f.s_lo > 0) || !(f.s_hi >= f.s_lo) || !(f.e0_deg > 0 && f.e0_deg < 89.0)) return false;
+    if (!std::isfinite(f.lat_s_deg) || !std::isfinite(f.lon_s_deg)) return false;
+    const double big_r = f.cam_r / f.r_min;
+    const double k = std::cos(f.e0_deg * kDeg2Rad) / big_r;
+    if (!(k > 0.0 && k < 1.0)) return false;
+    const double eta_k = std::asin(k);
+    const double g_k = 90.0 - f.e0_deg - eta_k / kDeg2Rad;
+    if (!(g_k > 0)) return false;
+    const double lat_hi = std::fabs(f.lat_s_deg) + g_k + 0.5;
+    if (!(lat_hi < kCoreMaxLat)) return false;
+    const double cos_lat = std::cos(lat_hi * kDeg2Rad), tan_lat = std::tan(lat_hi * kDeg2Rad);
+    const double sin_dl = std::sin((g_k + 0.5) * kDeg2Rad) / cos_lat;
+    if (!(sin_dl < 1.0)) return false;
+    auto slope = [&](double eta) { return big_r * std::cos(eta) / std::cos(std::asin(big_r * std::sin(eta))) - 1.0; };    // gamma'
+    auto second = [&](double eta) {                                                                                         // gamma''
+        const double a = std::asin(big_r * std::sin(eta)), ca = std::cos(a);
+        return big_r * (std::cos(eta) * std::sin(a) * (1.0 + slope(eta)) - std::sin(eta) * ca) / (ca * ca);
+    };
+    auto across = [&](double eta) {                                                                                         // sin gamma / sin eta
+        return eta > 0 ? std::sin(std::asin(big_r * std::sin(eta)) - eta) / std::sin(eta) : big_r - 1.0;
+    };
+    const double step = slope(eta_k) * f.s_hi / cos_lat;          // rad of longitude per pixel step, at most
+    if (!(step < 0.01)) return false;
+    // ... and at least 1e-9 rad of ground angle: the box also takes an item's last corner row as its own chain of small angles
+    // gives it, some 1e-13 deg from the value the item below stores for the same corner, which must stay far below a lattice step
+    if (!(f.s_lo * across(0.0) > 1e-9)) return false;
+    const double dl = std::asin(sin_dl) / kDeg2Rad + 1.0 + step / kDeg2Rad;
+    const double lo = f.lon_s_deg - dl, hi = f.lon_s_deg + dl;
+    if (!(lo > -178.0 && hi < 178.0) || (lo <= 0.0 && hi >= 0.0)) return false;
+    for (int i = 0; i < kCoreRings; ++i) {
+        const double e_in = eta_k * i / kCoreRings, e_out = eta_k * (i + 1) / kCoreRings;
+        const double g1 = slope(e_out), g2 = second(e_out);
+        if (!(f.s_lo * across(e_in) > kCoreFactor * f.s_hi * f.s_hi * (2.0 * tan_lat * g1 * g1 + 2.0 * g2 + 2.0 * g1))) return false;
+    }
+    return true;
+}
+
+// the core bands among the inner bands [in_begin, in_end) of a frame that passes: those with an inner band on either side (so
+// never the frame's first or last band); (0, 0) when there is none
+inline void core_bands(int in_begin, int in_end, bool frame_ok, int* begin, int* end) {
+    *begin = *end = 0;
+    if (frame_ok && in_end - in_begin >= 3) *begin = in_begin + 1, *end = in_end - 1;
+}
+
 // ---- map projections ----------------------------------------------------------------------------------------------------------
 // The constants of amt_project_forward / amt_project_inverse (csrc/amt_project.hip), computed once per projection.  Snyder, Map
 // Projections - A Working Manual, ch. 21 (stereographic, ellipsoid) and 25 (azimuthal equidistant, polar, sphere).

@@ -90,6 +90,7 @@ struct amt_run {
     hipStream_t launch_stream = nullptr;    // the stream of the latest launch (slot::known)
     int64_t bands_filled = 0, bands_skipped = 0;    // amt_run_fill_stats: since the last amt_run_begin
     int64_t role_items[3] = {0, 0, 0};              // amt_run_role_stats: likewise (generic, inner, low)
+    int64_t core_items = 0;                         // amt_run_core_stats: likewise (the inner items that took the core loop)
 
     slot& slot_of(int k) { return slots[k % cfg.n_slots]; }
 };
@@ -273,6 +274,12 @@ int amt_run_role_stats(amt_run* run, int64_t* generic, int64_t* inner, int64_t* 
     return AMT_OK;
 }
 
+int amt_run_core_stats(amt_run* run, int64_t* core) {
+    if (run == nullptr || core == nullptr) return AMT_EINVAL;
+    *core = run->core_items;
+    return AMT_OK;
+}
+
 int amt_run_reset_hints(amt_run* run) {
     if (run == nullptr) return AMT_EINVAL;
     forget_hints(run);
@@ -359,6 +366,7 @@ int launch_slots(amt_run* run, const int* slots, int m, bool nothing_known = fal
         run->slots[slots[j]].known = {sky[j].known_top_end, sky[j].known_bottom_begin};
         run->bands_filled += sky[j].bands_filled, run->bands_skipped += sky[j].bands_skipped;
         for (int k = 0; k < 3; ++k) run->role_items[k] += sky[j].role_items[k];
+        run->core_items += sky[j].core_items;
     }
     return AMT_OK;
 }
@@ -748,6 +756,7 @@ int amt_run_begin(amt_run* run, double* grids, int64_t grids_capacity, void* ima
     run->launch_stream = ctx->stream;
     run->bands_filled = run->bands_skipped = 0;
     run->role_items[0] = run->role_items[1] = run->role_items[2] = 0;
+    run->core_items = 0;
     run->active = true;
     return AMT_OK;
 }

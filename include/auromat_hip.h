@@ -51,7 +51,9 @@ extern "C" {
  *    amt_projection_stereographic, amt_projection_polar_aeqd, amt_project_forward, amt_project_inverse
  *    (auromat_amd.coordinates.projection) — and area-weighted binning on a map plane — amt_area_plane_frame
  *    (auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT, resampleMLatMLTPolar); scan-line maps —
- *    amt_scanline_select, amt_scanline_pack, amt_scanline_compose, amt_scanline_strip (auromat_amd.resample.resampleScanLines) */
+ *    amt_scanline_select, amt_scanline_pack, amt_scanline_compose, amt_scanline_strip (auromat_amd.resample.resampleScanLines);
+ *    the core role of the frame kernel's work items — amt_georef_last_core, amt_georef_core_bands, amt_run_core_stats,
+ *    amt_georef_set_roles(ctx, 2) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -144,6 +146,18 @@ int amt_georef_set_roles(amt_ctx* ctx, int enable);
 int amt_georef_last_roles(amt_ctx* ctx, int64_t* generic, int64_t* inner, int64_t* low);
 struct amt_frame_params;
 int amt_georef_band_roles(const struct amt_frame_params* p, double min_elevation, int32_t* rows_per_item, int32_t* ranges8);
+/* Core items (additions to ABI 10; csrc/amt_params.h amt_prm::core_frame_ok): inner rows of work items with an inner
+ * row on either side, in a frame whose inner cone stays below 75 deg of latitude, clear of longitude 0 and +-180 deg, and whose
+ * pixels are small enough for latitude and longitude to have no extreme on the pixel lattice there.  Their work items, but for the
+ * first and the last of each row, take the core loop of the row step: no bounding box (none of their corners can be an extreme of
+ * it), no keep flags, small angles without the test for the full arctangents after an item's first row.  Camera-model launches with a
+ * finite bbox_min_elevation whose box is reduced over (lat, lon) only; results do not depend on it, bit for bit.
+ * amt_georef_set_roles(ctx, 2): the roles stop at inner (A/B runs, tests).  Core items count as inner in amt_georef_last_roles and
+ * amt_run_role_stats; amt_georef_last_core / amt_run_core_stats give their own count (-1 before the first launch / since the
+ * last amt_run_begin).  amt_georef_core_bands (no context, no GPU call): core2 = the core rows of work items [begin, end) the rule
+ * names for frame p and the threshold (0, 0: none). */
+int amt_georef_last_core(amt_ctx* ctx, int64_t* core);
+int amt_georef_core_bands(const struct amt_frame_params* p, double min_elevation, int32_t* core2);
 
 /* ---- per-frame parameter block --------------------------------------------------------
  * Host scalars the reference derives once per frame:
@@ -1300,6 +1314,8 @@ int amt_run_fill_stats(amt_run* run, int64_t* bands_filled, int64_t* bands_skipp
 /* Work items that cast rays, per role (amt_georef_last_roles), of the launches since the last amt_run_begin (a frame launched
  * twice counts twice; addition to ABI 10).  Each pointer may be NULL. */
 int amt_run_role_stats(amt_run* run, int64_t* generic, int64_t* inner, int64_t* low);
+/* Likewise the inner items that took the core loop (amt_georef_last_core) */
+int amt_run_core_stats(amt_run* run, int64_t* core);
 /* Forget the box hints (the next frame gets a coarse pre-pass). */
 int amt_run_reset_hints(amt_run* run);
 /* Quantile sequences: the median pass of a runner created with statistic = 1 becomes a one-quantile pass — the frames it covers
