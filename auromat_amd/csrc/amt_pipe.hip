@@ -18,6 +18,7 @@ struct amt_pipe {
                                    // so it must not queue behind another frame's folds, which do wait
                                    // (all three owned by the context and shared with its other drivers)
     hipEvent_t coarse_done, kernel_done, bbox_done, tail_done;
+    hipEvent_t dirs_ready;         // the context's stream where a caller's direction array is handed to the pre-pass
     double* host_small;            // pinned host memory: [0..7] coarse bbox, [8..15] exact bbox
     double* host_small_dev;        // the same 16 doubles as the kernels address them (the folds write them directly)
     void* events;                  // on-edge pixels of the frame in flight (bin_event records, device)
@@ -140,6 +141,7 @@ int amt_pipe_create(amt_ctx* ctx, amt_pipe** out_pipe) {
               hipEventCreate(&pipe->kernel_done) == hipSuccess &&
               hipEventCreateWithFlags(&pipe->bbox_done, hipEventDisableTiming) == hipSuccess &&
               hipEventCreateWithFlags(&pipe->tail_done, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&pipe->dirs_ready, hipEventDisableTiming) == hipSuccess &&
               hipMalloc(&pipe->events, AMT_PIPE_MAX_EDGE_PIXELS * 32) == hipSuccess &&
               // (zeroed on the context's stream before the first fused launch, see pipe_prepare: a memset on the null stream
               // here is not ordered against the context's non-blocking stream and may run late when processes share the GPU)
@@ -165,6 +167,7 @@ int amt_pipe_destroy(amt_pipe* pipe) {
     if (pipe->kernel_done) (void)hipEventDestroy(pipe->kernel_done);
     if (pipe->bbox_done) (void)hipEventDestroy(pipe->bbox_done);
     if (pipe->tail_done) (void)hipEventDestroy(pipe->tail_done);
+    if (pipe->dirs_ready) (void)hipEventDestroy(pipe->dirs_ready);
     if (pipe->partials) (void)hipFree(pipe->partials);
     if (pipe->events) (void)hipFree(pipe->events);
     if (pipe->event_count) (void)hipFree(pipe->event_count);
@@ -184,6 +187,13 @@ int pipe_coarse(amt_pipe* pipe, const amt_frame_params* p, double min_elevation,
     // the pre-pass runs on the driver's own stream (and with that stream's workspace, see amt_workspace): the
     // context's stream is busy with the previous frames' kernels
     hipStream_t saved = ctx->stream;
+    if (dirs != nullptr) {
+        // the caller made the direction array on the context's stream (an upload, a kernel of its own camera model): the
+        // pre-pass reads it on another stream and starts behind what the context's stream holds now.  The camera model has no
+        // device input: no packet there.
+        AMT_HIP(ctx, hipEventRecord(pipe->dirs_ready, saved));
+        AMT_HIP(ctx, hipStreamWaitEvent(pipe->pre_stream, pipe->dirs_ready, 0));
+    }
     ctx->stream = pipe->pre_stream;
     const double thr = std::isinf(min_elevation) ? min_elevation : min_elevation - 0.5;
     const int shorter = p->width < p->height ? p->width : p->height;

@@ -14,7 +14,16 @@
  *    C-contiguous, float64 unless stated; small fixed-size parameter blocks
  *    (3-vectors, 3x3 matrices, amt_frame_params) are HOST pointers;
  *  - kernels are enqueued on the context's stream and the call returns without
- *    synchronising unless documented ("synchronises");
+ *    synchronising unless documented ("synchronises"): device inputs are read, and device
+ *    outputs written, in the order of that stream.  The exceptions are ordered against it by
+ *    the library, except where named: amt_upload_staged / amt_download_staged copy on streams
+ *    of their own between two events on the context's stream; the frame driver (amt_pipe_*)
+ *    runs its pre-pass, its box folds and amt_pipe_finalize[_many] on streams of the context's
+ *    own — the pre-pass of amt_pipe_coarse_dirs starts behind the context's stream, the folds
+ *    behind the frame kernel, and the finalise kernel's OUTPUTS are ordered for the context's
+ *    stream only by amt_pipe_join (see amt_pipe_finalize_stream for their allocation); the
+ *    sequence runner (amt_run_*) uploads page-locked host images on a copy stream and joins
+ *    every finalise kernel in amt_run_end.  DESIGN.md 4.3 has the table;
  *  - the caller owns every buffer; the library keeps no global state and contexts
  *    may be used from different threads (one thread per context at a time);
  *  - missing data is NaN (reference convention: intersection.py:50-56), never an error.
@@ -1099,7 +1108,12 @@ int amt_pipe_launch(amt_pipe* pipe, const amt_frame_params* p, const amt_georef_
  * block is not).  There is no camera model to project a pole through: pole_in_view 0 / 1 is the caller's decision (1: the
  * frame is not fused, amt_pipe_wait returns status 1), < 0 = unknown — then a frame whose estimated or exact box comes
  * within 5 deg of a pole of its grid's coordinates is handed back with status 1 and the caller decides from the corner
- * arrays (amt_bbox_corners counts the quads that wind around a pole). */
+ * arrays (amt_bbox_corners counts the quads that wind around a pole).
+ * Ordering: corner_dirs is the one device input a pre-pass has.  amt_pipe_coarse_dirs (and the pre-pass amt_pipe_launch_dirs
+ * starts when none is pending) records an event on the context's stream and lets the pre-pass stream wait for it, so the
+ * array may come from work that is still queued on the context's stream (an upload, a kernel of the caller's camera model).
+ * amt_pipe_launch_dirs waits on the host for the estimate, hence for that work.  amt_pipe_coarse has no device input and
+ * puts no such packet on either stream. */
 int amt_pipe_coarse_dirs(amt_pipe* pipe, const amt_frame_params* p, const double* corner_dirs, double min_elevation,
                          int magnetic);
 int amt_pipe_launch_dirs(amt_pipe* pipe, const amt_frame_params* p, const double* corner_dirs, const amt_georef_out* out,
