@@ -143,6 +143,17 @@ class LensDebug(C.Structure):
     _fields_ = [('force_path', C.c_int32), ('reserved', C.c_int32), ('tile_path', C.c_void_p)]
 
 
+class GatherMember(C.Structure):
+    """amt_gather_member"""
+    _fields_ = [('params', FrameParams), ('zenithal', C.POINTER(ZenithalWcs)), ('img', C.c_void_p), ('center_mask', C.c_void_p),
+                ('min_elevation', C.c_double)]
+
+
+class GatherDebug(C.Structure):
+    """amt_gather_debug"""
+    _fields_ = [('force_path', C.c_int32), ('reserved', C.c_int32), ('tile_path', C.c_void_p)]
+
+
 ABI_VERSION = 10         # include/auromat_hip.h AMT_ABI_VERSION
 QUANTILES_MAX = 8         # AMT_QUANTILES_MAX: quantiles per call of amt_quantile_frame[_async]
 PIPE_MAX_EDGE_PIXELS = 16384     # AMT_PIPE_MAX_EDGE_PIXELS: a fused frame with more on-edge pixels is not launched again
@@ -189,6 +200,8 @@ _SIGNATURES = {
     'amt_world_to_pixel': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, _P, _L, _P, _P, _P], _I),
     'amt_grid_to_pixel': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P,
                            _P], _I),
+    'amt_gather_mosaic': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
+                          [C.c_int32] * 4 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
     'amt_intersect_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersects_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersect_sphere': ([_P, _D, c_double_p, _P, _L, _I, _P], _I),

@@ -2100,8 +2100,8 @@ def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magne
     asked for its bounding box, and its centre mask (a device tensor) goes into the plan.
     """
     if not isinstance(mapping, BaseMapping):
-        raise NotImplementedError('resampleGather takes one mapping; gather mosaics of collections or lists are not built '
-                                  '(resampleMosaic bins a collection onto one grid)')
+        raise NotImplementedError('resampleGather takes one mapping; collections or lists are gathered onto one grid by '
+                                  'resampleGatherMosaic')
     params, zen = mapping._inverse_model()
     ctx = Context.current()
     plan = dict(altitude=mapping.altitude, params=params, zenithal=zen, min_elevation=None, center_mask=None)
@@ -2222,7 +2222,8 @@ def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, in
     remembers is applied as that threshold, without computing the frame's arrays.  ``.elevation`` of the result is the exact
     line-of-sight elevation of each cell centre.
 
-    For mappings with a zenithal (+ SIP) WCS camera model; ``NotImplementedError`` for collections and lists, for mappings
+    For mappings with a zenithal (+ SIP) WCS camera model; ``NotImplementedError`` for collections and lists
+    (:func:`resampleGatherMosaic` gathers those onto one grid), for mappings
     made from a bare direction array or a raw frame with a lens, and for MIRACLE / THEMIS.
 
     :param interpolation: 'nearest', 'linear' or 'lanczos4'
@@ -2235,3 +2236,223 @@ def resampleGatherMLatMLT(mapping, **kw):
     """:func:`resampleGather` on the (MLat, SM longitude) grid of :func:`resampleMLatMLT`; see there for the parameters."""
     return _resample_gather(mapping, kw.pop('pxPerDeg', 25), kw.pop('arcsecPerPx', None), kw.pop('containsPole', None),
                             kw.pop('interpolation', 'linear'), True, **kw)
+
+
+# ---- gather mosaics: a collection gathered onto one grid, one fused kernel ---------------------------------------------------------
+_GATHER_INTERP_CODES = {'linear': 0, 'lanczos4': 1, 'nearest': 2}      # AMT_INTERP_LINEAR / _LANCZOS4 / _NEAREST
+GATHER_PATH_AUTO, GATHER_PATH_STAGED, GATHER_PATH_CELL = 0, 1, 2      # AMT_GATHER_PATH_*
+
+
+def _gather_collection(collection):
+    """A list of mappings is a collection whose members may overlap."""
+    if isinstance(collection, MappingCollection):
+        return collection
+    if isinstance(collection, BaseMapping):
+        return MappingCollection([collection], collection.identifier, mayOverlap=True)
+    members = list(collection)
+    return MappingCollection(members, members[0].identifier if members else None, mayOverlap=True)
+
+
+def gather_mosaic_plan(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magnetic=False):
+    """
+    The host side of :func:`resampleGatherMosaic`: checks the members the way :func:`mosaic_plan` does (not empty, equal
+    altitudes, equal image dtype and channel count), asks every member for its camera model (``_inverse_model``; its
+    ``NotImplementedError`` passes through with the member's identifier) and lays out the common grid: :func:`mosaic_layout`
+    of the members' boxes, which is :func:`resample`'s grid for the merged box, date-line rule included.  A camera mapping
+    whose arrays do not exist gets its box from the box pass of the frame kernel and keeps a remembered ``maskedByElevation``
+    as its threshold, as in :func:`gather_plan`; any other member is asked for ``boundingBox`` and its centre mask goes along.
+    With a pole in view (`containsPole` True, or None and a member's box pass or ``containsPole`` says so) the layout is
+    :func:`mosaic_plan`'s pole layout, from the members' rotated outlines.
+
+    :return: mosaic_layout's dict plus altitude, contains_pole, contains_discontinuity, rule, identifiers and members: a list
+             of dict(params, zenithal, min_elevation, center_mask, image)
+    """
+    collection = _gather_collection(collection)
+    mappings = list(collection.mappings)
+    if not mappings:
+        raise ValueError('resampleGatherMosaic: the collection %r is empty' % (collection.identifier,))
+    altitudes = [m.altitude for m in mappings]
+    if any(a != altitudes[0] for a in altitudes):
+        raise ValueError('resampleGatherMosaic: the members differ in altitude: %s' %
+                         ', '.join('%s: %s km' % (m.identifier, m.altitude) for m in mappings))
+    images = [_gather_image(m) for m in mappings]
+    kinds = [(np.dtype(im.dtype), 1 if np.ndim(im) == 2 else int(np.shape(im)[2])) for im in images]
+    if any(k != kinds[0] for k in kinds):
+        raise ValueError('resampleGatherMosaic: the members differ in image dtype or channel count: %s' %
+                         ', '.join('%s: %s x %d' % (m.identifier, k[0], k[1]) for m, k in zip(mappings, kinds)))
+    models = []
+    for m in mappings:
+        try:
+            models.append(m._inverse_model())
+        except NotImplementedError as e:
+            raise NotImplementedError('resampleGatherMosaic: member %s: %s' % (m.identifier, e))
+    altitude = altitudes[0]
+    # the box pass for camera mappings whose arrays do not exist
+    reductions = []
+    for m, (params, zen) in zip(mappings, models):
+        red = None
+        if zen is None and getattr(m, '_frame', True) is None:
+            red = _gather_box(Context.current(), params, getattr(m, '_lazy_elev', None), magnetic)
+        reductions.append(red)
+    arrays = [None if red is not None else (convertMappingToSM(m) if magnetic else m) for m, red in zip(mappings, reductions)]
+    if containsPole is None:
+        pole = any(bool(red[7]) if red is not None else bool(src.containsPole) for red, src in zip(reductions, arrays))
+    else:
+        pole = bool(containsPole)
+    if pole:
+        # the rotated grid is laid out from the members' outlines: every member's arrays
+        reductions = [None] * len(mappings)
+        arrays = [convertMappingToSM(m) if magnetic else m for m in mappings]
+    from .mapping.mapping import bounding_box_from_reduction
+    boxes, members = [], []
+    for m, (params, zen), red, src, image in zip(mappings, models, reductions, arrays, images):
+        member = dict(params=params, zenithal=zen, min_elevation=None, center_mask=None, image=image)
+        if red is not None:
+            boxes.append(bounding_box_from_reduction(red))
+            member.update(min_elevation=getattr(m, '_lazy_elev', None))
+        else:
+            boxes.append(src.boundingBox)
+            member.update(center_mask=src.frame().center_mask_tensor())
+        members.append(member)
+    poleBoxes = None
+    if pole:
+        poleBoxes = []
+        for src in arrays:
+            outline = np.asarray(src.outline, dtype=np.float64)
+            ola, olo = _rotate_pole_host(outline[:, 0], outline[:, 1], altitude, 90)
+            poleBoxes.append((ola.min(), ola.max(), olo.min(), olo.max()))
+    plan = mosaic_layout(boxes, pxPerDeg, arcsecPerPx, poleBoxes)
+    plan.update(altitude=altitude, contains_pole=plan['pole'], contains_discontinuity=plan['discontinuity'],
+                rule=1 if collection.mayOverlap else 0, members=members, identifiers=[m.identifier for m in mappings])
+    return plan
+
+
+def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=False, debug=None, xy=False):
+    """
+    The device side of :func:`resampleGatherMosaic` on a :func:`gather_mosaic_plan`: ONE call of ``amt_gather_mosaic``
+    (include/auromat_hip.h states what it computes), which projects every cell centre through every member's camera model,
+    elects one member per cell by the plan's rule and samples that member's image alone.  With a pole in view the centres of
+    the rotated grid are rotated back on the host and go in through the point form, as in :func:`gather_frame`.
+
+    :param images: one image per member (default: the plan's)
+    :param debug: dict(force_path=GATHER_PATH_*, tile_path=True): amt_gather_debug; the result then holds ``tile_path``
+                  (tiles_y, tiles_x) uint8
+    :param xy: also return ``xy`` (ny, nx, 2) float64, the winner's pixel coordinates
+    :return: dict like :func:`mosaic_frames`': lat, lon, lat_c, lon_c, img (ny, nx, C), mask (ny, nx) bool, elevation (ny, nx;
+             the winner's, NaN where nobody sees the cell), source (ny, nx) int32 [-1: nobody], plan
+    """
+    import torch
+    from ._native import GatherDebug, GatherMember
+    from .coordinates.inverse import W2P_GEODETIC, W2P_SM
+    from .util.lensdistortion import _image_to_device
+    _check_gather_interpolation(interpolation)
+    ctx = Context.current()
+    grid, members = plan['grid'], plan['members']
+    images = [m['image'] for m in members] if images is None else list(images)
+    if len(images) != len(members):
+        raise ValueError('%d images for %d members' % (len(images), len(members)))
+    table = (GatherMember * len(members))()
+    keep, kinds, np_dtype = [], set(), None
+    for t, m, image in zip(table, members, images):
+        src, np_dtype, _ = _image_to_device(ctx, image)
+        h, w, nch = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+        if (w, h) != (m['params'].width, m['params'].height):
+            raise ValueError('the image is %d x %d, the camera model is for %d x %d' % (w, h, m['params'].width, m['params'].height))
+        kinds.add((np.dtype(np_dtype), nch, src.dtype))
+        C.memmove(C.byref(t.params), C.byref(m['params']), C.sizeof(m['params']))
+        if m['zenithal'] is not None:
+            t.zenithal = C.pointer(m['zenithal'])
+        t.img = ptr(src).value
+        cm = m['center_mask']
+        t.center_mask = None if cm is None else ptr(cm).value
+        t.min_elevation = float('nan') if m['min_elevation'] is None else float(m['min_elevation'])
+        keep.append((src, cm, m['zenithal']))
+    if len(kinds) != 1:
+        raise ValueError('the members\' images differ in dtype or channel count')
+    _, nch, tdtype = next(iter(kinds))
+    coords = grid_coordinates(plan)
+    ny, nx = grid.ny, grid.nx
+    if plan['contains_pole']:
+        lat_ax = lon_ax = None
+        cell_lat = ctx.to_device(np.ascontiguousarray(coords['lat_c']))
+        cell_lon = ctx.to_device(np.ascontiguousarray(coords['lon_c']))
+    else:
+        cell_lat = cell_lon = None
+        lat_ax = ctx.to_device(np.ascontiguousarray(coords['lat_c'][:, 0]))
+        lon_ax = ctx.to_device(np.ascontiguousarray(coords['lon_c'][0, :]))
+    img = torch.empty((ny, nx, nch), dtype=tdtype, device=ctx.device)
+    mask = ctx.empty((ny, nx), torch.uint8)
+    elev = ctx.empty((ny, nx))
+    source = ctx.empty((ny, nx), torch.int32)
+    out_xy = ctx.empty((ny, nx, 2)) if xy else None
+    dbg, tiles = None, None
+    if debug is not None:
+        dbg = GatherDebug()
+        dbg.force_path = int(debug.get('force_path', GATHER_PATH_AUTO))
+        if debug.get('tile_path'):
+            tiles = ctx.zeros(((ny + 31) // 32, (nx + 31) // 32), torch.uint8)
+            dbg.tile_path = ptr(tiles).value
+    ctx.call('amt_gather_mosaic', table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(lat_ax), ny, ptr(lon_ax), nx,
+             ptr(cell_lat), ptr(cell_lon), img.element_size(), nch, _GATHER_INTERP_CODES[interpolation], int(plan['rule']),
+             ptr(img), ptr(mask), ptr(elev), ptr(source), ptr(out_xy), None if dbg is None else C.byref(dbg))
+    out = dict(coords, grid=grid, img=to_host(img, dtype=np_dtype), mask=to_host(mask).astype(bool), elevation=to_host(elev),
+               source=to_host(source, dtype=np.int32), contains_pole=plan['contains_pole'],
+               contains_discontinuity=plan['contains_discontinuity'], altitude=plan['altitude'], plan=plan)
+    if out_xy is not None:
+        out['xy'] = to_host(out_xy)
+    if tiles is not None:
+        out['tile_path'] = to_host(tiles)
+    del keep                     # (after the read-back above: the kernel is done with them)
+    return out
+
+
+def _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic):
+    from .mapping.mapping import MosaicMapping
+    _check_gather_interpolation(interpolation)
+    collection = _gather_collection(collection)
+    plan = gather_mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole, magnetic)
+    res = gather_mosaic_frames(plan, None, interpolation, magnetic)
+    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
+    elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
+    source = ma.masked_array(res['source'], mask=res['source'] < 0)
+    members = collection.mappings
+    photoTime = collection.photoTime
+    first = next(m for m in members if m.photoTime == photoTime)
+    lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
+    if magnetic:
+        from .coordinates.transform import smToLatLon
+        nc = lat.size
+        la, lo = smToLatLon(np.concatenate((lat.ravel(), lat_c.ravel())), np.concatenate((lon.ravel(), lon_c.ravel())), photoTime)
+        lat, lon = la[:nc].reshape(lat.shape), lo[:nc].reshape(lon.shape)
+        lat_c, lon_c = la[nc:].reshape(lat_c.shape), lo[nc:].reshape(lon_c.shape)
+    return MosaicMapping(lat, lon, lat_c, lon_c, elevation, plan['altitude'], img, first.cameraPosGCRS, photoTime,
+                         collection.identifier, source, plan['identifiers'])
+
+
+def resampleGatherMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear'):
+    """
+    :func:`resampleGather` for a collection: every member gathered onto ONE grid — the grid :func:`resampleMosaic` lays out
+    for the same collection and arguments — in one fused kernel (``amt_gather_mosaic``).  Every cell centre is projected
+    through every member's camera model; member i sees a cell by :func:`resampleGather`'s four masking rules; one member wins
+    the cell and only its image is sampled there.  ``collection.mayOverlap`` True (a list of mappings counts as such a
+    collection): the member whose line of sight to the cell centre has the highest elevation wins (the reference's drawing
+    rule for overlapping mappings), the earlier member on a tie.  False: the first member that sees the cell.  Towards every
+    member's horizon, where binning leaves holes that the overlap rule then has to choose between, gathering leaves none.
+
+    ``.elevation`` of the result is the winner's exact line-of-sight elevation, ``.source`` the winner's index (masked where
+    nobody sees the cell), ``.members`` the members' identifiers.
+
+    :param interpolation: 'nearest', 'linear' or 'lanczos4'
+    :raises ValueError: for an unknown interpolation (before anything else), an empty collection, members of different
+                        altitudes or image dtypes / channel counts
+    :raises NotImplementedError: for a member without a camera model in closed form (named in the message)
+    :rtype: MosaicMapping
+    """
+    return _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, False)
+
+
+def resampleGatherMosaicMLatMLT(collection, **kw):
+    """:func:`resampleGatherMosaic` on the (MLat, SM longitude) grid of :func:`resampleMosaicMLatMLT`: the cell centres go
+    through the camera models as SM coordinates (``AMT_W2P_SM``) and the grid's coordinates are converted back."""
+    return _resample_gather_mosaic(collection, kw.pop('pxPerDeg', 25), kw.pop('arcsecPerPx', None), kw.pop('containsPole', None),
+                                   kw.pop('interpolation', 'linear'), True, **kw)

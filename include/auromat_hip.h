@@ -62,7 +62,8 @@ extern "C" {
  *    (auromat_amd.resample.resampleStereographic, resampleStereographicMLatMLT, resampleMLatMLTPolar); scan-line maps —
  *    amt_scanline_select, amt_scanline_pack, amt_scanline_compose, amt_scanline_strip (auromat_amd.resample.resampleScanLines);
  *    the core role of the frame kernel's work items — amt_georef_last_core, amt_georef_core_bands, amt_run_core_stats,
- *    amt_georef_set_roles(ctx, 2) */
+ *    amt_georef_set_roles(ctx, 2); gather mosaics — amt_gather_mosaic, amt_gather_member, amt_gather_debug, AMT_INTERP_NEAREST
+ *    (auromat_amd.resample.resampleGatherMosaic) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -438,6 +439,59 @@ int amt_world_to_pixel(amt_ctx* ctx, const amt_frame_params* params, const amt_z
 int amt_grid_to_pixel(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
                       const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx, float* out_xy32, double* out_xy,
                       double* out_elev, uint8_t* out_flags);
+
+/* ---- gather mosaic: a collection gathered onto one grid in one fused kernel (addition to ABI 10) --------------------------------
+ * auromat_amd.resample.resampleGatherMosaic.  Every cell centre of one grid is projected through EVERY member's camera model
+ * (the arithmetic of amt_grid_to_pixel above), the overlap rule elects one member per cell, and only that member's image is
+ * sampled (the arithmetic of amt_remap_coords).  No per-member coordinate array is written anywhere.
+ * A member: its amt_frame_params, an optional amt_zenithal_wcs (as amt_world_to_pixel takes them), img on the device,
+ * (params.height, params.width, channels) in the call's sample type, an optional center_mask (height x width bytes, non-zero =
+ * masked) and min_elevation (degrees; -inf or NaN: none).
+ * The cells: either the axes form - point (i, j) = (lat_centres[i], lon_centres[j]), as amt_grid_to_pixel - or, when both axes are
+ * NULL, the point form - cell_lat, cell_lon of (ny, nx) each (the centres of a rotated grid, rotated back: the pole plan).  frame:
+ * AMT_W2P_GEODETIC or AMT_W2P_SM.
+ * Member i SEES a cell iff
+ *   1. the flag byte of its centre is 0 (steps 1-8 above),
+ *   2. for AMT_INTERP_LINEAR / _LANCZOS4: the position rounded to float32 has support, 0 <= x <= width - 1 and 0 <= y <= height - 1
+ *      (amt_remap_coords' support byte for the array amt_grid_to_pixel writes),
+ *   3. its center_mask, if any, is clear at the nearest pixel (rint of the float64 x, y - half to even -, clamped to the frame),
+ *   4. elev >= min_elevation, if one is set,
+ * and its elevation is not NaN (a NaN elevation never wins).
+ * rule 1 (the reference's drawing rule for mappings that may overlap): of the members that see the cell, the one with the
+ * highest float64 line-of-sight elevation at the cell centre wins, the lower index on a tie.  rule 0: the lowest index that sees
+ * the cell (for collections that promise no overlap: the rules differ only where that promise is broken).
+ * The cell takes the winner's sample - linear / Lanczos-4 as "Sampling (both remap calls)" states it, on the float32-rounded
+ * coordinates; AMT_INTERP_NEAREST: the pixel at (rint x, rint y) of the float64 coordinates, clamped -, out_elev the winner's
+ * elevation, out_source its index, out_mask 0 and out_xy (optional, (ny, nx, 2) float64) the winner's coordinates.  Without a
+ * seeing member: image 0, out_mask 1, out_source -1, out_elev and out_xy NaN.  Every output equals, bit for bit, what
+ * amt_grid_to_pixel (amt_world_to_pixel for the point form) + amt_remap_coords give for the winning member alone.
+ * One block makes a 32 x 32 tile of cells.  A tile with ONE winner whose taps fit a 48 x 48 window of that member's image samples
+ * from the window staged in LDS; any other tile takes every cell's taps from its own winner's image in global memory; both give
+ * the same bits.  debug (optional): force_path AMT_GATHER_PATH_CELL makes every tile do the latter; tile_path (optional, one byte
+ * per tile, row-major) reports 0 nobody sees the tile, AMT_GATHER_PATH_STAGED or AMT_GATHER_PATH_CELL (nearest: always _CELL).
+ * Only enqueues work on the context's stream (the member table goes to the context's workspace).  AMT_EINVAL (nothing written):
+ * NULL required pointers, n_members < 1, an empty axis, both or neither coordinate form, an unknown frame (AMT_W2P_J2000
+ * included), interpolation, rule or force_path, sample_bytes outside 1, 2, 4, channels outside 1, 3, 4, a member without image,
+ * and whatever amt_world_to_pixel refuses in a member's model - the error names the member's index. */
+#define AMT_INTERP_NEAREST 2
+#define AMT_GATHER_PATH_AUTO 0
+#define AMT_GATHER_PATH_STAGED 1   /* as AUTO */
+#define AMT_GATHER_PATH_CELL 2
+typedef struct amt_gather_member {
+    amt_frame_params params;
+    const amt_zenithal_wcs* zenithal;
+    const void* img;
+    const uint8_t* center_mask;
+    double min_elevation;
+} amt_gather_member;
+typedef struct amt_gather_debug {
+    int32_t force_path, reserved;
+    uint8_t* tile_path;
+} amt_gather_debug;
+int amt_gather_mosaic(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame, const double* lat_centres,
+                      int32_t ny, const double* lon_centres, int32_t nx, const double* cell_lat, const double* cell_lon,
+                      int32_t sample_bytes, int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask,
+                      double* out_elev, int32_t* out_source, double* out_xy, const amt_gather_debug* debug);
 
 /* auromat/coordinates/intersection.py:144-163 ellipsoidLineIntersection (and
  * auromat/mapping/mapping.py:1474-1510 inflatedEarthIntersection with a=wgs84A+h, b=wgs84B+h).
