@@ -202,6 +202,8 @@ _SIGNATURES = {
                            _P], _I),
     'amt_gather_mosaic': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
                           [C.c_int32] * 4 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
+    'amt_gather_mosaic_supersampled': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
+                                       [C.c_int32] * 6 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
     'amt_intersect_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersects_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersect_sphere': ([_P, _D, c_double_p, _P, _L, _I, _P], _I),

@@ -11,8 +11,14 @@
 //
 // The member table (w2p_consts + w2p_sip + pointers per member) lies in the context's workspace; the member loop is uniform over
 // the block, so the table is read through scalar loads.
+//
+// The supersampled form (amt_gather_mosaic_supersampled) runs the same steps — load_points, elect, survey, stage_window,
+// sample_point below are the one code of both kernels — on the n x n sub-sample points of T x T cells, T = 32 / n, laid over the
+// same 32 x 32 threads' points, and then reduces the points to cells through LDS (k_gather_mosaic_ss).
+#include <algorithm>
 #include <cmath>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "amt_common.h"
@@ -47,55 +53,77 @@ struct gather_args {
     uint8_t* tile_path;
 };
 
+// the supersampled call: G.ny, G.nx count cells, the coordinate arrays of G hold the factor x factor sub-sample points of each
+struct gather_ss_args {
+    gather_args G;
+    int factor, min_count;
+    int head, pad_;             // bytes of the dynamic LDS ahead of the points' samples: the window, later the winners and elevations
+    uint8_t* count;
+};
+
+// a thread's four points (8 rows apart), the running best of the overlap rule at each, and the winner's taps
+struct gather_points {
+    bool in[kRowsPerThread];
+    double lat[kRowsPerThread];
+    lon_terms L[kRowsPerThread];
+    lat_terms T[kRowsPerThread];
+};
+struct gather_best {
+    int m[kRowsPerThread];
+    double x[kRowsPerThread], y[kRowsPerThread], e[kRowsPerThread];
+};
+struct gather_taps {
+    int ix[kRowsPerThread], iy[kRowsPerThread];
+    double fx[kRowsPerThread], fy[kRowsPerThread];
+};
+// what the block's points hold: the one winner and the box of its taps where the window serves (staged)
+struct gather_tile {
+    int m, x_lo, y_lo, nwx, nwy, pitch;
+    bool any, staged;
+};
+
+// N: taps per axis (2 linear, 8 Lanczos-4); 0: the nearest pixel, which needs no window
+template <int N>
+struct tap_range {
+    static constexpr int lo = N == 8 ? -3 : 0, hi = lo + (N ? N : 1) - 1;
+};
+
 // the nearest pixel of a seen point (half to even), kept inside the frame: x in [-0.5, n - 0.5] rounds to -0 or n at the ends
 __device__ __forceinline__ int nearest_index(double v, int n) { return (int)fmin(fmax(rint(v), 0.0), (double)(n - 1)); }
 
-// N: taps per axis (2 linear, 8 Lanczos-4); 0: the nearest pixel, which needs no window
-template <typename T, int N>
-__global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
-    extern __shared__ __align__(16) unsigned char gather_smem[];
-    T* win = reinterpret_cast<T*>(gather_smem);
-    __shared__ int fold[4][6];
-    constexpr int lo = N == 8 ? -3 : 0, hi = lo + (N ? N : 1) - 1;
-
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int X = blockIdx.x * kTile + tx;
+// the coordinates of a thread's points: column X and rows Y[k] of a point grid `pitch` points wide (the point form's rows)
+__device__ __forceinline__ void load_points(const gather_args& A, int X, bool x_in, const int (&Y)[kRowsPerThread],
+                                            const bool (&y_in)[kRowsPerThread], int64_t pitch, gather_points& P) {
     const bool points = A.cell_lat != nullptr;
-    const int C = A.C;
-
-    bool in_grid[kRowsPerThread];
-    double latv[kRowsPerThread];
-    lon_terms Lk[kRowsPerThread];
-    lat_terms Tk[kRowsPerThread];
-    // a thread's cells share their column: its longitude terms are computed once (the point form has a longitude per cell)
-    const lon_terms L0 = w2p_lon_terms(!points && X < A.nx ? A.lon[X] : 0.0);
+    // a thread's points share their column: its longitude terms are computed once (the point form has a longitude per point)
+    const lon_terms L0 = w2p_lon_terms(!points && x_in ? A.lon[X] : 0.0);
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
-        const int Y = blockIdx.y * kTile + ty + 8 * k;
-        in_grid[k] = X < A.nx && Y < A.ny;
-        const int64_t i = (int64_t)Y * A.nx + X;
-        latv[k] = !in_grid[k] ? 0.0 : (points ? A.cell_lat[i] : A.lat[Y]);
-        Lk[k] = points ? w2p_lon_terms(in_grid[k] ? A.cell_lon[i] : 0.0) : L0;
+        P.in[k] = x_in && y_in[k];
+        const int64_t i = (int64_t)Y[k] * pitch + X;
+        P.lat[k] = !P.in[k] ? 0.0 : (points ? A.cell_lat[i] : A.lat[Y[k]]);
+        P.L[k] = points ? w2p_lon_terms(P.in[k] ? A.cell_lon[i] : 0.0) : L0;
         // the latitude terms depend on the member through the WGS84 constants alone: one evaluation where all members agree
-        if (A.same_ellipsoid) Tk[k] = w2p_lat_terms(A.members[0].K, latv[k]);
+        if (A.same_ellipsoid) P.T[k] = w2p_lat_terms(A.members[0].K, P.lat[k]);
     }
+}
 
-    // ---- election: the running best per cell -------------------------------------------------------------------------
-    int bm[kRowsPerThread];
-    double bx[kRowsPerThread], by[kRowsPerThread], be[kRowsPerThread];
+// ---- election: the running best per point ----------------------------------------------------------------------------
+template <int N>
+__device__ __forceinline__ void elect(const gather_args& A, const gather_points& P, gather_best& B) {
 #pragma unroll
-    for (int k = 0; k < kRowsPerThread; ++k) bm[k] = -1, bx[k] = by[k] = be[k] = NAN;
+    for (int k = 0; k < kRowsPerThread; ++k) B.m[k] = -1, B.x[k] = B.y[k] = B.e[k] = NAN;
     for (int m = 0; m < A.n; ++m) {
         const gather_dev& M = A.members[m];
         const int w = M.K.width, h = M.K.height;
         const double least = M.min_elevation;
 #pragma unroll
         for (int k = 0; k < kRowsPerThread; ++k) {
-            if (!in_grid[k]) continue;
-            if (A.rule == 0 && bm[k] >= 0) continue;        // the first member that sees the cell keeps it
-            const lat_terms Tm = A.same_ellipsoid ? Tk[k] : w2p_lat_terms(M.K, latv[k]);
+            if (!P.in[k]) continue;
+            if (A.rule == 0 && B.m[k] >= 0) continue;       // the first member that sees the point keeps it
+            const lat_terms Tm = A.same_ellipsoid ? P.T[k] : w2p_lat_terms(M.K, P.lat[k]);
             double x, y, e;
-            bool seen = w2p_point(M.K, M.S, Tm, Lk[k], x, y, e) == 0;
+            bool seen = w2p_point(M.K, M.S, Tm, P.L[k], x, y, e) == 0;
             if (N != 0) {
                 // support, as k_remap evaluates it on the float32 coordinates it is given
                 const double xs = (double)(float)x, ys = (double)(float)y;
@@ -104,31 +132,34 @@ __global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
             if (seen && M.center_mask) seen = M.center_mask[(int64_t)nearest_index(y, h) * w + nearest_index(x, w)] == 0;
             if (least == least) seen = seen && e >= least;
             seen = seen && e == e;                          // a NaN elevation never wins
-            if (seen && (bm[k] < 0 || e > be[k])) bm[k] = m, bx[k] = x, by[k] = y, be[k] = e;       // (ties: the lower index)
+            if (seen && (B.m[k] < 0 || e > B.e[k])) B.m[k] = m, B.x[k] = x, B.y[k] = y, B.e[k] = e;   // (ties: the lower index)
         }
     }
+}
 
-    // ---- what the tile holds: the range of its winners and the box of their taps, as (min, -max) so that one fold serves all ----
-    int ix[kRowsPerThread], iy[kRowsPerThread];
-    double fx[kRowsPerThread], fy[kRowsPerThread];
+// ---- what the tile holds: the range of its winners and the box of their taps, as (min, -max) so that one fold serves all ----
+// (a barrier inside: every thread of the block calls it; `fold` is the block's)
+template <int N>
+__device__ __forceinline__ gather_tile survey(const gather_args& A, const gather_best& B, gather_taps& t, int (&fold)[4][6]) {
+    constexpr int lo = tap_range<N>::lo, hi = tap_range<N>::hi;
     int r0 = INT32_MAX, r1 = INT32_MAX, b0 = INT32_MAX, b1 = INT32_MAX, b2 = INT32_MAX, b3 = INT32_MAX;
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
-        ix[k] = iy[k] = 0, fx[k] = fy[k] = 0.0;
-        if (bm[k] < 0) continue;
-        r0 = min(r0, bm[k]), r1 = min(r1, -bm[k]);
+        t.ix[k] = t.iy[k] = 0, t.fx[k] = t.fy[k] = 0.0;
+        if (B.m[k] < 0) continue;
+        r0 = min(r0, B.m[k]), r1 = min(r1, -B.m[k]);
         if (N == 0) {
-            const w2p_consts& K = A.members[bm[k]].K;
-            ix[k] = nearest_index(bx[k], K.width), iy[k] = nearest_index(by[k], K.height);
+            const w2p_consts& K = A.members[B.m[k]].K;
+            t.ix[k] = nearest_index(B.x[k], K.width), t.iy[k] = nearest_index(B.y[k], K.height);
         } else {
-            // (a seen cell has support: k_remap's clamp of far-away coordinates would change nothing)
-            const double xs = (double)(float)bx[k], ys = (double)(float)by[k];
+            // (a seen point has support: k_remap's clamp of far-away coordinates would change nothing)
+            const double xs = (double)(float)B.x[k], ys = (double)(float)B.y[k];
             const double flx = floor(xs), fly = floor(ys);
-            ix[k] = (int)flx, iy[k] = (int)fly;
-            fx[k] = xs - flx, fy[k] = ys - fly;
+            t.ix[k] = (int)flx, t.iy[k] = (int)fly;
+            t.fx[k] = xs - flx, t.fy[k] = ys - fly;
         }
-        b0 = min(b0, ix[k] + lo), b1 = min(b1, -(ix[k] + hi));
-        b2 = min(b2, iy[k] + lo), b3 = min(b3, -(iy[k] + hi));
+        b0 = min(b0, t.ix[k] + lo), b1 = min(b1, -(t.ix[k] + hi));
+        b2 = min(b2, t.iy[k] + lo), b3 = min(b3, -(t.iy[k] + hi));
     }
     r0 = wave_min(r0), r1 = wave_min(r1), b0 = wave_min(b0), b1 = wave_min(b1), b2 = wave_min(b2), b3 = wave_min(b3);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -137,79 +168,324 @@ __global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
     auto folded = [&](int j) { return min(min(fold[0][j], fold[1][j]), min(fold[2][j], fold[3][j])); };
     const int m_lo = folded(0), m_hi = -folded(1);
     const int x_lo = folded(2), x_hi = -folded(3), y_lo = folded(4), y_hi = -folded(5);
-    const bool any = m_lo != INT32_MAX;
-    const int nwx = any ? x_hi - x_lo + 1 : 0, nwy = any ? y_hi - y_lo + 1 : 0;
+    gather_tile W;
+    W.any = m_lo != INT32_MAX;
+    W.m = m_lo, W.x_lo = x_lo, W.y_lo = y_lo;
+    W.nwx = W.any ? x_hi - x_lo + 1 : 0, W.nwy = W.any ? y_hi - y_lo + 1 : 0;
     // the same for the whole block
-    const bool staged = N != 0 && any && m_lo == m_hi && nwx <= kWin && nwy <= kWin && A.force != AMT_GATHER_PATH_CELL;
+    W.staged = N != 0 && W.any && m_lo == m_hi && W.nwx <= kWin && W.nwy <= kWin && A.force != AMT_GATHER_PATH_CELL;
+    W.pitch = W.nwx * A.C;
     if (A.tile_path && threadIdx.x == 0)
-        A.tile_path[blockIdx.y * gridDim.x + blockIdx.x] = !any ? 0 : (staged ? AMT_GATHER_PATH_STAGED : AMT_GATHER_PATH_CELL);
+        A.tile_path[blockIdx.y * gridDim.x + blockIdx.x] = !W.any ? 0 : (W.staged ? AMT_GATHER_PATH_STAGED : AMT_GATHER_PATH_CELL);
+    return W;
+}
 
-    const int pitch = nwx * C;
-    if (staged) {
-        const gather_dev& M = A.members[__builtin_amdgcn_readfirstlane(m_lo)];
-        const T* src = static_cast<const T*>(M.img);
-        const int sw = M.K.width, sh = M.K.height;
-        // a wave per window row, lanes along the row's samples: consecutive lanes read consecutive samples of the source row
-        for (int r = wave; r < nwy; r += 4) {
-            const int gy = y_lo + r;
-            const bool row_in = gy >= 0 && gy < sh;
-            const T* srow = src + ((int64_t)(row_in ? gy : 0) * sw) * C;
-            for (int e = lane; e < pitch; e += 64) {
-                const int gx = x_lo + e / C;
-                const bool in = row_in && gx >= 0 && gx < sw;
-                win[r * pitch + e] = in ? srow[(int64_t)x_lo * C + e] : (T)0;
-            }
+// the one winner's window into LDS (a barrier inside; W.staged is the same for the whole block)
+template <typename T>
+__device__ __forceinline__ void stage_window(const gather_args& A, const gather_tile& W, T* win) {
+    const int C = A.C, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const gather_dev& M = A.members[__builtin_amdgcn_readfirstlane(W.m)];
+    const T* src = static_cast<const T*>(M.img);
+    const int sw = M.K.width, sh = M.K.height;
+    // a wave per window row, lanes along the row's samples: consecutive lanes read consecutive samples of the source row
+    for (int r = wave; r < W.nwy; r += 4) {
+        const int gy = W.y_lo + r;
+        const bool row_in = gy >= 0 && gy < sh;
+        const T* srow = src + ((int64_t)(row_in ? gy : 0) * sw) * C;
+        for (int e = lane; e < W.pitch; e += 64) {
+            const int gx = W.x_lo + e / C;
+            const bool in = row_in && gx >= 0 && gx < sw;
+            win[r * W.pitch + e] = in ? srow[(int64_t)W.x_lo * C + e] : (T)0;
         }
-        __syncthreads();
     }
+    __syncthreads();
+}
+
+// the C samples of a won point: member m's image at the taps (ix, iy) + (fx, fy)
+template <typename T, int N>
+__device__ __forceinline__ void sample_point(const gather_args& A, const gather_tile& W, const T* win, int m, int ix, int iy, double fx,
+                                             double fy, T* out) {
+    constexpr int lo = tap_range<N>::lo;
+    const int C = A.C;
+    const gather_dev& M = A.members[m];
+    const T* src = static_cast<const T*>(M.img);
+    const int sw = M.K.width, sh = M.K.height;
+    if (N == 0) {
+        const T* px = src + ((int64_t)iy * sw + ix) * C;
+        for (int c = 0; c < C; ++c) out[c] = px[c];
+    } else {
+        constexpr int NT = N ? N : 2;
+        double wx[NT], wy[NT];
+        tap_weights<NT>(fx, wx);
+        tap_weights<NT>(fy, wy);
+        if (W.staged) {
+            const window_fetch<T> f = {win, W.x_lo, W.y_lo, W.pitch, C};
+            for (int c = 0; c < C; ++c) out[c] = to_sample<T>(sample<NT>(f, ix + lo, iy + lo, c, wx, wy));
+        } else {
+            const global_fetch<T> f = {src, sw, sh, C};
+            for (int c = 0; c < C; ++c) out[c] = to_sample<T>(sample<NT>(f, ix + lo, iy + lo, c, wx, wy));
+        }
+    }
+}
+
+template <typename T, int N>
+__global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
+    extern __shared__ __align__(16) unsigned char gather_smem[];
+    T* win = reinterpret_cast<T*>(gather_smem);
+    __shared__ int fold[4][6];
+
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int X = blockIdx.x * kTile + tx;
+    const int C = A.C;
+    int Y[kRowsPerThread];
+    bool y_in[kRowsPerThread];
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k) Y[k] = blockIdx.y * kTile + ty + 8 * k, y_in[k] = Y[k] < A.ny;
+
+    gather_points P;
+    gather_best B;
+    gather_taps t;
+    load_points(A, X, X < A.nx, Y, y_in, A.nx, P);
+    elect<N>(A, P, B);
+    const gather_tile W = survey<N>(A, B, t, fold);
+    if (W.staged) stage_window<T>(A, W, win);
 
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
-        const int Y = blockIdx.y * kTile + ty + 8 * k;
-        if (!in_grid[k]) continue;
-        const int64_t i = (int64_t)Y * A.nx + X;
+        if (!P.in[k]) continue;
+        const int64_t i = (int64_t)Y[k] * A.nx + X;
         T* out = static_cast<T*>(A.img) + i * C;
-        const bool won = bm[k] >= 0;
+        const bool won = B.m[k] >= 0;
         A.mask[i] = won ? 0 : 1;
-        A.source[i] = bm[k];
-        A.elev[i] = be[k];
-        if (A.xy) A.xy[2 * i + 0] = bx[k], A.xy[2 * i + 1] = by[k];
+        A.source[i] = B.m[k];
+        A.elev[i] = B.e[k];
+        if (A.xy) A.xy[2 * i + 0] = B.x[k], A.xy[2 * i + 1] = B.y[k];
         if (!won) {
             for (int c = 0; c < C; ++c) out[c] = (T)0;
             continue;
         }
-        const gather_dev& M = A.members[bm[k]];
-        const T* src = static_cast<const T*>(M.img);
-        const int sw = M.K.width, sh = M.K.height;
-        if (N == 0) {
-            const T* px = src + ((int64_t)iy[k] * sw + ix[k]) * C;
-            for (int c = 0; c < C; ++c) out[c] = px[c];
+        sample_point<T, N>(A, W, win, B.m[k], t.ix[k], t.iy[k], t.fx[k], t.fy[k], out);
+    }
+}
+
+// ---- the supersampled form --------------------------------------------------------------------------------------------
+// The block's 32 x 32 points are the factor x factor sub-samples of T x T cells, T = 32 / factor (threads whose point lies past
+// T * factor idle).  Every point is elected and sampled as a cell of k_gather_mosaic is; its samples go to LDS behind the window,
+// and once the block has sampled, the winners and elevations take the window's bytes.  Then one thread per (cell, quantity) —
+// the C channels, the elevation with count and mask, the source — walks its cell's points in row-major order, which is the order
+// the contract sums in.
+constexpr int kPoints = kTile * kTile;
+constexpr int kHeadMin = kPoints * (int)(sizeof(double) + sizeof(int));      // the elevations and winners of the block's points
+
+template <typename T, int N>
+__global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
+    extern __shared__ __align__(16) unsigned char gather_smem[];
+    const gather_args& A = S.G;
+    T* win = reinterpret_cast<T*>(gather_smem);
+    double* p_elev = reinterpret_cast<double*>(gather_smem);
+    int* p_win = reinterpret_cast<int*>(gather_smem + kPoints * sizeof(double));
+    T* p_val = reinterpret_cast<T*>(gather_smem + S.head);
+    __shared__ int fold[4][6];
+
+    const int n = S.factor, Tc = kTile / n, span = Tc * n;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int X = blockIdx.x * span + tx;
+    const int C = A.C;
+    int Y[kRowsPerThread];
+    bool y_in[kRowsPerThread];
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k) {
+        Y[k] = blockIdx.y * span + ty + 8 * k;
+        y_in[k] = ty + 8 * k < span && Y[k] < A.ny * n;
+    }
+
+    gather_points P;
+    gather_best B;
+    gather_taps t;
+    load_points(A, X, tx < span && X < A.nx * n, Y, y_in, (int64_t)A.nx * n, P);
+    elect<N>(A, P, B);
+    const gather_tile W = survey<N>(A, B, t, fold);
+    if (W.staged) stage_window<T>(A, W, win);
+
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k) {
+        if (B.m[k] < 0) continue;
+        const int p = (ty + 8 * k) * kTile + tx;
+        sample_point<T, N>(A, W, win, B.m[k], t.ix[k], t.iy[k], t.fx[k], t.fy[k], p_val + p * C);
+    }
+    __syncthreads();            // the window has been read: its bytes now hold the points' winners and elevations
+#pragma unroll
+    for (int k = 0; k < kRowsPerThread; ++k) {
+        const int p = (ty + 8 * k) * kTile + tx;
+        p_win[p] = B.m[k];      // (-1 also for the points outside the grid)
+        p_elev[p] = B.e[k];
+    }
+    __syncthreads();
+
+    const int cells = Tc * Tc, items = cells * (C + 2);
+    for (int w = threadIdx.x; w < items; w += 256) {
+        const int q = w / cells, cell = w - q * cells, cy = cell / Tc, cx = cell - cy * Tc;
+        const int Yc = blockIdx.y * Tc + cy, Xc = blockIdx.x * Tc + cx;
+        if (Yc >= A.ny || Xc >= A.nx) continue;
+        const int64_t i = (int64_t)Yc * A.nx + Xc;
+        const int p0 = cy * n * kTile + cx * n;
+        int count = 0;
+        if (q < C) {
+            // a channel: the exact integer sum, or the float64 sum in row-major order that the first seen value starts
+            uint32_t isum = 0;
+            double acc = 0.0;
+            for (int s = 0; s < n; ++s)
+                for (int u = 0; u < n; ++u) {
+                    const int p = p0 + s * kTile + u;
+                    if (p_win[p] < 0) continue;
+                    const T v = p_val[p * C + q];
+                    if (std::is_same<T, float>::value)
+                        acc = count ? acc + (double)v : (double)v;
+                    else
+                        isum += (uint32_t)v;
+                    ++count;
+                }
+            T out = (T)0;
+            if (count >= S.min_count)
+                out = std::is_same<T, float>::value ? (T)(float)(acc / (double)count) : (T)rint((double)isum / (double)count);
+            static_cast<T*>(A.img)[i * C + q] = out;
+        } else if (q == C) {
+            double acc = 0.0;
+            for (int s = 0; s < n; ++s)
+                for (int u = 0; u < n; ++u) {
+                    const int p = p0 + s * kTile + u;
+                    if (p_win[p] < 0) continue;
+                    acc = count ? acc + p_elev[p] : p_elev[p];
+                    ++count;
+                }
+            const bool valid = count >= S.min_count;
+            S.count[i] = (uint8_t)count;
+            A.mask[i] = valid ? 0 : 1;
+            A.elev[i] = valid ? acc / (double)count : (double)NAN;
         } else {
-            constexpr int NT = N ? N : 2;
-            double wx[NT], wy[NT];
-            tap_weights<NT>(fx[k], wx);
-            tap_weights<NT>(fy[k], wy);
-            if (staged) {
-                const window_fetch<T> f = {win, x_lo, y_lo, pitch, C};
-                for (int c = 0; c < C; ++c) out[c] = to_sample<T>(sample<NT>(f, ix[k] + lo, iy[k] + lo, c, wx, wy));
-            } else {
-                const global_fetch<T> f = {src, sw, sh, C};
-                for (int c = 0; c < C; ++c) out[c] = to_sample<T>(sample<NT>(f, ix[k] + lo, iy[k] + lo, c, wx, wy));
+            // the member that won the most points, the lower index on a tie: the winners are counted in ascending order
+            int cur = INT32_MAX;
+            for (int s = 0; s < n; ++s)
+                for (int u = 0; u < n; ++u) {
+                    const int m = p_win[p0 + s * kTile + u];
+                    if (m < 0) continue;
+                    cur = min(cur, m);
+                    ++count;
+                }
+            int best = -1, most = 0;
+            while (cur != INT32_MAX) {
+                int won = 0, next = INT32_MAX;
+                for (int s = 0; s < n; ++s)
+                    for (int u = 0; u < n; ++u) {
+                        const int m = p_win[p0 + s * kTile + u];
+                        won += m == cur ? 1 : 0;
+                        if (m > cur) next = min(next, m);
+                    }
+                if (won > most) best = cur, most = won;
+                cur = next;
             }
+            A.source[i] = count >= S.min_count ? best : -1;
         }
     }
 }
 
 template <typename T>
+size_t window_bytes(int C) {
+    return (size_t)kWin * kWin * (size_t)C * sizeof(T);
+}
+
+template <typename T>
 void launch_gather(amt_ctx* ctx, const gather_args& A, int interpolation) {
     const dim3 grid((unsigned)((A.nx + kTile - 1) / kTile), (unsigned)((A.ny + kTile - 1) / kTile));
-    const size_t lds = (size_t)kWin * kWin * (size_t)A.C * sizeof(T);
+    const size_t lds = window_bytes<T>(A.C);
     if (interpolation == AMT_INTERP_LINEAR)
         hipLaunchKernelGGL((k_gather_mosaic<T, 2>), grid, dim3(256), lds, ctx->stream, A);
     else if (interpolation == AMT_INTERP_LANCZOS4)
         hipLaunchKernelGGL((k_gather_mosaic<T, 8>), grid, dim3(256), lds, ctx->stream, A);
     else
         hipLaunchKernelGGL((k_gather_mosaic<T, 0>), grid, dim3(256), 0, ctx->stream, A);
+}
+
+template <typename T>
+void launch_gather_ss(amt_ctx* ctx, gather_ss_args S, int interpolation) {
+    const int Tc = kTile / S.factor;
+    const dim3 grid((unsigned)((S.G.nx + Tc - 1) / Tc), (unsigned)((S.G.ny + Tc - 1) / Tc));
+    // the window (none for the nearest pixel) or the winners and elevations, whichever is larger; then the points' samples:
+    // at most 36 KB + 16 KB (float32 x 4 channels)
+    const size_t window = interpolation == AMT_INTERP_NEAREST ? 0 : window_bytes<T>(S.G.C);
+    const size_t head = (std::max(window, (size_t)kHeadMin) + 15) & ~(size_t)15;
+    const size_t lds = head + (size_t)kPoints * (size_t)S.G.C * sizeof(T);
+    S.head = (int)head;
+    if (interpolation == AMT_INTERP_LINEAR)
+        hipLaunchKernelGGL((k_gather_mosaic_ss<T, 2>), grid, dim3(256), lds, ctx->stream, S);
+    else if (interpolation == AMT_INTERP_LANCZOS4)
+        hipLaunchKernelGGL((k_gather_mosaic_ss<T, 8>), grid, dim3(256), lds, ctx->stream, S);
+    else
+        hipLaunchKernelGGL((k_gather_mosaic_ss<T, 0>), grid, dim3(256), lds, ctx->stream, S);
+}
+
+#define GATHER_REQUIRE(cond, msg)                                      \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            ctx->last_error = std::string(fn) + ": " + (msg);          \
+            return AMT_EINVAL;                                         \
+        }                                                              \
+    } while (0)
+
+// what both entry points check and prepare: the arguments they share, the member table in the context's workspace, and the
+// kernel's arguments for a grid of ny x nx cells (the supersampled call adds its own)
+int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* members, int32_t n_members, int32_t frame, const double* lat_axis,
+                   int32_t ny, const double* lon_axis, int32_t nx, const double* cell_lat, const double* cell_lon, int32_t sample_bytes,
+                   int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev,
+                   int32_t* out_source, const amt_gather_debug* debug, gather_args& A) {
+    GATHER_REQUIRE(members && out_img && out_mask && out_elev && out_source, "NULL argument");
+    GATHER_REQUIRE(n_members >= 1, "no members");
+    GATHER_REQUIRE(ny > 0 && nx > 0, "empty axis");
+    const bool axes = lat_axis && lon_axis, cells = cell_lat && cell_lon;
+    GATHER_REQUIRE((lat_axis != nullptr) == (lon_axis != nullptr) && (cell_lat != nullptr) == (cell_lon != nullptr) && axes != cells,
+                   "give either the two axes or the two cell arrays");
+    GATHER_REQUIRE(frame == AMT_W2P_GEODETIC || frame == AMT_W2P_SM, "unknown frame (AMT_W2P_GEODETIC or AMT_W2P_SM)");
+    GATHER_REQUIRE(interpolation == AMT_INTERP_LINEAR || interpolation == AMT_INTERP_LANCZOS4 || interpolation == AMT_INTERP_NEAREST,
+                   "unknown interpolation");
+    GATHER_REQUIRE(rule == 0 || rule == 1, "unknown rule");
+    GATHER_REQUIRE(sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4, "sample_bytes must be 1 (uint8), 2 (uint16) or 4 (float32)");
+    GATHER_REQUIRE(channels == 1 || channels == 3 || channels == 4, "channels must be 1, 3 or 4");
+    GATHER_REQUIRE(!debug || (debug->force_path >= AMT_GATHER_PATH_AUTO && debug->force_path <= AMT_GATHER_PATH_CELL), "unknown force_path");
+
+    std::vector<gather_dev> dev((size_t)n_members);
+    bool same = true;
+    for (int32_t i = 0; i < n_members; ++i) {
+        const amt_gather_member& m = members[i];
+        gather_dev& d = dev[(size_t)i];
+        const char* err = m.img ? w2p_prepare(&m.params, m.zenithal, frame, &d.K, &d.S) : "member without image";
+        GATHER_REQUIRE(err == nullptr, "member " + std::to_string(i) + ": " + err);
+        d.img = m.img;
+        d.center_mask = m.center_mask;
+        d.min_elevation = m.min_elevation > -INFINITY ? m.min_elevation : (double)NAN;      // (-inf and NaN: none)
+        same = same && d.K.a0 == dev[0].K.a0 && d.K.e2 == dev[0].K.e2;
+    }
+    if (amt_set_device(ctx)) return AMT_EHIP;
+    const size_t bytes = dev.size() * sizeof(gather_dev);
+    char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
+    if (ws == nullptr) {
+        ctx->last_error = std::string(fn) + ": workspace allocation failed";
+        return AMT_ENOMEM;
+    }
+    // (pageable source: the copy has consumed the staging buffer when the call returns)
+    const hipError_t err = hipMemcpyAsync(ws, dev.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (err != hipSuccess) {
+        ctx->last_error = std::string(fn) + ": hipMemcpyAsync -> " + hipGetErrorString(err);
+        return AMT_EHIP;
+    }
+
+    A.members = reinterpret_cast<const gather_dev*>(ws);
+    A.lat = axes ? lat_axis : nullptr, A.lon = axes ? lon_axis : nullptr;
+    A.cell_lat = axes ? nullptr : cell_lat, A.cell_lon = axes ? nullptr : cell_lon;
+    A.n = n_members, A.ny = ny, A.nx = nx, A.C = channels;
+    A.rule = rule, A.same_ellipsoid = same ? 1 : 0, A.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, A.pad_ = 0;
+    A.img = out_img, A.mask = out_mask, A.elev = out_elev, A.source = out_source, A.xy = nullptr;
+    A.tile_path = debug ? debug->tile_path : nullptr;
+    return AMT_OK;
 }
 
 }  // namespace
@@ -220,54 +496,41 @@ extern "C" int amt_gather_mosaic(amt_ctx* ctx, const amt_gather_member* members,
                                  int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev,
                                  int32_t* out_source, double* out_xy, const amt_gather_debug* debug) {
     AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, members && out_img && out_mask && out_elev && out_source, "NULL argument");
-    AMT_REQUIRE(ctx, n_members >= 1, "no members");
-    AMT_REQUIRE(ctx, ny > 0 && nx > 0, "empty axis");
-    const bool axes = lat_centres && lon_centres, cells = cell_lat && cell_lon;
-    AMT_REQUIRE(ctx, (lat_centres != nullptr) == (lon_centres != nullptr) && (cell_lat != nullptr) == (cell_lon != nullptr) && axes != cells,
-                "give either the two axes or the two cell arrays");
-    AMT_REQUIRE(ctx, frame == AMT_W2P_GEODETIC || frame == AMT_W2P_SM, "unknown frame (AMT_W2P_GEODETIC or AMT_W2P_SM)");
-    AMT_REQUIRE(ctx, interpolation == AMT_INTERP_LINEAR || interpolation == AMT_INTERP_LANCZOS4 || interpolation == AMT_INTERP_NEAREST,
-                "unknown interpolation");
-    AMT_REQUIRE(ctx, rule == 0 || rule == 1, "unknown rule");
-    AMT_REQUIRE(ctx, sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4, "sample_bytes must be 1 (uint8), 2 (uint16) or 4 (float32)");
-    AMT_REQUIRE(ctx, channels == 1 || channels == 3 || channels == 4, "channels must be 1, 3 or 4");
-    AMT_REQUIRE(ctx, !debug || (debug->force_path >= AMT_GATHER_PATH_AUTO && debug->force_path <= AMT_GATHER_PATH_CELL), "unknown force_path");
-
-    std::vector<gather_dev> dev((size_t)n_members);
-    bool same = true;
-    for (int32_t i = 0; i < n_members; ++i) {
-        const amt_gather_member& m = members[i];
-        gather_dev& d = dev[(size_t)i];
-        const char* err = m.img ? w2p_prepare(&m.params, m.zenithal, frame, &d.K, &d.S) : "member without image";
-        AMT_REQUIRE(ctx, err == nullptr, "member " + std::to_string(i) + ": " + err);
-        d.img = m.img;
-        d.center_mask = m.center_mask;
-        d.min_elevation = m.min_elevation > -INFINITY ? m.min_elevation : (double)NAN;      // (-inf and NaN: none)
-        same = same && d.K.a0 == dev[0].K.a0 && d.K.e2 == dev[0].K.e2;
-    }
-    if (amt_set_device(ctx)) return AMT_EHIP;
-    const size_t bytes = dev.size() * sizeof(gather_dev);
-    char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
-    if (ws == nullptr) {
-        ctx->last_error = "amt_gather_mosaic: workspace allocation failed";
-        return AMT_ENOMEM;
-    }
-    // (pageable source: the copy has consumed the staging buffer when the call returns)
-    AMT_HIP(ctx, hipMemcpyAsync(ws, dev.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-
     gather_args A;
-    A.members = reinterpret_cast<const gather_dev*>(ws);
-    A.lat = axes ? lat_centres : nullptr, A.lon = axes ? lon_centres : nullptr;
-    A.cell_lat = axes ? nullptr : cell_lat, A.cell_lon = axes ? nullptr : cell_lon;
-    A.n = n_members, A.ny = ny, A.nx = nx, A.C = channels;
-    A.rule = rule, A.same_ellipsoid = same ? 1 : 0, A.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, A.pad_ = 0;
-    A.img = out_img, A.mask = out_mask, A.elev = out_elev, A.source = out_source, A.xy = out_xy;
-    A.tile_path = debug ? debug->tile_path : nullptr;
+    const int rc = gather_prepare(ctx, __func__, members, n_members, frame, lat_centres, ny, lon_centres, nx, cell_lat, cell_lon,
+                                  sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, A);
+    if (rc != AMT_OK) return rc;
+    A.xy = out_xy;
     switch (sample_bytes) {
         case 1: launch_gather<uint8_t>(ctx, A, interpolation); break;
         case 2: launch_gather<uint16_t>(ctx, A, interpolation); break;
         default: launch_gather<float>(ctx, A, interpolation); break;
+    }
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+extern "C" int amt_gather_mosaic_supersampled(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                                              const double* sub_lat, int32_t ny, const double* sub_lon, int32_t nx,
+                                              const double* sub_cell_lat, const double* sub_cell_lon, int32_t factor,
+                                              int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
+                                              int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev, int32_t* out_source,
+                                              uint8_t* out_count, const amt_gather_debug* debug) {
+    AMT_CHECK_CTX(ctx);
+    AMT_REQUIRE(ctx, out_count, "NULL argument");
+    AMT_REQUIRE(ctx, factor >= 1 && factor <= 8, "factor must be 1 ... 8");
+    AMT_REQUIRE(ctx, min_count >= 1 && min_count <= factor * factor, "min_count must be 1 ... factor * factor");
+    AMT_REQUIRE(ctx, ny <= INT32_MAX / factor && nx <= INT32_MAX / factor, "the sub-sample grid does not fit 32-bit indices");
+    gather_ss_args S;
+    const int rc = gather_prepare(ctx, __func__, members, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon,
+                                  sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, S.G);
+    if (rc != AMT_OK) return rc;
+    S.factor = factor, S.min_count = min_count, S.head = 0, S.pad_ = 0;
+    S.count = out_count;
+    switch (sample_bytes) {
+        case 1: launch_gather_ss<uint8_t>(ctx, S, interpolation); break;
+        case 2: launch_gather_ss<uint16_t>(ctx, S, interpolation); break;
+        default: launch_gather_ss<float>(ctx, S, interpolation); break;
     }
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;

@@ -13,6 +13,7 @@ from __future__ import division, print_function
 
 import copy
 import ctypes as C
+import math
 from functools import partial
 
 import numpy as np
@@ -2078,6 +2079,66 @@ def _check_gather_interpolation(interpolation):
         raise ValueError('interpolation must be one of %s, not %r' % (', '.join(GATHER_INTERPOLATIONS), interpolation))
 
 
+SUPERSAMPLE_MAX = 8
+
+
+def supersample_min_count(minCoverage, n):
+    """The least number of seen sub-samples of a valid cell of a gathering with `n` x `n` sub-samples per cell:
+    ``max(1, ceil(minCoverage * n * n))``; None means 0.5, as in :func:`resampleArea`."""
+    if minCoverage is None:
+        minCoverage = 0.5
+    return max(1, int(math.ceil(minCoverage * n * n)))
+
+
+def _check_supersample(supersample, minCoverage):
+    """ValueError for a `supersample` that is not an int in 1 ... 8 (a bool is none), then for a `minCoverage` outside (0, 1],
+    then for a `minCoverage` given with ``supersample == 1``; returns (n, min_count), min_count None for n = 1."""
+    if isinstance(supersample, bool) or not isinstance(supersample, (int, np.integer)) or not 1 <= supersample <= SUPERSAMPLE_MAX:
+        raise ValueError('supersample must be an int in 1 ... %d, but is: %r' % (SUPERSAMPLE_MAX, supersample))
+    n = int(supersample)
+    if minCoverage is not None:
+        try:
+            v = float(minCoverage)
+        except (TypeError, ValueError):
+            raise ValueError('minCoverage must be a number in (0, 1], but is: {!r}'.format(minCoverage))
+        if not 0.0 < v <= 1.0:
+            raise ValueError('minCoverage must be in the range (0, 1], got {!r}'.format(minCoverage))
+        if n == 1:
+            raise ValueError('minCoverage={!r} goes with supersample > 1: one point is sampled per cell'.format(minCoverage))
+        minCoverage = v
+    return n, (None if n == 1 else supersample_min_count(minCoverage, n))
+
+
+def _subsample_axis(corners, n):
+    """n sub-sample positions per cell of an axis given by its cells' corners: corner + step * (2 s + 1) / (2 n)"""
+    c = np.asarray(corners, dtype=np.float64)
+    f = (2 * np.arange(n) + 1) / (2 * n)
+    return (c[:-1, None] + (c[1:, None] - c[:-1, None]) * f[None, :]).reshape(-1)
+
+
+def gather_subsample_coordinates(plan, n):
+    """
+    Where a gathering with `n` x `n` sub-samples per cell samples: the sub-samples split every cell of the plan's grid
+    (:func:`gather_plan` or :func:`gather_mosaic_plan`) into n x n equal parts and sit at the parts' centres — with
+    ``c = grid.lat[:, 0]`` the latitude of sub-sample s of row i is ``c[i] + (c[i + 1] - c[i]) * ((2 s + 1) / (2 n))``, the
+    longitudes likewise from ``grid.lon[0, :]``.  With the date line in the grid the longitudes are shifted the way
+    :func:`grid_coordinates` shifts the centres; with a pole the fine mesh of the rotated grid is rotated back.
+
+    :return: dict(lat (ny n), lon (nx n), cell_lat, cell_lon): the axes form with cell_lat = cell_lon = None, or, with a pole,
+             the point form — cell_lat, cell_lon of (ny n, nx n) — with lat = lon = None; the two forms of
+             ``amt_gather_mosaic_supersampled``
+    """
+    grid = plan['grid']
+    lat = _subsample_axis(grid.lat[:, 0], n)
+    lon = _subsample_axis(grid.lon[0, :], n)
+    if plan['contains_pole']:
+        la, lo = _rotate_pole_host(np.repeat(lat[:, None], lon.size, 1), np.repeat(lon[None, :], lat.size, 0), plan['altitude'], -90)
+        return dict(lat=None, lon=None, cell_lat=la, cell_lon=lo)
+    if plan['contains_discontinuity']:
+        lon = wrap_at_180(lon + 180)
+    return dict(lat=lat, lon=lon, cell_lat=None, cell_lon=None)
+
+
 def _gather_box(ctx, params, min_elevation, magnetic):
     """The 8-number bounding-box reduction of a camera frame whose arrays do not exist (the box pass of the frame kernel:
     no per-pixel array is written), in (lat, lon) or (MLat, SM longitude); [7]: a pole of those coordinates is in view."""
@@ -2130,17 +2191,29 @@ def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magne
     return plan
 
 
-def gather_frame(plan, image, interpolation='linear', magnetic=False):
+def gather_frame(plan, image, interpolation='linear', magnetic=False, supersample=1, minCoverage=None):
     """
     The device side of :func:`resampleGather` on a :func:`gather_plan`: cell centres through ``amt_grid_to_pixel`` (with a pole
     in view the centres of the rotated grid are rotated back and go through ``amt_world_to_pixel``), the image through
     ``amt_remap_coords`` or, for 'nearest', a gather of pixel (rint x, rint y).  Returns a :func:`resample_frame`-like dict:
     lat, lon, lat_c, lon_c, img, mask, elevation (exact line-of-sight elevation of every cell centre), flags, support.
+
+    ``supersample`` n > 1: one call of ``amt_gather_mosaic_supersampled`` on a table of this one member — n x n sub-samples per
+    cell (:func:`gather_subsample_coordinates`), each masked by the same rules, the seen ones averaged.  The dict then holds
+    ``count`` (ny, nx) uint8, the seen sub-samples of every cell, in place of flags and support; a cell is masked unless
+    ``count >= supersample_min_count(minCoverage, n)``, and elevation is the mean over the seen sub-samples.
     """
     import torch
     from .coordinates.inverse import W2P_GEODETIC, W2P_SM, grid_to_pixel, world_to_pixel
     from .util.lensdistortion import INTERPOLATIONS, _image_to_device
     _check_gather_interpolation(interpolation)
+    n, min_count = _check_supersample(supersample, minCoverage)
+    if n > 1:
+        member = dict(params=plan['params'], zenithal=plan['zenithal'], min_elevation=plan['min_elevation'],
+                      center_mask=plan['center_mask'])
+        out = _gather_supersampled(plan, [member], [image], interpolation, magnetic, 1, n, min_count, None)
+        del out['source']
+        return out
     ctx = Context.current()
     grid, params, zen = plan['grid'], plan['params'], plan['zenithal']
     frame = W2P_SM if magnetic else W2P_GEODETIC
@@ -2187,33 +2260,47 @@ def _gather_image(mapping):
     return mapping.img_unmasked if img is None else img
 
 
-def _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic):
+def _with_coverage(mapping, res, n):
+    """the fraction of every cell's sub-samples that were seen, as a plain attribute of a supersampled result"""
+    if n > 1:
+        mapping.coverage = res['count'] / float(n * n)
+    return mapping
+
+
+def _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic, supersample=1, minCoverage=None):
     _check_gather_interpolation(interpolation)
+    n, _ = _check_supersample(supersample, minCoverage)
     plan = gather_plan(mapping, pxPerDeg, arcsecPerPx, containsPole, magnetic)
-    res = gather_frame(plan, _gather_image(mapping), interpolation, magnetic)
+    res = gather_frame(plan, _gather_image(mapping), interpolation, magnetic, supersample, minCoverage)
     img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
     elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
     if not magnetic:
-        return mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img)
+        return _with_coverage(mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img), res, n)
     from .coordinates.transform import smToLatLon
     from .mapping.mapping import GenericMapping
     nc = res['lat'].size
     la, lo = smToLatLon(np.concatenate((res['lat'].ravel(), res['lat_c'].ravel())),
                         np.concatenate((res['lon'].ravel(), res['lon_c'].ravel())), mapping.photoTime)
-    return GenericMapping(la[:nc].reshape(res['lat'].shape), lo[:nc].reshape(res['lon'].shape),
-                          la[nc:].reshape(res['lat_c'].shape), lo[nc:].reshape(res['lon_c'].shape), elevation,
-                          mapping.altitude, img, mapping.cameraPosGCRS, mapping.photoTime, mapping.identifier)
+    return _with_coverage(GenericMapping(la[:nc].reshape(res['lat'].shape), lo[:nc].reshape(res['lon'].shape),
+                                         la[nc:].reshape(res['lat_c'].shape), lo[nc:].reshape(res['lon_c'].shape), elevation,
+                                         mapping.altitude, img, mapping.cameraPosGCRS, mapping.photoTime, mapping.identifier),
+                          res, n)
 
 
-def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear'):
+def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear', supersample=1,
+                   minCoverage=None):
     """
     Resampling by gathering: every cell centre of the grid that :func:`resample` would choose for the same arguments is
     projected into the image through the inverse of the camera model (``amt_grid_to_pixel``) and the image is sampled there
     (``amt_remap_coords``: 'linear' or 'lanczos4'; 'nearest': the pixel at (rint x, rint y)).  The result has no holes at any
     resolution, also finer than the pixel footprint, where binning pixel centres leaves cells empty, and it needs no
     triangulation: unlike ``resample(method='linear')`` (scipy's griddata) it interpolates in the pixel plane, not in the
-    lat / lon plane.  For cells much coarser than a pixel it samples one point per cell without averaging (aliasing); mean and
-    area binning serve that case.
+    lat / lon plane.  With ``supersample=1`` it samples one point per cell without averaging, which aliases where cells are
+    much coarser than a pixel; ``supersample=n`` (2 ... 8) serves that case: every cell is split into n x n equal parts, the
+    centre of each is gathered by the same rules, and the cell takes the mean of the seen ones, in one fused kernel
+    (``amt_gather_mosaic_supersampled``; :func:`gather_subsample_coordinates` says where the sub-samples lie).  A cell is then
+    masked unless at least ``supersample_min_count(minCoverage, n)`` of its n x n sub-samples are seen (`minCoverage` None: half of
+    them), ``.elevation`` is the mean over the seen ones, and the result carries ``.coverage`` (ny, nx), the seen fraction.
 
     A cell is masked where its centre is not seen in the frame (any flag of ``amt_world_to_pixel``: invalid, hidden, outside
     the projection's domain or the frame), where the sampled point has no support (it lies outside [0, width - 1] x
@@ -2227,9 +2314,13 @@ def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, in
     made from a bare direction array or a raw frame with a lens, and for MIRACLE / THEMIS.
 
     :param interpolation: 'nearest', 'linear' or 'lanczos4'
+    :param int supersample: sub-samples per cell and axis, 1 ... 8
+    :param None|number minCoverage: with ``supersample > 1`` only: the least seen fraction of a valid cell, in (0, 1]
+    :raises ValueError: for an unknown interpolation, then for a `supersample` that is not an int in 1 ... 8, a `minCoverage`
+                        outside (0, 1], and a `minCoverage` given with ``supersample=1`` — before any device work
     :rtype: GenericMapping (what ``mapping.createResampled`` returns)
     """
-    return _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation, False)
+    return _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation, False, supersample, minCoverage)
 
 
 def resampleGatherMLatMLT(mapping, **kw):
@@ -2327,30 +2418,11 @@ def gather_mosaic_plan(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=N
     return plan
 
 
-def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=False, debug=None, xy=False):
-    """
-    The device side of :func:`resampleGatherMosaic` on a :func:`gather_mosaic_plan`: ONE call of ``amt_gather_mosaic``
-    (include/auromat_hip.h states what it computes), which projects every cell centre through every member's camera model,
-    elects one member per cell by the plan's rule and samples that member's image alone.  With a pole in view the centres of
-    the rotated grid are rotated back on the host and go in through the point form, as in :func:`gather_frame`.
-
-    :param images: one image per member (default: the plan's)
-    :param debug: dict(force_path=GATHER_PATH_*, tile_path=True): amt_gather_debug; the result then holds ``tile_path``
-                  (tiles_y, tiles_x) uint8
-    :param xy: also return ``xy`` (ny, nx, 2) float64, the winner's pixel coordinates
-    :return: dict like :func:`mosaic_frames`': lat, lon, lat_c, lon_c, img (ny, nx, C), mask (ny, nx) bool, elevation (ny, nx;
-             the winner's, NaN where nobody sees the cell), source (ny, nx) int32 [-1: nobody], plan
-    """
-    import torch
-    from ._native import GatherDebug, GatherMember
-    from .coordinates.inverse import W2P_GEODETIC, W2P_SM
+def _gather_member_table(ctx, members, images):
+    """The amt_gather_member table of a gather call: (table, keep, channels, torch dtype, numpy dtype); `keep` holds what the
+    table points to and has to outlive the call's kernel."""
+    from ._native import GatherMember
     from .util.lensdistortion import _image_to_device
-    _check_gather_interpolation(interpolation)
-    ctx = Context.current()
-    grid, members = plan['grid'], plan['members']
-    images = [m['image'] for m in members] if images is None else list(images)
-    if len(images) != len(members):
-        raise ValueError('%d images for %d members' % (len(images), len(members)))
     table = (GatherMember * len(members))()
     keep, kinds, np_dtype = [], set(), None
     for t, m, image in zip(table, members, images):
@@ -2370,6 +2442,88 @@ def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=Fal
     if len(kinds) != 1:
         raise ValueError('the members\' images differ in dtype or channel count')
     _, nch, tdtype = next(iter(kinds))
+    return table, keep, nch, tdtype, np_dtype
+
+
+def _gather_debug(ctx, debug, ny, nx, tile):
+    """amt_gather_debug of a `debug` dict and the tensor of its tile_path (one byte per `tile` x `tile` cells), or None, None"""
+    from ._native import GatherDebug
+    if debug is None:
+        return None, None
+    import torch
+    dbg, tiles = GatherDebug(), None
+    dbg.force_path = int(debug.get('force_path', GATHER_PATH_AUTO))
+    if debug.get('tile_path'):
+        tiles = ctx.zeros(((ny + tile - 1) // tile, (nx + tile - 1) // tile), torch.uint8)
+        dbg.tile_path = ptr(tiles).value
+    return dbg, tiles
+
+
+def _gather_supersampled(plan, members, images, interpolation, magnetic, rule, n, min_count, debug):
+    """ONE call of ``amt_gather_mosaic_supersampled`` (include/auromat_hip.h states what it computes) on the plan's grid with
+    n x n sub-samples per cell: the result dict of :func:`gather_mosaic_frames` plus ``count``."""
+    import torch
+    from .coordinates.inverse import W2P_GEODETIC, W2P_SM
+    ctx = Context.current()
+    grid = plan['grid']
+    ny, nx = grid.ny, grid.nx
+    table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, members, images)
+    sub = gather_subsample_coordinates(plan, n)
+    dev = {k: None if v is None else ctx.to_device(np.ascontiguousarray(v)) for k, v in sub.items()}
+    img = torch.empty((ny, nx, nch), dtype=tdtype, device=ctx.device)
+    mask = ctx.empty((ny, nx), torch.uint8)
+    elev = ctx.empty((ny, nx))
+    source = ctx.empty((ny, nx), torch.int32)
+    count = ctx.empty((ny, nx), torch.uint8)
+    dbg, tiles = _gather_debug(ctx, debug, ny, nx, 32 // n)
+    ctx.call('amt_gather_mosaic_supersampled', table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(dev['lat']), ny,
+             ptr(dev['lon']), nx, ptr(dev['cell_lat']), ptr(dev['cell_lon']), n, min_count, img.element_size(), nch,
+             _GATHER_INTERP_CODES[interpolation], int(rule), ptr(img), ptr(mask), ptr(elev), ptr(source), ptr(count),
+             None if dbg is None else C.byref(dbg))
+    out = dict(grid_coordinates(plan), grid=grid, img=to_host(img, dtype=np_dtype), mask=to_host(mask).astype(bool),
+               elevation=to_host(elev), source=to_host(source, dtype=np.int32), count=to_host(count, dtype=np.uint8),
+               contains_pole=plan['contains_pole'], contains_discontinuity=plan['contains_discontinuity'],
+               altitude=plan['altitude'], plan=plan)
+    if tiles is not None:
+        out['tile_path'] = to_host(tiles)
+    del keep, dev                # (after the read-back above: the kernel is done with them)
+    return out
+
+
+def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=False, debug=None, xy=False, supersample=1,
+                         minCoverage=None):
+    """
+    The device side of :func:`resampleGatherMosaic` on a :func:`gather_mosaic_plan`: ONE call of ``amt_gather_mosaic``
+    (include/auromat_hip.h states what it computes), which projects every cell centre through every member's camera model,
+    elects one member per cell by the plan's rule and samples that member's image alone.  With a pole in view the centres of
+    the rotated grid are rotated back on the host and go in through the point form, as in :func:`gather_frame`.
+
+    ``supersample`` n > 1: ONE call of ``amt_gather_mosaic_supersampled`` instead — the same at each of the n x n sub-samples
+    of every cell (:func:`gather_subsample_coordinates`), reduced to cells in the kernel: the mean of the seen sub-samples'
+    samples and elevations, ``source`` the member that won most of them, ``count`` (ny, nx) uint8 how many were seen, and a
+    cell masked unless ``count >= supersample_min_count(minCoverage, n)``.  `xy` does not go with it.
+
+    :param images: one image per member (default: the plan's)
+    :param debug: dict(force_path=GATHER_PATH_*, tile_path=True): amt_gather_debug; the result then holds ``tile_path``
+                  (tiles_y, tiles_x) uint8, a tile being 32 x 32 cells (32 // n x 32 // n with ``supersample`` n)
+    :param xy: also return ``xy`` (ny, nx, 2) float64, the winner's pixel coordinates
+    :return: dict like :func:`mosaic_frames`': lat, lon, lat_c, lon_c, img (ny, nx, C), mask (ny, nx) bool, elevation (ny, nx;
+             the winner's, NaN where nobody sees the cell), source (ny, nx) int32 [-1: nobody], plan
+    """
+    import torch
+    from .coordinates.inverse import W2P_GEODETIC, W2P_SM
+    _check_gather_interpolation(interpolation)
+    n, min_count = _check_supersample(supersample, minCoverage)
+    ctx = Context.current()
+    grid, members = plan['grid'], plan['members']
+    images = [m['image'] for m in members] if images is None else list(images)
+    if len(images) != len(members):
+        raise ValueError('%d images for %d members' % (len(images), len(members)))
+    if n > 1:
+        if xy:
+            raise ValueError('xy: a supersampled cell has no single pixel position')
+        return _gather_supersampled(plan, members, images, interpolation, magnetic, plan['rule'], n, min_count, debug)
+    table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, members, images)
     coords = grid_coordinates(plan)
     ny, nx = grid.ny, grid.nx
     if plan['contains_pole']:
@@ -2385,13 +2539,7 @@ def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=Fal
     elev = ctx.empty((ny, nx))
     source = ctx.empty((ny, nx), torch.int32)
     out_xy = ctx.empty((ny, nx, 2)) if xy else None
-    dbg, tiles = None, None
-    if debug is not None:
-        dbg = GatherDebug()
-        dbg.force_path = int(debug.get('force_path', GATHER_PATH_AUTO))
-        if debug.get('tile_path'):
-            tiles = ctx.zeros(((ny + 31) // 32, (nx + 31) // 32), torch.uint8)
-            dbg.tile_path = ptr(tiles).value
+    dbg, tiles = _gather_debug(ctx, debug, ny, nx, 32)
     ctx.call('amt_gather_mosaic', table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(lat_ax), ny, ptr(lon_ax), nx,
              ptr(cell_lat), ptr(cell_lon), img.element_size(), nch, _GATHER_INTERP_CODES[interpolation], int(plan['rule']),
              ptr(img), ptr(mask), ptr(elev), ptr(source), ptr(out_xy), None if dbg is None else C.byref(dbg))
@@ -2406,12 +2554,14 @@ def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=Fal
     return out
 
 
-def _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic):
+def _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic, supersample=1,
+                            minCoverage=None):
     from .mapping.mapping import MosaicMapping
     _check_gather_interpolation(interpolation)
+    n, _ = _check_supersample(supersample, minCoverage)
     collection = _gather_collection(collection)
     plan = gather_mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole, magnetic)
-    res = gather_mosaic_frames(plan, None, interpolation, magnetic)
+    res = gather_mosaic_frames(plan, None, interpolation, magnetic, supersample=supersample, minCoverage=minCoverage)
     img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
     elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
     source = ma.masked_array(res['source'], mask=res['source'] < 0)
@@ -2425,11 +2575,12 @@ def _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, int
         la, lo = smToLatLon(np.concatenate((lat.ravel(), lat_c.ravel())), np.concatenate((lon.ravel(), lon_c.ravel())), photoTime)
         lat, lon = la[:nc].reshape(lat.shape), lo[:nc].reshape(lon.shape)
         lat_c, lon_c = la[nc:].reshape(lat_c.shape), lo[nc:].reshape(lon_c.shape)
-    return MosaicMapping(lat, lon, lat_c, lon_c, elevation, plan['altitude'], img, first.cameraPosGCRS, photoTime,
-                         collection.identifier, source, plan['identifiers'])
+    return _with_coverage(MosaicMapping(lat, lon, lat_c, lon_c, elevation, plan['altitude'], img, first.cameraPosGCRS, photoTime,
+                                        collection.identifier, source, plan['identifiers']), res, n)
 
 
-def resampleGatherMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear'):
+def resampleGatherMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear', supersample=1,
+                         minCoverage=None):
     """
     :func:`resampleGather` for a collection: every member gathered onto ONE grid — the grid :func:`resampleMosaic` lays out
     for the same collection and arguments — in one fused kernel (``amt_gather_mosaic``).  Every cell centre is projected
@@ -2442,13 +2593,24 @@ def resampleGatherMosaic(collection, pxPerDeg=25, arcsecPerPx=None, containsPole
     ``.elevation`` of the result is the winner's exact line-of-sight elevation, ``.source`` the winner's index (masked where
     nobody sees the cell), ``.members`` the members' identifiers.
 
+    ``supersample=n`` (2 ... 8), for cells much coarser than a pixel: all of the above happens at the n x n sub-samples of
+    every cell (:func:`gather_subsample_coordinates`) — each has its own winner — and the cell takes the mean of the seen
+    sub-samples' samples and elevations, in the same kernel launch (``amt_gather_mosaic_supersampled``).  ``.source`` is then
+    the member that won most sub-samples (the earlier one on a tie), a cell is masked unless at least
+    ``supersample_min_count(minCoverage, n)`` sub-samples are seen (`minCoverage` None: half of them), and the result
+    carries ``.coverage`` (ny, nx), the seen fraction.
+
     :param interpolation: 'nearest', 'linear' or 'lanczos4'
-    :raises ValueError: for an unknown interpolation (before anything else), an empty collection, members of different
-                        altitudes or image dtypes / channel counts
+    :param int supersample: sub-samples per cell and axis, 1 ... 8
+    :param None|number minCoverage: with ``supersample > 1`` only: the least seen fraction of a valid cell, in (0, 1]
+    :raises ValueError: for an unknown interpolation (before anything else), then a `supersample` that is not an int in
+                        1 ... 8, a `minCoverage` outside (0, 1] or given with ``supersample=1``; an empty collection, members
+                        of different altitudes or image dtypes / channel counts
     :raises NotImplementedError: for a member without a camera model in closed form (named in the message)
     :rtype: MosaicMapping
     """
-    return _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, False)
+    return _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, False, supersample,
+                                   minCoverage)
 
 
 def resampleGatherMosaicMLatMLT(collection, **kw):

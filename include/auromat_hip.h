@@ -63,7 +63,8 @@ extern "C" {
  *    amt_scanline_select, amt_scanline_pack, amt_scanline_compose, amt_scanline_strip (auromat_amd.resample.resampleScanLines);
  *    the core role of the frame kernel's work items — amt_georef_last_core, amt_georef_core_bands, amt_run_core_stats,
  *    amt_georef_set_roles(ctx, 2); gather mosaics — amt_gather_mosaic, amt_gather_member, amt_gather_debug, AMT_INTERP_NEAREST
- *    (auromat_amd.resample.resampleGatherMosaic) */
+ *    (auromat_amd.resample.resampleGatherMosaic); supersampled gathering — amt_gather_mosaic_supersampled
+ *    (auromat_amd.resample.resampleGather / resampleGatherMosaic with supersample > 1) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -492,6 +493,39 @@ int amt_gather_mosaic(amt_ctx* ctx, const amt_gather_member* members, int32_t n_
                       int32_t ny, const double* lon_centres, int32_t nx, const double* cell_lat, const double* cell_lon,
                       int32_t sample_bytes, int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask,
                       double* out_elev, int32_t* out_source, double* out_xy, const amt_gather_debug* debug);
+
+/* ---- supersampled gather mosaic: n x n sub-samples per cell, reduced in the same kernel (addition to ABI 10) ----------------------
+ * auromat_amd.resample.resampleGather / resampleGatherMosaic with supersample > 1: for cells much coarser than a pixel.
+ * Cell (i, j) of the ny x nx grid has n x n sub-samples (s, t), s, t = 0 ... n - 1, n = factor in 1 ... 8.  Their coordinates come
+ * in the two forms of amt_gather_mosaic: the axes form - sub_lat[ny * n], sub_lon[nx * n], sub-sample (s, t) of cell (i, j) is the
+ * point (sub_lat[i * n + s], sub_lon[j * n + t]) - or, when both axes are NULL, the point form - sub_cell_lat, sub_cell_lon of
+ * (ny * n, nx * n) each, sub-sample (s, t) of cell (i, j) at [i * n + s][j * n + t].
+ * For every sub-sample the kernel computes exactly what amt_gather_mosaic computes for a cell centre at that point: which members
+ * see it (rules 1-4 above; a NaN elevation never wins), the winner by `rule`, the winner's sample in the image type (integer samples
+ * are already rounded and clamped) and the winner's float64 elevation.  Then, per cell:
+ *   out_count (uint8, ny x nx): the number of sub-samples with a winner, always written;
+ *   the cell is valid iff count >= min_count, 1 <= min_count <= n * n; out_mask = !valid;
+ *   a valid cell, integer samples: per channel S = the exact integer sum of the seen sub-samples' samples, the output
+ *     rint((double)S / (double)count), half to even;
+ *   a valid cell, float32 samples: per channel the float64 sum of the seen sub-samples in row-major order (s outer, t inner), which
+ *     the first seen value starts, divided by (double)count and rounded to float32;
+ *   out_elev: the float64 sum of the seen sub-samples' elevations in the same order, divided by (double)count;
+ *   out_source: the member that won the most sub-samples, the lower index on a tie;
+ *   an invalid cell: image 0, out_source -1, out_elev NaN (out_count still the real count).
+ * There is no out_xy.  factor 1 with min_count 1 gives amt_gather_mosaic's outputs bit for bit.
+ * One block makes T x T cells, T = 32 / factor (integer division): at most 32 x 32 sub-sample points, elected and sampled by the
+ * code of amt_gather_mosaic's kernel, staged window or per-point taps alike, and reduced to cells through LDS; no array of the
+ * sub-sample grid exists in device memory.  debug as above, per T x T tile: tile_path has ceil(ny / T) x ceil(nx / T) bytes, 0 nobody
+ * sees any sub-sample of the tile, AMT_GATHER_PATH_STAGED all winners of the tile are one member and their taps fit the window,
+ * AMT_GATHER_PATH_CELL any other tile (nearest: always); force_path AMT_GATHER_PATH_CELL gives the same bits.
+ * Only enqueues work on the context's stream (the member table goes to the context's workspace).  AMT_EINVAL (nothing written):
+ * everything amt_gather_mosaic refuses, factor outside 1 ... 8, min_count outside 1 ... factor * factor, NULL out_count, and a
+ * sub-sample grid whose side does not fit an int32. */
+int amt_gather_mosaic_supersampled(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                                   const double* sub_lat, int32_t ny, const double* sub_lon, int32_t nx, const double* sub_cell_lat,
+                                   const double* sub_cell_lon, int32_t factor, int32_t min_count, int32_t sample_bytes,
+                                   int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask,
+                                   double* out_elev, int32_t* out_source, uint8_t* out_count, const amt_gather_debug* debug);
 
 /* auromat/coordinates/intersection.py:144-163 ellipsoidLineIntersection (and
  * auromat/mapping/mapping.py:1474-1510 inflatedEarthIntersection with a=wgs84A+h, b=wgs84B+h).
