@@ -154,6 +154,14 @@ class GatherDebug(C.Structure):
     _fields_ = [('force_path', C.c_int32), ('reserved', C.c_int32), ('tile_path', C.c_void_p)]
 
 
+class GatherJob(C.Structure):
+    """amt_gather_job"""
+    _fields_ = [('member', GatherMember), ('ny', C.c_int32), ('nx', C.c_int32), ('lat', C.c_void_p), ('lon', C.c_void_p),
+                ('cell_lat', C.c_void_p), ('cell_lon', C.c_void_p), ('out_img', C.c_void_p), ('out_mask', C.c_void_p),
+                ('out_elev', C.c_void_p), ('out_count', C.c_void_p)]
+
+
+GATHER_MAX_JOBS = 64     # AMT_GATHER_MAX_JOBS: jobs per call of amt_gather_frames
 ABI_VERSION = 10         # include/auromat_hip.h AMT_ABI_VERSION
 QUANTILES_MAX = 8         # AMT_QUANTILES_MAX: quantiles per call of amt_quantile_frame[_async]
 PIPE_MAX_EDGE_PIXELS = 16384     # AMT_PIPE_MAX_EDGE_PIXELS: a fused frame with more on-edge pixels is not launched again
@@ -204,6 +212,7 @@ _SIGNATURES = {
                           [C.c_int32] * 4 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
     'amt_gather_mosaic_supersampled': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
                                        [C.c_int32] * 6 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
+    'amt_gather_frames': ([_P, C.POINTER(GatherJob)] + [C.c_int32] * 7 + [C.POINTER(GatherDebug)], _I),
     'amt_intersect_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersects_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersect_sphere': ([_P, _D, c_double_p, _P, _L, _I, _P], _I),

@@ -28,6 +28,12 @@ What differs, and why:
   the cells it overlaps, weighted with the covered fraction of the cell (:func:`auromat_amd.resample.resampleArea` /
   ``resampleAreaMLatMLT``), through the same two routes: no holes between the pixel centres on fine grids.  ``--min-coverage F``
   (default 0.5, in [0, 1]) masks the cells of which the pixels cover less than F.  The files hold the variables a mean grid's do.
+* ``--gather {nearest,linear,lanczos4}`` (an addition; needs ``--resample``, not with a ``--statistic`` other than mean or with
+  ``--lens-route raw``) gathers in place of binning: every cell centre of the frame's grid is projected into the image and the image
+  is sampled there (:func:`auromat_amd.resample.resampleGather` / ``resampleGatherMLatMLT``; the pipeline route is
+  :class:`auromat_amd.pipeline.GatherSequence`, a batch of frames per kernel launch).  ``--supersample N`` (1 ... 8) averages N x N
+  sub-samples per cell; ``--min-coverage F`` (in (0, 1], default 0.5) then masks the cells of which fewer are seen.  The files hold
+  the variables a mean grid's do.
 * ``--lens-model`` / ``--lens-params`` (an addition): the images are RAW-developed frames that have not been corrected for lens
   distortion, while their ``.wcs`` files were solved on the corrected image, cropped to a multiple of ``--crop-divisible-by`` — the
   state of the ESA ISS archive, whose ``distortion_correction`` entry (reference mapping/iss.py:233-237) is honoured when it is
@@ -53,6 +59,9 @@ auromat-convert --data frames/ --format netcdf --resample --resolution 80
 
 Resample a long sequence on a fixed 0.1 degree geographic grid, as fast as the GPU goes:
 auromat-convert --data frames/ --format netcdf --resample --grid geo --px-per-deg 10
+
+Gather instead of binning, 4 x 4 sub-samples per cell (no holes on fine grids, no aliasing on coarse ones):
+auromat-convert --data frames/ --format netcdf --resample --gather linear --supersample 4
 
 Don't store pixel corner coordinates:
 auromat-convert --data frames/ --format netcdf --without-bounds
@@ -118,6 +127,13 @@ def getParser():
     resampleArgs.add_argument('--min-coverage', dest='minCoverage', metavar='F', type=float,
                               help='for --statistic area: a cell is masked unless the pixels cover at least this fraction of it, '
                                    'in [0, 1], default 0.5 (0: any overlap at all)')
+    resampleArgs.add_argument('--gather', choices=['nearest', 'linear', 'lanczos4'],
+                              help='with --resample: gather in place of binning - every cell centre of the grid is projected into '
+                                   'the image and the image is sampled there with this interpolation; no holes at any resolution')
+    resampleArgs.add_argument('--supersample', metavar='N', type=int,
+                              help='for --gather: N x N sub-samples per cell, averaged, 1 ... 8, default 1; for cells much coarser '
+                                   'than a pixel.  --min-coverage F, in (0, 1], then masks the cells of which fewer than that '
+                                   'fraction of the sub-samples is seen, default 0.5')
     lensArgs = parser.add_argument_group('lens distortion', 'For images that are not yet corrected for lens distortion (an addition; '
                                          'by default the distortion_correction entry of metadata.json or <id>.json, if any).')
     lensArgs.add_argument('--lens-model', dest='lensModel', choices=['poly3', 'poly5', 'ptlens'],
@@ -176,8 +192,26 @@ def parseargs(argv=None):
             args.minCoverage = 0.5
         if not 0.0 <= args.minCoverage <= 1.0:
             parser.error('--min-coverage must be in the range [0, 1]')
-    elif args.minCoverage is not None:
+    elif args.minCoverage is not None and not args.gather:
         parser.error('--min-coverage is only usable with --statistic area')
+    if args.supersample is not None and not args.gather:
+        parser.error('--supersample is only usable with --gather')
+    if args.gather:
+        if not args.resample:
+            parser.error('--gather needs --resample')
+        if args.statistic != 'mean':
+            parser.error('--gather takes the place of binning: not with --statistic %s' % args.statistic)
+        if args.lensRoute == 'raw':
+            parser.error('--gather needs the inverse of the camera model, which --lens-route raw does not have')
+        if args.supersample is None:
+            args.supersample = 1
+        if not 1 <= args.supersample <= 8:
+            parser.error('--supersample must be in the range 1 ... 8')
+        if args.minCoverage is not None:
+            if args.supersample == 1:
+                parser.error('--min-coverage goes with --supersample above 1: one point is sampled per cell')
+            if not 0.0 < args.minCoverage <= 1.0:
+                parser.error('--min-coverage must be in the range (0, 1] with --gather')
     if (args.lensModel is None) != (args.lensParams is None):
         parser.error('--lens-model and --lens-params go together')
     if args.lensModel is not None:
@@ -310,8 +344,8 @@ def extension(args):
 def convert_with_classes(args, frames, export):
     """Frame by frame through the mapping classes: the reference's flow, its resolution rule included."""
     from ..mapping.spacecraft import getMapping
-    from ..resample import (resample, resampleArea, resampleAreaMLatMLT, resampleMedian, resampleMedianMLatMLT, resampleMLatMLT,
-                            resampleQuantile, resampleQuantileMLatMLT)
+    from ..resample import (resample, resampleArea, resampleAreaMLatMLT, resampleGather, resampleGatherMLatMLT, resampleMedian,
+                            resampleMedianMLatMLT, resampleMLatMLT, resampleQuantile, resampleQuantileMLatMLT)
     metadata = read_metadata(args.data)
     for identifier, hdr, img_path in frames:
         path = target_path(args, identifier)
@@ -323,7 +357,11 @@ def convert_with_classes(args, frames, export):
         if args.resample:
             if args.minElevation >= 0:
                 mapping = mapping.maskedByElevation(args.minElevation)
-            if args.statistic == 'median':
+            if args.gather:
+                fn = resampleGather if args.grid == Grid.geo else resampleGatherMLatMLT
+                mapping = fn(mapping, interpolation=args.gather, supersample=args.supersample, minCoverage=args.minCoverage,
+                             **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
+            elif args.statistic == 'median':
                 fn = resampleMedian if args.grid == Grid.geo else resampleMedianMLatMLT
                 mapping = fn(mapping, **(dict(pxPerDeg=args.pxPerDeg) if args.pxPerDeg else dict(arcsecPerPx=args.resolution)))
             elif args.statistic == 'quantile':
@@ -346,7 +384,7 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
     ``resample`` / ``resampleMLatMLT`` would have returned: a GenericMapping in geodetic coordinates; a grid that is
     regular in (MLat, SM longitude) goes through SM -> GEO like ``convertSMMappingToGeo`` (reference
     mapping.py:1549-1559).  The elevation comes from the 'mean' block or, for median, quantile and area-weighted grids, the
-    'median' / 'quantile' / 'area' block."""
+    'median' / 'quantile' / 'area' block; a gathered grid has no block and brings a plain 'elevation' (NaN where masked)."""
     from ..coordinates.transform import smToLatLon
     from ..mapping.mapping import GenericMapping
     lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
@@ -354,8 +392,9 @@ def grid_mapping(res, cam, t, altitude, identifier, magnetic):
         lat, lon = smToLatLon(lat, lon, t)
         lat_c, lon_c = smToLatLon(lat_c, lon_c, t)
     img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    block = next(res[k] for k in ('mean', 'median', 'quantile', 'area') if k in res)
-    return GenericMapping(lat, lon, lat_c, lon_c, ma.masked_invalid(block[:, :, -1]), altitude, img, cam, t, identifier)
+    block = next((res[k] for k in ('mean', 'median', 'quantile', 'area') if k in res), None)
+    elevation = res['elevation'] if block is None else block[:, :, -1]
+    return GenericMapping(lat, lon, lat_c, lon_c, ma.masked_invalid(elevation), altitude, img, cam, t, identifier)
 
 
 def host_snapshot(mapping, with_mag):
@@ -379,7 +418,7 @@ def convert_with_pipeline(args, frames, export):
     import torch
     import torch.distributed as dist
     from ..mapping.spacecraft import frame_inputs
-    from ..pipeline import SequencePipeline
+    from ..pipeline import GatherSequence, SequencePipeline
     from ..resample import grid_coordinates
     from ..sequence import shard
     from .._native import to_host
@@ -417,12 +456,19 @@ def convert_with_pipeline(args, frames, export):
         if any(m is not None for m in lenses) and any(m is None or m.corrected_size != lenses[0].corrected_size for m in lenses):
             raise NotImplementedError('a sequence of which only some frames carry a lens distortion')
         size = lenses[0].corrected_size if lenses[0] is not None else (first.shape[1], first.shape[0])
-        seq = SequencePipeline(size[0], size[1], nchan=first.shape[2], img_dtype=first.dtype,
-                               altitude=args.altitude, fast=not args.exactCenters,
-                               min_elevation=args.minElevation if args.minElevation >= 0 else None,
-                               pxPerDeg=args.pxPerDeg or 10, magnetic=magnetic, keep_coordinates=False,
-                               arcsecPerPx=None if args.pxPerDeg else args.resolution, statistic=args.statistic,
-                               quantile=args.quantile, minCoverage=args.minCoverage)
+        if args.gather:
+            # gathering in place of binning: a batch of frames per launch of the gather kernel (GatherSequence)
+            seq = GatherSequence(size[0], size[1], nchan=first.shape[2], img_dtype=first.dtype, altitude=args.altitude,
+                                 min_elevation=args.minElevation if args.minElevation >= 0 else None, pxPerDeg=args.pxPerDeg or 25,
+                                 arcsecPerPx=None if args.pxPerDeg else args.resolution, magnetic=magnetic,
+                                 interpolation=args.gather, supersample=args.supersample, minCoverage=args.minCoverage)
+        else:
+            seq = SequencePipeline(size[0], size[1], nchan=first.shape[2], img_dtype=first.dtype,
+                                   altitude=args.altitude, fast=not args.exactCenters,
+                                   min_elevation=args.minElevation if args.minElevation >= 0 else None,
+                                   pxPerDeg=args.pxPerDeg or 10, magnetic=magnetic, keep_coordinates=False,
+                                   arcsecPerPx=None if args.pxPerDeg else args.resolution, statistic=args.statistic,
+                                   quantile=args.quantile, minCoverage=args.minCoverage)
 
         def feed():
             # decoding a 12 Mpx JPEG takes ~100 ms of host time, the GPU 0.2 ms per frame: images are read ahead on a
@@ -470,7 +516,8 @@ def convert_with_pipeline(args, frames, export):
                     continue
                 host = dict(res)
                 host.update(grid_coordinates(res))
-                stat = args.statistic               # the name of the block: 'mean', 'median', 'quantile' or 'area'
+                # the name of the block: 'mean', 'median', 'quantile' or 'area'; a gathered grid brings a plain elevation
+                stat = 'elevation' if args.gather else args.statistic
                 host[stat] = to_host(res[stat])
                 host.update(img=to_host(res['img'], dtype=first.dtype), mask=to_host(res['mask']).astype(bool))
                 print('storing', path)

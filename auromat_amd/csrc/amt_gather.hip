@@ -15,6 +15,10 @@
 // The supersampled form (amt_gather_mosaic_supersampled) runs the same steps — load_points, elect, survey, stage_window,
 // sample_point below are the one code of both kernels — on the n x n sub-sample points of T x T cells, T = 32 / n, laid over the
 // same 32 x 32 threads' points, and then reduces the points to cells through LDS (k_gather_mosaic_ss).
+//
+// A batch of frames (amt_gather_frames): up to 64 jobs, each one member with its own grid and outputs, in ONE launch over the sum
+// of their tiles.  The two kernels' bodies are device functions that take the tile's position (gather_tile_body, gather_ss_body);
+// k_gather_frames looks its block's job up in a prefix table of tile counts and calls the same bodies.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -138,9 +142,9 @@ __device__ __forceinline__ void elect(const gather_args& A, const gather_points&
 }
 
 // ---- what the tile holds: the range of its winners and the box of their taps, as (min, -max) so that one fold serves all ----
-// (a barrier inside: every thread of the block calls it; `fold` is the block's)
+// (a barrier inside: every thread of the block calls it; `fold` is the block's, `tile` its tile's row-major index in the grid)
 template <int N>
-__device__ __forceinline__ gather_tile survey(const gather_args& A, const gather_best& B, gather_taps& t, int (&fold)[4][6]) {
+__device__ __forceinline__ gather_tile survey(const gather_args& A, const gather_best& B, gather_taps& t, int (&fold)[4][6], int tile) {
     constexpr int lo = tap_range<N>::lo, hi = tap_range<N>::hi;
     int r0 = INT32_MAX, r1 = INT32_MAX, b0 = INT32_MAX, b1 = INT32_MAX, b2 = INT32_MAX, b3 = INT32_MAX;
 #pragma unroll
@@ -176,7 +180,7 @@ __device__ __forceinline__ gather_tile survey(const gather_args& A, const gather
     W.staged = N != 0 && W.any && m_lo == m_hi && W.nwx <= kWin && W.nwy <= kWin && A.force != AMT_GATHER_PATH_CELL;
     W.pitch = W.nwx * A.C;
     if (A.tile_path && threadIdx.x == 0)
-        A.tile_path[blockIdx.y * gridDim.x + blockIdx.x] = !W.any ? 0 : (W.staged ? AMT_GATHER_PATH_STAGED : AMT_GATHER_PATH_CELL);
+        A.tile_path[tile] = !W.any ? 0 : (W.staged ? AMT_GATHER_PATH_STAGED : AMT_GATHER_PATH_CELL);
     return W;
 }
 
@@ -228,26 +232,24 @@ __device__ __forceinline__ void sample_point(const gather_args& A, const gather_
     }
 }
 
+// A block's work on the tile (bx, by) of A's grid; `tile` = by * tiles_x + bx.  k_gather_mosaic runs it on its own block index,
+// k_gather_frames (below) on the tile of the job that the block has looked up.
 template <typename T, int N>
-__global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
-    extern __shared__ __align__(16) unsigned char gather_smem[];
-    T* win = reinterpret_cast<T*>(gather_smem);
-    __shared__ int fold[4][6];
-
+__device__ __forceinline__ void gather_tile_body(const gather_args& A, int bx, int by, int tile, T* win, int (&fold)[4][6]) {
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int X = blockIdx.x * kTile + tx;
+    const int X = bx * kTile + tx;
     const int C = A.C;
     int Y[kRowsPerThread];
     bool y_in[kRowsPerThread];
 #pragma unroll
-    for (int k = 0; k < kRowsPerThread; ++k) Y[k] = blockIdx.y * kTile + ty + 8 * k, y_in[k] = Y[k] < A.ny;
+    for (int k = 0; k < kRowsPerThread; ++k) Y[k] = by * kTile + ty + 8 * k, y_in[k] = Y[k] < A.ny;
 
     gather_points P;
     gather_best B;
     gather_taps t;
     load_points(A, X, X < A.nx, Y, y_in, A.nx, P);
     elect<N>(A, P, B);
-    const gather_tile W = survey<N>(A, B, t, fold);
+    const gather_tile W = survey<N>(A, B, t, fold, tile);
     if (W.staged) stage_window<T>(A, W, win);
 
 #pragma unroll
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
         T* out = static_cast<T*>(A.img) + i * C;
         const bool won = B.m[k] >= 0;
         A.mask[i] = won ? 0 : 1;
-        A.source[i] = B.m[k];
+        if (A.source) A.source[i] = B.m[k];
         A.elev[i] = B.e[k];
         if (A.xy) A.xy[2 * i + 0] = B.x[k], A.xy[2 * i + 1] = B.y[k];
         if (!won) {
@@ -266,6 +268,14 @@ __global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
         }
         sample_point<T, N>(A, W, win, B.m[k], t.ix[k], t.iy[k], t.fx[k], t.fy[k], out);
     }
+}
+
+template <typename T, int N>
+__global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
+    extern __shared__ __align__(16) unsigned char gather_smem[];
+    __shared__ int fold[4][6];
+    gather_tile_body<T, N>(A, (int)blockIdx.x, (int)blockIdx.y, (int)(blockIdx.y * gridDim.x + blockIdx.x),
+                           reinterpret_cast<T*>(gather_smem), fold);
 }
 
 // ---- the supersampled form --------------------------------------------------------------------------------------------
@@ -278,24 +288,23 @@ constexpr int kPoints = kTile * kTile;
 constexpr int kHeadMin = kPoints * (int)(sizeof(double) + sizeof(int));      // the elevations and winners of the block's points
 
 template <typename T, int N>
-__global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
-    extern __shared__ __align__(16) unsigned char gather_smem[];
+__device__ __forceinline__ void gather_ss_body(const gather_ss_args& S, int bx, int by, int tile, unsigned char* gather_smem,
+                                               int (&fold)[4][6]) {
     const gather_args& A = S.G;
     T* win = reinterpret_cast<T*>(gather_smem);
     double* p_elev = reinterpret_cast<double*>(gather_smem);
     int* p_win = reinterpret_cast<int*>(gather_smem + kPoints * sizeof(double));
     T* p_val = reinterpret_cast<T*>(gather_smem + S.head);
-    __shared__ int fold[4][6];
 
     const int n = S.factor, Tc = kTile / n, span = Tc * n;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int X = blockIdx.x * span + tx;
+    const int X = bx * span + tx;
     const int C = A.C;
     int Y[kRowsPerThread];
     bool y_in[kRowsPerThread];
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) {
-        Y[k] = blockIdx.y * span + ty + 8 * k;
+        Y[k] = by * span + ty + 8 * k;
         y_in[k] = ty + 8 * k < span && Y[k] < A.ny * n;
     }
 
@@ -304,7 +313,7 @@ __global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
     gather_taps t;
     load_points(A, X, tx < span && X < A.nx * n, Y, y_in, (int64_t)A.nx * n, P);
     elect<N>(A, P, B);
-    const gather_tile W = survey<N>(A, B, t, fold);
+    const gather_tile W = survey<N>(A, B, t, fold, tile);
     if (W.staged) stage_window<T>(A, W, win);
 
 #pragma unroll
@@ -322,10 +331,10 @@ __global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
     }
     __syncthreads();
 
-    const int cells = Tc * Tc, items = cells * (C + 2);
+    const int cells = Tc * Tc, items = cells * (C + (A.source ? 2 : 1));       // (no source: nobody to count the winners for)
     for (int w = threadIdx.x; w < items; w += 256) {
         const int q = w / cells, cell = w - q * cells, cy = cell / Tc, cx = cell - cy * Tc;
-        const int Yc = blockIdx.y * Tc + cy, Xc = blockIdx.x * Tc + cx;
+        const int Yc = by * Tc + cy, Xc = bx * Tc + cx;
         if (Yc >= A.ny || Xc >= A.nx) continue;
         const int64_t i = (int64_t)Yc * A.nx + Xc;
         const int p0 = cy * n * kTile + cx * n;
@@ -389,6 +398,71 @@ __global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
     }
 }
 
+template <typename T, int N>
+__global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
+    extern __shared__ __align__(16) unsigned char gather_smem[];
+    __shared__ int fold[4][6];
+    gather_ss_body<T, N>(S, (int)blockIdx.x, (int)blockIdx.y, (int)(blockIdx.y * gridDim.x + blockIdx.x), gather_smem, fold);
+}
+
+// ---- a batch of frames (amt_gather_frames): one launch over the tiles of all jobs -----------------------------------------------
+// A job is one member with a grid and outputs of its own.  The jobs' tile counts are summed into `first` (n_jobs + 1 entries,
+// first[0] = 0); block b belongs to the job j with first[j] <= b < first[j + 1] and makes that job's tile b - first[j].  The
+// look-up depends on the block index alone, so it runs on scalar loads; what it finds — the job's gather_args, with a member
+// table of one — is uniform over the block as the kernel arguments of k_gather_mosaic are, and the block runs the same body.
+struct gather_job_dev {
+    gather_dev M;
+    const double *lat, *lon, *cell_lat, *cell_lon;
+    void* img;
+    uint8_t* mask;
+    double* elev;
+    uint8_t* count;
+    int ny, nx, tiles_x, pad_;
+};
+
+struct gather_frames_args {
+    const int* __restrict__ first;
+    const gather_job_dev* __restrict__ jobs;
+    int n_jobs, C, force, factor;
+    int min_count, head;
+    uint8_t* tile_path;         // the jobs' tiles one job after the other
+};
+
+template <typename T, int N, bool SS>
+__global__ __launch_bounds__(256) void k_gather_frames(gather_frames_args F) {
+    extern __shared__ __align__(16) unsigned char gather_smem[];
+    __shared__ int fold[4][6];
+
+    const int b = (int)blockIdx.x;
+    int lo = 0, hi = F.n_jobs;              // first[lo] <= b < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (F.first[mid] <= b)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const gather_job_dev& J = F.jobs[lo];
+    const int start = F.first[lo], tile = b - start;
+    const int by = tile / J.tiles_x, bx = tile - by * J.tiles_x;
+
+    gather_ss_args S;
+    gather_args& A = S.G;
+    A.members = &J.M;
+    A.lat = J.lat, A.lon = J.lon, A.cell_lat = J.cell_lat, A.cell_lon = J.cell_lon;
+    A.n = 1, A.ny = J.ny, A.nx = J.nx, A.C = F.C;
+    A.rule = 1, A.same_ellipsoid = 1, A.force = F.force, A.pad_ = 0;
+    A.img = J.img, A.mask = J.mask, A.elev = J.elev, A.source = nullptr, A.xy = nullptr;
+    A.tile_path = F.tile_path ? F.tile_path + start : nullptr;
+    if (SS) {
+        S.factor = F.factor, S.min_count = F.min_count, S.head = F.head, S.pad_ = 0;
+        S.count = J.count;
+        gather_ss_body<T, N>(S, bx, by, tile, gather_smem, fold);
+    } else {
+        gather_tile_body<T, N>(A, bx, by, tile, reinterpret_cast<T*>(gather_smem), fold);
+    }
+}
+
 template <typename T>
 size_t window_bytes(int C) {
     return (size_t)kWin * kWin * (size_t)C * sizeof(T);
@@ -424,7 +498,26 @@ void launch_gather_ss(amt_ctx* ctx, gather_ss_args S, int interpolation) {
         hipLaunchKernelGGL((k_gather_mosaic_ss<T, 0>), grid, dim3(256), lds, ctx->stream, S);
 }
 
-#define GATHER_REQUIRE(cond, msg)                                      \
+template <typename T, bool SS>
+void launch_gather_frames(amt_ctx* ctx, gather_frames_args F, int tiles, int interpolation) {
+    // the dynamic LDS of launch_gather (SS false) or launch_gather_ss (SS true)
+    const size_t window = interpolation == AMT_INTERP_NEAREST ? 0 : window_bytes<T>(F.C);
+    size_t lds = window;
+    if (SS) {
+        const size_t head = (std::max(window, (size_t)kHeadMin) + 15) & ~(size_t)15;
+        lds = head + (size_t)kPoints * (size_t)F.C * sizeof(T);
+        F.head = (int)head;
+    }
+    const dim3 grid((unsigned)tiles);
+    if (interpolation == AMT_INTERP_LINEAR)
+        hipLaunchKernelGGL((k_gather_frames<T, 2, SS>), grid, dim3(256), lds, ctx->stream, F);
+    else if (interpolation == AMT_INTERP_LANCZOS4)
+        hipLaunchKernelGGL((k_gather_frames<T, 8, SS>), grid, dim3(256), lds, ctx->stream, F);
+    else
+        hipLaunchKernelGGL((k_gather_frames<T, 0, SS>), grid, dim3(256), lds, ctx->stream, F);
+}
+
+#define GATHER_REQUIRE(cond, msg)                                     \
     do {                                                               \
         if (!(cond)) {                                                 \
             ctx->last_error = std::string(fn) + ": " + (msg);          \
@@ -531,6 +624,80 @@ extern "C" int amt_gather_mosaic_supersampled(amt_ctx* ctx, const amt_gather_mem
         case 1: launch_gather_ss<uint8_t>(ctx, S, interpolation); break;
         case 2: launch_gather_ss<uint16_t>(ctx, S, interpolation); break;
         default: launch_gather_ss<float>(ctx, S, interpolation); break;
+    }
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
+extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor,
+                                 int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
+                                 const amt_gather_debug* debug) {
+    AMT_CHECK_CTX(ctx);
+    const char* fn = __func__;
+    GATHER_REQUIRE(jobs, "NULL argument");
+    GATHER_REQUIRE(n_jobs >= 1 && n_jobs <= AMT_GATHER_MAX_JOBS, "n_jobs must be 1 ... " + std::to_string(AMT_GATHER_MAX_JOBS));
+    GATHER_REQUIRE(frame == AMT_W2P_GEODETIC || frame == AMT_W2P_SM, "unknown frame (AMT_W2P_GEODETIC or AMT_W2P_SM)");
+    GATHER_REQUIRE(interpolation == AMT_INTERP_LINEAR || interpolation == AMT_INTERP_LANCZOS4 || interpolation == AMT_INTERP_NEAREST,
+                   "unknown interpolation");
+    GATHER_REQUIRE(sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4, "sample_bytes must be 1 (uint8), 2 (uint16) or 4 (float32)");
+    GATHER_REQUIRE(channels == 1 || channels == 3 || channels == 4, "channels must be 1, 3 or 4");
+    GATHER_REQUIRE(!debug || (debug->force_path >= AMT_GATHER_PATH_AUTO && debug->force_path <= AMT_GATHER_PATH_CELL), "unknown force_path");
+    GATHER_REQUIRE(factor >= 1 && factor <= 8, "factor must be 1 ... 8");
+    GATHER_REQUIRE(min_count >= 1 && min_count <= factor * factor, "min_count must be 1 ... factor * factor");
+
+    // the prefix table of tile counts, then the jobs, in one staging buffer: one copy
+    const size_t jobs_at = (((size_t)n_jobs + 1) * sizeof(int) + 15) & ~(size_t)15;
+    std::vector<unsigned char> staged(jobs_at + (size_t)n_jobs * sizeof(gather_job_dev));
+    int* first = reinterpret_cast<int*>(staged.data());
+    gather_job_dev* dev = reinterpret_cast<gather_job_dev*>(staged.data() + jobs_at);
+    const int Tc = kTile / factor;          // cells per tile side
+    int64_t tiles = 0;
+    for (int32_t k = 0; k < n_jobs; ++k) {
+        const amt_gather_job& j = jobs[k];
+        const std::string job = "job " + std::to_string(k) + ": ";
+        GATHER_REQUIRE(j.out_img && j.out_mask && j.out_elev, job + "NULL argument");
+        GATHER_REQUIRE(factor == 1 || j.out_count, job + "NULL out_count with factor > 1");
+        GATHER_REQUIRE(j.ny > 0 && j.nx > 0, job + "empty axis");
+        GATHER_REQUIRE(j.ny <= INT32_MAX / factor && j.nx <= INT32_MAX / factor, job + "the sub-sample grid does not fit 32-bit indices");
+        const bool axes = j.lat && j.lon, cells = j.cell_lat && j.cell_lon;
+        GATHER_REQUIRE((j.lat != nullptr) == (j.lon != nullptr) && (j.cell_lat != nullptr) == (j.cell_lon != nullptr) && axes != cells,
+                       job + "give either the two axes or the two cell arrays");
+        gather_job_dev& d = dev[k];
+        const char* err = j.member.img ? w2p_prepare(&j.member.params, j.member.zenithal, frame, &d.M.K, &d.M.S) : "member without image";
+        GATHER_REQUIRE(err == nullptr, job + err);
+        d.M.img = j.member.img;
+        d.M.center_mask = j.member.center_mask;
+        d.M.min_elevation = j.member.min_elevation > -INFINITY ? j.member.min_elevation : (double)NAN;      // (-inf and NaN: none)
+        d.lat = axes ? j.lat : nullptr, d.lon = axes ? j.lon : nullptr;
+        d.cell_lat = axes ? nullptr : j.cell_lat, d.cell_lon = axes ? nullptr : j.cell_lon;
+        d.img = j.out_img, d.mask = j.out_mask, d.elev = j.out_elev, d.count = factor > 1 ? j.out_count : nullptr;
+        d.ny = j.ny, d.nx = j.nx, d.tiles_x = (j.nx + Tc - 1) / Tc, d.pad_ = 0;
+        first[k] = (int)tiles;
+        tiles += (int64_t)d.tiles_x * (int64_t)((j.ny + Tc - 1) / Tc);
+        GATHER_REQUIRE(tiles <= INT32_MAX, "the jobs' tiles (up to " + job + std::to_string(tiles) + ") do not fit one launch");
+    }
+    first[n_jobs] = (int)tiles;
+
+    if (amt_set_device(ctx)) return AMT_EHIP;
+    char* ws = static_cast<char*>(amt_workspace(ctx, staged.size()));
+    if (ws == nullptr) {
+        ctx->last_error = std::string(fn) + ": workspace allocation failed";
+        return AMT_ENOMEM;
+    }
+    // (pageable source: the copy has consumed the staging buffer when the call returns)
+    AMT_HIP(ctx, hipMemcpyAsync(ws, staged.data(), staged.size(), hipMemcpyHostToDevice, ctx->stream));
+
+    gather_frames_args F;
+    F.first = reinterpret_cast<const int*>(ws);
+    F.jobs = reinterpret_cast<const gather_job_dev*>(ws + jobs_at);
+    F.n_jobs = n_jobs, F.C = channels, F.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, F.factor = factor;
+    F.min_count = min_count, F.head = 0;
+    F.tile_path = debug ? debug->tile_path : nullptr;
+    const bool ss = factor > 1;
+    switch (sample_bytes) {
+        case 1: ss ? launch_gather_frames<uint8_t, true>(ctx, F, (int)tiles, interpolation) : launch_gather_frames<uint8_t, false>(ctx, F, (int)tiles, interpolation); break;
+        case 2: ss ? launch_gather_frames<uint16_t, true>(ctx, F, (int)tiles, interpolation) : launch_gather_frames<uint16_t, false>(ctx, F, (int)tiles, interpolation); break;
+        default: ss ? launch_gather_frames<float, true>(ctx, F, (int)tiles, interpolation) : launch_gather_frames<float, false>(ctx, F, (int)tiles, interpolation); break;
     }
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;

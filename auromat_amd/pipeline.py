@@ -1643,3 +1643,317 @@ class SequencePipeline(object):
                         v.record_stream(cur)
         self._frames_done += len(out)
         return out
+
+
+class GatherSequence(object):
+    """
+    A sequence of equally sized frames resampled by gathering (:func:`auromat_amd.resample.resampleGather` /
+    ``resampleGatherMLatMLT`` of every frame's ``maskedByElevation(min_elevation)``), a batch of frames per kernel launch.
+
+    A gathered frame needs two pieces of device work: the box pass of the frame kernel (no output array, image or binning:
+    the 8-number bounding-box reduction), from which the host lays out :func:`auromat_amd.resample.resample`'s grid for that
+    frame, and the gather of the image onto that grid.  At a sequence's resolutions a grid is a few 32 x 32 tiles, so a gather
+    per frame is a member-table copy and a launch.  Here the frames of a batch share them:
+
+        box(j)     the box passes of batch j (``amt_pipe_launch_box_many``, up to three frames per launch of the frame kernel),
+                   enqueued before the host waits for the boxes of batch j - 1
+        gather(j)  wait for those boxes, lay out every frame's grid (the date-line rule, ``plateCarreeResolution`` per frame
+                   with `arcsecPerPx`), ONE copy of the whole batch's axes from a page-locked staging buffer (three rotate; one
+                   is reused only after the event of its copy) and ONE ``amt_gather_frames`` call into two arenas — the
+                   samples, and elevation | mask | count
+
+    in the order box(0) | box(1) gather(0) | box(2) gather(1) | ...  No per-pixel coordinate array exists anywhere, so the
+    pipes are made without frame buffers.  :class:`SequencePipeline` is not involved and does not change.
+
+    A frame whose box pass reports a pole of the grid's coordinates in view takes, with a fixed `pxPerDeg`, the class route —
+    an ``ArraySpacecraftMapping``, :func:`auromat_amd.resample.gather_plan` and ``gather_frame``: plan 'class' —; with
+    `arcsecPerPx` it has no longitude resolution: None / 'pole-without-resolution', as in :class:`SequencePipeline`.  A frame
+    without a valid pixel: None / 'empty'.  Camera models are the plain TAN headers of a spacecraft sequence, with fast centres.
+    """
+
+    _TORCH_OF = {np.dtype(np.uint8): 'uint8', np.dtype(np.uint16): 'int16', np.dtype(np.float32): 'float32'}
+
+    def __init__(self, width, height, nchan=3, img_dtype=np.uint16, device=None, altitude=110, min_elevation=10.0, pxPerDeg=25,
+                 arcsecPerPx=None, magnetic=False, interpolation='linear', supersample=1, minCoverage=None, batch=8):
+        from ._native import GATHER_MAX_JOBS
+        from .resample import _check_gather_interpolation, _check_supersample
+        # (the argument checks of resampleGather, in its order, then the pipeline's own: all before any device work)
+        _check_gather_interpolation(interpolation)
+        self.supersample, self._min_count = _check_supersample(supersample, minCoverage)
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or not 1 <= batch <= GATHER_MAX_JOBS:
+            raise ValueError('batch must be an int in 1 ... %d, but is: %r' % (GATHER_MAX_JOBS, batch))
+        if nchan not in (1, 3, 4):
+            raise ValueError('nchan must be 1, 3 or 4, but is: %r' % (nchan,))
+        if np.dtype(img_dtype) not in self._TORCH_OF:
+            raise ValueError('img_dtype must be uint8, uint16 or float32, but is: %r' % (img_dtype,))
+        if not (int(width) > 0 and int(height) > 0):
+            raise ValueError('width and height must be positive, but are: %r, %r' % (width, height))
+        if arcsecPerPx is not None and not float(arcsecPerPx) > 0:
+            raise ValueError('arcsecPerPx must be positive, but is: %r' % (arcsecPerPx,))
+        self.width, self.height, self.nchan, self.img_dtype = int(width), int(height), int(nchan), np.dtype(img_dtype)
+        self.interpolation, self.minCoverage = interpolation, minCoverage
+        self.arcsecPerPx = float(arcsecPerPx) if arcsecPerPx else None
+        self.pxPerDeg = None if self.arcsecPerPx else _px_per_deg(pxPerDeg)
+        self.altitude, self.min_elevation, self.magnetic = altitude, min_elevation, bool(magnetic)
+        self.batch = int(batch)
+        self.plans = []                     # plan taken by each frame of the last process() call
+        self.uploaded_bytes = 0             # image bytes the last process() call sent over the link (host images)
+        self.gather_calls = 0               # amt_gather_frames calls of the last process() call
+        import torch
+        self._img_torch_dtype = getattr(torch, self._TORCH_OF[self.img_dtype])
+        # two sets of `batch` drivers: the box passes of batch j + 1 are in flight while the host reads those of batch j
+        self.pipes = [FramePipeline(self.width, self.height, self.nchan, self.img_dtype if self.img_dtype != np.float32 else np.uint16,
+                                    device, alloc_image=False, alloc_coords=False) for _ in range(2 * self.batch)]
+        self.ctx = self.pipes[0].ctx
+        self.s_main = _shared_stream(self.ctx.device, 'main')
+        self.s_copy = None                  # (created with the first host image)
+        self._staging = [[None, None] for _ in range(3)]      # [page-locked float64 tensor, event of its latest copy]
+        self._staged = 0
+        self._arenas = []                   # the arenas of the last process() call: its keep_on_device results are views
+
+    # -- inputs -------------------------------------------------------------------------------------
+    def _prepared(self, f):
+        """A frame tuple -> (amt_frame_params, header, camera, time, image, altitude)."""
+        hdr, cam, t, img = f[:4]
+        alt = f[4] if len(f) > 4 and f[4] is not None else self.altitude
+        if not isinstance(hdr, dict):
+            raise NotImplementedError('GatherSequence takes frames as (WCS header dict, cameraPosGCRS, photoTime, image[, altitude])')
+        if not (str(hdr.get('CTYPE1', 'RA---TAN')).strip() == 'RA---TAN' and str(hdr.get('CTYPE2', 'DEC--TAN')).strip() == 'DEC--TAN') \
+                or any(k in hdr for k in ('A_ORDER', 'B_ORDER')):
+            raise NotImplementedError('GatherSequence takes plain TAN headers (got CTYPE1=%r, CTYPE2=%r%s); resampleGather of a '
+                                      'mapping with the header gathers any zenithal (+ SIP) model, one frame per call' %
+                                      (hdr.get('CTYPE1'), hdr.get('CTYPE2'), ', SIP' if 'A_ORDER' in hdr or 'B_ORDER' in hdr else ''))
+        if (int(hdr['IMAGEW']), int(hdr['IMAGEH'])) != (self.width, self.height):
+            raise ValueError('the header is for %d x %d, the pipeline for %d x %d' %
+                             (int(hdr['IMAGEW']), int(hdr['IMAGEH']), self.width, self.height))
+        # (the parameters of the class API's camera mappings: _inverse_model)
+        return frame_params(hdr, alt, cam, t, True), hdr, cam, t, img, alt
+
+    def _device_image(self, img):
+        """The frame's image on the device, ordered for s_main: a device-resident tensor of the layout is used in place, a
+        host image is uploaded whole on the copy stream."""
+        import torch
+        shape = (self.height, self.width, self.nchan)
+        if isinstance(img, torch.Tensor) and img.is_cuda:
+            if img.dtype != self._img_torch_dtype or img.numel() != int(np.prod(shape)):
+                raise ValueError('device image of the wrong layout: %s %s, the pipeline takes %s %s' %
+                                 (tuple(img.shape), img.dtype, shape, self._img_torch_dtype))
+            self.s_main.wait_stream(self._caller)       # (a generator may have written it on the caller's stream just now)
+            return img.contiguous().view(shape)
+        if self.s_copy is None:
+            self.s_copy = _shared_stream(self.ctx.device, 'copy')
+        with torch.cuda.stream(self.s_copy):
+            dev = torch.empty(shape, dtype=self._img_torch_dtype, device=self.ctx.device)
+            if isinstance(img, torch.Tensor):
+                if img.dtype != self._img_torch_dtype or img.numel() != dev.numel():
+                    raise ValueError('host tensor image of the wrong layout: %s %s' % (tuple(img.shape), img.dtype))
+                dev.copy_(img.reshape(shape), non_blocking=img.is_pinned())
+            else:
+                a = np.ascontiguousarray(img, dtype=self.img_dtype)
+                if a.size != dev.numel():
+                    raise ValueError('image of %s values, the pipeline takes %s' % (a.shape, shape))
+                Context.current(self.ctx.device)
+                self.ctx.upload(a.view(np.int16) if a.dtype == np.uint16 else a, dev)
+            uploaded = torch.cuda.Event()
+            uploaded.record(self.s_copy)
+        self.s_main.wait_event(uploaded)
+        dev.record_stream(self.s_main)
+        self.uploaded_bytes += dev.numel() * dev.element_size()
+        return dev
+
+    def _stage(self, flat):
+        """One copy of `flat` (float64, host) to the device on s_main (current), from the next page-locked staging buffer."""
+        import torch
+        slot = self._staging[self._staged % len(self._staging)]
+        self._staged += 1
+        if slot[1] is not None:
+            slot[1].synchronize()           # the buffer's latest copy has read it
+        if slot[0] is None or slot[0].numel() < flat.size:
+            slot[0] = torch.empty(max(int(flat.size) * 2, 1 << 14), dtype=torch.float64, pin_memory=True)
+        slot[0][:flat.size].copy_(torch.from_numpy(flat))
+        dev = torch.empty(int(flat.size), dtype=torch.float64, device=self.ctx.device)
+        dev.copy_(slot[0][:flat.size], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(self.s_main)
+        return dev
+
+    def _arena(self, keep):
+        def make(cells, nch, tdtype, n):
+            import torch
+            # two arenas: the samples; elevation | mask | count
+            images = torch.empty((cells * nch,), dtype=tdtype, device=self.ctx.device)
+            grids = torch.empty((cells * (10 if n > 1 else 9),), dtype=torch.uint8, device=self.ctx.device)
+            keep.extend((images, grids))
+            made = dict(img=images, elevation=grids[:8 * cells].view(torch.float64), mask=grids[8 * cells:9 * cells])
+            if n > 1:
+                made['count'] = grids[9 * cells:10 * cells]
+            return made
+        return make
+
+    # -- the grid of a box --------------------------------------------------------------------------
+    def _plan_of(self, red, params):
+        """:func:`auromat_amd.resample.gather_plan`'s plan for a box pass's reduction, or 'pole' where plateCarreeResolution
+        has no longitude resolution to give."""
+        from .resample import plateCarreeResolution, wrap_at_180
+        bb = bounding_box_from_reduction(red)
+        if self.arcsecPerPx:
+            ppd = plateCarreeResolution(bb, self.arcsecPerPx)
+            if not ppd[1] > 0:
+                return 'pole'
+        else:
+            ppd = self.pxPerDeg
+        lonMin, lonMax = bb.lonWest, bb.lonEast
+        if bb.containsDiscontinuity:
+            lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
+        return dict(grid=cached_grid(ppd, bb.latSouth, bb.latNorth, lonMin, lonMax), contains_pole=False,
+                    contains_discontinuity=bool(bb.containsDiscontinuity), altitude=None, params=params, zenithal=None,
+                    min_elevation=self.min_elevation, center_mask=None, bbox=list(red), pxPerDeg=ppd)
+
+    def _class_route(self, pr, keep_on_device):
+        """A frame with a pole in view, at a fixed resolution: the class API's plan and gather (a rotated grid laid out from the
+        frame's arrays)."""
+        import torch
+        from .mapping.spacecraft import ArraySpacecraftMapping
+        from .resample import gather_frame, gather_plan
+        _, hdr, cam, t, img, alt = pr
+        if isinstance(img, torch.Tensor):
+            img = to_host(img.contiguous(), dtype=self.img_dtype, shape=(self.height, self.width, self.nchan)) \
+                if img.is_cuda else img.numpy().view(self.img_dtype).reshape(self.height, self.width, self.nchan)
+        img = np.asarray(img).reshape(self.height, self.width, self.nchan)
+        m = ArraySpacecraftMapping(hdr, alt, img, cam, t, 'gather-sequence', fastCenterCalculation=True)
+        if self.min_elevation is not None:
+            m = m.maskedByElevation(self.min_elevation)
+        plan = gather_plan(m, self.pxPerDeg, None, None, self.magnetic)
+        res = gather_frame(plan, img, self.interpolation, self.magnetic, self.supersample, self.minCoverage)
+        res.update(bbox=None, pxPerDeg=self.pxPerDeg, altitude=alt)
+        if keep_on_device:
+            for k in ('img', 'mask', 'elevation', 'count'):
+                if k in res:
+                    a = res[k].astype(np.uint8) if k == 'mask' else res[k]
+                    res[k] = torch.from_numpy(np.ascontiguousarray(a.view(np.int16) if a.dtype == np.uint16 else a)).to(self.ctx.device)
+                    self._arenas.append(res[k])
+        return res
+
+    # -- the loop -----------------------------------------------------------------------------------
+    def process(self, frames, keep_on_device=True, on_batch=None):
+        """
+        frames: iterable of (WCS header dict, cameraPosGCRS, photoTime, image[, altitude]) — :class:`SequencePipeline`'s tuples,
+        consumed once, a batch ahead.  An image is a device tensor of the pipeline's layout ((h, w, c) uint8, the bits of uint16
+        as int16, or float32), used in place, or a host array / tensor, uploaded whole on a copy stream.
+
+        Returns per frame a dict — lat, lon, lat_c, lon_c, grid, img, mask, elevation, with ``supersample`` > 1 also count
+        (and, for host results, coverage = count / n^2), contains_pole, contains_discontinuity, altitude, bbox (the box pass's
+        reduction) and pxPerDeg — or None; `plans` holds 'gather', 'empty', 'pole-without-resolution' or 'class' per frame.
+        With `keep_on_device` img, mask (uint8), elevation and count are device tensors, views into this call's arenas: valid
+        for work on the current stream, which is ordered behind everything enqueued, until the next process() call.
+        `on_batch(k0, results)` is called with every finished batch while the next one's box passes run.
+        """
+        import torch
+        from .resample import _gather_frames_call, gather_frames_coordinates
+        del self.plans[:]
+        del self._arenas[:]
+        self.uploaded_bytes = self.gather_calls = 0
+        out = []
+        it = iter(frames)
+        B, nb = self.batch, len(self.pipes)
+        caller = self._caller = torch.cuda.current_stream(self.ctx.device)
+        min_elev = NEG_INF if self.min_elevation is None else float(self.min_elevation)
+        mag = 1 if self.magnetic else 0
+        lib, ctx = self.ctx._lib, self.ctx
+        n = self.supersample
+        self.s_main.wait_stream(caller)         # (device-resident images may have been written on the caller's stream)
+
+        def box(parity):
+            """Parameters + box passes of up to B frames on the drivers of set `parity` -> list of prepared frames."""
+            prepared = []
+            for _ in range(B):
+                f = next(it, None)
+                if f is None:
+                    break
+                prepared.append(self._prepared(f))
+            with torch.cuda.stream(self.s_main):
+                Context.current(ctx.device)
+                for i in range(0, len(prepared), 3):            # AMT_PIPE_MAX_BATCH frames per launch of the frame kernel
+                    part = prepared[i:i + 3]
+                    handles = (C.c_void_p * len(part))(*[self.pipes[parity * B + i + m]._pipe() for m in range(len(part))])
+                    pp = (C.c_void_p * len(part))(*[C.addressof(pr[0]) for pr in part])
+                    ctx.check(lib.amt_pipe_launch_box_many(handles, len(part), pp, min_elev, mag))
+            return prepared
+
+        def gather(parity, prepared):
+            results, jobs = [], []
+            for i, pr in enumerate(prepared):
+                res = PipeResult()
+                self.pipes[parity * B + i]._pcall('amt_pipe_wait', C.byref(res))
+                if res.status == 2 or res.bbox[6] == 0:
+                    self.plans.append('empty')
+                    results.append(None)
+                    continue
+                red = list(res.bbox)
+                if red[7]:
+                    if self.arcsecPerPx:
+                        self.plans.append('pole-without-resolution')
+                        results.append(None)
+                    else:
+                        self.plans.append('class')
+                        with torch.cuda.stream(self.s_main):
+                            results.append(self._class_route(pr, keep_on_device))
+                    continue
+                plan = self._plan_of(red, pr[0])
+                if plan == 'pole':
+                    self.plans.append('pole-without-resolution')
+                    results.append(None)
+                    continue
+                plan['altitude'] = pr[5]
+                self.plans.append('gather')
+                jobs.append((len(results), plan, pr[4]))
+                results.append(None)
+            if jobs:
+                plans = [p for _, p, _ in jobs]
+                with torch.cuda.stream(self.s_main):
+                    images = [self._device_image(img) for _, _, img in jobs]
+                    Context.current(ctx.device)         # (an upload has bound the context to the copy stream)
+                    sizes, flat = gather_frames_coordinates(plans, n)
+                    outs, _, _ = _gather_frames_call(ctx, plans, images, self.interpolation, self.magnetic, n, self._min_count,
+                                                     coords=(sizes, self._stage(flat)), arena=self._arena(self._arenas))
+                    self.gather_calls += 1
+                for (k, plan, _), o in zip(jobs, outs):
+                    r = dict(grid_coordinates(plan), grid=plan['grid'], contains_pole=False,
+                             contains_discontinuity=plan['contains_discontinuity'], altitude=plan['altitude'], bbox=plan['bbox'],
+                             pxPerDeg=plan['pxPerDeg'])
+                    r.update(o)
+                    results[k] = r
+            return results
+
+        def deliver(k0, results):
+            if not keep_on_device:
+                # (one wait per batch: the read-backs are ordered behind the batch's kernel on s_main)
+                with torch.cuda.stream(self.s_main):
+                    for r in results:
+                        if r is None or not isinstance(r['img'], torch.Tensor):
+                            continue
+                        r['img'] = to_host(r['img'].contiguous(), dtype=self.img_dtype)
+                        r['mask'] = to_host(r['mask'].contiguous()).astype(bool)
+                        r['elevation'] = to_host(r['elevation'].contiguous())
+                        if n > 1:
+                            r['count'] = to_host(r['count'].contiguous(), dtype=np.uint8)
+            for r in results:
+                if r is not None and n > 1 and not isinstance(r['count'], torch.Tensor):
+                    r['coverage'] = r['count'] / float(n * n)
+            out.extend(results)
+            if on_batch is not None:
+                on_batch(k0, results)
+
+        current = box(0)
+        j = 0
+        while current:
+            following = box((j + 1) % 2)
+            deliver(len(out), gather(j % 2, current))
+            current = following
+            j += 1
+        caller.wait_stream(self.s_main)
+        for a in self._arenas:
+            a.record_stream(caller)
+        if not keep_on_device:
+            del self._arenas[:]
+        return out

@@ -2618,3 +2618,140 @@ def resampleGatherMosaicMLatMLT(collection, **kw):
     through the camera models as SM coordinates (``AMT_W2P_SM``) and the grid's coordinates are converted back."""
     return _resample_gather_mosaic(collection, kw.pop('pxPerDeg', 25), kw.pop('arcsecPerPx', None), kw.pop('containsPole', None),
                                    kw.pop('interpolation', 'linear'), True, **kw)
+
+
+# ---- gathered frames: a batch of frames, each onto its own grid, one fused kernel ----------------------------------------------
+def _gather_job_coordinates(plan, n):
+    """The coordinate arrays of one job of ``amt_gather_frames``: (a, b, points) — the two axes, or with a pole in view
+    (`points` True) the two point arrays; the cell centres for n = 1, the sub-samples of :func:`gather_subsample_coordinates`
+    else."""
+    if n > 1:
+        sub = gather_subsample_coordinates(plan, n)
+        if sub['lat'] is None:
+            return sub['cell_lat'], sub['cell_lon'], True
+        return sub['lat'], sub['lon'], False
+    coords = grid_coordinates(plan)
+    if plan['contains_pole']:
+        return coords['lat_c'], coords['lon_c'], True
+    return coords['lat_c'][:, 0], coords['lon_c'][0, :], False
+
+
+def gather_frames_coordinates(plans, n):
+    """The coordinates of a batch of ``amt_gather_frames``: (per plan (size of a, size of b, points), every plan's two arrays
+    flattened one after the other into ONE float64 array — what a single copy takes to the device)."""
+    host = [_gather_job_coordinates(p, n) for p in plans]
+    flat = np.concatenate([np.ravel(np.asarray(v, dtype=np.float64)) for a, b, _ in host for v in (a, b)])
+    return [(int(np.size(a)), int(np.size(b)), points) for a, b, points in host], flat
+
+
+def _gather_frames_call(ctx, plans, images, interpolation, magnetic, n, min_count, debug=None, coords=None, arena=None):
+    """ONE call of ``amt_gather_frames`` on at most GATHER_MAX_JOBS plans: (a list of dict(img, mask, elevation[, count]) of
+    device tensors — views into one flat tensor per output kind —, the call's tile_path tensor or None, the images' numpy dtype).
+    `coords`: (sizes, the flat device tensor) of :func:`gather_frames_coordinates` when the caller has copied them already;
+    `arena`: function (cells, channels, torch dtype, n) -> dict(img, mask, elevation[, count]) of flat tensors, in place of fresh
+    ones."""
+    import torch
+    from ._native import GATHER_MAX_JOBS, GatherDebug, GatherJob
+    from .coordinates.inverse import W2P_GEODETIC, W2P_SM
+    assert 1 <= len(plans) <= GATHER_MAX_JOBS
+    members = [dict(params=p['params'], zenithal=p['zenithal'], min_elevation=p['min_elevation'], center_mask=p['center_mask'])
+               for p in plans]
+    table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, members, images)
+    if coords is None:
+        sizes, flat = gather_frames_coordinates(plans, n)
+        coords = (sizes, ctx.to_device(flat))           # every job's coordinates in one copy
+    sizes, coords = coords
+    cells = [p['grid'].ny * p['grid'].nx for p in plans]
+    total = sum(cells)
+    if arena is None:
+        made = dict(img=torch.empty((total * nch,), dtype=tdtype, device=ctx.device), mask=ctx.empty((total,), torch.uint8),
+                    elevation=ctx.empty((total,)))
+        if n > 1:
+            made['count'] = ctx.empty((total,), torch.uint8)
+    else:
+        made = arena(total, nch, tdtype, n)
+    jobs = (GatherJob * len(plans))()
+    outs, at, cell0, T, tiles = [], 0, 0, 32 // n, 0
+    for job, member, plan, (na, nb, points), ncell in zip(jobs, table, plans, sizes, cells):
+        ny, nx = plan['grid'].ny, plan['grid'].nx
+        C.memmove(C.byref(job.member), C.byref(member), C.sizeof(member))
+        job.ny, job.nx = ny, nx
+        pa = coords.data_ptr() + 8 * at
+        pb = pa + 8 * na
+        at += na + nb
+        if points:
+            job.cell_lat, job.cell_lon = pa, pb
+        else:
+            job.lat, job.lon = pa, pb
+        out = dict(img=made['img'][cell0 * nch:(cell0 + ncell) * nch].view(ny, nx, nch),
+                   mask=made['mask'][cell0:cell0 + ncell].view(ny, nx), elevation=made['elevation'][cell0:cell0 + ncell].view(ny, nx))
+        if n > 1:
+            out['count'] = made['count'][cell0:cell0 + ncell].view(ny, nx)
+            job.out_count = out['count'].data_ptr()
+        job.out_img, job.out_mask, job.out_elev = out['img'].data_ptr(), out['mask'].data_ptr(), out['elevation'].data_ptr()
+        outs.append(out)
+        cell0 += ncell
+        tiles += ((ny + T - 1) // T) * ((nx + T - 1) // T)
+    assert at == coords.numel()
+    dbg, tile_path = None, None
+    if debug is not None:
+        dbg = GatherDebug()
+        dbg.force_path = int(debug.get('force_path', GATHER_PATH_AUTO))
+        if debug.get('tile_path'):
+            tile_path = ctx.zeros((tiles,), torch.uint8)
+            dbg.tile_path = ptr(tile_path).value
+    ctx.call('amt_gather_frames', jobs, len(plans), W2P_SM if magnetic else W2P_GEODETIC, n, 1 if n == 1 else min_count,
+             made['img'].element_size(), nch, _GATHER_INTERP_CODES[interpolation], None if dbg is None else C.byref(dbg))
+    # the kernel is enqueued on the current stream: the caching allocator hands the inputs' memory to nobody who is not behind it
+    del keep, coords
+    return outs, tile_path, np_dtype
+
+
+def gather_frames(plans, images, interpolation='linear', magnetic=False, supersample=1, minCoverage=None, keep_on_device=False,
+                  debug=None):
+    """
+    :func:`gather_frame` for a batch: the frames of `plans` (:func:`gather_plan` results, each with a grid of its own) and their
+    `images` gathered by ONE call of ``amt_gather_frames`` per at most 64 plans — one kernel launch over the tiles of all of
+    them, where a loop over :func:`gather_frame` pays a member-table copy and at least one launch per frame for grids of a few
+    tiles.  The images may differ in size but not in dtype or channel count.
+
+    Every cell holds what ``amt_gather_mosaic`` (``amt_gather_mosaic_supersampled`` with ``supersample`` > 1) gives for that one
+    frame: the mask is :func:`gather_frame`'s, `img` and `elevation` are its values where unmasked, and 0 / NaN where masked.
+
+    :param debug: dict(force_path=GATHER_PATH_*, tile_path=True): amt_gather_debug; every result then holds ``tile_path``, the
+                  flat bytes of its job's tiles
+    :return: one dict per plan with :func:`gather_frame`'s keys lat, lon, lat_c, lon_c, grid, img, mask, elevation,
+             contains_pole, contains_discontinuity and, with ``supersample`` > 1, count; no flags and no support: no coordinate
+             array exists.  With `keep_on_device` img, mask (uint8), elevation and count are device tensors.
+    :raises ValueError: as :func:`resampleGather`, in its order and before any device work; then for lists of different lengths
+    """
+    from ._native import GATHER_MAX_JOBS
+    _check_gather_interpolation(interpolation)
+    n, min_count = _check_supersample(supersample, minCoverage)
+    plans, images = list(plans), list(images)
+    if len(images) != len(plans):
+        raise ValueError('%d images for %d plans' % (len(images), len(plans)))
+    ctx = Context.current()
+    results = []
+    for k in range(0, len(plans), GATHER_MAX_JOBS):
+        chunk = plans[k:k + GATHER_MAX_JOBS]
+        outs, tile_path, dtype = _gather_frames_call(ctx, chunk, images[k:k + GATHER_MAX_JOBS], interpolation, magnetic, n, min_count,
+                                                     debug)
+        tiles = None if tile_path is None else to_host(tile_path)
+        T, t0 = 32 // n, 0
+        for plan, out in zip(chunk, outs):
+            res = dict(grid_coordinates(plan), grid=plan['grid'], contains_pole=plan['contains_pole'],
+                       contains_discontinuity=plan['contains_discontinuity'])
+            if keep_on_device:
+                res.update(out)
+            else:
+                res.update(img=to_host(out['img'].contiguous(), dtype=dtype), mask=to_host(out['mask']).astype(bool),
+                           elevation=to_host(out['elevation']))
+                if n > 1:
+                    res['count'] = to_host(out['count'], dtype=np.uint8)
+            if tiles is not None:
+                nt = ((plan['grid'].ny + T - 1) // T) * ((plan['grid'].nx + T - 1) // T)
+                res['tile_path'] = tiles[t0:t0 + nt]
+                t0 += nt
+            results.append(res)
+    return results

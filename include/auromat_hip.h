@@ -64,7 +64,8 @@ extern "C" {
  *    the core role of the frame kernel's work items — amt_georef_last_core, amt_georef_core_bands, amt_run_core_stats,
  *    amt_georef_set_roles(ctx, 2); gather mosaics — amt_gather_mosaic, amt_gather_member, amt_gather_debug, AMT_INTERP_NEAREST
  *    (auromat_amd.resample.resampleGatherMosaic); supersampled gathering — amt_gather_mosaic_supersampled
- *    (auromat_amd.resample.resampleGather / resampleGatherMosaic with supersample > 1) */
+ *    (auromat_amd.resample.resampleGather / resampleGatherMosaic with supersample > 1); gathered frames — amt_gather_frames,
+ *    amt_gather_job (auromat_amd.resample.gather_frames, auromat_amd.pipeline.GatherSequence) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -526,6 +527,39 @@ int amt_gather_mosaic_supersampled(amt_ctx* ctx, const amt_gather_member* member
                                    const double* sub_cell_lon, int32_t factor, int32_t min_count, int32_t sample_bytes,
                                    int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask,
                                    double* out_elev, int32_t* out_source, uint8_t* out_count, const amt_gather_debug* debug);
+
+/* ---- gathered frames: a batch of frames, each onto a grid of its own, in one launch (addition to ABI 10) --------------------------
+ * auromat_amd.resample.gather_frames, auromat_amd.pipeline.GatherSequence.  n_jobs jobs, 1 ... AMT_GATHER_MAX_JOBS.  A job is one
+ * amt_gather_member, its grid - ny, nx and lat / lon (the axes form) or, when both are NULL, cell_lat / cell_lon (the point form),
+ * as amt_gather_mosaic takes them; with factor > 1 the sub-sample axes (ny * factor, nx * factor) or points
+ * (ny * factor, nx * factor each) as amt_gather_mosaic_supersampled takes them - and its outputs: out_img (ny, nx, channels),
+ * out_mask, out_elev and, required with factor > 1 and not touched with factor 1, out_count.  Per call: frame, factor 1 ... 8,
+ * min_count 1 ... factor * factor, sample_bytes, channels, interpolation.  Images of different sizes and jobs of either
+ * coordinate form may share a call.
+ * Job k's outputs are, byte for byte and in every cell, the masked ones included, what amt_gather_mosaic (factor 1) or
+ * amt_gather_mosaic_supersampled (factor > 1) writes for a table of that one member on that grid.  There is no out_source and no
+ * out_xy.
+ * One launch over the sum of the jobs' tiles (32 / factor cells on a side); a block finds its job in a prefix table of tile
+ * counts and runs the device code of the two kernels above on that job's tile.  debug: force_path as above; tile_path holds the
+ * jobs' tiles one job after the other, each job's row-major as the per-job call reports them.
+ * Only enqueues work on the context's stream (the job table goes to the context's workspace).  AMT_EINVAL (nothing written):
+ * everything the two calls above refuse - for what belongs to a job the error names the job's index -, n_jobs outside
+ * 1 ... AMT_GATHER_MAX_JOBS, out_count NULL with factor > 1, and a total tile count beyond INT32_MAX. */
+#define AMT_GATHER_MAX_JOBS 64
+typedef struct amt_gather_job {
+    amt_gather_member member;
+    int32_t ny, nx;
+    const double* lat;          /* axes form */
+    const double* lon;
+    const double* cell_lat;     /* point form */
+    const double* cell_lon;
+    void* out_img;
+    uint8_t* out_mask;
+    double* out_elev;
+    uint8_t* out_count;
+} amt_gather_job;
+int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor, int32_t min_count,
+                      int32_t sample_bytes, int32_t channels, int32_t interpolation, const amt_gather_debug* debug);
 
 /* auromat/coordinates/intersection.py:144-163 ellipsoidLineIntersection (and
  * auromat/mapping/mapping.py:1474-1510 inflatedEarthIntersection with a=wgs84A+h, b=wgs84B+h).
