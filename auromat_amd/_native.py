@@ -448,11 +448,18 @@ class Context(object):
             ctx = cls._cache.get(key)
             if ctx is None:
                 ctx = cls._cache[key] = cls(idx)
-        stream = torch.cuda.current_stream(ctx.device).cuda_stream
-        if stream != ctx.stream_handle:
-            ctx.check(ctx._lib.amt_ctx_set_stream(ctx.handle, C.c_void_p(stream)))
-            ctx.stream_handle = stream
-        return ctx
+        return ctx.bind()
+
+    def bind(self):
+        """Re-bind THIS context to the stream the calling thread has current on its device.  What an object that keeps a
+        context (a pipeline, a frame's arrays) calls before it enqueues: the object may have been handed to another thread
+        than the one that built it, and :meth:`current` would re-bind that thread's context instead of the object's."""
+        import torch
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if stream != self.stream_handle:
+            self.check(self._lib.amt_ctx_set_stream(self.handle, C.c_void_p(stream)))
+            self.stream_handle = stream
+        return self
 
     def check(self, rc):
         if rc != 0:
@@ -512,7 +519,7 @@ class Context(object):
         assert out.is_contiguous() and out.numel() * out.element_size() == src.nbytes, 'upload: sizes differ'
         # amt_upload_staged: a few host threads copy every n-th piece through page-locked staging pieces of their own and
         # hand it to the DMA engine on the current stream (one thread's memcpy into page-locked memory is half the link's rate)
-        Context.current(self.device)
+        self.bind()
         self.call('amt_upload_staged', C.c_void_p(out.data_ptr()), C.c_void_p(src.ctypes.data), src.nbytes)
 
     # -- per-kernel timing ----------------------------------------------------------------------

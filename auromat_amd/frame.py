@@ -178,7 +178,7 @@ class PaddedFrameData(FrameData):
         if t is None:
             cols = self.width + (1 if name in ('lat', 'lon', 'mlat', 'mlt') else 0)
             t = self.ctx.empty((src.shape[0], cols))
-            Context.current(self.ctx.device)
+            self.ctx.bind()
             self.ctx.call('amt_unpad_rows', ptr(src), int(src.shape[0]), cols, self.width, ptr(t))
             self._cache = dict(self._cache)
             self._cache[name] = t

@@ -32,7 +32,7 @@ import numpy as np
 from .frame import FrameData, PaddedFrameData, has_array
 from .mapping.astrometry import frame_params, pole_in_view, run_frame
 from .mapping.mapping import bounding_box_from_reduction, grid_box_from_reduction, mlt_to_sm_lon
-from .resample import (_px_per_deg, area_overflow_error, cached_grid, grid_coordinates, min_coverage_weight, quantile_list,
+from .resample import (ThreadPipes, _px_per_deg, area_overflow_error, cached_grid, grid_coordinates, min_coverage_weight, quantile_list,
                        resample_frame, resample_frame_area, resample_frame_median, resample_frame_quantile)
 from ._native import PIPE_MAX_EDGE_PIXELS, Context, GeorefOut, PipeResult, RunConfig, RunFrame, RunResult, ptr, to_host
 
@@ -210,7 +210,7 @@ class FramePipeline(object):
         demand: one more run of the georeferencing kernel) -> the FrameData."""
         if not self._coords_valid:
             self._alloc_coords(full=True)
-            Context.current(self.ctx.device)
+            self.ctx.bind()
             self._out.bbox_min_elevation = NEG_INF if self.min_elevation is None else float(self.min_elevation)
             self._written()
             if self._dirs is not None:
@@ -257,7 +257,7 @@ class FramePipeline(object):
             return
         a = np.ascontiguousarray(img, dtype=self.fd.img_dtype)
         assert a.size == self.fd.img.numel(), 'image of the wrong size'
-        Context.current(self.ctx.device)
+        self.ctx.bind()
         if band:
             a = a.reshape(self._img_shape)
             self.ctx.upload(a[rows[0]:rows[1]], self.fd.img[rows[0]:rows[1]])
@@ -311,7 +311,7 @@ class FramePipeline(object):
     def join(self):
         """Order the current stream behind the single-pass driver's finalise kernels (see amt_pipe_join)."""
         if self._driver is not None:
-            Context.current(self.ctx.device)
+            self.ctx.bind()
             self._pcall('amt_pipe_join')
 
     def start_coarse(self, params, min_elevation, magnetic=False, hint=None, dirs=None):
@@ -336,7 +336,7 @@ class FramePipeline(object):
         with `magnetic`, (MLat, SM longitude); [7] = 1 when a pole of those coordinates is in view (camera model).  One
         host synchronisation.  Raises EmptyFrame when no pixel is valid.
         """
-        Context.current(self.ctx.device)
+        self.ctx.bind()
         self._pcall('amt_pipe_launch_box', C.byref(params), NEG_INF if min_elevation is None else float(min_elevation),
                     1 if magnetic else 0)
         res = PipeResult()
@@ -381,7 +381,7 @@ class FramePipeline(object):
         p = params if params is not None else frame_params(wcsHeader, altitude, cameraPosGCRS, photoTime, fast,
                                                            magnetic=self.with_mag)
         fd = self.fd
-        Context.current(self.ctx.device)      # enqueue on whatever stream torch has current now
+        self.ctx.bind()      # enqueue on whatever stream torch has current now
         out = self._out
         min_elev = NEG_INF if min_elevation is None else float(min_elevation)
         if dirs is not None:
@@ -429,7 +429,7 @@ class FramePipeline(object):
         """
         n = len(pipes)
         ctx = pipes[0].ctx
-        Context.current(ctx.device)
+        ctx.bind()
         min_elev = NEG_INF if min_elevation is None else float(min_elevation)
         mag = 1 if fuse_magnetic else 0
         if not isinstance(altitudes, (list, tuple)):
@@ -640,7 +640,7 @@ class FramePipeline(object):
             q = quantile_list(q)
         pxPerDeg = _px_per_deg(pxPerDeg)
         fd = self.fd
-        Context.current(self.ctx.device)
+        self.ctx.bind()
         if statistic == 'mean' and self._fused is not None and self._fused['pxPerDeg'] == tuple(pxPerDeg) and \
                 self._fused['magnetic'] == bool(magnetic):
             res = self._wait_fused()
@@ -763,20 +763,16 @@ class FramePipeline(object):
         return {k: self.fd.host(k) for k in names}
 
 
-_CLASS_PIPES = {}
+_CLASS_PIPES = ThreadPipes()             # per host thread, like Context._cache
 
 
 def fused_class_pipeline(width, height, img_dtype, magnetic=False):
-    """The frame pipeline behind the mapping classes' fused resample() (one per frame size / image type / grid kind and
-    device, grids only: its per-pixel arrays are only allocated when a frame has to take the two-pass plan)."""
+    """The frame pipeline behind the mapping classes' fused resample() (one per host thread, frame size / image type / grid
+    kind and device, grids only: its per-pixel arrays are only allocated when a frame has to take the two-pass plan)."""
     ctx = Context.current()
     key = (str(ctx.device), int(width), int(height), np.dtype(img_dtype).str, bool(magnetic))
-    pipe = _CLASS_PIPES.get(key)
-    if pipe is None:
-        if len(_CLASS_PIPES) >= 4:
-            _CLASS_PIPES.clear()                # (frames of many sizes: do not hoard their buffers)
-        pipe = _CLASS_PIPES[key] = FramePipeline(width, height, img_dtype=img_dtype, with_mag=bool(magnetic), alloc_coords=False)
-    return pipe
+    return _CLASS_PIPES.get(key, lambda: FramePipeline(width, height, img_dtype=img_dtype, with_mag=bool(magnetic),
+                                                       alloc_coords=False))
 
 
 _STREAMS = {}
@@ -1291,7 +1287,7 @@ class SequencePipeline(object):
         bpp = 3 if self.pipes[0].fd.img_dtype == np.uint8 else 6
         self.s_main.wait_stream(caller)
         with torch.cuda.stream(self.s_main):
-            Context.current(ctx.device)                     # the library enqueues on torch's current stream
+            ctx.bind()                     # the library enqueues on torch's current stream
             while done_total < n:
                 m = n - done_total
                 cells = self._arena_cells * m
@@ -1440,7 +1436,7 @@ class SequencePipeline(object):
                 n = len(prepared)
                 qs = [self.pipes[(k0 + i) % nb] for i in range(n)]
                 with torch.cuda.stream(self.s_main):
-                    Context.current(ctx.device)
+                    ctx.bind()
                     handles = (C.c_void_p * n)(*[q._pipe() for q in qs])
                     pp = (C.c_void_p * n)(*[C.addressof(pr[0]) for pr in prepared])
                     ctx.check(lib.amt_pipe_launch_box_many(handles, n, pp, min_elev, mag))
@@ -1752,7 +1748,7 @@ class GatherSequence(object):
                 a = np.ascontiguousarray(img, dtype=self.img_dtype)
                 if a.size != dev.numel():
                     raise ValueError('image of %s values, the pipeline takes %s' % (a.shape, shape))
-                Context.current(self.ctx.device)
+                self.ctx.bind()
                 self.ctx.upload(a.view(np.int16) if a.dtype == np.uint16 else a, dev)
             uploaded = torch.cuda.Event()
             uploaded.record(self.s_copy)
@@ -1872,7 +1868,7 @@ class GatherSequence(object):
                     break
                 prepared.append(self._prepared(f))
             with torch.cuda.stream(self.s_main):
-                Context.current(ctx.device)
+                ctx.bind()
                 for i in range(0, len(prepared), 3):            # AMT_PIPE_MAX_BATCH frames per launch of the frame kernel
                     part = prepared[i:i + 3]
                     handles = (C.c_void_p * len(part))(*[self.pipes[parity * B + i + m]._pipe() for m in range(len(part))])
@@ -1912,7 +1908,7 @@ class GatherSequence(object):
                 plans = [p for _, p, _ in jobs]
                 with torch.cuda.stream(self.s_main):
                     images = [self._device_image(img) for _, _, img in jobs]
-                    Context.current(ctx.device)         # (an upload has bound the context to the copy stream)
+                    ctx.bind()         # (an upload has bound the context to the copy stream)
                     sizes, flat = gather_frames_coordinates(plans, n)
                     outs, _, _ = _gather_frames_call(ctx, plans, images, self.interpolation, self.magnetic, n, self._min_count,
                                                      coords=(sizes, self._stage(flat)), arena=self._arena(self._arenas))

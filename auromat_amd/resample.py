@@ -14,6 +14,7 @@ from __future__ import division, print_function
 import copy
 import ctypes as C
 import math
+import threading
 from functools import partial
 
 import numpy as np
@@ -764,7 +765,7 @@ def resample_frame_area(fd, altitude, boundingBox, pxPerDeg, containsDiscontinui
     ctx = fd.ctx
     # (the accumulators are zeroed by torch on its current stream and added to by the library on the context's: the same one,
     #  also after a sequence pipeline has left the context on its own stream)
-    Context.current(ctx.device)
+    ctx.bind()
     grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
                                                min_elevation, outline, None)
     lat, lon = fd.lat, fd.lon
@@ -864,7 +865,7 @@ def project_and_bin(frames, projection, xEdges, yEdges, min_elevation=None):
     import torch
     fd0 = frames[0]
     ctx = fd0.ctx
-    Context.current(ctx.device)
+    ctx.bind()
     nch, code = fd0.nchan, fd0.img_dtype_code
     for fd in frames:
         if fd.nchan != nch or fd.img_dtype_code != code:
@@ -1524,21 +1525,28 @@ class _Grid(object):
         (xaxis, _), (yaxis, _) = self._axes[key]
         return xaxis, yaxis
 
+    def _settled(self, key, ctx, arrays):
+        """Device tables of this grid under `key`: uploaded once and SETTLED before they are kept.  Grids are cached per process
+        (cached_grid) and arrays of 1 MiB and more travel asynchronously on the uploading thread's stream (Context.upload), so a
+        reader on another stream — another host thread — is ordered behind nothing: the uploading stream is waited for once,
+        when the tables are made, which costs a sequence that finds them in the cache nothing."""
+        import torch
+        tables = self._axes.get(key)
+        if tables is None:
+            tables = tuple(ctx.to_device(a) for a in arrays())
+            torch.cuda.current_stream(ctx.device).synchronize()
+            tables = self._axes.setdefault(key, tables)
+        return tables
+
     def device_corners(self, ctx):
         """(lat, lon) of the corner grid on the device, longitude-major ((nx+1, ny+1)), kept with the grid."""
-        key = ('corners', ctx.device.index)
-        if key not in self._axes:
-            self._axes[key] = (ctx.to_device(np.ascontiguousarray(self.lat.T, dtype=np.float64)),
-                               ctx.to_device(np.ascontiguousarray(self.lon.T, dtype=np.float64)))
-        return self._axes[key]
+        return self._settled(('corners', ctx.device.index), ctx,
+                             lambda: (np.ascontiguousarray(self.lat.T, dtype=np.float64), np.ascontiguousarray(self.lon.T, dtype=np.float64)))
 
     def device_centers(self, ctx):
         """(latCenters (ny), lonCenters (nx)) on the device, kept with the grid."""
-        key = ('centers', ctx.device.index)
-        if key not in self._axes:
-            self._axes[key] = (ctx.to_device(np.ascontiguousarray(self.latCenters)),
-                               ctx.to_device(np.ascontiguousarray(self.lonCenters)))
-        return self._axes[key]
+        return self._settled(('centers', ctx.device.index), ctx,
+                             lambda: (np.ascontiguousarray(self.latCenters), np.ascontiguousarray(self.lonCenters)))
 
     # 2-D coordinate arrays of the output mapping (reference resample.py:239-241), built on first use
     def _corners(self):
@@ -2071,7 +2079,27 @@ def ResampleProvider(provider, **kw):
 
 # ---- gather resampling: every grid cell centre projected into the image ---------------------------------------------------------
 GATHER_INTERPOLATIONS = ('nearest', 'linear', 'lanczos4')
-_GATHER_PIPES = {}
+
+
+class ThreadPipes(threading.local):
+    """A cache of frame pipelines of the calling thread (`pipes`: key -> FramePipeline, at most 4).  A pipeline is one amt_ctx,
+    one amt_pipe, one set of accumulators and one stored layout, and "contexts may be used from different threads (one thread
+    per context at a time)" (include/auromat_hip.h): like Context._cache, the pipeline caches of the class paths are kept per
+    host thread, so that two threads that resample mappings of one frame size never drive one pipeline."""
+
+    def __init__(self):
+        self.pipes = {}
+
+    def get(self, key, make):
+        pipe = self.pipes.get(key)
+        if pipe is None:
+            if len(self.pipes) >= 4:
+                self.pipes.clear()              # (frames of many sizes: do not hoard their buffers)
+            pipe = self.pipes[key] = make()
+        return pipe
+
+
+_GATHER_PIPES = ThreadPipes()
 
 
 def _check_gather_interpolation(interpolation):
@@ -2139,17 +2167,18 @@ def gather_subsample_coordinates(plan, n):
     return dict(lat=lat, lon=lon, cell_lat=None, cell_lon=None)
 
 
+def gather_box_pipeline(ctx, width, height):
+    """The frame pipeline behind the box pass of the gather plans (one per host thread, device and frame size; it holds no
+    image and no per-pixel array)."""
+    from .pipeline import FramePipeline
+    key = (str(ctx.device), int(width), int(height))
+    return _GATHER_PIPES.get(key, lambda: FramePipeline(width, height, alloc_image=False, alloc_coords=False))
+
+
 def _gather_box(ctx, params, min_elevation, magnetic):
     """The 8-number bounding-box reduction of a camera frame whose arrays do not exist (the box pass of the frame kernel:
     no per-pixel array is written), in (lat, lon) or (MLat, SM longitude); [7]: a pole of those coordinates is in view."""
-    from .pipeline import FramePipeline
-    key = (str(ctx.device), params.width, params.height)
-    pipe = _GATHER_PIPES.get(key)
-    if pipe is None:
-        if len(_GATHER_PIPES) >= 4:
-            _GATHER_PIPES.clear()
-        pipe = _GATHER_PIPES[key] = FramePipeline(params.width, params.height, alloc_image=False, alloc_coords=False)
-    return pipe.box_first(params, min_elevation, magnetic)
+    return gather_box_pipeline(ctx, params.width, params.height).box_first(params, min_elevation, magnetic)
 
 
 def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magnetic=False):

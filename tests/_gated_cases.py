@@ -61,6 +61,11 @@ TRUE, DECOY = scene(1, 40.0, 10.0), scene(2, 41.25, 11.75)
 _kept = {}                                       # device constants and host tables that live as long as the session
 
 
+def _key(name, ctx):
+    """what a case keeps per context — a host thread has a context of its own (Context.current), hence kept objects of its own"""
+    return (name, ctx.handle.value)
+
+
 def pair(*names):
     return OrderedDict((k, (TRUE[k], DECOY[k])) for k in names)
 
@@ -473,9 +478,10 @@ def _call_nearest(env):
     from _gated_stream import dev
     i, o = env.inp, env.out
     xa, ya = _axes(env.ctx)
-    if 'targets' not in _kept:                                           # (constants of the case: uploaded once, by the baseline)
-        _kept['targets'] = (dev(TARGET_LAT), dev(TARGET_LON))
-    tlat, tlon = _kept['targets']
+    key = _key('targets', env.ctx)
+    if key not in _kept:                                                 # (constants of the case: uploaded once per context)
+        _kept[key] = (dev(TARGET_LAT), dev(TARGET_LON))
+    tlat, tlon = _kept[key]
     env.ctx.call('amt_nearest_frame', _ptr(i['lat_c']), _ptr(i['lon_c']), _ptr(i['elev']), None, H, W, MIN_ELEV, C.byref(xa),
                  C.byref(ya), 0, _ptr(tlat), _ptr(tlon), _ptr(i['target_mask']), _ptr(o['index']))
     env.closed('amt_nearest_frame')
@@ -530,7 +536,8 @@ def _call_mosaic(name, synchronises):
         table = _members(env, AreaMosaicMember if area else MosaicMember, area)
         env.ctx.call(name, table, 2, 2, 3, MIN_ELEV, C.byref(xa), C.byref(ya), 0, 1, *(([C.c_uint64(HALF)] if area else []) +
                                                                                     _grid_ptrs(o) + [_ptr(o['source'])]))
-        _kept.setdefault('tables', []).append(table)        # (never freed in a session: a late reader would find valid pointers)
+        # (never freed in a session: a late reader would find valid pointers)
+        _kept.setdefault(_key('tables', env.ctx), []).append(table)
         if not synchronises:
             env.closed(name)
     return call
@@ -669,9 +676,10 @@ def _call_scanline(env):
     from _gated_stream import dev
     from auromat_amd._native import ScanLineStrip
     i, o, ctx = env.inp, env.out, env.ctx
-    if 'scan_axes' not in _kept:
-        _kept['scan_axes'] = (dev(S_LAT), dev(S_LON))
-    lat, lon = _kept['scan_axes']
+    key = _key('scan_axes', ctx)
+    if key not in _kept:
+        _kept[key] = (dev(S_LAT), dev(S_LON))
+    lat, lon = _kept[key]
     table = (ScanLineStrip * 2)()
     held = []
     for s in range(2):
@@ -694,7 +702,7 @@ def _call_scanline(env):
         held.append((keep, stats, rec))
     ctx.call('amt_scanline_compose', table, 2, 2, 3, 4, 0, 0, NY, S_NX, _ptr(o['planes']), _ptr(o['img']), _ptr(o['mask']),
              _ptr(o['frame_index']))
-    _kept.setdefault('tables', []).append((table, held))
+    _kept.setdefault(_key('tables', ctx), []).append((table, held))
 
 
 def _oracle_scanline(a):
@@ -840,16 +848,18 @@ def _georef_out(out, names=GEO):
 
 
 class Driver(object):
-    """amt_pipe handles of the calling thread's context, kept for the session (their streams belong to the context)"""
-    _pipes = []
+    """amt_pipe handles per context (keyed by its handle: every host thread has a context of its own), kept for the session
+    (their streams belong to the context)"""
+    _pipes = {}
 
     @classmethod
     def get(cls, ctx, n=1):
-        while len(cls._pipes) < n:
+        pipes = cls._pipes.setdefault(ctx.handle.value, [])
+        while len(pipes) < n:
             h = C.c_void_p()
             ctx.call('amt_pipe_create', C.byref(h))
-            cls._pipes.append(h)
-        return cls._pipes[:n]
+            pipes.append(h)
+        return pipes[:n]
 
 
 def release():
@@ -858,10 +868,10 @@ def release():
     torch.cuda.synchronize()
     from auromat_amd import _native
     while Driver._pipes:
-        _native.lib().amt_pipe_destroy(Driver._pipes.pop())
-    _kept.pop('seq', None)
-    for key in ('targets', 'scan_axes', 'host_images', 'tables'):
-        _kept.pop(key, None)
+        for h in Driver._pipes.popitem()[1]:
+            _native.lib().amt_pipe_destroy(h)
+    for key in [k for k in _kept if isinstance(k, tuple) and k[0] in ('seq', 'targets', 'scan_axes', 'host_images', 'tables')]:
+        del _kept[key]
 
 
 def _check(ctx, rc):
@@ -1088,15 +1098,16 @@ def _call_run_device(env):
 def _call_run_host(env):
     """page-locked host images: the runner's copy stream takes them to buffers of its own"""
     import torch
-    if 'host_images' not in _kept:
-        _kept['host_images'] = [torch.from_numpy(image(40 + k, RW, RH).view(np.int16)).pin_memory() for k in range(R_FRAMES)]
-    return _run_frames(env, lambda k: (None, _kept['host_images'][k].data_ptr()))
+    key = _key('host_images', env.ctx)
+    if key not in _kept:
+        _kept[key] = [torch.from_numpy(image(40 + k, RW, RH).view(np.int16)).pin_memory() for k in range(R_FRAMES)]
+    return _run_frames(env, lambda k: (None, _kept[key][k].data_ptr()))
 
 
 def _call_sequence_pipeline(env):
     """SequencePipeline.process with device images on whatever stream torch has current"""
     from auromat_amd.pipeline import SequencePipeline
-    key = 'seq'
+    key = _key('seq', env.ctx)
     if key not in _kept:
         _kept[key] = SequencePipeline(RW, RH, pxPerDeg=PX_PER_DEG, min_elevation=MIN_ELEV, own_image_buffers=False)
     seq = _kept[key]
