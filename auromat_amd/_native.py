@@ -173,6 +173,9 @@ _SIGNATURES = {
     'amt_ctx_set_stream': ([_P, _P], _I),
     'amt_ctx_get_stream': ([_P], _P),
     'amt_ctx_synchronize': ([_P], _I),
+    'amt_debug_scratch_info': ([_P, C.POINTER(C.c_size_t), c_void_pp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)], _I),
+    'amt_debug_scratch_fill': ([_P, C.c_size_t, _I], _I),
+    'amt_debug_scratch_release': ([_P], _I),
     'amt_last_error': ([_P], C.c_char_p),
     'amt_device_info': ([_P, C.c_char_p, C.c_size_t, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_size_t)], _I),
     'amt_malloc': ([_P, C.c_size_t, c_void_pp], _I),

@@ -21,7 +21,6 @@ struct amt_ctx {
     amt_copier* copier;
     hipStream_t stream;
     bool owns_stream;
-    double* scratch;        // small device scratch (counters)
     // grow-only device workspaces (per-block partial reductions, sort buffers), ONE PER STREAM the context has been
     // used on: kernels of different streams run concurrently and must not share scratch memory
     struct workspace {
@@ -147,8 +146,10 @@ int amt_pipe_finish_on(amt_ctx* ctx, hipStream_t stream, const finish_batch& B, 
 // while frame k+1 is georeferenced on another), so scratch memory is kept per stream.
 // At most kMaxWorkspaces streams keep one: a host that keeps creating streams (torch does, per thread) would otherwise
 // leak a megabyte per stream ever seen; the least recently used one is synchronised and freed.
+// `request` false (amt_debug_scratch_fill): the same lookup, eviction and growth without counting as a request — workspace_clock
+// stays, and the buffer counts as used at the latest request.
 constexpr size_t kMaxWorkspaces = 16;
-static inline void* amt_workspace(amt_ctx* ctx, size_t bytes) {
+static inline void* amt_workspace(amt_ctx* ctx, size_t bytes, bool request = true) {
     amt_ctx::workspace* w = nullptr;
     for (auto& e : ctx->workspaces)
         if (e.stream == ctx->stream) w = &e;
@@ -169,7 +170,7 @@ static inline void* amt_workspace(amt_ctx* ctx, size_t bytes) {
         ctx->workspaces.push_back({ctx->stream, nullptr, 0, 0});
         w = &ctx->workspaces.back();
     }
-    w->last_use = ++ctx->workspace_clock;
+    w->last_use = request ? ++ctx->workspace_clock : ctx->workspace_clock;
     if (bytes <= w->bytes) return w->ptr;
     if (w->ptr) {
         (void)hipStreamSynchronize(ctx->stream);

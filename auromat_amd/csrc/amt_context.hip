@@ -20,7 +20,6 @@ int amt_ctx_create(int device_id, void* stream, int own_stream, amt_ctx** out_ct
     ctx->device = device_id;
     ctx->stream = nullptr;
     ctx->owns_stream = false;
-    ctx->scratch = nullptr;
     ctx->timing = 0;
     ctx->copier = nullptr;
     ctx->last_second = ctx->last_bin = ctx->last_frames = -1;
@@ -45,11 +44,6 @@ int amt_ctx_create(int device_id, void* stream, int own_stream, amt_ctx** out_ct
         }
         ctx->owns_stream = true;
     }
-    if (hipMalloc(reinterpret_cast<void**>(&ctx->scratch), 256) != hipSuccess) {
-        if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
-        delete ctx;
-        return AMT_ENOMEM;
-    }
     *out_ctx = ctx;
     return AMT_OK;
 }
@@ -58,7 +52,6 @@ int amt_ctx_destroy(amt_ctx* ctx) {
     AMT_CHECK_CTX(ctx);
     (void)hipSetDevice(ctx->device);
     amt_copier_destroy(ctx->copier);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
     for (auto& w : ctx->workspaces)
         if (w.ptr) (void)hipFree(w.ptr);
     for (int k = 0; k < 2; ++k)
@@ -92,6 +85,51 @@ void* amt_ctx_get_stream(amt_ctx* ctx) { return ctx ? reinterpret_cast<void*>(ct
 int amt_ctx_synchronize(amt_ctx* ctx) {
     AMT_CHECK_CTX(ctx);
     AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return AMT_OK;
+}
+
+int amt_debug_scratch_info(amt_ctx* ctx, size_t* bytes, void** ptr, int32_t* streams, uint64_t* requests) {
+    AMT_CHECK_CTX(ctx);
+    const amt_ctx::workspace* w = nullptr;
+    for (const auto& e : ctx->workspaces)
+        if (e.stream == ctx->stream) w = &e;
+    if (bytes) *bytes = w ? w->bytes : 0;
+    if (ptr) *ptr = w ? w->ptr : nullptr;
+    if (streams) {
+        *streams = 0;
+        for (const auto& e : ctx->workspaces) *streams += e.ptr != nullptr;
+    }
+    if (requests) *requests = ctx->workspace_clock;
+    return AMT_OK;
+}
+
+int amt_debug_scratch_fill(amt_ctx* ctx, size_t at_least, int byte) {
+    AMT_CHECK_CTX(ctx);
+    if (amt_set_device(ctx)) return AMT_EHIP;
+    void* ws = amt_workspace(ctx, at_least ? at_least : 1, false);       // (0: the buffer as it is, or a first one)
+    if (ws == nullptr) {
+        ctx->last_error = "amt_debug_scratch_fill: workspace allocation failed";
+        return AMT_ENOMEM;
+    }
+    size_t bytes = 0;
+    for (const auto& e : ctx->workspaces)
+        if (e.stream == ctx->stream) bytes = e.bytes;
+    AMT_HIP(ctx, hipMemsetAsync(ws, byte & 255, bytes, ctx->stream));
+    return AMT_OK;
+}
+
+int amt_debug_scratch_release(amt_ctx* ctx) {
+    AMT_CHECK_CTX(ctx);
+    if (amt_set_device(ctx)) return AMT_EHIP;
+    for (size_t i = 0; i < ctx->workspaces.size(); ++i) {
+        if (ctx->workspaces[i].stream != ctx->stream) continue;
+        if (ctx->workspaces[i].ptr) {
+            AMT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            AMT_HIP(ctx, hipFree(ctx->workspaces[i].ptr));
+        }
+        ctx->workspaces.erase(ctx->workspaces.begin() + (long)i);
+        break;
+    }
     return AMT_OK;
 }
 

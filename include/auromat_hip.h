@@ -93,6 +93,21 @@ int amt_ctx_destroy(amt_ctx* ctx);
 int amt_ctx_set_stream(amt_ctx* ctx, void* stream);
 void* amt_ctx_get_stream(amt_ctx* ctx);
 int amt_ctx_synchronize(amt_ctx* ctx);                 /* synchronises */
+/* A test and debugging aid for that scratch memory: it changes no result of a correct library (every entry point writes what it
+   reads there, in stream order), so a test can put the memory into any state and ask for the same bytes.  An addition to ABI
+   v10; nothing else in the library calls it.
+   amt_debug_scratch_info: of the context's CURRENT stream the size of its scratch buffer (*bytes, 0: it has none) and its
+   device address (*ptr); how many streams of this context hold a buffer (*streams, at most 16: the least recently used
+   one is synchronised and freed for a 17th); how many times entry points of this context have asked for scratch memory
+   (*requests: a call that uses it adds one or more, the two functions below add none).  Every pointer is optional.
+   amt_debug_scratch_fill: grows the current stream's buffer to at least `at_least` bytes exactly as an entry point that needs
+   as much would (a first buffer has 1 MiB at least; growing synchronises that stream once and frees the old buffer; 0: the
+   buffer as it is, or a first one), then enqueues on that stream a fill of the WHOLE buffer with `byte` (its low 8 bits).
+   amt_debug_scratch_release: synchronises the current stream and frees its buffer (if any): the next entry point on that
+   stream starts from a fresh allocation. */
+int amt_debug_scratch_info(amt_ctx* ctx, size_t* bytes, void** ptr, int32_t* streams, uint64_t* requests);
+int amt_debug_scratch_fill(amt_ctx* ctx, size_t at_least, int byte);
+int amt_debug_scratch_release(amt_ctx* ctx);                                       /* synchronises */
 const char* amt_last_error(amt_ctx* ctx);
 /* Device properties the host side prints next to roofline numbers. */
 int amt_device_info(amt_ctx* ctx, char* name, size_t name_len, int* compute_units, int* clock_khz,
