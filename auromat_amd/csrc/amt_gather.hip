@@ -468,53 +468,68 @@ size_t window_bytes(int C) {
     return (size_t)kWin * kWin * (size_t)C * sizeof(T);
 }
 
+// the dynamic LDS of a launch: the window (none for the nearest pixel); a supersampled launch holds the window or the winners and
+// elevations, whichever is larger (`head`: its bytes, 16-byte rounded), then the points' samples: at most 36 KB + 16 KB
+// (float32 x 4 channels)
 template <typename T>
-void launch_gather(amt_ctx* ctx, const gather_args& A, int interpolation) {
-    const dim3 grid((unsigned)((A.nx + kTile - 1) / kTile), (unsigned)((A.ny + kTile - 1) / kTile));
-    const size_t lds = window_bytes<T>(A.C);
-    if (interpolation == AMT_INTERP_LINEAR)
-        hipLaunchKernelGGL((k_gather_mosaic<T, 2>), grid, dim3(256), lds, ctx->stream, A);
-    else if (interpolation == AMT_INTERP_LANCZOS4)
-        hipLaunchKernelGGL((k_gather_mosaic<T, 8>), grid, dim3(256), lds, ctx->stream, A);
-    else
-        hipLaunchKernelGGL((k_gather_mosaic<T, 0>), grid, dim3(256), 0, ctx->stream, A);
+size_t gather_lds(int C, int interpolation, bool supersampled, int& head) {
+    const size_t window = interpolation == AMT_INTERP_NEAREST ? 0 : window_bytes<T>(C);
+    if (!supersampled) return window;
+    const size_t h = (std::max(window, (size_t)kHeadMin) + 15) & ~(size_t)15;
+    head = (int)h;
+    return h + (size_t)kPoints * (size_t)C * sizeof(T);
 }
 
-template <typename T>
-void launch_gather_ss(amt_ctx* ctx, gather_ss_args S, int interpolation) {
+// the one dispatch over (sample type, taps per axis): launch(T(), integral_constant<int, N>())
+template <typename F>
+void gather_dispatch(int sample_bytes, int interpolation, F launch) {
+    const auto taps = [&](auto t) {
+        if (interpolation == AMT_INTERP_LINEAR)
+            launch(t, std::integral_constant<int, 2>());
+        else if (interpolation == AMT_INTERP_LANCZOS4)
+            launch(t, std::integral_constant<int, 8>());
+        else
+            launch(t, std::integral_constant<int, 0>());
+    };
+    switch (sample_bytes) {
+        case 1: taps(uint8_t()); break;
+        case 2: taps(uint16_t()); break;
+        default: taps(float()); break;
+    }
+}
+
+void launch_gather(amt_ctx* ctx, const gather_args& A, int sample_bytes, int interpolation) {
+    const dim3 grid((unsigned)((A.nx + kTile - 1) / kTile), (unsigned)((A.ny + kTile - 1) / kTile));
+    gather_dispatch(sample_bytes, interpolation, [&](auto t, auto taps) {
+        using T = decltype(t);
+        int head;
+        const size_t lds = gather_lds<T>(A.C, interpolation, false, head);
+        hipLaunchKernelGGL((k_gather_mosaic<T, decltype(taps)::value>), grid, dim3(256), lds, ctx->stream, A);
+    });
+}
+
+void launch_gather_ss(amt_ctx* ctx, gather_ss_args S, int sample_bytes, int interpolation) {
     const int Tc = kTile / S.factor;
     const dim3 grid((unsigned)((S.G.nx + Tc - 1) / Tc), (unsigned)((S.G.ny + Tc - 1) / Tc));
-    // the window (none for the nearest pixel) or the winners and elevations, whichever is larger; then the points' samples:
-    // at most 36 KB + 16 KB (float32 x 4 channels)
-    const size_t window = interpolation == AMT_INTERP_NEAREST ? 0 : window_bytes<T>(S.G.C);
-    const size_t head = (std::max(window, (size_t)kHeadMin) + 15) & ~(size_t)15;
-    const size_t lds = head + (size_t)kPoints * (size_t)S.G.C * sizeof(T);
-    S.head = (int)head;
-    if (interpolation == AMT_INTERP_LINEAR)
-        hipLaunchKernelGGL((k_gather_mosaic_ss<T, 2>), grid, dim3(256), lds, ctx->stream, S);
-    else if (interpolation == AMT_INTERP_LANCZOS4)
-        hipLaunchKernelGGL((k_gather_mosaic_ss<T, 8>), grid, dim3(256), lds, ctx->stream, S);
-    else
-        hipLaunchKernelGGL((k_gather_mosaic_ss<T, 0>), grid, dim3(256), lds, ctx->stream, S);
+    gather_dispatch(sample_bytes, interpolation, [&](auto t, auto taps) {
+        using T = decltype(t);
+        const size_t lds = gather_lds<T>(S.G.C, interpolation, true, S.head);
+        hipLaunchKernelGGL((k_gather_mosaic_ss<T, decltype(taps)::value>), grid, dim3(256), lds, ctx->stream, S);
+    });
 }
 
-template <typename T, bool SS>
-void launch_gather_frames(amt_ctx* ctx, gather_frames_args F, int tiles, int interpolation) {
-    // the dynamic LDS of launch_gather (SS false) or launch_gather_ss (SS true)
-    const size_t window = interpolation == AMT_INTERP_NEAREST ? 0 : window_bytes<T>(F.C);
-    size_t lds = window;
-    if (SS) {
-        const size_t head = (std::max(window, (size_t)kHeadMin) + 15) & ~(size_t)15;
-        lds = head + (size_t)kPoints * (size_t)F.C * sizeof(T);
-        F.head = (int)head;
-    }
+void launch_gather_frames(amt_ctx* ctx, gather_frames_args F, int tiles, int sample_bytes, int interpolation) {
     const dim3 grid((unsigned)tiles);
-    if (interpolation == AMT_INTERP_LINEAR)
-        hipLaunchKernelGGL((k_gather_frames<T, 2, SS>), grid, dim3(256), lds, ctx->stream, F);
-    else if (interpolation == AMT_INTERP_LANCZOS4)
-        hipLaunchKernelGGL((k_gather_frames<T, 8, SS>), grid, dim3(256), lds, ctx->stream, F);
-    else
-        hipLaunchKernelGGL((k_gather_frames<T, 0, SS>), grid, dim3(256), lds, ctx->stream, F);
+    gather_dispatch(sample_bytes, interpolation, [&](auto t, auto taps) {
+        using T = decltype(t);
+        constexpr int N = decltype(taps)::value;
+        const bool ss = F.factor > 1;
+        const size_t lds = gather_lds<T>(F.C, interpolation, ss, F.head);
+        if (ss)
+            hipLaunchKernelGGL((k_gather_frames<T, N, true>), grid, dim3(256), lds, ctx->stream, F);
+        else
+            hipLaunchKernelGGL((k_gather_frames<T, N, false>), grid, dim3(256), lds, ctx->stream, F);
+    });
 }
 
 #define GATHER_REQUIRE(cond, msg)                                     \
@@ -525,7 +540,53 @@ void launch_gather_frames(amt_ctx* ctx, gather_frames_args F, int tiles, int int
         }                                                              \
     } while (0)
 
-// what both entry points check and prepare: the arguments they share, the member table in the context's workspace, and the
+// the arguments every entry point takes (`rule`: a batch of frames has one member per job and passes the kernel's 1)
+int gather_check(amt_ctx* ctx, const char* fn, int32_t frame, int32_t interpolation, int32_t rule, int32_t sample_bytes, int32_t channels,
+                 const amt_gather_debug* debug) {
+    GATHER_REQUIRE(frame == AMT_W2P_GEODETIC || frame == AMT_W2P_SM, "unknown frame (AMT_W2P_GEODETIC or AMT_W2P_SM)");
+    GATHER_REQUIRE(interpolation == AMT_INTERP_LINEAR || interpolation == AMT_INTERP_LANCZOS4 || interpolation == AMT_INTERP_NEAREST,
+                   "unknown interpolation");
+    GATHER_REQUIRE(rule == 0 || rule == 1, "unknown rule");
+    GATHER_REQUIRE(sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4, "sample_bytes must be 1 (uint8), 2 (uint16) or 4 (float32)");
+    GATHER_REQUIRE(channels == 1 || channels == 3 || channels == 4, "channels must be 1, 3 or 4");
+    GATHER_REQUIRE(!debug || (debug->force_path >= AMT_GATHER_PATH_AUTO && debug->force_path <= AMT_GATHER_PATH_CELL), "unknown force_path");
+    return AMT_OK;
+}
+
+// the supersampled calls' own: the factor and the least count, then (per grid; `job`: "job k: " or nothing) the sub-sample grid
+int gather_check_factor(amt_ctx* ctx, const char* fn, int32_t factor, int32_t min_count) {
+    GATHER_REQUIRE(factor >= 1 && factor <= 8, "factor must be 1 ... 8");
+    GATHER_REQUIRE(min_count >= 1 && min_count <= factor * factor, "min_count must be 1 ... factor * factor");
+    return AMT_OK;
+}
+
+int gather_check_subgrid(amt_ctx* ctx, const char* fn, const std::string& job, int32_t ny, int32_t nx, int32_t factor) {
+    GATHER_REQUIRE(ny <= INT32_MAX / factor && nx <= INT32_MAX / factor, job + "the sub-sample grid does not fit 32-bit indices");
+    return AMT_OK;
+}
+
+// "either the two axes or the two cell arrays": the pair that is given goes to `to` (gather_args, gather_job_dev), the other is NULL
+template <typename To>
+int gather_coordinates(amt_ctx* ctx, const char* fn, const std::string& job, const double* lat, const double* lon, const double* cell_lat,
+                       const double* cell_lon, To& to) {
+    const bool axes = lat && lon, cells = cell_lat && cell_lon;
+    GATHER_REQUIRE((lat != nullptr) == (lon != nullptr) && (cell_lat != nullptr) == (cell_lon != nullptr) && axes != cells,
+                   job + "give either the two axes or the two cell arrays");
+    to.lat = axes ? lat : nullptr, to.lon = axes ? lon : nullptr;
+    to.cell_lat = axes ? nullptr : cell_lat, to.cell_lon = axes ? nullptr : cell_lon;
+    return AMT_OK;
+}
+
+// a member as the kernels read it: w2p_prepare's message, or "member without image", or NULL
+const char* gather_member(const amt_gather_member& m, int32_t frame, gather_dev& d) {
+    const char* err = m.img ? w2p_prepare(&m.params, m.zenithal, frame, &d.K, &d.S) : "member without image";
+    d.img = m.img;
+    d.center_mask = m.center_mask;
+    d.min_elevation = m.min_elevation > -INFINITY ? m.min_elevation : (double)NAN;      // (-inf and NaN: none)
+    return err;
+}
+
+// what both mosaic entry points check and prepare: the arguments they share, the member table in the context's workspace, and the
 // kernel's arguments for a grid of ny x nx cells (the supersampled call adds its own)
 int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* members, int32_t n_members, int32_t frame, const double* lat_axis,
                    int32_t ny, const double* lon_axis, int32_t nx, const double* cell_lat, const double* cell_lon, int32_t sample_bytes,
@@ -534,27 +595,16 @@ int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* member
     GATHER_REQUIRE(members && out_img && out_mask && out_elev && out_source, "NULL argument");
     GATHER_REQUIRE(n_members >= 1, "no members");
     GATHER_REQUIRE(ny > 0 && nx > 0, "empty axis");
-    const bool axes = lat_axis && lon_axis, cells = cell_lat && cell_lon;
-    GATHER_REQUIRE((lat_axis != nullptr) == (lon_axis != nullptr) && (cell_lat != nullptr) == (cell_lon != nullptr) && axes != cells,
-                   "give either the two axes or the two cell arrays");
-    GATHER_REQUIRE(frame == AMT_W2P_GEODETIC || frame == AMT_W2P_SM, "unknown frame (AMT_W2P_GEODETIC or AMT_W2P_SM)");
-    GATHER_REQUIRE(interpolation == AMT_INTERP_LINEAR || interpolation == AMT_INTERP_LANCZOS4 || interpolation == AMT_INTERP_NEAREST,
-                   "unknown interpolation");
-    GATHER_REQUIRE(rule == 0 || rule == 1, "unknown rule");
-    GATHER_REQUIRE(sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4, "sample_bytes must be 1 (uint8), 2 (uint16) or 4 (float32)");
-    GATHER_REQUIRE(channels == 1 || channels == 3 || channels == 4, "channels must be 1, 3 or 4");
-    GATHER_REQUIRE(!debug || (debug->force_path >= AMT_GATHER_PATH_AUTO && debug->force_path <= AMT_GATHER_PATH_CELL), "unknown force_path");
+    int rc = gather_coordinates(ctx, fn, "", lat_axis, lon_axis, cell_lat, cell_lon, A);
+    if (rc == AMT_OK) rc = gather_check(ctx, fn, frame, interpolation, rule, sample_bytes, channels, debug);
+    if (rc != AMT_OK) return rc;
 
     std::vector<gather_dev> dev((size_t)n_members);
     bool same = true;
     for (int32_t i = 0; i < n_members; ++i) {
-        const amt_gather_member& m = members[i];
         gather_dev& d = dev[(size_t)i];
-        const char* err = m.img ? w2p_prepare(&m.params, m.zenithal, frame, &d.K, &d.S) : "member without image";
+        const char* err = gather_member(members[i], frame, d);
         GATHER_REQUIRE(err == nullptr, "member " + std::to_string(i) + ": " + err);
-        d.img = m.img;
-        d.center_mask = m.center_mask;
-        d.min_elevation = m.min_elevation > -INFINITY ? m.min_elevation : (double)NAN;      // (-inf and NaN: none)
         same = same && d.K.a0 == dev[0].K.a0 && d.K.e2 == dev[0].K.e2;
     }
     if (amt_set_device(ctx)) return AMT_EHIP;
@@ -572,8 +622,6 @@ int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* member
     }
 
     A.members = reinterpret_cast<const gather_dev*>(ws);
-    A.lat = axes ? lat_axis : nullptr, A.lon = axes ? lon_axis : nullptr;
-    A.cell_lat = axes ? nullptr : cell_lat, A.cell_lon = axes ? nullptr : cell_lon;
     A.n = n_members, A.ny = ny, A.nx = nx, A.C = channels;
     A.rule = rule, A.same_ellipsoid = same ? 1 : 0, A.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, A.pad_ = 0;
     A.img = out_img, A.mask = out_mask, A.elev = out_elev, A.source = out_source, A.xy = nullptr;
@@ -594,11 +642,7 @@ extern "C" int amt_gather_mosaic(amt_ctx* ctx, const amt_gather_member* members,
                                   sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, A);
     if (rc != AMT_OK) return rc;
     A.xy = out_xy;
-    switch (sample_bytes) {
-        case 1: launch_gather<uint8_t>(ctx, A, interpolation); break;
-        case 2: launch_gather<uint16_t>(ctx, A, interpolation); break;
-        default: launch_gather<float>(ctx, A, interpolation); break;
-    }
+    launch_gather(ctx, A, sample_bytes, interpolation);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
@@ -611,20 +655,16 @@ extern "C" int amt_gather_mosaic_supersampled(amt_ctx* ctx, const amt_gather_mem
                                               uint8_t* out_count, const amt_gather_debug* debug) {
     AMT_CHECK_CTX(ctx);
     AMT_REQUIRE(ctx, out_count, "NULL argument");
-    AMT_REQUIRE(ctx, factor >= 1 && factor <= 8, "factor must be 1 ... 8");
-    AMT_REQUIRE(ctx, min_count >= 1 && min_count <= factor * factor, "min_count must be 1 ... factor * factor");
-    AMT_REQUIRE(ctx, ny <= INT32_MAX / factor && nx <= INT32_MAX / factor, "the sub-sample grid does not fit 32-bit indices");
     gather_ss_args S;
-    const int rc = gather_prepare(ctx, __func__, members, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon,
-                                  sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, S.G);
+    int rc = gather_check_factor(ctx, __func__, factor, min_count);
+    if (rc == AMT_OK) rc = gather_check_subgrid(ctx, __func__, "", ny, nx, factor);
+    if (rc == AMT_OK)
+        rc = gather_prepare(ctx, __func__, members, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon, sample_bytes,
+                            channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, S.G);
     if (rc != AMT_OK) return rc;
     S.factor = factor, S.min_count = min_count, S.head = 0, S.pad_ = 0;
     S.count = out_count;
-    switch (sample_bytes) {
-        case 1: launch_gather_ss<uint8_t>(ctx, S, interpolation); break;
-        case 2: launch_gather_ss<uint16_t>(ctx, S, interpolation); break;
-        default: launch_gather_ss<float>(ctx, S, interpolation); break;
-    }
+    launch_gather_ss(ctx, S, sample_bytes, interpolation);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
@@ -636,14 +676,9 @@ extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32
     const char* fn = __func__;
     GATHER_REQUIRE(jobs, "NULL argument");
     GATHER_REQUIRE(n_jobs >= 1 && n_jobs <= AMT_GATHER_MAX_JOBS, "n_jobs must be 1 ... " + std::to_string(AMT_GATHER_MAX_JOBS));
-    GATHER_REQUIRE(frame == AMT_W2P_GEODETIC || frame == AMT_W2P_SM, "unknown frame (AMT_W2P_GEODETIC or AMT_W2P_SM)");
-    GATHER_REQUIRE(interpolation == AMT_INTERP_LINEAR || interpolation == AMT_INTERP_LANCZOS4 || interpolation == AMT_INTERP_NEAREST,
-                   "unknown interpolation");
-    GATHER_REQUIRE(sample_bytes == 1 || sample_bytes == 2 || sample_bytes == 4, "sample_bytes must be 1 (uint8), 2 (uint16) or 4 (float32)");
-    GATHER_REQUIRE(channels == 1 || channels == 3 || channels == 4, "channels must be 1, 3 or 4");
-    GATHER_REQUIRE(!debug || (debug->force_path >= AMT_GATHER_PATH_AUTO && debug->force_path <= AMT_GATHER_PATH_CELL), "unknown force_path");
-    GATHER_REQUIRE(factor >= 1 && factor <= 8, "factor must be 1 ... 8");
-    GATHER_REQUIRE(min_count >= 1 && min_count <= factor * factor, "min_count must be 1 ... factor * factor");
+    int rc = gather_check(ctx, fn, frame, interpolation, 1, sample_bytes, channels, debug);
+    if (rc == AMT_OK) rc = gather_check_factor(ctx, fn, factor, min_count);
+    if (rc != AMT_OK) return rc;
 
     // the prefix table of tile counts, then the jobs, in one staging buffer: one copy
     const size_t jobs_at = (((size_t)n_jobs + 1) * sizeof(int) + 15) & ~(size_t)15;
@@ -655,21 +690,15 @@ extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32
     for (int32_t k = 0; k < n_jobs; ++k) {
         const amt_gather_job& j = jobs[k];
         const std::string job = "job " + std::to_string(k) + ": ";
+        gather_job_dev& d = dev[k];
         GATHER_REQUIRE(j.out_img && j.out_mask && j.out_elev, job + "NULL argument");
         GATHER_REQUIRE(factor == 1 || j.out_count, job + "NULL out_count with factor > 1");
         GATHER_REQUIRE(j.ny > 0 && j.nx > 0, job + "empty axis");
-        GATHER_REQUIRE(j.ny <= INT32_MAX / factor && j.nx <= INT32_MAX / factor, job + "the sub-sample grid does not fit 32-bit indices");
-        const bool axes = j.lat && j.lon, cells = j.cell_lat && j.cell_lon;
-        GATHER_REQUIRE((j.lat != nullptr) == (j.lon != nullptr) && (j.cell_lat != nullptr) == (j.cell_lon != nullptr) && axes != cells,
-                       job + "give either the two axes or the two cell arrays");
-        gather_job_dev& d = dev[k];
-        const char* err = j.member.img ? w2p_prepare(&j.member.params, j.member.zenithal, frame, &d.M.K, &d.M.S) : "member without image";
+        rc = gather_check_subgrid(ctx, fn, job, j.ny, j.nx, factor);
+        if (rc == AMT_OK) rc = gather_coordinates(ctx, fn, job, j.lat, j.lon, j.cell_lat, j.cell_lon, d);
+        if (rc != AMT_OK) return rc;
+        const char* err = gather_member(j.member, frame, d.M);
         GATHER_REQUIRE(err == nullptr, job + err);
-        d.M.img = j.member.img;
-        d.M.center_mask = j.member.center_mask;
-        d.M.min_elevation = j.member.min_elevation > -INFINITY ? j.member.min_elevation : (double)NAN;      // (-inf and NaN: none)
-        d.lat = axes ? j.lat : nullptr, d.lon = axes ? j.lon : nullptr;
-        d.cell_lat = axes ? nullptr : j.cell_lat, d.cell_lon = axes ? nullptr : j.cell_lon;
         d.img = j.out_img, d.mask = j.out_mask, d.elev = j.out_elev, d.count = factor > 1 ? j.out_count : nullptr;
         d.ny = j.ny, d.nx = j.nx, d.tiles_x = (j.nx + Tc - 1) / Tc, d.pad_ = 0;
         first[k] = (int)tiles;
@@ -693,12 +722,7 @@ extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32
     F.n_jobs = n_jobs, F.C = channels, F.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, F.factor = factor;
     F.min_count = min_count, F.head = 0;
     F.tile_path = debug ? debug->tile_path : nullptr;
-    const bool ss = factor > 1;
-    switch (sample_bytes) {
-        case 1: ss ? launch_gather_frames<uint8_t, true>(ctx, F, (int)tiles, interpolation) : launch_gather_frames<uint8_t, false>(ctx, F, (int)tiles, interpolation); break;
-        case 2: ss ? launch_gather_frames<uint16_t, true>(ctx, F, (int)tiles, interpolation) : launch_gather_frames<uint16_t, false>(ctx, F, (int)tiles, interpolation); break;
-        default: ss ? launch_gather_frames<float, true>(ctx, F, (int)tiles, interpolation) : launch_gather_frames<float, false>(ctx, F, (int)tiles, interpolation); break;
-    }
+    launch_gather_frames(ctx, F, (int)tiles, sample_bytes, interpolation);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }

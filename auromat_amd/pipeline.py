@@ -1790,20 +1790,13 @@ class GatherSequence(object):
     def _plan_of(self, red, params):
         """:func:`auromat_amd.resample.gather_plan`'s plan for a box pass's reduction, or 'pole' where plateCarreeResolution
         has no longitude resolution to give."""
-        from .resample import plateCarreeResolution, wrap_at_180
-        bb = bounding_box_from_reduction(red)
-        if self.arcsecPerPx:
-            ppd = plateCarreeResolution(bb, self.arcsecPerPx)
-            if not ppd[1] > 0:
-                return 'pole'
-        else:
-            ppd = self.pxPerDeg
-        lonMin, lonMax = bb.lonWest, bb.lonEast
-        if bb.containsDiscontinuity:
-            lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
-        return dict(grid=cached_grid(ppd, bb.latSouth, bb.latNorth, lonMin, lonMax), contains_pole=False,
-                    contains_discontinuity=bool(bb.containsDiscontinuity), altitude=None, params=params, zenithal=None,
-                    min_elevation=self.min_elevation, center_mask=None, bbox=list(red), pxPerDeg=ppd)
+        from .resample import gather_box_grid
+        part, ppd = gather_box_grid(red, self.pxPerDeg, self.arcsecPerPx)
+        if part['grid'] is None:
+            assert self.arcsecPerPx           # (a fixed resolution is positive)
+            return 'pole'
+        return dict(part, altitude=None, params=params, zenithal=None, min_elevation=self.min_elevation, center_mask=None,
+                    bbox=list(red), pxPerDeg=ppd)
 
     def _class_route(self, pr, keep_on_device):
         """A frame with a pole in view, at a fixed resolution: the class API's plan and gather (a rotated grid laid out from the
@@ -1845,7 +1838,7 @@ class GatherSequence(object):
         `on_batch(k0, results)` is called with every finished batch while the next one's box passes run.
         """
         import torch
-        from .resample import _gather_frames_call, gather_frames_coordinates
+        from .resample import _gather_frames_call, gather_frames_coordinates, gather_result, gather_to_host
         del self.plans[:]
         del self._arenas[:]
         self.uploaded_bytes = self.gather_calls = 0
@@ -1914,11 +1907,7 @@ class GatherSequence(object):
                                                      coords=(sizes, self._stage(flat)), arena=self._arena(self._arenas))
                     self.gather_calls += 1
                 for (k, plan, _), o in zip(jobs, outs):
-                    r = dict(grid_coordinates(plan), grid=plan['grid'], contains_pole=False,
-                             contains_discontinuity=plan['contains_discontinuity'], altitude=plan['altitude'], bbox=plan['bbox'],
-                             pxPerDeg=plan['pxPerDeg'])
-                    r.update(o)
-                    results[k] = r
+                    results[k] = gather_result(plan, altitude=plan['altitude'], bbox=plan['bbox'], pxPerDeg=plan['pxPerDeg'], **o)
             return results
 
         def deliver(k0, results):
@@ -1928,11 +1917,7 @@ class GatherSequence(object):
                     for r in results:
                         if r is None or not isinstance(r['img'], torch.Tensor):
                             continue
-                        r['img'] = to_host(r['img'].contiguous(), dtype=self.img_dtype)
-                        r['mask'] = to_host(r['mask'].contiguous()).astype(bool)
-                        r['elevation'] = to_host(r['elevation'].contiguous())
-                        if n > 1:
-                            r['count'] = to_host(r['count'].contiguous(), dtype=np.uint8)
+                        r.update(gather_to_host(r, self.img_dtype))
             for r in results:
                 if r is not None and n > 1 and not isinstance(r['count'], torch.Tensor):
                     r['coverage'] = r['count'] / float(n * n)

@@ -92,19 +92,25 @@ def resampleMLatMLT(mapping, **kw):
         if res is not None:
             last_plan = res['plan']
             img, elevation = _masked_image_and_elevation(res['mask'], res['mean'], res['img'], True)
-            # convertSMMappingToGeo (reference mapping.py:1549-1559) on the grid's arrays as they are: building the SM mapping
-            # first would send the grid to the device and back through its properties, for the same numbers
-            from .coordinates.transform import smToLatLon
             from .mapping.mapping import GenericMapping
-            nc = res['lat'].size
-            la, lo = smToLatLon(np.concatenate((res['lat'].ravel(), res['lat_c'].ravel())),
-                                np.concatenate((res['lon'].ravel(), res['lon_c'].ravel())), mapping.photoTime)
-            return GenericMapping(la[:nc].reshape(res['lat'].shape), lo[:nc].reshape(res['lon'].shape),
-                                  la[nc:].reshape(res['lat_c'].shape), lo[nc:].reshape(res['lon_c'].shape), elevation,
-                                  mapping.altitude, img, mapping.cameraPosGCRS, mapping.photoTime, mapping.identifier)
+            lat, lon, lat_c, lon_c = sm_grid_to_geographic(res, mapping.photoTime)
+            return GenericMapping(lat, lon, lat_c, lon_c, elevation, mapping.altitude, img, mapping.cameraPosGCRS,
+                                  mapping.photoTime, mapping.identifier)
     sm = convertMappingToSM(mapping)
     smResampled = resample(sm, **kw)
     return convertSMMappingToGeo(smResampled)
+
+
+def sm_grid_to_geographic(res, time):
+    """(lat, lon, lat_c, lon_c) of a result whose grid is in SM coordinates, as geographic coordinates at `time`:
+    convertSMMappingToGeo (reference mapping.py:1549-1559) on the grid's arrays as they are, corners and centres through ONE
+    ``smToLatLon`` call — building the SM mapping first would send the grid to the device and back through its properties,
+    for the same numbers."""
+    from .coordinates.transform import smToLatLon
+    lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
+    nc = lat.size
+    la, lo = smToLatLon(np.concatenate((lat.ravel(), lat_c.ravel())), np.concatenate((lon.ravel(), lon_c.ravel())), time)
+    return la[:nc].reshape(lat.shape), lo[:nc].reshape(lon.shape), la[nc:].reshape(lat_c.shape), lo[nc:].reshape(lon_c.shape)
 
 
 # 'single-pass' / 'two-pass': the plan the last resample() of a camera mapping took (None: the array pipeline)
@@ -937,11 +943,7 @@ def _projected_mapping(members, res, projection, xEdges, yEdges, frame):
     first = next(m for m in members if m.photoTime == photoTime)
     lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
     if frame == 'sm':
-        from .coordinates.transform import smToLatLon
-        nc = lat.size
-        la, lo = smToLatLon(np.concatenate((lat.ravel(), lat_c.ravel())), np.concatenate((lon.ravel(), lon_c.ravel())), photoTime)
-        lat, lon = la[:nc].reshape(lat.shape), lo[:nc].reshape(lon.shape)
-        lat_c, lon_c = la[nc:].reshape(lat_c.shape), lo[nc:].reshape(lon_c.shape)
+        lat, lon, lat_c, lon_c = sm_grid_to_geographic(res, photoTime)
     img, elevation = _masked_image_and_elevation(res['mask'], res['area'], res['img'], res['has_elev'])
     return ProjectedMapping(lat, lon, lat_c, lon_c, elevation, first.altitude, img, first.cameraPosGCRS, photoTime,
                             first.identifier, projection, xEdges, yEdges, res['coverage'], frame)
@@ -2156,15 +2158,30 @@ def gather_subsample_coordinates(plan, n):
              the point form — cell_lat, cell_lon of (ny n, nx n) — with lat = lon = None; the two forms of
              ``amt_gather_mosaic_supersampled``
     """
-    grid = plan['grid']
-    lat = _subsample_axis(grid.lat[:, 0], n)
-    lon = _subsample_axis(grid.lon[0, :], n)
-    if plan['contains_pole']:
-        la, lo = _rotate_pole_host(np.repeat(lat[:, None], lon.size, 1), np.repeat(lon[None, :], lat.size, 0), plan['altitude'], -90)
-        return dict(lat=None, lon=None, cell_lat=la, cell_lon=lo)
-    if plan['contains_discontinuity']:
-        lon = wrap_at_180(lon + 180)
-    return dict(lat=lat, lon=lon, cell_lat=None, cell_lon=None)
+    a, b, points = _gather_job_coordinates(plan, n, True)
+    return dict(lat=None, lon=None, cell_lat=a, cell_lon=b) if points else dict(lat=a, lon=b, cell_lat=None, cell_lon=None)
+
+
+def _gather_job_coordinates(plan, n, sub=None):
+    """The coordinate arrays of one grid of a gather call: (a, b, points) — the two axes, or with a pole in view (`points` True)
+    the two point arrays.  They hold the grid's cell centres, or (`sub`; default: n > 1) the n x n sub-samples per cell that
+    :func:`gather_subsample_coordinates` describes.  The only place that decides between the two forms."""
+    points = bool(plan['contains_pole'])
+    if sub is None:
+        sub = n > 1
+    if sub:
+        grid = plan['grid']
+        a = _subsample_axis(grid.lat[:, 0], n)
+        b = _subsample_axis(grid.lon[0, :], n)
+        if points:
+            a, b = _rotate_pole_host(np.repeat(a[:, None], b.size, 1), np.repeat(b[None, :], a.size, 0), plan['altitude'], -90)
+        elif plan['contains_discontinuity']:
+            b = wrap_at_180(b + 180)
+        return a, b, points
+    coords = grid_coordinates(plan)
+    if points:
+        return coords['lat_c'], coords['lon_c'], True
+    return coords['lat_c'][:, 0], coords['lon_c'][0, :], False
 
 
 def gather_box_pipeline(ctx, width, height):
@@ -2175,10 +2192,29 @@ def gather_box_pipeline(ctx, width, height):
     return _GATHER_PIPES.get(key, lambda: FramePipeline(width, height, alloc_image=False, alloc_coords=False))
 
 
-def _gather_box(ctx, params, min_elevation, magnetic):
-    """The 8-number bounding-box reduction of a camera frame whose arrays do not exist (the box pass of the frame kernel:
-    no per-pixel array is written), in (lat, lon) or (MLat, SM longitude); [7]: a pole of those coordinates is in view."""
-    return gather_box_pipeline(ctx, params.width, params.height).box_first(params, min_elevation, magnetic)
+def _gather_box(mapping, params, zen, magnetic):
+    """The box pass for a camera mapping whose arrays do not exist: (the 8-number bounding-box reduction of the frame kernel's
+    box pass — no per-pixel array is written —, in (lat, lon) or (MLat, SM longitude), [7]: a pole of those coordinates is in
+    view; the ``maskedByElevation`` the mapping remembers, which stays a threshold).  None, None for any other mapping."""
+    if zen is None and getattr(mapping, '_frame', True) is None:
+        lazy = getattr(mapping, '_lazy_elev', None)
+        return gather_box_pipeline(Context.current(), params.width, params.height).box_first(params, lazy, magnetic), lazy
+    return None, None
+
+
+def gather_box_grid(red, pxPerDeg, arcsecPerPx):
+    """The grid part of a gather plan from a box pass's reduction — :func:`resample`'s grid for that box: its resolution
+    (``plateCarreeResolution`` with `arcsecPerPx`), the date-line shift, :func:`cached_grid` —, and the resolution used:
+    (dict(grid, contains_pole=False, contains_discontinuity), (latPxPerDeg, lonPxPerDeg)).  `grid` is None where there is no
+    longitude resolution (``plateCarreeResolution`` of a box that goes all the way round): the callers refuse that."""
+    from .mapping.mapping import bounding_box_from_reduction
+    bb = bounding_box_from_reduction(red)
+    ppd = plateCarreeResolution(bb, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
+    lonMin, lonMax = bb.lonWest, bb.lonEast
+    if bb.containsDiscontinuity:
+        lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
+    grid = cached_grid(ppd, bb.latSouth, bb.latNorth, lonMin, lonMax) if ppd[1] > 0 else None
+    return dict(grid=grid, contains_pole=False, contains_discontinuity=bool(bb.containsDiscontinuity)), ppd
 
 
 def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magnetic=False):
@@ -2193,22 +2229,13 @@ def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magne
         raise NotImplementedError('resampleGather takes one mapping; collections or lists are gathered onto one grid by '
                                   'resampleGatherMosaic')
     params, zen = mapping._inverse_model()
-    ctx = Context.current()
     plan = dict(altitude=mapping.altitude, params=params, zenithal=zen, min_elevation=None, center_mask=None)
-    if zen is None and getattr(mapping, '_frame', True) is None:
-        from .mapping.mapping import bounding_box_from_reduction
-        lazy = getattr(mapping, '_lazy_elev', None)
-        red = _gather_box(ctx, params, lazy, magnetic)
-        pole = bool(red[7]) if containsPole is None else bool(containsPole)
-        if not pole:
-            bb = bounding_box_from_reduction(red)
-            ppd = plateCarreeResolution(bb, arcsecPerPx) if arcsecPerPx else _px_per_deg(pxPerDeg)
-            lonMin, lonMax = bb.lonWest, bb.lonEast
-            if bb.containsDiscontinuity:
-                lonMin, lonMax = wrap_at_180(lonMin + 180), wrap_at_180(lonMax + 180)
-            plan.update(grid=cached_grid(ppd, bb.latSouth, bb.latNorth, lonMin, lonMax), contains_pole=False,
-                        contains_discontinuity=bool(bb.containsDiscontinuity), min_elevation=lazy)
-            return plan
+    red, lazy = _gather_box(mapping, params, zen, magnetic)
+    if red is not None and not (bool(red[7]) if containsPole is None else bool(containsPole)):
+        part, _ = gather_box_grid(red, pxPerDeg, arcsecPerPx)
+        assert part['grid'] is not None         # (what _Grid asserts: a longitude resolution)
+        plan.update(part, min_elevation=lazy)
+        return plan
     # arrays exist (or a pole is in view, whose rotated grid is laid out from them): the two-pass plan's grid
     src = convertMappingToSM(mapping) if magnetic else mapping
     pole, ppd = _pole_and_resolution(src, pxPerDeg, arcsecPerPx, containsPole)
@@ -2238,23 +2265,20 @@ def gather_frame(plan, image, interpolation='linear', magnetic=False, supersampl
     _check_gather_interpolation(interpolation)
     n, min_count = _check_supersample(supersample, minCoverage)
     if n > 1:
-        member = dict(params=plan['params'], zenithal=plan['zenithal'], min_elevation=plan['min_elevation'],
-                      center_mask=plan['center_mask'])
-        out = _gather_supersampled(plan, [member], [image], interpolation, magnetic, 1, n, min_count, None)
+        out = _gather_mosaic_call(plan, [plan], [image], interpolation, magnetic, 1, n, min_count, None)   # (the plan is the member)
         del out['source']
         return out
     ctx = Context.current()
     grid, params, zen = plan['grid'], plan['params'], plan['zenithal']
     frame = W2P_SM if magnetic else W2P_GEODETIC
-    coords = grid_coordinates(plan)
     need64 = interpolation == 'nearest' or plan['center_mask'] is not None
-    if plan['contains_pole']:
-        xy, elev, flags = world_to_pixel(params, zen, frame, ctx.to_device(np.ascontiguousarray(coords['lat_c'])),
-                                         ctx.to_device(np.ascontiguousarray(coords['lon_c'])))
+    a, b, points = _gather_job_coordinates(plan, 1)
+    a, b = ctx.to_device(np.ascontiguousarray(a)), ctx.to_device(np.ascontiguousarray(b))
+    if points:
+        xy, elev, flags = world_to_pixel(params, zen, frame, a, b)
         xy32 = xy.to(torch.float32)
     else:
-        xy32, xy, elev, flags = grid_to_pixel(ctx, params, zen, frame, ctx.to_device(np.ascontiguousarray(coords['lat_c'][:, 0])),
-                                              ctx.to_device(np.ascontiguousarray(coords['lon_c'][0, :])), xy64=need64)
+        xy32, xy, elev, flags = grid_to_pixel(ctx, params, zen, frame, a, b, xy64=need64)
     src, np_dtype, _ = _image_to_device(ctx, image)
     h, w, nch = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
     if (w, h) != (params.width, params.height):
@@ -2278,15 +2302,39 @@ def gather_frame(plan, image, interpolation='linear', magnetic=False, supersampl
         mask |= support == 0
     if plan['min_elevation'] is not None:
         mask |= ~(elev >= float(plan['min_elevation']))
-    out = dict(coords, grid=grid, img=to_host(dst.contiguous(), dtype=np_dtype), mask=to_host(mask.to(torch.uint8)).astype(bool),
-               elevation=to_host(elev), flags=to_host(flags), support=None if support is None else to_host(support),
-               contains_pole=plan['contains_pole'], contains_discontinuity=plan['contains_discontinuity'])
-    return out
+    return gather_result(plan, flags=to_host(flags), support=None if support is None else to_host(support),
+                         **gather_to_host(dict(img=dst, mask=mask.to(torch.uint8), elevation=elev), np_dtype))
 
 
 def _gather_image(mapping):
     img = getattr(mapping, '_img_array', None)
     return mapping.img_unmasked if img is None else img
+
+
+def gather_result(plan, /, **arrays):
+    """The dict every gather call returns for a plan: the grid's coordinates (:func:`grid_coordinates`), grid, contains_pole and
+    contains_discontinuity, then `arrays`."""
+    return dict(grid_coordinates(plan), grid=plan['grid'], contains_pole=plan['contains_pole'],
+                contains_discontinuity=plan['contains_discontinuity'], **arrays)
+
+
+def gather_to_host(out, np_dtype):
+    """dict(img, mask, elevation[, count]) of a grid's device tensors as host arrays: img of the image's numpy dtype, from a
+    contiguous tensor, mask bool, count uint8 (each read synchronises on the current stream)"""
+    host = dict(img=to_host(out['img'].contiguous(), dtype=np_dtype), mask=to_host(out['mask']).astype(bool),
+                elevation=to_host(out['elevation']))
+    if 'count' in out:
+        host['count'] = to_host(out['count'], dtype=np.uint8)
+    return host
+
+
+def _gather_finish(res, smTime=None):
+    """What the class functions make a mapping of: (lat, lon, lat_c, lon_c, masked elevation, masked img) of a gather result; with
+    `smTime` the coordinates of an (MLat, SM longitude) grid are converted back for that time."""
+    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
+    elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
+    corners = (res['lat'], res['lon'], res['lat_c'], res['lon_c']) if smTime is None else sm_grid_to_geographic(res, smTime)
+    return corners + (elevation, img)
 
 
 def _with_coverage(mapping, res, n):
@@ -2301,19 +2349,12 @@ def _resample_gather(mapping, pxPerDeg, arcsecPerPx, containsPole, interpolation
     n, _ = _check_supersample(supersample, minCoverage)
     plan = gather_plan(mapping, pxPerDeg, arcsecPerPx, containsPole, magnetic)
     res = gather_frame(plan, _gather_image(mapping), interpolation, magnetic, supersample, minCoverage)
-    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
     if not magnetic:
-        return _with_coverage(mapping.createResampled(res['lat'], res['lon'], res['lat_c'], res['lon_c'], elevation, img), res, n)
-    from .coordinates.transform import smToLatLon
+        return _with_coverage(mapping.createResampled(*_gather_finish(res)), res, n)
     from .mapping.mapping import GenericMapping
-    nc = res['lat'].size
-    la, lo = smToLatLon(np.concatenate((res['lat'].ravel(), res['lat_c'].ravel())),
-                        np.concatenate((res['lon'].ravel(), res['lon_c'].ravel())), mapping.photoTime)
-    return _with_coverage(GenericMapping(la[:nc].reshape(res['lat'].shape), lo[:nc].reshape(res['lon'].shape),
-                                         la[nc:].reshape(res['lat_c'].shape), lo[nc:].reshape(res['lon_c'].shape), elevation,
-                                         mapping.altitude, img, mapping.cameraPosGCRS, mapping.photoTime, mapping.identifier),
-                          res, n)
+    lat, lon, lat_c, lon_c, elevation, img = _gather_finish(res, mapping.photoTime)
+    return _with_coverage(GenericMapping(lat, lon, lat_c, lon_c, elevation, mapping.altitude, img, mapping.cameraPosGCRS,
+                                         mapping.photoTime, mapping.identifier), res, n)
 
 
 def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, interpolation='linear', supersample=1,
@@ -2408,28 +2449,23 @@ def gather_mosaic_plan(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=N
             raise NotImplementedError('resampleGatherMosaic: member %s: %s' % (m.identifier, e))
     altitude = altitudes[0]
     # the box pass for camera mappings whose arrays do not exist
-    reductions = []
-    for m, (params, zen) in zip(mappings, models):
-        red = None
-        if zen is None and getattr(m, '_frame', True) is None:
-            red = _gather_box(Context.current(), params, getattr(m, '_lazy_elev', None), magnetic)
-        reductions.append(red)
-    arrays = [None if red is not None else (convertMappingToSM(m) if magnetic else m) for m, red in zip(mappings, reductions)]
+    passes = [_gather_box(m, params, zen, magnetic) for m, (params, zen) in zip(mappings, models)]
+    arrays = [None if red is not None else (convertMappingToSM(m) if magnetic else m) for m, (red, _) in zip(mappings, passes)]
     if containsPole is None:
-        pole = any(bool(red[7]) if red is not None else bool(src.containsPole) for red, src in zip(reductions, arrays))
+        pole = any(bool(red[7]) if red is not None else bool(src.containsPole) for (red, _), src in zip(passes, arrays))
     else:
         pole = bool(containsPole)
     if pole:
         # the rotated grid is laid out from the members' outlines: every member's arrays
-        reductions = [None] * len(mappings)
+        passes = [(None, None)] * len(mappings)
         arrays = [convertMappingToSM(m) if magnetic else m for m in mappings]
     from .mapping.mapping import bounding_box_from_reduction
     boxes, members = [], []
-    for m, (params, zen), red, src, image in zip(mappings, models, reductions, arrays, images):
+    for (params, zen), (red, lazy), src, image in zip(models, passes, arrays, images):
         member = dict(params=params, zenithal=zen, min_elevation=None, center_mask=None, image=image)
         if red is not None:
             boxes.append(bounding_box_from_reduction(red))
-            member.update(min_elevation=getattr(m, '_lazy_elev', None))
+            member.update(min_elevation=lazy)
         else:
             boxes.append(src.boundingBox)
             member.update(center_mask=src.frame().center_mask_tensor())
@@ -2474,48 +2510,60 @@ def _gather_member_table(ctx, members, images):
     return table, keep, nch, tdtype, np_dtype
 
 
-def _gather_debug(ctx, debug, ny, nx, tile):
-    """amt_gather_debug of a `debug` dict and the tensor of its tile_path (one byte per `tile` x `tile` cells), or None, None"""
+def gather_tiles(grid, n):
+    """(tiles_y, tiles_x) of a grid gathered with n x n sub-samples per cell: a tile is 32 // n cells a side"""
+    T = 32 // n
+    return (grid.ny + T - 1) // T, (grid.nx + T - 1) // T
+
+
+def _gather_debug(ctx, debug, tiles):
+    """amt_gather_debug of a `debug` dict and the tensor of its tile_path (one byte per tile, of shape `tiles`), or None, None"""
     from ._native import GatherDebug
     if debug is None:
         return None, None
     import torch
-    dbg, tiles = GatherDebug(), None
+    dbg, tile_path = GatherDebug(), None
     dbg.force_path = int(debug.get('force_path', GATHER_PATH_AUTO))
     if debug.get('tile_path'):
-        tiles = ctx.zeros(((ny + tile - 1) // tile, (nx + tile - 1) // tile), torch.uint8)
-        dbg.tile_path = ptr(tiles).value
-    return dbg, tiles
+        tile_path = ctx.zeros(tiles, torch.uint8)
+        dbg.tile_path = ptr(tile_path).value
+    return dbg, tile_path
 
 
-def _gather_supersampled(plan, members, images, interpolation, magnetic, rule, n, min_count, debug):
-    """ONE call of ``amt_gather_mosaic_supersampled`` (include/auromat_hip.h states what it computes) on the plan's grid with
-    n x n sub-samples per cell: the result dict of :func:`gather_mosaic_frames` plus ``count``."""
+def _gather_mosaic_call(plan, members, images, interpolation, magnetic, rule, n, min_count, debug, xy=False, supersampled=None):
+    """ONE call of ``amt_gather_mosaic`` or, `supersampled` (default: n > 1), of ``amt_gather_mosaic_supersampled`` with n x n
+    sub-samples per cell (include/auromat_hip.h states what they compute) on the plan's grid: the result dict of
+    :func:`gather_mosaic_frames`, with ``count`` from the supersampled entry point and, if asked for, ``xy`` from the plain one."""
     import torch
     from .coordinates.inverse import W2P_GEODETIC, W2P_SM
+    if supersampled is None:
+        supersampled = n > 1
     ctx = Context.current()
     grid = plan['grid']
     ny, nx = grid.ny, grid.nx
     table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, members, images)
-    sub = gather_subsample_coordinates(plan, n)
-    dev = {k: None if v is None else ctx.to_device(np.ascontiguousarray(v)) for k, v in sub.items()}
-    img = torch.empty((ny, nx, nch), dtype=tdtype, device=ctx.device)
-    mask = ctx.empty((ny, nx), torch.uint8)
-    elev = ctx.empty((ny, nx))
+    a, b, points = _gather_job_coordinates(plan, n, supersampled)
+    a, b = ctx.to_device(np.ascontiguousarray(a)), ctx.to_device(np.ascontiguousarray(b))
+    lat, lon, cell_lat, cell_lon = (None, None, a, b) if points else (a, b, None, None)
+    dev = dict(img=torch.empty((ny, nx, nch), dtype=tdtype, device=ctx.device), mask=ctx.empty((ny, nx), torch.uint8),
+               elevation=ctx.empty((ny, nx)))
     source = ctx.empty((ny, nx), torch.int32)
-    count = ctx.empty((ny, nx), torch.uint8)
-    dbg, tiles = _gather_debug(ctx, debug, ny, nx, 32 // n)
-    ctx.call('amt_gather_mosaic_supersampled', table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(dev['lat']), ny,
-             ptr(dev['lon']), nx, ptr(dev['cell_lat']), ptr(dev['cell_lon']), n, min_count, img.element_size(), nch,
-             _GATHER_INTERP_CODES[interpolation], int(rule), ptr(img), ptr(mask), ptr(elev), ptr(source), ptr(count),
-             None if dbg is None else C.byref(dbg))
-    out = dict(grid_coordinates(plan), grid=grid, img=to_host(img, dtype=np_dtype), mask=to_host(mask).astype(bool),
-               elevation=to_host(elev), source=to_host(source, dtype=np.int32), count=to_host(count, dtype=np.uint8),
-               contains_pole=plan['contains_pole'], contains_discontinuity=plan['contains_discontinuity'],
-               altitude=plan['altitude'], plan=plan)
-    if tiles is not None:
-        out['tile_path'] = to_host(tiles)
-    del keep, dev                # (after the read-back above: the kernel is done with them)
+    if supersampled:
+        dev['count'] = ctx.empty((ny, nx), torch.uint8)
+        fn, factor, last = 'amt_gather_mosaic_supersampled', (n, min_count), dev['count']
+    else:
+        fn, factor, last = 'amt_gather_mosaic', (), ctx.empty((ny, nx, 2)) if xy else None
+    dbg, tile_path = _gather_debug(ctx, debug, gather_tiles(grid, n))
+    ctx.call(fn, table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(lat), ny, ptr(lon), nx, ptr(cell_lat), ptr(cell_lon),
+             *factor + (dev['img'].element_size(), nch, _GATHER_INTERP_CODES[interpolation], int(rule), ptr(dev['img']),
+                        ptr(dev['mask']), ptr(dev['elevation']), ptr(source), ptr(last), None if dbg is None else C.byref(dbg)))
+    out = gather_result(plan, source=to_host(source, dtype=np.int32), altitude=plan['altitude'], plan=plan,
+                        **gather_to_host(dev, np_dtype))
+    if xy and not supersampled:
+        out['xy'] = to_host(last)
+    if tile_path is not None:
+        out['tile_path'] = to_host(tile_path)
+    del keep                     # (after the read-back above: the kernel is done with them)
     return out
 
 
@@ -2539,48 +2587,15 @@ def gather_mosaic_frames(plan, images=None, interpolation='linear', magnetic=Fal
     :return: dict like :func:`mosaic_frames`': lat, lon, lat_c, lon_c, img (ny, nx, C), mask (ny, nx) bool, elevation (ny, nx;
              the winner's, NaN where nobody sees the cell), source (ny, nx) int32 [-1: nobody], plan
     """
-    import torch
-    from .coordinates.inverse import W2P_GEODETIC, W2P_SM
     _check_gather_interpolation(interpolation)
     n, min_count = _check_supersample(supersample, minCoverage)
-    ctx = Context.current()
-    grid, members = plan['grid'], plan['members']
+    members = plan['members']
     images = [m['image'] for m in members] if images is None else list(images)
     if len(images) != len(members):
         raise ValueError('%d images for %d members' % (len(images), len(members)))
-    if n > 1:
-        if xy:
-            raise ValueError('xy: a supersampled cell has no single pixel position')
-        return _gather_supersampled(plan, members, images, interpolation, magnetic, plan['rule'], n, min_count, debug)
-    table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, members, images)
-    coords = grid_coordinates(plan)
-    ny, nx = grid.ny, grid.nx
-    if plan['contains_pole']:
-        lat_ax = lon_ax = None
-        cell_lat = ctx.to_device(np.ascontiguousarray(coords['lat_c']))
-        cell_lon = ctx.to_device(np.ascontiguousarray(coords['lon_c']))
-    else:
-        cell_lat = cell_lon = None
-        lat_ax = ctx.to_device(np.ascontiguousarray(coords['lat_c'][:, 0]))
-        lon_ax = ctx.to_device(np.ascontiguousarray(coords['lon_c'][0, :]))
-    img = torch.empty((ny, nx, nch), dtype=tdtype, device=ctx.device)
-    mask = ctx.empty((ny, nx), torch.uint8)
-    elev = ctx.empty((ny, nx))
-    source = ctx.empty((ny, nx), torch.int32)
-    out_xy = ctx.empty((ny, nx, 2)) if xy else None
-    dbg, tiles = _gather_debug(ctx, debug, ny, nx, 32)
-    ctx.call('amt_gather_mosaic', table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(lat_ax), ny, ptr(lon_ax), nx,
-             ptr(cell_lat), ptr(cell_lon), img.element_size(), nch, _GATHER_INTERP_CODES[interpolation], int(plan['rule']),
-             ptr(img), ptr(mask), ptr(elev), ptr(source), ptr(out_xy), None if dbg is None else C.byref(dbg))
-    out = dict(coords, grid=grid, img=to_host(img, dtype=np_dtype), mask=to_host(mask).astype(bool), elevation=to_host(elev),
-               source=to_host(source, dtype=np.int32), contains_pole=plan['contains_pole'],
-               contains_discontinuity=plan['contains_discontinuity'], altitude=plan['altitude'], plan=plan)
-    if out_xy is not None:
-        out['xy'] = to_host(out_xy)
-    if tiles is not None:
-        out['tile_path'] = to_host(tiles)
-    del keep                     # (after the read-back above: the kernel is done with them)
-    return out
+    if n > 1 and xy:
+        raise ValueError('xy: a supersampled cell has no single pixel position')
+    return _gather_mosaic_call(plan, members, images, interpolation, magnetic, plan['rule'], n, min_count, debug, xy)
 
 
 def _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, interpolation, magnetic, supersample=1,
@@ -2591,19 +2606,11 @@ def _resample_gather_mosaic(collection, pxPerDeg, arcsecPerPx, containsPole, int
     collection = _gather_collection(collection)
     plan = gather_mosaic_plan(collection, pxPerDeg, arcsecPerPx, containsPole, magnetic)
     res = gather_mosaic_frames(plan, None, interpolation, magnetic, supersample=supersample, minCoverage=minCoverage)
-    img = ma.masked_array(res['img'], mask=np.repeat(res['mask'][:, :, None], res['img'].shape[2], 2))
-    elevation = ma.masked_array(res['elevation'], mask=res['mask'] | np.isnan(res['elevation']))
     source = ma.masked_array(res['source'], mask=res['source'] < 0)
     members = collection.mappings
     photoTime = collection.photoTime
     first = next(m for m in members if m.photoTime == photoTime)
-    lat, lon, lat_c, lon_c = res['lat'], res['lon'], res['lat_c'], res['lon_c']
-    if magnetic:
-        from .coordinates.transform import smToLatLon
-        nc = lat.size
-        la, lo = smToLatLon(np.concatenate((lat.ravel(), lat_c.ravel())), np.concatenate((lon.ravel(), lon_c.ravel())), photoTime)
-        lat, lon = la[:nc].reshape(lat.shape), lo[:nc].reshape(lon.shape)
-        lat_c, lon_c = la[nc:].reshape(lat_c.shape), lo[nc:].reshape(lon_c.shape)
+    lat, lon, lat_c, lon_c, elevation, img = _gather_finish(res, photoTime if magnetic else None)
     return _with_coverage(MosaicMapping(lat, lon, lat_c, lon_c, elevation, plan['altitude'], img, first.cameraPosGCRS, photoTime,
                                         collection.identifier, source, plan['identifiers']), res, n)
 
@@ -2650,21 +2657,6 @@ def resampleGatherMosaicMLatMLT(collection, **kw):
 
 
 # ---- gathered frames: a batch of frames, each onto its own grid, one fused kernel ----------------------------------------------
-def _gather_job_coordinates(plan, n):
-    """The coordinate arrays of one job of ``amt_gather_frames``: (a, b, points) — the two axes, or with a pole in view
-    (`points` True) the two point arrays; the cell centres for n = 1, the sub-samples of :func:`gather_subsample_coordinates`
-    else."""
-    if n > 1:
-        sub = gather_subsample_coordinates(plan, n)
-        if sub['lat'] is None:
-            return sub['cell_lat'], sub['cell_lon'], True
-        return sub['lat'], sub['lon'], False
-    coords = grid_coordinates(plan)
-    if plan['contains_pole']:
-        return coords['lat_c'], coords['lon_c'], True
-    return coords['lat_c'][:, 0], coords['lon_c'][0, :], False
-
-
 def gather_frames_coordinates(plans, n):
     """The coordinates of a batch of ``amt_gather_frames``: (per plan (size of a, size of b, points), every plan's two arrays
     flattened one after the other into ONE float64 array — what a single copy takes to the device)."""
@@ -2680,12 +2672,10 @@ def _gather_frames_call(ctx, plans, images, interpolation, magnetic, n, min_coun
     `arena`: function (cells, channels, torch dtype, n) -> dict(img, mask, elevation[, count]) of flat tensors, in place of fresh
     ones."""
     import torch
-    from ._native import GATHER_MAX_JOBS, GatherDebug, GatherJob
+    from ._native import GATHER_MAX_JOBS, GatherJob
     from .coordinates.inverse import W2P_GEODETIC, W2P_SM
     assert 1 <= len(plans) <= GATHER_MAX_JOBS
-    members = [dict(params=p['params'], zenithal=p['zenithal'], min_elevation=p['min_elevation'], center_mask=p['center_mask'])
-               for p in plans]
-    table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, members, images)
+    table, keep, nch, tdtype, np_dtype = _gather_member_table(ctx, plans, images)      # (a plan holds a member's keys)
     if coords is None:
         sizes, flat = gather_frames_coordinates(plans, n)
         coords = (sizes, ctx.to_device(flat))           # every job's coordinates in one copy
@@ -2700,7 +2690,7 @@ def _gather_frames_call(ctx, plans, images, interpolation, magnetic, n, min_coun
     else:
         made = arena(total, nch, tdtype, n)
     jobs = (GatherJob * len(plans))()
-    outs, at, cell0, T, tiles = [], 0, 0, 32 // n, 0
+    outs, at, cell0, tiles = [], 0, 0, 0
     for job, member, plan, (na, nb, points), ncell in zip(jobs, table, plans, sizes, cells):
         ny, nx = plan['grid'].ny, plan['grid'].nx
         C.memmove(C.byref(job.member), C.byref(member), C.sizeof(member))
@@ -2720,15 +2710,10 @@ def _gather_frames_call(ctx, plans, images, interpolation, magnetic, n, min_coun
         job.out_img, job.out_mask, job.out_elev = out['img'].data_ptr(), out['mask'].data_ptr(), out['elevation'].data_ptr()
         outs.append(out)
         cell0 += ncell
-        tiles += ((ny + T - 1) // T) * ((nx + T - 1) // T)
+        ty, tx = gather_tiles(plan['grid'], n)
+        tiles += ty * tx
     assert at == coords.numel()
-    dbg, tile_path = None, None
-    if debug is not None:
-        dbg = GatherDebug()
-        dbg.force_path = int(debug.get('force_path', GATHER_PATH_AUTO))
-        if debug.get('tile_path'):
-            tile_path = ctx.zeros((tiles,), torch.uint8)
-            dbg.tile_path = ptr(tile_path).value
+    dbg, tile_path = _gather_debug(ctx, debug, (tiles,))
     ctx.call('amt_gather_frames', jobs, len(plans), W2P_SM if magnetic else W2P_GEODETIC, n, 1 if n == 1 else min_count,
              made['img'].element_size(), nch, _GATHER_INTERP_CODES[interpolation], None if dbg is None else C.byref(dbg))
     # the kernel is enqueued on the current stream: the caching allocator hands the inputs' memory to nobody who is not behind it
@@ -2767,19 +2752,12 @@ def gather_frames(plans, images, interpolation='linear', magnetic=False, supersa
         outs, tile_path, dtype = _gather_frames_call(ctx, chunk, images[k:k + GATHER_MAX_JOBS], interpolation, magnetic, n, min_count,
                                                      debug)
         tiles = None if tile_path is None else to_host(tile_path)
-        T, t0 = 32 // n, 0
+        t0 = 0
         for plan, out in zip(chunk, outs):
-            res = dict(grid_coordinates(plan), grid=plan['grid'], contains_pole=plan['contains_pole'],
-                       contains_discontinuity=plan['contains_discontinuity'])
-            if keep_on_device:
-                res.update(out)
-            else:
-                res.update(img=to_host(out['img'].contiguous(), dtype=dtype), mask=to_host(out['mask']).astype(bool),
-                           elevation=to_host(out['elevation']))
-                if n > 1:
-                    res['count'] = to_host(out['count'], dtype=np.uint8)
+            res = gather_result(plan, **(out if keep_on_device else gather_to_host(out, dtype)))
             if tiles is not None:
-                nt = ((plan['grid'].ny + T - 1) // T) * ((plan['grid'].nx + T - 1) // T)
+                ty, tx = gather_tiles(plan['grid'], n)
+                nt = ty * tx
                 res['tile_path'] = tiles[t0:t0 + nt]
                 t0 += nt
             results.append(res)

@@ -93,6 +93,30 @@ def test_plan_grid_is_the_mosaic_layout_of_the_boxes(boxes):
     assert gather_mosaic_plan(members, pxPerDeg=10)['rule'] == 1
 
 
+#   reduction: lat_min, lat_max, lon_min, lon_max, the least positive and the largest non-positive longitude, valid pixels, poles
+@pytest.mark.parametrize('red,kw,ppd,box,dateline', [
+    # inside one hemisphere
+    ([40.2, 50.7, 10.1, 20.3, 10.1, 0.0, 1000, 0], dict(pxPerDeg=10), (10, 10), (40.2, 50.7, 10.1, 20.3), False),
+    # across the date line, 171.3 E ... 172.6 W: the grid is laid out in longitudes shifted by 180 degrees
+    ([-5.5, 4.5, -179.9, 179.8, 171.3, -172.6, 1000, 0], dict(pxPerDeg=(7, 13)), (7, 13), (-5.5, 4.5, -8.7, 7.4), True),
+    # a spherical resolution: px / deg from the box
+    ([40.2, 50.7, 10.1, 20.3, 10.1, 0.0, 1000, 0], dict(arcsecPerPx=400), None, (40.2, 50.7, 10.1, 20.3), False)])
+def test_box_grid_of_a_reduction(red, kw, ppd, box, dateline):
+    from auromat_amd.mapping.mapping import BoundingBox
+    from auromat_amd.resample import cached_grid, fixedGrid, gather_box_grid, plateCarreeResolution
+    if ppd is None:
+        ppd = plateCarreeResolution(BoundingBox(40.2, 10.1, 50.7, 20.3), 400)
+        assert abs(ppd[0] - 9) < 1e-12 and 5 < ppd[1] < 7          # (3600 / 400; a degree of longitude is shorter at 45 N)
+    part, used = gather_box_grid(red, kw.get('pxPerDeg'), kw.get('arcsecPerPx'))
+    assert sorted(part) == ['contains_discontinuity', 'contains_pole', 'grid'] and tuple(used) == tuple(ppd)
+    assert part['contains_pole'] is False and part['contains_discontinuity'] is dateline
+    g, w = part['grid'], cached_grid(ppd, *box)
+    nLat, nLon = fixedGrid(ppd, *box)[:2]
+    assert (g.ny, g.nx) == (w.ny, w.nx) == (nLat - 2, nLon - 2) and g.ny > 1 and g.nx > 1
+    for a in ('lat', 'lon', 'lat_c', 'lon_c'):
+        assert np.array_equal(getattr(g, a), getattr(w, a)), a
+
+
 def test_refusals_come_before_any_device_call():
     from auromat_amd.mapping.astrometry import DirectionArrayMapping
     from auromat_amd.resample import (gather_mosaic_frames, gather_mosaic_plan, resampleGatherMosaic,

@@ -123,7 +123,8 @@ def test_factor_one_is_the_gather_mosaic():
     plan = pair_plan(np.float32, 4, pxPerDeg=10)
     images = [m['image'] for m in plan['members']]
     for interpolation in ('nearest', 'linear', 'lanczos4'):
-        res = R._gather_supersampled(plan, plan['members'], images, interpolation, False, plan['rule'], 1, 1, dict(tile_path=True))
+        res = R._gather_mosaic_call(plan, plan['members'], images, interpolation, False, plan['rule'], 1, 1, dict(tile_path=True),
+                                    supersampled=True)
         one = fine(plan, 1, interpolation)
         for k in ('img', 'mask', 'source'):
             assert same_bits(res[k], one[k]), (interpolation, k)
