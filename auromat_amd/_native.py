@@ -211,11 +211,23 @@ _SIGNATURES = {
     'amt_world_to_pixel': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, _P, _L, _P, _P, _P], _I),
     'amt_grid_to_pixel': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P, _P,
                            _P], _I),
+    'amt_world_to_pixel_lens': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, _P, _L, _P, _P, _P,
+                                 C.POINTER(LensModel)], _I),
+    'amt_grid_to_pixel_lens': ([_P, C.POINTER(FrameParams), C.POINTER(ZenithalWcs), C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P,
+                                _P, _P, C.POINTER(LensModel)], _I),
+    'amt_lens_fold_radius': ([C.POINTER(LensModel), c_double_p], _I),
     'amt_gather_mosaic': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
                           [C.c_int32] * 4 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
     'amt_gather_mosaic_supersampled': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
                                        [C.c_int32] * 6 + [_P] * 5 + [C.POINTER(GatherDebug)], _I),
     'amt_gather_frames': ([_P, C.POINTER(GatherJob)] + [C.c_int32] * 7 + [C.POINTER(GatherDebug)], _I),
+    'amt_gather_mosaic_lens': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
+                               [C.c_int32] * 4 + [_P] * 5 + [C.POINTER(GatherDebug), C.POINTER(C.POINTER(LensModel))], _I),
+    'amt_gather_mosaic_supersampled_lens': ([_P, C.POINTER(GatherMember), C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P, _P] +
+                                            [C.c_int32] * 6 + [_P] * 5 +
+                                            [C.POINTER(GatherDebug), C.POINTER(C.POINTER(LensModel))], _I),
+    'amt_gather_frames_lens': ([_P, C.POINTER(GatherJob)] + [C.c_int32] * 7 +
+                               [C.POINTER(GatherDebug), C.POINTER(C.POINTER(LensModel))], _I),
     'amt_intersect_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersects_ellipsoid': ([_P, _D, _D, c_double_p, _P, _L, _I, _P], _I),
     'amt_intersect_sphere': ([_P, _D, c_double_p, _P, _L, _I, _P], _I),

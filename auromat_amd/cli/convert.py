@@ -40,6 +40,8 @@ What differs, and why:
   found in ``metadata.json`` or a frame's ``<id>.json`` and no flag is given.  ``--lens-route resample`` (default) corrects and
   crops every image on the GPU (:meth:`auromat_amd.util.lensdistortion.LensModifier.remap_device`) and goes on as ever;
   ``--lens-route raw`` maps the uncorrected pixels themselves (``getMapping(..., lensRoute='raw')``), through the mapping classes.
+  ``--lens-route fused`` (only with ``--gather``) builds the same raw-route mappings and gathers them through the lens
+  (``resampleGather`` / ``resampleGatherMLatMLT``): the uncorrected image is interpolated once, no corrected image is made.
 """
 from __future__ import print_function
 
@@ -140,9 +142,11 @@ def getParser():
                           help='lensfun distortion model of the frames')
     lensArgs.add_argument('--lens-params', dest='lensParams', metavar='P', type=float, nargs='+',
                           help='its coefficients: k1 (poly3), k1 k2 (poly5) or a b c (ptlens)')
-    lensArgs.add_argument('--lens-route', dest='lensRoute', choices=['resample', 'raw'], default='resample',
+    lensArgs.add_argument('--lens-route', dest='lensRoute', choices=['resample', 'raw', 'fused'], default='resample',
                           help='resample: correct (Lanczos-4) and crop every image on the GPU first, default; raw: map the '
-                               'uncorrected pixels themselves, nothing interpolated')
+                               'uncorrected pixels themselves, nothing interpolated; fused (only with --gather): gather through '
+                               'the lens - the grid\'s cell centres go through the camera model and the lens model into the '
+                               'uncorrected image, which is interpolated once')
     lensArgs.add_argument('--crop-divisible-by', dest='cropDivisibleBy', metavar='N', type=int,
                           help='the .wcs files belong to the corrected image cropped to the next smaller width and height '
                                'divisible by N (16 for the ESA ISS archive); default: not cropped')
@@ -202,7 +206,8 @@ def parseargs(argv=None):
         if args.statistic != 'mean':
             parser.error('--gather takes the place of binning: not with --statistic %s' % args.statistic)
         if args.lensRoute == 'raw':
-            parser.error('--gather needs the inverse of the camera model, which --lens-route raw does not have')
+            parser.error('--gather needs the inverse of the camera model, which --lens-route raw does not have '
+                         '(--lens-route fused gathers through the lens)')
         if args.supersample is None:
             args.supersample = 1
         if not 1 <= args.supersample <= 8:
@@ -212,6 +217,8 @@ def parseargs(argv=None):
                 parser.error('--min-coverage goes with --supersample above 1: one point is sampled per cell')
             if not 0.0 < args.minCoverage <= 1.0:
                 parser.error('--min-coverage must be in the range (0, 1] with --gather')
+    if args.lensRoute == 'fused' and not args.gather:
+        parser.error('--lens-route fused needs --gather: it is the gather that goes through the lens')
     if (args.lensModel is None) != (args.lensParams is None):
         parser.error('--lens-model and --lens-params go together')
     if args.lensModel is not None:
@@ -353,7 +360,8 @@ def convert_with_classes(args, frames, export):
             continue
         img = read_image(img_path)
         mapping = getMapping(img, hdr, altitude=args.altitude, fastCenterCalculation=not args.exactCenters, identifier=identifier,
-                             lens=lens_of(args, hdr, metadata, img.shape[1], img.shape[0]), lensRoute=args.lensRoute)
+                             lens=lens_of(args, hdr, metadata, img.shape[1], img.shape[0]),
+                             lensRoute='raw' if args.lensRoute == 'fused' else args.lensRoute)     # (fused: a raw-route mapping, gathered)
         if args.resample:
             if args.minElevation >= 0:
                 mapping = mapping.maskedByElevation(args.minElevation)
@@ -559,7 +567,7 @@ def main(argv=None):
     # resampling runs that way too: the reference's flow frame by frame, for A/B runs)
     # (the raw lens route maps through direction arrays, which the sequence pipeline's runner does not take)
     metadata = read_metadata(args.data)
-    raw_route = args.lensRoute == 'raw' and any(lens_spec(args, hdr, metadata) for _, hdr, _ in frames)
+    raw_route = args.lensRoute in ('raw', 'fused') and any(lens_spec(args, hdr, metadata) for _, hdr, _ in frames)
     if args.resample and not raw_route and not os.environ.get('AMT_CONVERT_CLASSES'):
         convert_with_pipeline(args, frames, export)
     else:

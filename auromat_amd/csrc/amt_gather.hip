@@ -12,6 +12,15 @@
 // The member table (w2p_consts + w2p_sip + pointers per member) lies in the context's workspace; the member loop is uniform over
 // the block, so the table is read through scalar loads.
 //
+// A member with a lens (the _lens entry points) is a raw frame that still carries its lens distortion: in elect() its (x, y) of
+// the corrected frame goes on through step 9 (w2p_lens_step, amt_w2p.h: the arithmetic of amt_grid_to_pixel_lens) into the raw
+// frame before the support test, and everything downstream works on the raw coordinates and the raw image.  The lenses (w2p_lens)
+// are a table of their own behind the member table, and a launch without any lens has no such table.  Every kernel is compiled
+// with and without step 9 (the template argument LENS of the one source: 72 instantiations of the 36); the host takes the one with
+// it only where the launch has a lens table, so a launch without lenses runs the code it ran before step 9 existed.  With a table,
+// "this member has a lens" is the same for the whole block; the lens constants are read, through scalar loads, inside that branch
+// alone.
+//
 // The supersampled form (amt_gather_mosaic_supersampled) runs the same steps — load_points, elect, survey, stage_window,
 // sample_point below are the one code of both kernels — on the n x n sub-sample points of T x T cells, T = 32 / n, laid over the
 // same 32 x 32 threads' points, and then reduces the points to cells through LDS (k_gather_mosaic_ss).
@@ -55,6 +64,9 @@ struct gather_args {
     int32_t* source;
     double* xy;
     uint8_t* tile_path;
+    // (last: the arguments before it lie where they lay without it)  One per member, or NULL: no member has a lens; a member's
+    // img and center_mask are the raw frame's, K.width x K.height, where its lens is not of kind AMT_LENS_NONE
+    const w2p_lens* __restrict__ lenses;
 };
 
 // the supersampled call: G.ny, G.nx count cells, the coordinate arrays of G hold the factor x factor sub-sample points of each
@@ -113,7 +125,8 @@ __device__ __forceinline__ void load_points(const gather_args& A, int X, bool x_
 }
 
 // ---- election: the running best per point ----------------------------------------------------------------------------
-template <int N>
+// LENS: some member of the launch has a lens (A.lenses is not NULL); without, step 9 is not part of the kernel
+template <int N, bool LENS>
 __device__ __forceinline__ void elect(const gather_args& A, const gather_points& P, gather_best& B) {
 #pragma unroll
     for (int k = 0; k < kRowsPerThread; ++k) B.m[k] = -1, B.x[k] = B.y[k] = B.e[k] = NAN;
@@ -127,7 +140,10 @@ __device__ __forceinline__ void elect(const gather_args& A, const gather_points&
             if (A.rule == 0 && B.m[k] >= 0) continue;       // the first member that sees the point keeps it
             const lat_terms Tm = A.same_ellipsoid ? P.T[k] : w2p_lat_terms(M.K, P.lat[k]);
             double x, y, e;
-            bool seen = w2p_point(M.K, M.S, Tm, P.L[k], x, y, e) == 0;
+            unsigned fl = w2p_point(M.K, M.S, Tm, P.L[k], x, y, e);
+            // a raw frame with its lens: (x, y) goes on through the lens into the raw frame (wave-uniform: M is the block's)
+            if (LENS && A.lenses[m].m.kind != AMT_LENS_NONE) fl = w2p_lens_step(A.lenses[m], w, h, fl, x, y);
+            bool seen = fl == 0;
             if (N != 0) {
                 // support, as k_remap evaluates it on the float32 coordinates it is given
                 const double xs = (double)(float)x, ys = (double)(float)y;
@@ -234,7 +250,7 @@ __device__ __forceinline__ void sample_point(const gather_args& A, const gather_
 
 // A block's work on the tile (bx, by) of A's grid; `tile` = by * tiles_x + bx.  k_gather_mosaic runs it on its own block index,
 // k_gather_frames (below) on the tile of the job that the block has looked up.
-template <typename T, int N>
+template <typename T, int N, bool LENS>
 __device__ __forceinline__ void gather_tile_body(const gather_args& A, int bx, int by, int tile, T* win, int (&fold)[4][6]) {
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int X = bx * kTile + tx;
@@ -248,7 +264,7 @@ __device__ __forceinline__ void gather_tile_body(const gather_args& A, int bx, i
     gather_best B;
     gather_taps t;
     load_points(A, X, X < A.nx, Y, y_in, A.nx, P);
-    elect<N>(A, P, B);
+    elect<N, LENS>(A, P, B);
     const gather_tile W = survey<N>(A, B, t, fold, tile);
     if (W.staged) stage_window<T>(A, W, win);
 
@@ -270,11 +286,11 @@ __device__ __forceinline__ void gather_tile_body(const gather_args& A, int bx, i
     }
 }
 
-template <typename T, int N>
+template <typename T, int N, bool LENS>
 __global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
     extern __shared__ __align__(16) unsigned char gather_smem[];
     __shared__ int fold[4][6];
-    gather_tile_body<T, N>(A, (int)blockIdx.x, (int)blockIdx.y, (int)(blockIdx.y * gridDim.x + blockIdx.x),
+    gather_tile_body<T, N, LENS>(A, (int)blockIdx.x, (int)blockIdx.y, (int)(blockIdx.y * gridDim.x + blockIdx.x),
                            reinterpret_cast<T*>(gather_smem), fold);
 }
 
@@ -287,7 +303,7 @@ __global__ __launch_bounds__(256) void k_gather_mosaic(gather_args A) {
 constexpr int kPoints = kTile * kTile;
 constexpr int kHeadMin = kPoints * (int)(sizeof(double) + sizeof(int));      // the elevations and winners of the block's points
 
-template <typename T, int N>
+template <typename T, int N, bool LENS>
 __device__ __forceinline__ void gather_ss_body(const gather_ss_args& S, int bx, int by, int tile, unsigned char* gather_smem,
                                                int (&fold)[4][6]) {
     const gather_args& A = S.G;
@@ -312,7 +328,7 @@ __device__ __forceinline__ void gather_ss_body(const gather_ss_args& S, int bx, 
     gather_best B;
     gather_taps t;
     load_points(A, X, tx < span && X < A.nx * n, Y, y_in, (int64_t)A.nx * n, P);
-    elect<N>(A, P, B);
+    elect<N, LENS>(A, P, B);
     const gather_tile W = survey<N>(A, B, t, fold, tile);
     if (W.staged) stage_window<T>(A, W, win);
 
@@ -398,11 +414,11 @@ __device__ __forceinline__ void gather_ss_body(const gather_ss_args& S, int bx, 
     }
 }
 
-template <typename T, int N>
+template <typename T, int N, bool LENS>
 __global__ __launch_bounds__(256) void k_gather_mosaic_ss(gather_ss_args S) {
     extern __shared__ __align__(16) unsigned char gather_smem[];
     __shared__ int fold[4][6];
-    gather_ss_body<T, N>(S, (int)blockIdx.x, (int)blockIdx.y, (int)(blockIdx.y * gridDim.x + blockIdx.x), gather_smem, fold);
+    gather_ss_body<T, N, LENS>(S, (int)blockIdx.x, (int)blockIdx.y, (int)(blockIdx.y * gridDim.x + blockIdx.x), gather_smem, fold);
 }
 
 // ---- a batch of frames (amt_gather_frames): one launch over the tiles of all jobs -----------------------------------------------
@@ -426,9 +442,10 @@ struct gather_frames_args {
     int n_jobs, C, force, factor;
     int min_count, head;
     uint8_t* tile_path;         // the jobs' tiles one job after the other
+    const w2p_lens* __restrict__ lenses;    // (last, as in gather_args) one per job, or NULL
 };
 
-template <typename T, int N, bool SS>
+template <typename T, int N, bool SS, bool LENS>
 __global__ __launch_bounds__(256) void k_gather_frames(gather_frames_args F) {
     extern __shared__ __align__(16) unsigned char gather_smem[];
     __shared__ int fold[4][6];
@@ -449,6 +466,7 @@ __global__ __launch_bounds__(256) void k_gather_frames(gather_frames_args F) {
     gather_ss_args S;
     gather_args& A = S.G;
     A.members = &J.M;
+    A.lenses = LENS ? F.lenses + lo : nullptr;
     A.lat = J.lat, A.lon = J.lon, A.cell_lat = J.cell_lat, A.cell_lon = J.cell_lon;
     A.n = 1, A.ny = J.ny, A.nx = J.nx, A.C = F.C;
     A.rule = 1, A.same_ellipsoid = 1, A.force = F.force, A.pad_ = 0;
@@ -457,9 +475,9 @@ __global__ __launch_bounds__(256) void k_gather_frames(gather_frames_args F) {
     if (SS) {
         S.factor = F.factor, S.min_count = F.min_count, S.head = F.head, S.pad_ = 0;
         S.count = J.count;
-        gather_ss_body<T, N>(S, bx, by, tile, gather_smem, fold);
+        gather_ss_body<T, N, LENS>(S, bx, by, tile, gather_smem, fold);
     } else {
-        gather_tile_body<T, N>(A, bx, by, tile, reinterpret_cast<T*>(gather_smem), fold);
+        gather_tile_body<T, N, LENS>(A, bx, by, tile, reinterpret_cast<T*>(gather_smem), fold);
     }
 }
 
@@ -504,7 +522,11 @@ void launch_gather(amt_ctx* ctx, const gather_args& A, int sample_bytes, int int
         using T = decltype(t);
         int head;
         const size_t lds = gather_lds<T>(A.C, interpolation, false, head);
-        hipLaunchKernelGGL((k_gather_mosaic<T, decltype(taps)::value>), grid, dim3(256), lds, ctx->stream, A);
+        constexpr int N = decltype(taps)::value;
+        if (A.lenses)
+            hipLaunchKernelGGL((k_gather_mosaic<T, N, true>), grid, dim3(256), lds, ctx->stream, A);
+        else
+            hipLaunchKernelGGL((k_gather_mosaic<T, N, false>), grid, dim3(256), lds, ctx->stream, A);
     });
 }
 
@@ -514,7 +536,11 @@ void launch_gather_ss(amt_ctx* ctx, gather_ss_args S, int sample_bytes, int inte
     gather_dispatch(sample_bytes, interpolation, [&](auto t, auto taps) {
         using T = decltype(t);
         const size_t lds = gather_lds<T>(S.G.C, interpolation, true, S.head);
-        hipLaunchKernelGGL((k_gather_mosaic_ss<T, decltype(taps)::value>), grid, dim3(256), lds, ctx->stream, S);
+        constexpr int N = decltype(taps)::value;
+        if (S.G.lenses)
+            hipLaunchKernelGGL((k_gather_mosaic_ss<T, N, true>), grid, dim3(256), lds, ctx->stream, S);
+        else
+            hipLaunchKernelGGL((k_gather_mosaic_ss<T, N, false>), grid, dim3(256), lds, ctx->stream, S);
     });
 }
 
@@ -525,10 +551,14 @@ void launch_gather_frames(amt_ctx* ctx, gather_frames_args F, int tiles, int sam
         constexpr int N = decltype(taps)::value;
         const bool ss = F.factor > 1;
         const size_t lds = gather_lds<T>(F.C, interpolation, ss, F.head);
-        if (ss)
-            hipLaunchKernelGGL((k_gather_frames<T, N, true>), grid, dim3(256), lds, ctx->stream, F);
+        if (ss && F.lenses)
+            hipLaunchKernelGGL((k_gather_frames<T, N, true, true>), grid, dim3(256), lds, ctx->stream, F);
+        else if (ss)
+            hipLaunchKernelGGL((k_gather_frames<T, N, true, false>), grid, dim3(256), lds, ctx->stream, F);
+        else if (F.lenses)
+            hipLaunchKernelGGL((k_gather_frames<T, N, false, true>), grid, dim3(256), lds, ctx->stream, F);
         else
-            hipLaunchKernelGGL((k_gather_frames<T, N, false>), grid, dim3(256), lds, ctx->stream, F);
+            hipLaunchKernelGGL((k_gather_frames<T, N, false, false>), grid, dim3(256), lds, ctx->stream, F);
     });
 }
 
@@ -577,9 +607,11 @@ int gather_coordinates(amt_ctx* ctx, const char* fn, const std::string& job, con
     return AMT_OK;
 }
 
-// a member as the kernels read it: w2p_prepare's message, or "member without image", or NULL
-const char* gather_member(const amt_gather_member& m, int32_t frame, gather_dev& d) {
+// a member as the kernels read it: w2p_prepare's or w2p_lens_prepare's message, or "member without image", or NULL
+// (Ln: NULL where the call has no lenses at all)
+const char* gather_member(const amt_gather_member& m, const amt_lens_model* lens, int32_t frame, gather_dev& d, w2p_lens* Ln) {
     const char* err = m.img ? w2p_prepare(&m.params, m.zenithal, frame, &d.K, &d.S) : "member without image";
+    if (err == nullptr && Ln) err = w2p_lens_prepare(lens, &m.params, m.zenithal, Ln);
     d.img = m.img;
     d.center_mask = m.center_mask;
     d.min_elevation = m.min_elevation > -INFINITY ? m.min_elevation : (double)NAN;      // (-inf and NaN: none)
@@ -588,7 +620,8 @@ const char* gather_member(const amt_gather_member& m, int32_t frame, gather_dev&
 
 // what both mosaic entry points check and prepare: the arguments they share, the member table in the context's workspace, and the
 // kernel's arguments for a grid of ny x nx cells (the supersampled call adds its own)
-int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* members, int32_t n_members, int32_t frame, const double* lat_axis,
+int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* members, const amt_lens_model* const* lenses,
+                   int32_t n_members, int32_t frame, const double* lat_axis,
                    int32_t ny, const double* lon_axis, int32_t nx, const double* cell_lat, const double* cell_lon, int32_t sample_bytes,
                    int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev,
                    int32_t* out_source, const amt_gather_debug* debug, gather_args& A) {
@@ -599,29 +632,35 @@ int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* member
     if (rc == AMT_OK) rc = gather_check(ctx, fn, frame, interpolation, rule, sample_bytes, channels, debug);
     if (rc != AMT_OK) return rc;
 
-    std::vector<gather_dev> dev((size_t)n_members);
-    bool same = true;
+    // the member table and, where a member has a lens, the lens table behind it, in one staging buffer: one copy
+    const size_t lens_at = (size_t)n_members * sizeof(gather_dev);
+    std::vector<unsigned char> staged(lens_at + (lenses ? (size_t)n_members * sizeof(w2p_lens) : 0));
+    gather_dev* dev = reinterpret_cast<gather_dev*>(staged.data());
+    w2p_lens* lens = reinterpret_cast<w2p_lens*>(staged.data() + lens_at);
+    bool same = true, any_lens = false;
     for (int32_t i = 0; i < n_members; ++i) {
-        gather_dev& d = dev[(size_t)i];
-        const char* err = gather_member(members[i], frame, d);
+        gather_dev& d = dev[i];
+        const char* err = gather_member(members[i], lenses ? lenses[i] : nullptr, frame, d, lenses ? &lens[i] : nullptr);
         GATHER_REQUIRE(err == nullptr, "member " + std::to_string(i) + ": " + err);
         same = same && d.K.a0 == dev[0].K.a0 && d.K.e2 == dev[0].K.e2;
+        any_lens = any_lens || (lenses && lens[i].m.kind != AMT_LENS_NONE);
     }
     if (amt_set_device(ctx)) return AMT_EHIP;
-    const size_t bytes = dev.size() * sizeof(gather_dev);
+    const size_t bytes = any_lens ? staged.size() : lens_at;
     char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
     if (ws == nullptr) {
         ctx->last_error = std::string(fn) + ": workspace allocation failed";
         return AMT_ENOMEM;
     }
     // (pageable source: the copy has consumed the staging buffer when the call returns)
-    const hipError_t err = hipMemcpyAsync(ws, dev.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    const hipError_t err = hipMemcpyAsync(ws, staged.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
     if (err != hipSuccess) {
         ctx->last_error = std::string(fn) + ": hipMemcpyAsync -> " + hipGetErrorString(err);
         return AMT_EHIP;
     }
 
     A.members = reinterpret_cast<const gather_dev*>(ws);
+    A.lenses = any_lens ? reinterpret_cast<const w2p_lens*>(ws + lens_at) : nullptr;
     A.n = n_members, A.ny = ny, A.nx = nx, A.C = channels;
     A.rule = rule, A.same_ellipsoid = same ? 1 : 0, A.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, A.pad_ = 0;
     A.img = out_img, A.mask = out_mask, A.elev = out_elev, A.source = out_source, A.xy = nullptr;
@@ -631,18 +670,60 @@ int gather_prepare(amt_ctx* ctx, const char* fn, const amt_gather_member* member
 
 }  // namespace
 
+// The three entry points with and without lenses: `fn` is the name the caller knows, for the error texts.
+static int gather_mosaic_call(amt_ctx* ctx, const char* fn, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                              const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx, const double* cell_lat,
+                              const double* cell_lon, int32_t sample_bytes, int32_t channels, int32_t interpolation, int32_t rule,
+                              void* out_img, uint8_t* out_mask, double* out_elev, int32_t* out_source, double* out_xy,
+                              const amt_gather_debug* debug, const amt_lens_model* const* lenses) {
+    AMT_CHECK_CTX(ctx);
+    gather_args A;
+    const int rc = gather_prepare(ctx, fn, members, lenses, n_members, frame, lat_centres, ny, lon_centres, nx, cell_lat, cell_lon,
+                                  sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, A);
+    if (rc != AMT_OK) return rc;
+    A.xy = out_xy;
+    launch_gather(ctx, A, sample_bytes, interpolation);
+    AMT_LAUNCH_CHECK(ctx);
+    return AMT_OK;
+}
+
 extern "C" int amt_gather_mosaic(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame,
                                  const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx,
                                  const double* cell_lat, const double* cell_lon, int32_t sample_bytes, int32_t channels,
                                  int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev,
                                  int32_t* out_source, double* out_xy, const amt_gather_debug* debug) {
+    return gather_mosaic_call(ctx, __func__, members, n_members, frame, lat_centres, ny, lon_centres, nx, cell_lat, cell_lon, sample_bytes,
+                              channels, interpolation, rule, out_img, out_mask, out_elev, out_source, out_xy, debug, nullptr);
+}
+
+extern "C" int amt_gather_mosaic_lens(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                                      const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx,
+                                      const double* cell_lat, const double* cell_lon, int32_t sample_bytes, int32_t channels,
+                                      int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev,
+                                      int32_t* out_source, double* out_xy, const amt_gather_debug* debug,
+                                      const amt_lens_model* const* lenses) {
+    return gather_mosaic_call(ctx, __func__, members, n_members, frame, lat_centres, ny, lon_centres, nx, cell_lat, cell_lon, sample_bytes,
+                              channels, interpolation, rule, out_img, out_mask, out_elev, out_source, out_xy, debug, lenses);
+}
+
+static int gather_supersampled_call(amt_ctx* ctx, const char* fn, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                                    const double* sub_lat, int32_t ny, const double* sub_lon, int32_t nx, const double* sub_cell_lat,
+                                    const double* sub_cell_lon, int32_t factor, int32_t min_count, int32_t sample_bytes,
+                                    int32_t channels, int32_t interpolation, int32_t rule, void* out_img, uint8_t* out_mask,
+                                    double* out_elev, int32_t* out_source, uint8_t* out_count, const amt_gather_debug* debug,
+                                    const amt_lens_model* const* lenses) {
     AMT_CHECK_CTX(ctx);
-    gather_args A;
-    const int rc = gather_prepare(ctx, __func__, members, n_members, frame, lat_centres, ny, lon_centres, nx, cell_lat, cell_lon,
-                                  sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, A);
+    GATHER_REQUIRE(out_count, "NULL argument");
+    gather_ss_args S;
+    int rc = gather_check_factor(ctx, fn, factor, min_count);
+    if (rc == AMT_OK) rc = gather_check_subgrid(ctx, fn, "", ny, nx, factor);
+    if (rc == AMT_OK)
+        rc = gather_prepare(ctx, fn, members, lenses, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon, sample_bytes,
+                            channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, S.G);
     if (rc != AMT_OK) return rc;
-    A.xy = out_xy;
-    launch_gather(ctx, A, sample_bytes, interpolation);
+    S.factor = factor, S.min_count = min_count, S.head = 0, S.pad_ = 0;
+    S.count = out_count;
+    launch_gather_ss(ctx, S, sample_bytes, interpolation);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
 }
@@ -653,27 +734,29 @@ extern "C" int amt_gather_mosaic_supersampled(amt_ctx* ctx, const amt_gather_mem
                                               int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
                                               int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev, int32_t* out_source,
                                               uint8_t* out_count, const amt_gather_debug* debug) {
-    AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, out_count, "NULL argument");
-    gather_ss_args S;
-    int rc = gather_check_factor(ctx, __func__, factor, min_count);
-    if (rc == AMT_OK) rc = gather_check_subgrid(ctx, __func__, "", ny, nx, factor);
-    if (rc == AMT_OK)
-        rc = gather_prepare(ctx, __func__, members, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon, sample_bytes,
-                            channels, interpolation, rule, out_img, out_mask, out_elev, out_source, debug, S.G);
-    if (rc != AMT_OK) return rc;
-    S.factor = factor, S.min_count = min_count, S.head = 0, S.pad_ = 0;
-    S.count = out_count;
-    launch_gather_ss(ctx, S, sample_bytes, interpolation);
-    AMT_LAUNCH_CHECK(ctx);
-    return AMT_OK;
+    return gather_supersampled_call(ctx, __func__, members, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon, factor,
+                                    min_count, sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source,
+                                    out_count, debug, nullptr);
 }
 
-extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor,
-                                 int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
-                                 const amt_gather_debug* debug) {
+extern "C" int amt_gather_mosaic_supersampled_lens(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                                                   const double* sub_lat, int32_t ny, const double* sub_lon, int32_t nx,
+                                                   const double* sub_cell_lat, const double* sub_cell_lon, int32_t factor,
+                                                   int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
+                                                   int32_t rule, void* out_img, uint8_t* out_mask, double* out_elev,
+                                                   int32_t* out_source, uint8_t* out_count, const amt_gather_debug* debug,
+                                                   const amt_lens_model* const* lenses) {
+    return gather_supersampled_call(ctx, __func__, members, n_members, frame, sub_lat, ny, sub_lon, nx, sub_cell_lat, sub_cell_lon, factor,
+                                    min_count, sample_bytes, channels, interpolation, rule, out_img, out_mask, out_elev, out_source,
+                                    out_count, debug, lenses);
+}
+
+// The body of both entry points is an overload of the older one's name, not a gather_frames_call: the registry of scratch-memory
+// users (tests/_scratch_cases.py, tests/test_scratch_cases_cpu.py) knows the call of amt_workspace below as amt_gather_frames'.
+static int amt_gather_frames(amt_ctx* ctx, const char* fn, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor,
+                             int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
+                             const amt_gather_debug* debug, const amt_lens_model* const* lenses) {
     AMT_CHECK_CTX(ctx);
-    const char* fn = __func__;
     GATHER_REQUIRE(jobs, "NULL argument");
     GATHER_REQUIRE(n_jobs >= 1 && n_jobs <= AMT_GATHER_MAX_JOBS, "n_jobs must be 1 ... " + std::to_string(AMT_GATHER_MAX_JOBS));
     int rc = gather_check(ctx, fn, frame, interpolation, 1, sample_bytes, channels, debug);
@@ -682,9 +765,12 @@ extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32
 
     // the prefix table of tile counts, then the jobs, in one staging buffer: one copy
     const size_t jobs_at = (((size_t)n_jobs + 1) * sizeof(int) + 15) & ~(size_t)15;
-    std::vector<unsigned char> staged(jobs_at + (size_t)n_jobs * sizeof(gather_job_dev));
+    const size_t lens_at = jobs_at + (size_t)n_jobs * sizeof(gather_job_dev);      // (a multiple of 8: the structs hold doubles)
+    std::vector<unsigned char> staged(lens_at + (lenses ? (size_t)n_jobs * sizeof(w2p_lens) : 0));
     int* first = reinterpret_cast<int*>(staged.data());
     gather_job_dev* dev = reinterpret_cast<gather_job_dev*>(staged.data() + jobs_at);
+    w2p_lens* lens = reinterpret_cast<w2p_lens*>(staged.data() + lens_at);
+    bool any_lens = false;
     const int Tc = kTile / factor;          // cells per tile side
     int64_t tiles = 0;
     for (int32_t k = 0; k < n_jobs; ++k) {
@@ -697,8 +783,9 @@ extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32
         rc = gather_check_subgrid(ctx, fn, job, j.ny, j.nx, factor);
         if (rc == AMT_OK) rc = gather_coordinates(ctx, fn, job, j.lat, j.lon, j.cell_lat, j.cell_lon, d);
         if (rc != AMT_OK) return rc;
-        const char* err = gather_member(j.member, frame, d.M);
+        const char* err = gather_member(j.member, lenses ? lenses[k] : nullptr, frame, d.M, lenses ? &lens[k] : nullptr);
         GATHER_REQUIRE(err == nullptr, job + err);
+        any_lens = any_lens || (lenses && lens[k].m.kind != AMT_LENS_NONE);
         d.img = j.out_img, d.mask = j.out_mask, d.elev = j.out_elev, d.count = factor > 1 ? j.out_count : nullptr;
         d.ny = j.ny, d.nx = j.nx, d.tiles_x = (j.nx + Tc - 1) / Tc, d.pad_ = 0;
         first[k] = (int)tiles;
@@ -708,21 +795,35 @@ extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32
     first[n_jobs] = (int)tiles;
 
     if (amt_set_device(ctx)) return AMT_EHIP;
-    char* ws = static_cast<char*>(amt_workspace(ctx, staged.size()));
+    const size_t bytes = any_lens ? staged.size() : lens_at;      // (without a lens: the parent's buffer)
+    char* ws = static_cast<char*>(amt_workspace(ctx, bytes));
     if (ws == nullptr) {
         ctx->last_error = std::string(fn) + ": workspace allocation failed";
         return AMT_ENOMEM;
     }
     // (pageable source: the copy has consumed the staging buffer when the call returns)
-    AMT_HIP(ctx, hipMemcpyAsync(ws, staged.data(), staged.size(), hipMemcpyHostToDevice, ctx->stream));
+    AMT_HIP(ctx, hipMemcpyAsync(ws, staged.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
 
     gather_frames_args F;
     F.first = reinterpret_cast<const int*>(ws);
     F.jobs = reinterpret_cast<const gather_job_dev*>(ws + jobs_at);
+    F.lenses = any_lens ? reinterpret_cast<const w2p_lens*>(ws + lens_at) : nullptr;
     F.n_jobs = n_jobs, F.C = channels, F.force = debug ? debug->force_path : AMT_GATHER_PATH_AUTO, F.factor = factor;
     F.min_count = min_count, F.head = 0;
     F.tile_path = debug ? debug->tile_path : nullptr;
     launch_gather_frames(ctx, F, (int)tiles, sample_bytes, interpolation);
     AMT_LAUNCH_CHECK(ctx);
     return AMT_OK;
+}
+
+extern "C" int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor,
+                                 int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
+                                 const amt_gather_debug* debug) {
+    return amt_gather_frames(ctx, __func__, jobs, n_jobs, frame, factor, min_count, sample_bytes, channels, interpolation, debug, nullptr);
+}
+
+extern "C" int amt_gather_frames_lens(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor,
+                                      int32_t min_count, int32_t sample_bytes, int32_t channels, int32_t interpolation,
+                                      const amt_gather_debug* debug, const amt_lens_model* const* lenses) {
+    return amt_gather_frames(ctx, __func__, jobs, n_jobs, frame, factor, min_count, sample_bytes, channels, interpolation, debug, lenses);
 }

@@ -12,100 +12,12 @@
 // extreme coefficients, an arbitrary coordinate array) takes its taps from global memory with a bounds test each.  Both ways go
 // through the same sampling function with the same operands in the same order, so they give the same bits.
 #include "amt_common.h"
+#include "amt_lens.h"       // the models' constants and per-coordinate functions: shared with amt_w2p.h
 #include "amt_remap.h"      // the tiling, tap_weights, the two fetches and sample: shared with amt_gather.hip
 
 namespace {
 
 using namespace amt;
-
-struct lens_dev {
-    int kind, crop_x, crop_y, pad_;
-    double k0, k1, k2;
-    double cx, cy, norm;
-};
-
-inline lens_dev make_lens(const amt_lens_model* m) {
-    lens_dev d;
-    d.kind = m->kind;
-    d.crop_x = m->crop_x, d.crop_y = m->crop_y, d.pad_ = 0;
-    d.k0 = m->k[0], d.k1 = m->k[1], d.k2 = m->k[2];
-    d.cx = (m->width - 1) / 2.0;
-    d.cy = (m->height - 1) / 2.0;
-    const int side = (m->width < m->height ? m->width : m->height) - 1;
-    d.norm = 2.0 / (side < 1 ? 1 : side);      // (a frame one pixel wide has no half side: radius in pixels)
-    return d;
-}
-
-// g(r) of the model, from r^2; every operation spelled out so that the NumPy statement can follow it step by step
-__device__ __forceinline__ double lens_g(const lens_dev& m, double r2) {
-#pragma clang fp contract(off)
-    switch (m.kind) {
-        case AMT_LENS_POLY3: return (1.0 - m.k0) + m.k0 * r2;
-        case AMT_LENS_POLY5: return (1.0 + m.k0 * r2) + m.k1 * (r2 * r2);
-        case AMT_LENS_PTLENS: {
-            const double r = sqrt(r2);
-            return ((m.k0 * (r2 * r) + m.k1 * r2) + m.k2 * r) + (((1.0 - m.k0) - m.k1) - m.k2);
-        }
-        default: return 1.0;
-    }
-}
-
-// d(r g(r)) / dr
-__device__ __forceinline__ double lens_slope(const lens_dev& m, double r) {
-#pragma clang fp contract(off)
-    const double r2 = r * r;
-    switch (m.kind) {
-        case AMT_LENS_POLY3: return (1.0 - m.k0) + (3.0 * m.k0) * r2;
-        case AMT_LENS_POLY5: return (1.0 + (3.0 * m.k0) * r2) + (5.0 * m.k1) * (r2 * r2);
-        case AMT_LENS_PTLENS:
-            return (((4.0 * m.k0) * (r2 * r) + (3.0 * m.k1) * r2) + (2.0 * m.k2) * r) + (((1.0 - m.k0) - m.k1) - m.k2);
-        default: return 1.0;
-    }
-}
-
-// corrected full-frame coordinate (X, Y) -> where to sample the raw frame
-__device__ __forceinline__ void lens_forward(const lens_dev& m, double X, double Y, double& xs, double& ys) {
-#pragma clang fp contract(off)
-    const double u = (X - m.cx) * m.norm, v = (Y - m.cy) * m.norm;
-    const double g = lens_g(m, u * u + v * v);
-    // (a n) / n need not round back to a: a factor of exactly 1 returns the pixel's own coordinate
-    const bool same = g == 1.0;
-    xs = same ? X : m.cx + (u * g) / m.norm;
-    ys = same ? Y : m.cy + (v * g) / m.norm;
-}
-
-constexpr int kNewtonCap = 24;
-
-// raw coordinate -> corrected full-frame coordinate: ru with ru g(ru) = rd by Newton's method from ru = rd.  NaN where the
-// slope d(ru g)/dru is not positive on the way (the model folds over), where kNewtonCap steps do not converge, and for NaN input
-__device__ __forceinline__ void lens_inverse(const lens_dev& m, double x, double y, double& X, double& Y) {
-#pragma clang fp contract(off)
-    const double u = (x - m.cx) * m.norm, v = (y - m.cy) * m.norm;
-    const double rd = sqrt(u * u + v * v);
-    if (rd == 0.0) {
-        // the centre maps to itself whatever the model, unless a coefficient is NaN
-        const bool bad = lens_g(m, 0.0) != lens_g(m, 0.0);
-        X = bad ? NAN : m.cx, Y = bad ? NAN : m.cy;
-        return;
-    }
-    double ru = rd;
-    bool ok = false;
-    for (int it = 0; it < kNewtonCap; ++it) {
-        const double slope = lens_slope(m, ru);
-        if (!(slope > 0.0)) break;
-        const double step = (ru * lens_g(m, ru * ru) - rd) / slope;
-        ru = ru - step;
-        if (!(ru > 0.0)) break;
-        if (fabs(step) <= 1e-13 * ru) {
-            ok = lens_slope(m, ru) > 0.0;
-            break;
-        }
-    }
-    const double s = ok ? ru / rd : NAN;
-    const bool same = s == 1.0;             // as in lens_forward
-    X = same ? x : m.cx + (u * s) / m.norm;
-    Y = same ? y : m.cy + (v * s) / m.norm;
-}
 
 template <bool INVERSE>
 __global__ __launch_bounds__(256) void k_lens_coords(lens_dev m, double x0, double y0, int cols, double* __restrict__ out,
@@ -261,16 +173,9 @@ int launch_remap(amt_ctx* ctx, const Coord& coord, const void* src, int sw, int 
     }
 }
 
-bool model_ok(const amt_lens_model* m) {
-    if (m == nullptr || m->kind < AMT_LENS_NONE || m->kind > AMT_LENS_PTLENS || m->width <= 0 || m->height <= 0) return false;
-    if (m->crop_width == 0 && m->crop_height == 0) return m->crop_x == 0 && m->crop_y == 0;
-    return m->crop_width > 0 && m->crop_height > 0 && m->crop_x >= 0 && m->crop_y >= 0 && m->crop_x + m->crop_width <= m->width &&
-           m->crop_y + m->crop_height <= m->height;
-}
-
 int coords_call(amt_ctx* ctx, const amt_lens_model* model, int inverse, int32_t x0, int32_t y0, int32_t cols, int32_t rows, int corner,
                 double* out_xy, float* out_xy32) {
-    AMT_REQUIRE(ctx, model_ok(model), "bad lens model (kind, size or crop)");
+    AMT_REQUIRE(ctx, lens_model_ok(model), "bad lens model (kind, size or crop)");
     AMT_REQUIRE(ctx, out_xy != nullptr, "NULL argument");
     AMT_REQUIRE(ctx, cols >= 0 && rows >= 0, "negative size");
     const int c = corner ? 1 : 0;
@@ -305,7 +210,7 @@ int amt_lens_undistort(amt_ctx* ctx, const amt_lens_model* model, int32_t x0, in
 int amt_lens_remap(amt_ctx* ctx, const amt_lens_model* model, const void* src, int32_t sample_bytes, int32_t channels, int32_t interpolation,
                    void* dst, uint8_t* support, const amt_lens_debug* debug) {
     AMT_CHECK_CTX(ctx);
-    AMT_REQUIRE(ctx, model_ok(model), "bad lens model (kind, size or crop)");
+    AMT_REQUIRE(ctx, lens_model_ok(model), "bad lens model (kind, size or crop)");
     const model_coord coord = {make_lens(model)};
     const int dw = model->crop_width ? model->crop_width : model->width, dh = model->crop_height ? model->crop_height : model->height;
     return launch_remap(ctx, coord, src, model->width, model->height, sample_bytes, channels, interpolation, dst, dw, dh, support, debug);
@@ -319,6 +224,12 @@ int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t s
     const array_coord coord = {coords, dst_width};
     return launch_remap(ctx, coord, src, src_width, src_height, sample_bytes, channels, interpolation, dst, dst_width, dst_height, support,
                         debug);
+}
+
+int amt_lens_fold_radius(const amt_lens_model* model, double* out_r) {
+    if (model == nullptr || out_r == nullptr || model->kind < AMT_LENS_NONE || model->kind > AMT_LENS_PTLENS) return AMT_EINVAL;
+    *out_r = lens_fold_radius(*model);
+    return AMT_OK;
 }
 
 }  // extern "C"

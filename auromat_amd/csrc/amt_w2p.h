@@ -1,12 +1,16 @@
 // World -> pixel, the per-point arithmetic (include/auromat_hip.h, "inverse georeferencing", is the statement): the constants of a
 // frame prepared on the host (w2p_prepare) and one __device__ function per step.  Shared by the kernels of amt_inverse.hip (points
 // and grids to coordinate arrays) and amt_gather.hip (the fused gather mosaic), which must give identical bits for identical points.
+// Step 9, the lens of a raw frame applied after the camera model (w2p_lens, w2p_lens_step), is what its three callers add behind
+// w2p_point when a frame has a lens: k_world_to_pixel and k_grid_to_pixel of amt_inverse.hip (through w2p_point_lens) and elect()
+// of amt_gather.hip.
 #pragma once
 
 #include <cmath>
 #include <cstring>
 
 #include "amt_common.h"
+#include "amt_lens.h"
 
 // Every operation of the per-point arithmetic is rounded on its own (fused multiply-adds are written out where wanted): the
 // kernels must give identical bits for identical points whatever code surrounds the shared functions.  (At file scope: it holds
@@ -188,6 +192,55 @@ __device__ __forceinline__ unsigned w2p_point(const w2p_consts& K, const w2p_sip
     }
     if (!(x >= -0.5 && x <= K.width - 0.5 && y >= -0.5 && y <= K.height - 0.5)) flags |= AMT_W2P_OUTSIDE;
     return flags;
+}
+
+// ---- step 9: through the lens ----------------------------------------------------------------------------------------------
+// the constants of a frame's lens (kind AMT_LENS_NONE: the frame has none) and the square of the radius at which the model folds
+struct w2p_lens {
+    lens_dev m;
+    double fold2;       // r_fold^2: +inf where the model never folds, NaN with a NaN coefficient (no point is kept then)
+};
+
+// Step 9 for a point that w2p_point has placed at (x, y) of the cropped corrected frame with the flags `flags`: (x, y) becomes the
+// point of the raw frame, width x height, that lens_forward samples for it, and OUTSIDE is decided there.
+__device__ __forceinline__ unsigned w2p_lens_step(const w2p_lens& Ln, int width, int height, unsigned flags, double& x, double& y) {
+    if (!(x == x)) return flags;        // INVALID, UNPROJECTABLE, NOT_CONVERGED: no pixel to take through the lens
+    flags &= ~(unsigned)AMT_W2P_OUTSIDE;
+    const double Xf = x + (double)Ln.m.crop_x, Yf = y + (double)Ln.m.crop_y;
+    const double r2 = lens_r2(Ln.m, Xf, Yf);
+    const double g = lens_g(Ln.m, r2);
+    // the principal branch alone: beyond the fold the polynomial maps far-off points back into the frame
+    if (!(r2 < Ln.fold2) || !finite(g)) {
+        x = y = NAN;
+        return flags | AMT_W2P_LENS_FOLD;
+    }
+    lens_forward(Ln.m, Xf, Yf, x, y);
+    if (!(x >= -0.5 && x <= width - 0.5 && y >= -0.5 && y <= height - 0.5)) flags |= AMT_W2P_OUTSIDE;
+    return flags;
+}
+
+// Steps 1-9: w2p_point, then the lens where the frame has one (the same for every thread of a launch)
+__device__ __forceinline__ unsigned w2p_point_lens(const w2p_consts& K, const w2p_sip& S, const w2p_lens& Ln, const lat_terms& T,
+                                                   const lon_terms& L, double& x, double& y, double& elev) {
+    const unsigned flags = w2p_point(K, S, T, L, x, y, elev);
+    return Ln.m.kind == AMT_LENS_NONE ? flags : w2p_lens_step(Ln, K.width, K.height, flags, x, y);
+}
+
+// Host: a frame's lens as the kernels read it.  NULL or kind AMT_LENS_NONE: no lens.  `p`, `z`: the frame the lens belongs to, as
+// w2p_prepare takes them.  NULL: all is well.
+inline const char* w2p_lens_prepare(const amt_lens_model* lens, const amt_frame_params* p, const amt_zenithal_wcs* z, w2p_lens* L) {
+    std::memset(L, 0, sizeof(*L));
+    if (lens == nullptr || lens->kind == AMT_LENS_NONE) return nullptr;
+    if (lens->kind < AMT_LENS_NONE || lens->kind > AMT_LENS_PTLENS) return "unknown lens kind";
+    if (!(lens->width > 0 && lens->height > 0)) return "lens: empty raw frame";
+    if (!lens_model_ok(lens)) return "lens: the crop window does not lie in the corrected frame";
+    if (lens->width != p->width || lens->height != p->height) return "lens: the raw frame's size is not the params' width x height";
+    const int cw = lens->crop_width ? lens->crop_width : lens->width, ch = lens->crop_height ? lens->crop_height : lens->height;
+    if (z && (z->width != cw || z->height != ch)) return "lens: the corrected frame's size is not the camera model's (zenithal width x height)";
+    L->m = make_lens(lens);
+    const double r = lens_fold_radius(*lens);
+    L->fold2 = r * r;
+    return nullptr;
 }
 
 // Host: the argument checks shared by the entry points and the constants of the frame.  NULL: all is well.

@@ -317,11 +317,21 @@ class DirectionArrayMapping(BaseAstrometryMapping):
     """
 
     def __init__(self, cornerDirections, alti, img, cameraPosGCRS, photoTime, identifier, metadata=None, cameraHeader=None,
-                 noInverse=None):
+                 noInverse=None, cameraLens=None):
         """`cornerDirections`: (h + 1, w + 1, 3) array, or a float64 device tensor of that shape (e.g. from
         ``coordinates.wcs.zenithal_directions_device``), which is used where it lies.  `cameraHeader`: the zenithal (+ SIP)
         WCS header the directions were made from, if any; it is what ``latLonToPixel`` & co. invert.  `noInverse`: why they
-        cannot (a sentence), for directions that went through something else as well."""
+        cannot (a sentence), for directions that went through something else as well.  `cameraLens` (a
+        :class:`auromat_amd.util.lensdistortion.LensModifier`, only together with `cameraHeader`): the image is a raw frame of
+        the lens's size and the directions are those of its pixel corners taken through the lens's inverse into the header's
+        corrected (cropped) frame; ``latLonToPixel`` & co. then apply the lens after the camera model and answer in raw
+        pixels."""
+        if cameraLens is not None:
+            if cameraHeader is None:
+                raise ValueError('cameraLens= needs cameraHeader=: the lens is applied after the camera model of that header')
+            if (int(cameraHeader['IMAGEW']), int(cameraHeader['IMAGEH'])) != tuple(cameraLens.corrected_size):
+                raise ValueError('the header is for a %d x %d image, the lens corrects to %d x %d'
+                                 % ((cameraHeader['IMAGEW'], cameraHeader['IMAGEH']) + tuple(cameraLens.corrected_size)))
         img = np.asarray(img)
         on_device = hasattr(cornerDirections, 'is_cuda') and cornerDirections.is_cuda
         d = cornerDirections.contiguous() if on_device else np.ascontiguousarray(cornerDirections, dtype=np.float64)
@@ -335,6 +345,13 @@ class DirectionArrayMapping(BaseAstrometryMapping):
         self._img_array = img
         self._cameraHeader = cameraHeader
         self._noInverse = noInverse
+        self._cameraLens = cameraLens
+        if cameraLens is not None and (img.shape[1], img.shape[0]) != (cameraLens.width, cameraLens.height):
+            raise ValueError('the image is %d x %d, the lens is for a raw frame of %d x %d'
+                             % (img.shape[1], img.shape[0], cameraLens.width, cameraLens.height))
+
+    def _inverse_lens(self):
+        return None if self._cameraLens is None else self._cameraLens._native()
 
     def _inverse_model(self, altitude=None):
         if self._cameraHeader is None:
@@ -344,7 +361,9 @@ class DirectionArrayMapping(BaseAstrometryMapping):
         p = self._params()
         if altitude is not None:
             p.a, p.b = wgs84A + float(altitude), wgs84B + float(altitude)
-        return p, zenithal_params(self._cameraHeader, p.width, p.height, corner=False)
+        # (with a lens the params hold the raw frame's size and the zenithal block that of the header's corrected frame)
+        w, h = (p.width, p.height) if self._cameraLens is None else self._cameraLens.corrected_size
+        return p, zenithal_params(self._cameraHeader, w, h, corner=False)
 
     def _params(self):
         p = FrameParams()

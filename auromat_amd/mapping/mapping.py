@@ -511,11 +511,16 @@ class BaseMapping(object):
         raise NotImplementedError('%s has no closed-form camera model to invert: its pixels come from per-pixel tables '
                                   '(all-sky calibration arrays, gridded files), not from a WCS header' % type(self).__name__)
 
+    def _inverse_lens(self):
+        """The ``amt_lens_model`` that goes with :meth:`_inverse_model` (step 9 of world -> pixel), for a mapping of a raw frame
+        that still carries its lens distortion; None for every other mapping."""
+        return None
+
     def _to_pixel(self, frame, c0, c1, altitude, returnFlags):
         from ..coordinates.inverse import NOT_SEEN, world_to_pixel
         params, zen = self._inverse_model(altitude)
         xy, _, flags = world_to_pixel(params, zen, frame, np.asarray(c0, dtype=np.float64), np.asarray(c1, dtype=np.float64),
-                                      elevation=False)
+                                      elevation=False, lens=self._inverse_lens())
         mask = (flags & NOT_SEEN) != 0
         x, y = ma.masked_array(xy[..., 0], mask=mask), ma.masked_array(xy[..., 1], mask=mask)
         return (x, y, flags) if returnFlags else (x, y)
@@ -525,7 +530,8 @@ class BaseMapping(object):
         Where in this frame is the point of geodetic latitude / longitude (degrees, arrays of one shape) at `altitude` km
         (None: the mapping's own; 0 for cities and coastlines)?  ``(x, y)`` masked arrays of 0-based pixel coordinates, a pixel's
         centre at (column, row); masked where the point does not exist, is hidden behind the shell's limb, lies outside the
-        projection's domain or the SIP inverse did not converge.  Points outside the frame keep their coordinates (a drawn
+        projection's domain, the SIP inverse did not converge or (a raw frame with its lens, ``getMapping(lensRoute='raw')``:
+        the coordinates are the raw frame's) the point lies beyond the radius at which the lens model folds over.  Points outside the frame keep their coordinates (a drawn
         line needs its off-frame end).  ``returnFlags``: also the flag array (``auromat_amd.coordinates.inverse``).
         """
         from ..coordinates.inverse import W2P_GEODETIC

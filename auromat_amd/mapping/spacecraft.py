@@ -140,6 +140,8 @@ def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, 
     its full size, and maps it through a :class:`DirectionArrayMapping`: every raw pixel corner's place in the corrected frame
     (``amt_lens_undistort``) goes through the TAN model into a direction — no interpolated image in between.  Raw pixels that the
     model cannot be inverted for are masked.  The raw route's centres are the mean of their corners' hits (the fast mode).
+    ``latLonToPixel`` & co. of a raw-route mapping answer in raw pixels (the camera model, then the lens), and
+    ``resampleGather`` samples the raw frame once.
     Only plain TAN headers take a lens.
     """
     imageArray, wcsHeader = imagePathOrArray, wcsPathOrHeader
@@ -185,10 +187,9 @@ def getMapping(imagePathOrArray, wcsPathOrHeader, timeshift=None, noradId=None, 
             from .astrometry import DirectionArrayMapping
             xy = mod.undistorted_coordinates_device(corner=True)
             dirs = tan_pix2world(wcsHeader, xy[..., 0].contiguous(), xy[..., 1].contiguous(), 0, ascartesian=True)
+            # world -> pixel of such a mapping: the header's camera model, then the lens (step 9 of the statement)
             m = DirectionArrayMapping(dirs, altitude, np.asarray(imageArray), cam, photoTime, identifier, metadata,
-                                      noInverse='this mapping is a raw frame with its lens distortion: world -> pixel would need '
-                                                "the lens model applied after the camera model, which is not built "
-                                                "(lensRoute='resample' gives an invertible mapping)")
+                                      cameraHeader=wcsHeader, cameraLens=mod)
             m.originalPhotoTime = originalPhotoTime
             return m
         imageArray = mod.remap(np.asarray(imageArray), 'lanczos4')

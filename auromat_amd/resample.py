@@ -2217,10 +2217,18 @@ def gather_box_grid(red, pxPerDeg, arcsecPerPx):
     return dict(grid=grid, contains_pole=False, contains_discontinuity=bool(bb.containsDiscontinuity)), ppd
 
 
+def _mapping_lens(mapping):
+    """the ``amt_lens_model`` that goes with a mapping's ``_inverse_model``, or None (also for objects that only model one)"""
+    lens = getattr(mapping, '_inverse_lens', None)
+    return None if lens is None else lens()
+
+
 def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magnetic=False):
     """
     What :func:`resampleGather` samples where: dict(grid, contains_pole, contains_discontinuity, altitude, params, zenithal,
-    min_elevation, center_mask).  The grid is the one :func:`resample` chooses for the same arguments (same bounding box,
+    lens, min_elevation, center_mask).  `lens` is the ``amt_lens_model`` of a raw frame that still carries its lens distortion
+    (``getMapping(lensRoute='raw')``; None otherwise): the cells are then projected through the camera model and the lens into
+    the raw frame, whose pixels are sampled once.  The grid is the one :func:`resample` chooses for the same arguments (same bounding box,
     :func:`fixedGrid`, longitude frame).  A camera mapping whose arrays nobody has asked for yet gets its box from the box pass
     of the frame kernel and keeps a remembered ``maskedByElevation`` as a threshold (`min_elevation`); any other mapping is
     asked for its bounding box, and its centre mask (a device tensor) goes into the plan.
@@ -2229,7 +2237,8 @@ def gather_plan(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, magne
         raise NotImplementedError('resampleGather takes one mapping; collections or lists are gathered onto one grid by '
                                   'resampleGatherMosaic')
     params, zen = mapping._inverse_model()
-    plan = dict(altitude=mapping.altitude, params=params, zenithal=zen, min_elevation=None, center_mask=None)
+    plan = dict(altitude=mapping.altitude, params=params, zenithal=zen, lens=_mapping_lens(mapping), min_elevation=None,
+                center_mask=None)
     red, lazy = _gather_box(mapping, params, zen, magnetic)
     if red is not None and not (bool(red[7]) if containsPole is None else bool(containsPole)):
         part, _ = gather_box_grid(red, pxPerDeg, arcsecPerPx)
@@ -2269,16 +2278,16 @@ def gather_frame(plan, image, interpolation='linear', magnetic=False, supersampl
         del out['source']
         return out
     ctx = Context.current()
-    grid, params, zen = plan['grid'], plan['params'], plan['zenithal']
+    grid, params, zen, lens = plan['grid'], plan['params'], plan['zenithal'], plan.get('lens')
     frame = W2P_SM if magnetic else W2P_GEODETIC
     need64 = interpolation == 'nearest' or plan['center_mask'] is not None
     a, b, points = _gather_job_coordinates(plan, 1)
     a, b = ctx.to_device(np.ascontiguousarray(a)), ctx.to_device(np.ascontiguousarray(b))
     if points:
-        xy, elev, flags = world_to_pixel(params, zen, frame, a, b)
+        xy, elev, flags = world_to_pixel(params, zen, frame, a, b, lens=lens)
         xy32 = xy.to(torch.float32)
     else:
-        xy32, xy, elev, flags = grid_to_pixel(ctx, params, zen, frame, a, b, xy64=need64)
+        xy32, xy, elev, flags = grid_to_pixel(ctx, params, zen, frame, a, b, xy64=need64, lens=lens)
     src, np_dtype, _ = _image_to_device(ctx, image)
     h, w, nch = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
     if (w, h) != (params.width, params.height):
@@ -2381,7 +2390,10 @@ def resampleGather(mapping, pxPerDeg=25, arcsecPerPx=None, containsPole=None, in
 
     For mappings with a zenithal (+ SIP) WCS camera model; ``NotImplementedError`` for collections and lists
     (:func:`resampleGatherMosaic` gathers those onto one grid), for mappings
-    made from a bare direction array or a raw frame with a lens, and for MIRACLE / THEMIS.
+    made from a bare direction array, and for MIRACLE / THEMIS.  A raw frame that still carries its lens distortion
+    (``getMapping(lens=, lensRoute='raw')``) is gathered through its lens: the cell centres go through the camera model and
+    then the lens model (``amt_grid_to_pixel_lens``) into the raw frame, whose pixels are interpolated once — no corrected
+    image in between; ``supersample`` goes with it (``amt_gather_mosaic_supersampled_lens``).
 
     :param interpolation: 'nearest', 'linear' or 'lanczos4'
     :param int supersample: sub-samples per cell and axis, 1 ... 8
@@ -2426,7 +2438,8 @@ def gather_mosaic_plan(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=N
     :func:`mosaic_plan`'s pole layout, from the members' rotated outlines.
 
     :return: mosaic_layout's dict plus altitude, contains_pole, contains_discontinuity, rule, identifiers and members: a list
-             of dict(params, zenithal, min_elevation, center_mask, image)
+             of dict(params, zenithal, lens, min_elevation, center_mask, image); `lens` as in :func:`gather_plan`: members that
+             are raw frames with their lens (``getMapping(lensRoute='raw')``) and members without mix freely
     """
     collection = _gather_collection(collection)
     mappings = list(collection.mappings)
@@ -2461,8 +2474,8 @@ def gather_mosaic_plan(collection, pxPerDeg=25, arcsecPerPx=None, containsPole=N
         arrays = [convertMappingToSM(m) if magnetic else m for m in mappings]
     from .mapping.mapping import bounding_box_from_reduction
     boxes, members = [], []
-    for (params, zen), (red, lazy), src, image in zip(models, passes, arrays, images):
-        member = dict(params=params, zenithal=zen, min_elevation=None, center_mask=None, image=image)
+    for (params, zen), lens, (red, lazy), src, image in zip(models, [_mapping_lens(m) for m in mappings], passes, arrays, images):
+        member = dict(params=params, zenithal=zen, lens=lens, min_elevation=None, center_mask=None, image=image)
         if red is not None:
             boxes.append(bounding_box_from_reduction(red))
             member.update(min_elevation=lazy)
@@ -2510,6 +2523,21 @@ def _gather_member_table(ctx, members, images):
     return table, keep, nch, tdtype, np_dtype
 
 
+def _gather_lens_table(members):
+    """The `lenses` argument of the ``_lens`` gather entry points for `members` (dicts that may hold ``lens``, an
+    ``amt_lens_model``): an array of pointers, NULL where a member has no lens, or None where nobody has one — the caller then
+    takes the entry point without ``_lens``.  The array refers to the members' models, which the members keep alive."""
+    from ._native import LensModel
+    lenses = [m.get('lens') for m in members]
+    if all(lens is None for lens in lenses):
+        return None
+    table = (C.POINTER(LensModel) * len(members))()
+    for i, lens in enumerate(lenses):
+        if lens is not None:
+            table[i] = C.pointer(lens)
+    return table
+
+
 def gather_tiles(grid, n):
     """(tiles_y, tiles_x) of a grid gathered with n x n sub-samples per cell: a tile is 32 // n cells a side"""
     T = 32 // n
@@ -2554,9 +2582,12 @@ def _gather_mosaic_call(plan, members, images, interpolation, magnetic, rule, n,
     else:
         fn, factor, last = 'amt_gather_mosaic', (), ctx.empty((ny, nx, 2)) if xy else None
     dbg, tile_path = _gather_debug(ctx, debug, gather_tiles(grid, n))
-    ctx.call(fn, table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(lat), ny, ptr(lon), nx, ptr(cell_lat), ptr(cell_lon),
+    lenses = _gather_lens_table(members)
+    ctx.call(fn if lenses is None else fn + '_lens', table, len(members), W2P_SM if magnetic else W2P_GEODETIC, ptr(lat), ny, ptr(lon),
+             nx, ptr(cell_lat), ptr(cell_lon),
              *factor + (dev['img'].element_size(), nch, _GATHER_INTERP_CODES[interpolation], int(rule), ptr(dev['img']),
-                        ptr(dev['mask']), ptr(dev['elevation']), ptr(source), ptr(last), None if dbg is None else C.byref(dbg)))
+                        ptr(dev['mask']), ptr(dev['elevation']), ptr(source), ptr(last), None if dbg is None else C.byref(dbg)) +
+             (() if lenses is None else (lenses,)))
     out = gather_result(plan, source=to_host(source, dtype=np.int32), altitude=plan['altitude'], plan=plan,
                         **gather_to_host(dev, np_dtype))
     if xy and not supersampled:
@@ -2714,8 +2745,10 @@ def _gather_frames_call(ctx, plans, images, interpolation, magnetic, n, min_coun
         tiles += ty * tx
     assert at == coords.numel()
     dbg, tile_path = _gather_debug(ctx, debug, (tiles,))
-    ctx.call('amt_gather_frames', jobs, len(plans), W2P_SM if magnetic else W2P_GEODETIC, n, 1 if n == 1 else min_count,
-             made['img'].element_size(), nch, _GATHER_INTERP_CODES[interpolation], None if dbg is None else C.byref(dbg))
+    lenses = _gather_lens_table(plans)
+    ctx.call('amt_gather_frames' if lenses is None else 'amt_gather_frames_lens', jobs, len(plans), W2P_SM if magnetic else W2P_GEODETIC,
+             n, 1 if n == 1 else min_count, made['img'].element_size(), nch, _GATHER_INTERP_CODES[interpolation],
+             None if dbg is None else C.byref(dbg), *(() if lenses is None else (lenses,)))
     # the kernel is enqueued on the current stream: the caching allocator hands the inputs' memory to nobody who is not behind it
     del keep, coords
     return outs, tile_path, np_dtype

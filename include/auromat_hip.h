@@ -389,6 +389,14 @@ int amt_lens_remap(amt_ctx* ctx, const amt_lens_model* model, const void* src, i
 int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t src_height, int32_t sample_bytes, int32_t channels,
                      const float* coords, int32_t dst_width, int32_t dst_height, int32_t interpolation, void* dst, uint8_t* support,
                      const amt_lens_debug* debug);
+/* Where a model folds over (host only, no device work, no context): *out_r = r_fold, the smallest r > 0 with d(r g)/dr = 0 -
+ * of the polynomial the kernels evaluate, whose coefficients 3 k0, 5 k1 (poly3, poly5), 4 a, 3 b, 2 c and 1 - a - b - c (ptlens)
+ * are float64 roundings -, +inf where there is none, 0 where the slope is not positive at r = 0 already, NaN where a coefficient
+ * the model reads is NaN; kind AMT_LENS_NONE: +inf.  Closed form for poly3 and poly5 (linear and quadratic in r^2); ptlens: the
+ * root of the cubic is bracketed between the positive roots of its derivative and bisected to the last bit.  Only kind and k are
+ * read.  Beyond r_fold the forward polynomial maps far-off corrected points back into the raw frame and the inverse has no
+ * value.  AMT_EINVAL: NULL argument, unknown kind. */
+int amt_lens_fold_radius(const amt_lens_model* model, double* out_r);
 
 /* ---- inverse georeferencing: world -> pixel (additions to ABI 10) -------------------------------------------------------------
  * The way back from a place to the pixel that sees it: what the reference asks astropy's wcs_world2pix for (fits.py:193-216,
@@ -433,7 +441,23 @@ int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t s
  *   AMT_W2P_UNPROJECTABLE  outside the projection's domain (or P = cam)
  *   AMT_W2P_NOT_CONVERGED  step 6 did not converge
  *   AMT_W2P_OUTSIDE        xy is a number and not in [-0.5, width - 0.5] x [-0.5, height - 0.5]
- * xy is NaN exactly where INVALID, UNPROJECTABLE or NOT_CONVERGED is set; it stays a number for points that are only hidden or
+ *   AMT_W2P_LENS_FOLD      step 9b: beyond the radius at which the lens model folds over (or a non-finite lens factor)
+ * 9. the lens (the _lens entry points with a model of kind != AMT_LENS_NONE): the frame is a RAW frame that still carries its
+ *    lens distortion, and the camera model (the .wcs) belongs to the corrected image, cropped to the model's window: the X, Y of
+ *    step 7 are coordinates in the cropped corrected frame.
+ *    9a. Xf = X + crop_x, Yf = Y + crop_y; u, v, r^2 = u^2 + v^2 as the FORWARD of "lens distortion" forms them.
+ *    9b. the principal branch: the point is kept iff r^2 < r_fold^2 (amt_lens_fold_radius, squared in float64; a constant of
+ *        the model, computed once on the host) and g(r) is finite.  Beyond r_fold the forward polynomial maps far-off world
+ *        points back into the raw frame, and the raw route's inverse (amt_lens_undistort) is NaN there.  A point not kept gets
+ *        AMT_W2P_LENS_FOLD and xy NaN; so does every point of a model with a NaN coefficient, and of one with r_fold = 0.
+ *    9c. (xs, ys) = FORWARD(Xf, Yf): the operations of amt_lens_coords in their order, its "g == 1 returns the coordinate
+ *        itself" rule included.  xy is (xs, ys).
+ *    9d. AMT_W2P_OUTSIDE is decided on (xs, ys) against the RAW frame: with a lens params.width x params.height is the raw
+ *        frame's size (= the model's width x height), and the corrected, cropped size is the model's crop size (the header's
+ *        IMAGEW / IMAGEH).  Without a lens that is the frame of step 7.
+ *    Elevation, HIDDEN, UNPROJECTABLE and NOT_CONVERGED are as without a lens.  Any zenithal header, SIP included, may carry a
+ *    lens at this level.
+ * xy is NaN exactly where INVALID, UNPROJECTABLE, NOT_CONVERGED or LENS_FOLD is set; it stays a number for points that are only hidden or
  * outside the frame (a drawn line needs its off-frame end).  c1 is taken modulo 360 into [-180, 180): 180, -180 and 540 give the
  * same bits; c0 = +-90 is a valid point.
  * amt_world_to_pixel: n points, c0 / c1 / out_elev (optional) / out_flags of n elements, out_xy (n, 2) float64 [x, y].
@@ -442,7 +466,13 @@ int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t s
  * the float64 value rounded once; out_xy32 and out_xy are each optional, but one of them is required.  The two entry points share their device
  * functions and give identical bits for identical points.  AMT_EINVAL (nothing written): NULL required pointers, n < 0, an
  * empty axis or frame, an unknown `frame`, a projection index out of range, a SIP order >= AMT_SIP_MAX, a singular CD matrix.
- * n = 0 is AMT_OK.  Both only enqueue work on the context's stream. */
+ * n = 0 is AMT_OK.  Both only enqueue work on the context's stream.
+ * amt_world_to_pixel_lens, amt_grid_to_pixel_lens: the same argument lists plus `lens` (NULL or kind AMT_LENS_NONE: no lens, and
+ * the bits of the calls without; those are calls of these with NULL - one kernel family).  AMT_EINVAL as well for an unknown
+ * lens kind, a non-positive raw size, a crop window outside the full corrected frame, a raw size (the model's width x height)
+ * that is not params' width x height, and a corrected size (the crop size, or the raw size without crop) that is not the camera
+ * model's frame where that is known: zenithal's width x height.  With zenithal absent the params hold the raw size alone and
+ * the camera model's frame cannot be checked. */
 #define AMT_W2P_GEODETIC 0
 #define AMT_W2P_SM 1
 #define AMT_W2P_J2000 2
@@ -451,11 +481,18 @@ int amt_remap_coords(amt_ctx* ctx, const void* src, int32_t src_width, int32_t s
 #define AMT_W2P_UNPROJECTABLE 4
 #define AMT_W2P_NOT_CONVERGED 8
 #define AMT_W2P_OUTSIDE 16
+#define AMT_W2P_LENS_FOLD 32
 int amt_world_to_pixel(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
                        const double* c0, const double* c1, int64_t n, double* out_xy, double* out_elev, uint8_t* out_flags);
 int amt_grid_to_pixel(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
                       const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx, float* out_xy32, double* out_xy,
                       double* out_elev, uint8_t* out_flags);
+int amt_world_to_pixel_lens(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
+                            const double* c0, const double* c1, int64_t n, double* out_xy, double* out_elev, uint8_t* out_flags,
+                            const amt_lens_model* lens);
+int amt_grid_to_pixel_lens(amt_ctx* ctx, const amt_frame_params* params, const amt_zenithal_wcs* zenithal, int32_t frame,
+                           const double* lat_centres, int32_t ny, const double* lon_centres, int32_t nx, float* out_xy32,
+                           double* out_xy, double* out_elev, uint8_t* out_flags, const amt_lens_model* lens);
 
 /* ---- gather mosaic: a collection gathered onto one grid in one fused kernel (addition to ABI 10) --------------------------------
  * auromat_amd.resample.resampleGatherMosaic.  Every cell centre of one grid is projected through EVERY member's camera model
@@ -575,6 +612,32 @@ typedef struct amt_gather_job {
 } amt_gather_job;
 int amt_gather_frames(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor, int32_t min_count,
                       int32_t sample_bytes, int32_t channels, int32_t interpolation, const amt_gather_debug* debug);
+
+/* ---- gathering through the lens (additions to ABI 10) ---------------------------------------------------------------------------
+ * The three gather entry points for members that are RAW frames still carrying their lens distortion: the existing argument
+ * lists plus `lenses`, one pointer per member (per job for amt_gather_frames_lens); a NULL entry, an entry of kind AMT_LENS_NONE
+ * or a NULL array means no lens, and the calls without _lens are these with a NULL array (one kernel family; members with and
+ * without a lens mix freely).  A member with a lens is projected by steps 1-9 of world -> pixel (the arithmetic of
+ * amt_grid_to_pixel_lens, bit for bit), and "member i sees a cell" reads the same four rules on the raw coordinates: flag byte
+ * 0, support of the float32-rounded (xs, ys) in the raw frame, center_mask at the nearest raw pixel, min_elevation.  The img
+ * and center_mask of such a member are the raw frame's, params.width x params.height = the model's width x height; out_xy is
+ * (xs, ys).  The raw pixels are interpolated once; no corrected image and no coordinate array is made.
+ * AMT_EINVAL (nothing written; the text names the member or job) as the calls without _lens, and for what
+ * amt_world_to_pixel_lens refuses in a lens. */
+int amt_gather_mosaic_lens(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame, const double* lat_centres,
+                           int32_t ny, const double* lon_centres, int32_t nx, const double* cell_lat, const double* cell_lon,
+                           int32_t sample_bytes, int32_t channels, int32_t interpolation, int32_t rule, void* out_img,
+                           uint8_t* out_mask, double* out_elev, int32_t* out_source, double* out_xy, const amt_gather_debug* debug,
+                           const amt_lens_model* const* lenses);
+int amt_gather_mosaic_supersampled_lens(amt_ctx* ctx, const amt_gather_member* members, int32_t n_members, int32_t frame,
+                                        const double* sub_lat, int32_t ny, const double* sub_lon, int32_t nx,
+                                        const double* sub_cell_lat, const double* sub_cell_lon, int32_t factor, int32_t min_count,
+                                        int32_t sample_bytes, int32_t channels, int32_t interpolation, int32_t rule, void* out_img,
+                                        uint8_t* out_mask, double* out_elev, int32_t* out_source, uint8_t* out_count,
+                                        const amt_gather_debug* debug, const amt_lens_model* const* lenses);
+int amt_gather_frames_lens(amt_ctx* ctx, const amt_gather_job* jobs, int32_t n_jobs, int32_t frame, int32_t factor, int32_t min_count,
+                           int32_t sample_bytes, int32_t channels, int32_t interpolation, const amt_gather_debug* debug,
+                           const amt_lens_model* const* lenses);
 
 /* auromat/coordinates/intersection.py:144-163 ellipsoidLineIntersection (and
  * auromat/mapping/mapping.py:1474-1510 inflatedEarthIntersection with a=wgs84A+h, b=wgs84B+h).
