@@ -292,6 +292,8 @@ _SIGNATURES = {
     'amt_area_frame_finalize': ([_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, _P, _P, _P, _P], _I),
     'amt_area_frame_async': ([_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                               C.POINTER(Axis), _I, _I, C.c_int32, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P], _I),
+    'amt_mesh_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
+                        C.POINTER(Axis), _I, _P, _P, _P, _P, _P, _P, _P], _I),
     'amt_median_frame': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),
                           C.POINTER(Axis), _I, _P, _P, _P, _P], _I),
     'amt_median_frame_async': ([_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _D, C.POINTER(Axis),

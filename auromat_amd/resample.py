@@ -378,6 +378,57 @@ def resampleAreaMLatMLT(mapping, **kw):
     return convertSMMappingToGeo(resampleArea(convertMappingToSM(mapping), **kw))
 
 
+def resampleMesh(mappingOrCollection, pxPerDeg=25, arcsecPerPx=None, containsPole=None):
+    """
+    Mesh resampling: linear interpolation on the pixel lattice, on the grid of :func:`resample`.  The pixel centres form a
+    smoothly deformed lattice that carries a triangulation of its own, two triangles per quad of neighbouring centres; a cell
+    takes the value that is linear inside the lattice triangle holding its centre, colours and elevation alike.  On a fine
+    grid it fills the holes that centre binning leaves, smoothly where :func:`resampleArea` repeats a pixel's value over many
+    cells.  One device call (``amt_mesh_frame``): no global triangulation, no host pass.
+
+    Which pixels take part: those ``resample(method='mean')`` bins (unmasked centre, finite latitude — mask the mapping by
+    elevation first) with a finite longitude.  A quad with four such corners gives two triangles, one with three gives their one
+    triangle, so the mesh follows masks and the limb as closely as the data allows; a triangle as wide as half the globe (across
+    the seam of the longitudes, after the pole rotation or the date-line shift) is dropped.  Cells outside every triangle are
+    masked: the mesh itself is the footprint, no outline is used.
+
+    How this differs from ``resample(method='linear')``: that is scipy's griddata, the barycentric sum in the DELAUNAY triangles
+    of the pixel centres in (lon, lat) degrees, which takes an exact global triangulation (a third of a second for a 12 Mpx
+    frame) and, on an oblique view, joins pixels that are not neighbours in the image.  Here the triangles are the lattice's:
+    they always join image neighbours, and the diagonal of a quad is chosen by the empty-circle rule, so on a smooth convex
+    lattice both triangulations coincide.  The contract (triangles, diagonal rule, watertight edge values, lowest id wins) is
+    DESIGN.md §4.6; results are the same bits on every run.
+
+    How this differs from :func:`resampleGather`: that samples the image through the camera model in closed form and needs one;
+    it raises NotImplementedError for MIRACLE and THEMIS mappings, direction-array mappings and mappings read back from a file.
+    This needs the per-pixel centre arrays only and works for every ``BaseMapping``.
+
+    No counterpart in the reference; ``resample(method=...)`` keeps the reference's method list.
+
+    :param mappingOrCollection, pxPerDeg, arcsecPerPx, containsPole: see :func:`resample`
+    :rtype: a subclass of BaseMapping or MappingCollection
+    """
+    def doResample(mapping):
+        global last_plan
+        last_plan = None
+        pole, ppd = _pole_and_resolution(mapping, pxPerDeg, arcsecPerPx, containsPole)
+        res = resample_frame_mesh(mapping.frame(), mapping.altitude, mapping.boundingBox, ppd, mapping.containsDiscontinuity,
+                                  pole, outline=mapping.outline if pole else None)
+        return _created(mapping, res, res['mesh'], res['img'], res['has_elev'])
+
+    members, rebuild = _members(mappingOrCollection)
+    return rebuild([doResample(m) for m in members])
+
+
+def resampleMeshMLatMLT(mapping, **kw):
+    """:func:`resampleMesh` such that MLat/MLT become regular grids (``convertMappingToSM`` -> ``resampleMesh`` ->
+    ``convertSMMappingToGeo``, as :func:`resampleMedianMLatMLT`): the lattice's triangles in (SM longitude, MLat).
+
+    See :func:`resampleMesh` for parameters.
+    """
+    return convertSMMappingToGeo(resampleMesh(convertMappingToSM(mapping), **kw))
+
+
 MOSAIC_STATISTICS = ('mean', 'median', 'quantile', 'area')
 
 
@@ -795,6 +846,40 @@ def resample_frame_area(fd, altitude, boundingBox, pxPerDeg, containsDiscontinui
         img.zero_()                         # (ny,nx,1) so that the result has an image; no kernel writes it without channels
     return _result(grid, bool(containsPole), bool(containsDiscontinuity), altitude, fd.elev is not None,
                    dict(area=area, img=img, mask=mask, coverage=coverage), keep_on_device, fd.img_dtype if nch else None)
+
+
+def resample_frame_mesh(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity=False, containsPole=False,
+                        min_elevation=None, keep_on_device=False, outline=None):
+    """
+    Mesh resampling of a device-resident frame on the grid :func:`resample_frame` lays out (one ``amt_mesh_frame`` call, which
+    only enqueues): see :func:`resampleMesh`.  The centre arrays are rotated with the pole, or wrapped out of the date line in
+    the kernel, like those of the other frame functions.
+
+    :param outline: the mapping's outline, needed for the pole box only (as for :func:`resample_frame_area`); no cell is
+                    masked by it — the mesh is the footprint
+    :param keep_on_device, min_elevation: as for :func:`resample_frame`
+    :return: dict(lat, lon, lat_c, lon_c [grid coordinates, host], mesh (ny,nx,C+1) [NaN where masked], img (ny,nx,C),
+                  mask (ny,nx), triangle (ny,nx) int32 [the id of the lattice triangle that holds the cell's centre: 2 q + k for
+                  triangle k of the quad q = r * (width - 1) + c; -1 where masked], has_elev)
+    """
+    import torch
+    ctx = fd.ctx
+    ctx.bind()
+    grid, lat_c, lon_c, lon_wrap = _frame_grid(fd, altitude, boundingBox, pxPerDeg, containsDiscontinuity, containsPole,
+                                               min_elevation, outline, None)
+    xaxis, yaxis = grid.axes(ctx)
+    cell_lat, cell_lon = grid.device_centers(ctx)
+    nch = fd.nchan
+    mesh, img, mask, _ = _bin_outputs(ctx, grid, nch, fd.img_dtype_code, count=False)
+    triangle = ctx.empty((grid.ny, grid.nx), torch.int32)
+    claim = ctx.empty((grid.nx * grid.ny,), torch.int32)        # the call's claim words: any contents, set anew by the call
+    ctx.call('amt_mesh_frame', ptr(lat_c), ptr(lon_c), ptr(fd.elev), ptr(fd.img), fd.img_dtype_code or 1, nch,
+             ptr(fd.center_mask), fd.height, fd.width, _min_elevation(min_elevation), C.byref(xaxis), C.byref(yaxis), lon_wrap,
+             ptr(cell_lat), ptr(cell_lon), ptr(mesh), ptr(img) if nch else None, ptr(mask), ptr(triangle), ptr(claim))
+    if not nch:
+        img.zero_()                         # (ny,nx,1) so that the result has an image; no kernel writes it without channels
+    return _result(grid, bool(containsPole), bool(containsDiscontinuity), altitude, fd.elev is not None,
+                   dict(mesh=mesh, img=img, mask=mask, triangle=triangle), keep_on_device, fd.img_dtype if nch else None)
 
 
 # ---- map-projected resampling ------------------------------------------------------------------------------------------------

@@ -65,7 +65,8 @@ extern "C" {
  *    amt_georef_set_roles(ctx, 2); gather mosaics — amt_gather_mosaic, amt_gather_member, amt_gather_debug, AMT_INTERP_NEAREST
  *    (auromat_amd.resample.resampleGatherMosaic); supersampled gathering — amt_gather_mosaic_supersampled
  *    (auromat_amd.resample.resampleGather / resampleGatherMosaic with supersample > 1); gathered frames — amt_gather_frames,
- *    amt_gather_job (auromat_amd.resample.gather_frames, auromat_amd.pipeline.GatherSequence) */
+ *    amt_gather_job (auromat_amd.resample.gather_frames, auromat_amd.pipeline.GatherSequence); mesh resampling —
+ *    amt_mesh_frame (auromat_amd.resample.resampleMesh) */
 #define AMT_ABI_VERSION 10
 
 #define AMT_OK 0
@@ -952,6 +953,40 @@ int amt_area_frame_async(amt_ctx* ctx, const double* lat, const double* lon, con
                          int32_t width, double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap,
                          int lon_from_mlt, int32_t row_begin, int32_t row_end, uint64_t min_weight, double* area, void* out_img,
                          uint8_t* out_mask, double* out_coverage, uint32_t* over);
+/* Mesh resampling (addition to ABI v10; auromat_amd.resample.resampleMesh; no counterpart in the reference): linear
+ * interpolation in the triangles of the pixel lattice itself, two per quad of neighbouring pixel centres.  DESIGN.md §4.6 is the
+ * contract; in short:
+ *   vertices   pixel (r, c), flat index r * width + c, at x = lon_c (after lon_wrap, as for amt_bin_frame), y = lat_c.  It takes
+ *              part when lat_c is finite, elev >= min_elevation (-inf: no threshold; elev may be NULL), center_mask == 0 (may be
+ *              NULL) and lon_c is finite.
+ *   triangles  quad q = r * (width - 1) + c has A = (r, c), B = (r, c+1), C = (r+1, c+1), D = (r+1, c).  Four valid vertices:
+ *              diagonal AC gives 2q = (A, B, C), 2q+1 = (A, C, D); diagonal BD gives 2q = (A, B, D), 2q+1 = (B, C, D).  Exactly
+ *              three: their one triangle, id 2q.  Fewer: none.  A triangle whose x extent reaches 180 is dropped.
+ *   diagonal   orient(P, Q, R) = (Qx-Px)*(Ry-Py) - (Qy-Py)*(Rx-Px).  AC is admissible when orient(A,B,C) and orient(A,C,D) are
+ *              both > 0 or both < 0, BD when orient(A,B,D) and orient(B,C,D) are.  Both: BD exactly when D lies strictly inside
+ *              the circle through A, B, C (3 x 3 in-circle determinant relative to D, with the sign of orient(A,B,C)), else AC.
+ *              One: that one.  None: AC.
+ *   edges      e_k of vertex k's opposite edge is orient(P, Q, cell centre) with P, Q the edge's end points in ascending flat
+ *              index, negated when the triangle runs from the higher index to the lower.  A triangle holds a centre when its
+ *              three values are all >= 0 or all <= 0 and not all zero (all zero: on the line of a triangle without area).
+ *   election   of the triangles that hold a cell's centre the lowest id wins (32-bit atomic minimum; order independent).
+ *   value      the winner's e_k with one common sign: v = ((e0*v0 + e1*v1) + e2*v2) / ((e0 + e1) + e2), every operation rounded
+ *              on its own, in float64, per image channel (uint16 samples unsigned) and for the elevation (NaN without elev).
+ * cell_lat (ny, north to south) / cell_lon (nx): the cell centres, each inside its cell of yaxis / xaxis (the candidate cells of a
+ * triangle are those its bounding box meets, by amt_area_frame's rule); the axes may be uniform or edge tables.
+ * Outputs in the layout of amt_bin_frame_finalize, each optional, at least one: mesh (ny, nx, nchan+1) float64, NaN where no
+ * triangle holds the centre; out_img (ny, nx, nchan) of img_dtype, round-half-even of the value, 0 where masked; out_mask 1
+ * where masked; out_triangle (ny, nx) int32 the winning id, -1 where masked.
+ * claim: nx * ny uint32 of device memory of the caller's for the claim words (cell ix * ny + iy), whatever they hold: every
+ * call sets them to 0xFFFFFFFF first, and leaves the winning ids there.  The call uses no memory of the context's, so it only
+ * enqueues on the context's stream, whatever the shape: it reads nothing back, allocates nothing and waits for nothing, and its
+ * results do not depend on what the context or the buffer held before.
+ * AMT_EINVAL: height or width < 2, nchan outside 0..4, height * width or 2 * (height-1) * (width-1) not below 2^31, 65535 or more
+ * bins on an axis, no output at all, claim NULL.  Alignment: any (claim: 4 bytes). */
+int amt_mesh_frame(amt_ctx* ctx, const double* lat_c, const double* lon_c, const double* elev, const void* img,
+                   int32_t img_dtype, int32_t nchan, const uint8_t* center_mask, int32_t height, int32_t width,
+                   double min_elevation, const amt_axis* xaxis, const amt_axis* yaxis, int lon_wrap, const double* cell_lat,
+                   const double* cell_lon, double* mesh, void* out_img, uint8_t* out_mask, int32_t* out_triangle, uint32_t* claim);
 /* Median binning (auromat_amd.resample.resampleMedian; the reference names method='median' and leaves it unbuilt,
  * auromat/resample.py:353-357): the pixels amt_bin_frame would bin into cell (ix, iy) — same arguments, same membership —
  * and for every cell and channel np.median of their values: the order statistic of rank (n-1)/2, or for an even count n
